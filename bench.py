@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the AvatarCraft hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -80,6 +80,14 @@ def measure_solo(dev, p, field, table, ro, rd, rank, a):
     return out
 
 
+def dump_outputs(res, out_dir):
+    """every floating-point array of one render_rays result as out_dir/<name>.npy (float32; a few hundred KB for a 4096-ray batch)"""
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in sorted(res.items()):
+        if isinstance(v, torch.Tensor) and v.is_floating_point():
+            np.save(os.path.join(out_dir, f"{k}.npy"), v.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -91,7 +99,9 @@ def main():
                     help="arithmetic of the render kernel (ac_render_opts.precision): exact = the product's default, every product an fp32 fma, GPU == CPU "
                          "oracle bit for bit; fast = opt-in split-bf16 correction for the six finite-difference evaluations + colour network (sample "
                          "positions bit-identical, pixels within 2e-4 of exact)")
-    ap.add_argument("--repeat", type=int, default=5, help="number of timed regions of --steps steps each; the headline is the MEDIAN region (all of them are listed)")
+    ap.add_argument("--repeat", type=int, default=5, help="number of timed regions of exactly --steps steps each; the headline is the MEDIAN region (all of them are listed)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed regions, write what the last timed step returned (image, weights_sum, depth, normal_map, eik, "
+                                                           "eik_res, gradient_error of the 4096-ray batch) as DIR/<name>.npy in float32; rank 0 only")
     ap.add_argument("--sds-steps", type=int, default=8, help="also time this many 4096-ray SDS steps (secondary metric); 0 = skip")
     ap.add_argument("--real-sd", action="store_true", help="time one SDS step with the real Stable-Diffusion guidance if diffusers + the weights are on this "
                                                            "machine (the line's real_sd field says why not otherwise; the probe itself always runs)")
@@ -106,6 +116,8 @@ def main():
     ap.add_argument("--no-geometry", action="store_true", help="skip the mesh-export (512^3 + marching cubes) and density-grid-update legs")
     ap.add_argument("--posed-frames", type=int, default=4, help="also time this many 256x256 posed-space frames (render_warp.py, secondary metric); 0 = skip")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own (the form the driver uses for N = 1): this process becomes the launcher of N ranks of itself
@@ -187,6 +199,9 @@ def main():
         else:
             dt_min = dt_r
         regions.append((dt_r, dt_min, float(np.mean([s.elapsed_time(e) for s, e in evs]))))
+    if a.dump_outputs and rank == 0:
+        # what the caller of the timed path received from its last step, before anything below reuses the buffers
+        dump_outputs(outs[(a.steps - 1) % nb], a.dump_outputs)
     order = sorted(range(len(regions)), key=lambda i: regions[i][0])
     dt, dt_rank_min, kern_ms = regions[order[len(order) // 2]]
     # the same launches in the OTHER arithmetic mode, outside the timed region (rank 0 reports it next to the headline: `exact` is bit-identical to the
