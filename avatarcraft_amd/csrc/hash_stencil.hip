@@ -22,25 +22,8 @@ using namespace acdev;
 
 namespace {
 
-#ifndef AC_RUN_EARLY_OUT
-#define AC_RUN_EARLY_OUT 1     // the segmented run scan stops as soon as every lane of the wave has met the head of its run (run_reduce)
-#endif
-#ifndef AC_FILL_PREFETCH
-#define AC_FILL_PREFETCH 1     // hash_stencil_bwd_binned_kernel requests the next group's inputs before it scatters the current one
-#endif
-#ifndef AC_ACC_SPLIT
-#define AC_ACC_SPLIT 0         // 1: the two channels of the bucket sums in separate halves of the LDS slice (fewer bank conflicts of the LDS atomics) -- measured: nothing
-#endif
 #ifndef AC_ACC_W
 #define AC_ACC_W 8             // bucket_accumulate_kernel: table elements per thread whose read-modify-write is issued together
-#endif
-#ifndef AC_ABL_FLUSH
-#define AC_ABL_FLUSH 0
-#endif
-#ifdef AC_ABL_NOATOMIC      // timing ablation (tools/ablate_stencil.sh): keep the address math, drop the atomic itself
-#define AC_ATOMIC_ADD(P, V) { if ((V) == 123456.789f) *(P) = (V); }
-#else
-#define AC_ATOMIC_ADD(P, V) unsafeAtomicAdd((P), (V))
 #endif
 
 __device__ __forceinline__ void wave_sync_lds()
@@ -243,24 +226,11 @@ __device__ __forceinline__ void run_step(float (&v)[N], int &f)
 template <int N>
 __device__ __forceinline__ bool run_reduce(float (&v)[N], bool head, int lane, bool norun = false)
 {
-#ifdef AC_ABL_NORUN         // timing ablation: every lane is its own run
-    return true;
-#endif
     // norun (wave-uniform): a lane of this wave carries an Inf / NaN upstream gradient.  The scan below adds `neighbour * {0, 1}`, and
     // Inf * 0 = NaN would leak into every lane of the row: such a group scatters lane by lane, so that a non-finite gradient reaches
     // exactly the entries the reference's atomicAdd would give it (hashencoder.cu:302-305)
     if (norun) return true;
     int f = head ? 1 : 0;
-#ifdef AC_RUN_SHUFFLE       // the first implementation: 6 Kogge-Stone steps over the whole wave with ds_bpermute
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int tf = __shfl_up(f, d);
-        const bool take = (lane >= d) && !f;
-#pragma unroll
-        for (int i = 0; i < N; ++i) { const float t = __shfl_up(v[i], d); v[i] += take ? t : 0.0f; }
-        if (lane >= d) f |= tf;
-    }
-#else
     // every value has to be final BEFORE the first DPP read (the scheduler may otherwise sink the instruction that produces v[i + 1]
     // between two of the inline-assembly statements, inside the hazard window): empty volatile statements pin them
     static_assert(N % 8 == 0, "run_reduce works on multiples of 8 values");
@@ -271,11 +241,7 @@ __device__ __forceinline__ bool run_reduce(float (&v)[N], bool head, int lane, b
     // remaining steps would add `neighbour * 0` everywhere and are skipped (wave-uniform branch; round 4: the scan is more than half of the
     // fill's vector instructions, and outside the densely sampled shell of the surface runs are a few lanes long on all but the coarsest levels).
     // The skipped additions of +-0 can only turn a -0 into +0: a value that the != 0 predicate drops or the fixed-point sum reads as 0 either way.
-#if AC_RUN_EARLY_OUT
 #define AC_RUN_DONE() (__builtin_amdgcn_ballot_w64(f == 0) == 0ull)
-#else
-#define AC_RUN_DONE() false
-#endif
     do {
         if (AC_RUN_DONE()) break;
         run_step<N, 0x111, 0xf>(v, f);
@@ -291,7 +257,6 @@ __device__ __forceinline__ bool run_reduce(float (&v)[N], bool head, int lane, b
         run_step<N, 0x143, 0xc>(v, f);          // row_bcast31: rows 2 and 3 take lane 31
     } while (false);
 #undef AC_RUN_DONE
-#endif
     const int next_head = __shfl_down(head ? 1 : 0, 1);
     return lane == 63 || next_head != 0;
 }
@@ -320,7 +285,7 @@ struct DirectSink {
     {
 #pragma unroll
         for (int k = 0; k < 8; ++k)
-            if (pred[k]) { float *t = reinterpret_cast<float *>(gg + index_of(k)); AC_ATOMIC_ADD(t, v[2 * k]); AC_ATOMIC_ADD(t + 1, v[2 * k + 1]); }
+            if (pred[k]) { float *t = reinterpret_cast<float *>(gg + index_of(k)); unsafeAtomicAdd(t, v[2 * k]); unsafeAtomicAdd(t + 1, v[2 * k + 1]); }
     }
 };
 
@@ -329,29 +294,21 @@ constexpr int NBUCKET = 64;
 #define AC_RCAP 1536
 #endif
 constexpr int RCAP = AC_RCAP;              // records per wave buffer; add8 reserves room for 8 x 64 records
-#ifndef AC_FILL_PACK
-#define AC_FILL_PACK 1      // coarse levels: the run tails' contributions transposed through LDS so that the records are formed by DENSE lanes (BinSink::add_packed)
-#endif
 #ifndef AC_FILL_PACK_MAX
 #define AC_FILL_PACK_MAX 32  // most run tails per wave for which the packed path is taken (8 per chunk; above ~40 the sparse walk is cheaper)
 #endif
 constexpr int PACK_TAILS = 8;                          // run tails staged per chunk: 8 tails x 8 entries = the wave's 64 lanes
 constexpr int PACK_STRIDE = 20;                        // staged words per tail: 16 values (8 entries x 2 channels) + the cell's three axis terms (+ 1 pad: 16-byte rows)
-constexpr int STAGE_WORDS = AC_FILL_PACK ? PACK_TAILS * PACK_STRIDE : 0;
+constexpr int STAGE_WORDS = PACK_TAILS * PACK_STRIDE;
 constexpr int WAVE_WORDS = 3 * RCAP + 2 * NBUCKET + STAGE_WORDS;     // LDS words per wave: ridx, rv0, rv1 [RCAP], hist, base [64], the packing stage
 static_assert(RCAP % 2 == 0 && RCAP >= 1024, "wave buffer: room for two batches of 8 x 64 records");
-#ifndef AC_REC16
-#define AC_REC16 0          // 1: queue records padded to 16 bytes (one aligned dwordx4 store / load per record instead of three dword accesses; +33 % queue bytes)
-#endif
 #ifndef AC_REC8
 #define AC_REC8 1           // 1 (round 4): 8-byte queue records -- 13 bits of entry index inside its bucket | v0 rounded to 16 explicit mantissa bits (25 bits) | v1
 #endif                      //    rounded to 17 (26 bits).  PRECISION CONTRACT of the table gradient: every (entry, v0, v1) contribution is rounded
                             //    to nearest at 2^-17 / 2^-18 of its own magnitude before the order-independent fixed-point sum -- below the fp32 round-off of a sum
                             //    of a few records, checked against the fp64 oracle backward at 3e-4 of max (observed 1.2e-4, unchanged).  The queue traffic is what
                             //    the two scatter passes are short of: 16-byte records cost the step +0.21 ms, 8-byte ones gain (profiles/r04_experiments.txt 8b).
-#if AC_REC16
-struct __attribute__((aligned(16))) Rec { uint32_t idx; float v0, v1; uint32_t pad; };
-#elif AC_REC8
+#if AC_REC8
 struct __attribute__((aligned(8))) Rec { uint32_t lo, hi; };
 // values are rounded when they are RECORDED (add8), so that the level's max |v| -- the fixed-point scale -- is taken over what is actually summed
 __device__ __forceinline__ float rec_round(float v, int drop)        // round to nearest at bit `drop` (quiet NaN and Inf survive; FLT_MAX may round to Inf)
@@ -387,7 +344,7 @@ struct BinSink {
     uint32_t cap;
     float2 *gg;                            // overflow path: direct atomics
     int lane;
-    float *stage;                          // this wave's LDS [PACK_TAILS][PACK_STRIDE] (AC_FILL_PACK)
+    float *stage;                          // this wave's LDS [PACK_TAILS][PACK_STRIDE] (add_packed)
 #ifdef AC_PROFILE_FILL                     // s_memtime per phase: 0 stencil combine + run scan, 1 records -> LDS, 2 flush: slot reservation, 3 flush: write-out
     unsigned long long ft, facc[4], nflush;
     __device__ __forceinline__ void tick(int slot) { const unsigned long long t2 = __builtin_amdgcn_s_memtime(); facc[slot] += t2 - ft; ft = t2; }
@@ -449,9 +406,6 @@ struct BinSink {
     }
     __device__ __forceinline__ void flush()
     {
-#if AC_ABL_FLUSH == 1       // timing ablation: drop the records
-        cnt = 0; return;
-#endif
         tick(1);
         wave_sync_lds();
         {
@@ -490,15 +444,9 @@ struct BinSink {
 #else
                     Rec r; r.idx = idx - (bucket << sh); r.v0 = v0[u]; r.v1 = v1[u];
 #endif
-#if AC_REC16
-                    r.pad = 0u;
-#endif
-#if AC_ABL_FLUSH == 2       // timing ablation: bin the records but do not write them
-                    if (v0[u] == 123456.789f)
-#endif
                     queue[(size_t)bucket * cap + slot] = r;
                 } else {                    // queue full (never with the default sizing): fall back to atomics
-                    float *t = reinterpret_cast<float *>(gg + idx); AC_ATOMIC_ADD(t, v0[u]); AC_ATOMIC_ADD(t + 1, v1[u]);
+                    float *t = reinterpret_cast<float *>(gg + idx); unsafeAtomicAdd(t, v0[u]); unsafeAtomicAdd(t + 1, v1[u]);
                 }
             }
         }
@@ -539,11 +487,7 @@ __device__ __forceinline__ void scatter8_runs(Sink &sink, const LevelC &L, const
         for (uint32_t d = 0; d < 3; ++d) w *= ((idx >> d) & 1u) ? q[d].fr : 1.0f - q[d].fr;
         v[2 * idx] = ok ? w * g0 : 0.0f; v[2 * idx + 1] = ok ? w * g1 : 0.0f;
     }
-#ifdef AC_FINE_NORUN        // experiment: no run combining on the per-point path (few same-cell neighbours on the fine levels)
-    const bool tail = ok;
-#else
     const bool tail = run_reduce<16>(v, run_head(q, ok, lane), lane, norun) && ok;
-#endif
     sink.tick(0);
     bool pred[8];
 #pragma unroll
@@ -630,7 +574,6 @@ __device__ __forceinline__ void stencil_scatter(Sink &sink, const LevelC &L, boo
     sink.tick(0);
     // the centre cell's pre-multiplied terms: every one of the 32 entries below is these plus / minus multiples of (1, cmy, cmz) (gindex_t)
     const uint32_t cmy = level_my(L), cmz = level_mz(L), cty = c[1].pg * cmy, ctz = c[2].pg * cmz;
-#if AC_FILL_PACK
     if constexpr (Sink::packs) {
         // After the run combining only the TAIL lanes carry anything -- a handful per wave on the coarse levels -- and the four add8 calls below walk 32 entries with
         // a tenth of the lanes live (half of the fill's time: tools/fill_profile.py, round 6).  With few tails the work is transposed through LDS instead: a chunk of
@@ -675,7 +618,6 @@ __device__ __forceinline__ void stencil_scatter(Sink &sink, const LevelC &L, boo
             return;
         }
     }
-#endif
     {
         bool pred[8]; float vv[16];
 #pragma unroll
@@ -791,13 +733,8 @@ __global__ __launch_bounds__(256) void hash_stencil_bwd_binned_kernel(const floa
         float2 gp[7];
 #pragma unroll
         for (int p = 0; p < 7; ++p) gp[p] = nxt.gp[p];
-#if AC_FILL_PREFETCH
         if (grp + gstride < ngroups) request(grp + gstride, nxt);
-#endif
         stencil_scatter(sink, L, fine, xc, gp, eps, bound, two_bound, lane, inv_tb);
-#if !AC_FILL_PREFETCH
-        if (grp + gstride < ngroups) request(grp + gstride, nxt);
-#endif
     }
     sink.finish();
 #ifdef AC_PROFILE_FILL
@@ -902,13 +839,9 @@ __global__ __launch_bounds__(1024) void bucket_accumulate_kernel(float *__restri
     }
     for (uint32_t e = threadIdx.x; e < per * 2; e += blockDim.x) acc[e] = 0ull;
     __syncthreads();
-    // fixed-point sums of the bucket's entries: channel c of entry i at AC_ACC_AT(i, c).  Split (round 4): the two channels in separate halves of the slice,
-    // so that the 64 lanes of one LDS atomic spread over 32 bank pairs instead of 16 bank quads
-#if AC_ACC_SPLIT
-#define AC_ACC_AT(I, CH) ((I) + (CH) * per)
-#else
+    // fixed-point sums of the bucket's entries: channel c of entry i at AC_ACC_AT(i, c).  (Round 4 measured the two channels in separate halves of the slice,
+    // so that the 64 lanes of one LDS atomic spread over 32 bank pairs instead of 16 bank quads: nothing.)
 #define AC_ACC_AT(I, CH) (2u * (I) + (CH))
-#endif
     const int emax = (int)(mbits >> 23) - 126;                                       // |v| < 2^emax for every record of the level
     const int head = 32 - __builtin_clz(n);                                          // ceil(log2(n + 1))
     const int k = 62 - head - emax;
@@ -933,12 +866,8 @@ __global__ __launch_bounds__(1024) void bucket_accumulate_kernel(float *__restri
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-#ifdef AC_ABL_NOLDSATOMIC
-            if (r[u].v0 != 0.0f || r[u].v1 != 0.0f) { acc[AC_ACC_AT(r[u].idx, 0u)] = 1ull; acc[AC_ACC_AT(r[u].idx, 1u)] = 1ull; }
-#else
             if (r[u].v0 != 0.0f) atomicAdd(&acc[AC_ACC_AT(r[u].idx, 0u)], (unsigned long long)__double2ll_rn(ldexp((double)r[u].v0, k)));
             if (r[u].v1 != 0.0f) atomicAdd(&acc[AC_ACC_AT(r[u].idx, 1u)], (unsigned long long)__double2ll_rn(ldexp((double)r[u].v1, k)));
-#endif
         }
     }
     __syncthreads();

@@ -11,20 +11,6 @@
 using namespace acdev;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-#ifdef AC_ABL_MFMA     // timing ablation: replace every MFMA by one VALU fma per accumulator register
-static __device__ __forceinline__ f32x4 abl_mfma(float a, float b, f32x4 c) { c[0] = __builtin_fmaf(a, b, c[0]); return c; }
-#define __builtin_amdgcn_mfma_f32_16x16x4f32(A, B, C, X, Y, Z) abl_mfma(A, B, C)
-#endif
-#ifdef AC_ABL_GATHER   // timing ablation: every gather reads table entry 0 (perfectly cached, fully coalesced)
-#define AC_GOFF(X) ((X) & 0u)
-#elif defined(AC_ABL_L0)   // timing ablation (round 3, "what could level 0 in LDS save at most?"): gathers below byte AC_ABL_L0 of the table -- 39304 = the
-// dense 17^3 level 0 -- go out of range (dropped by the descriptor's bounds check: free).  The threshold is a mutable device global so that the control
-// build (-DAC_ABL_L0=0) runs exactly the same instructions and drops nothing.  Results are wrong by construction; timing only.
-static __device__ uint32_t g_abl_l0_thr = AC_ABL_L0;
-#define AC_GOFF(X) (((X) < g_abl_l0_thr) ? 0xfffffff8u : (X))
-#else
-#define AC_GOFF(X) (X)
-#endif
 
 namespace {
 
@@ -35,21 +21,6 @@ constexpr int WAVES_PER_BLOCK = AC_WPB;
 constexpr int BLOCK = WAVES_PER_BLOCK * 64;
 constexpr int MAXT = 128;
 constexpr int SEG_STATE = MAXT + 16 + 64;   // floats per ray handed from one segment of a ray to the next: z [128] | cT, 10 running sums | pad | (view directions) the ray's layer-1 bias [64]
-#ifndef AC_FINE_BATCH
-#define AC_FINE_BATCH 3     // fine stencil levels: offset-point pairs gathered per memory round trip (1: x | y | z, 2: x+y | z, 3: all six: 221 VGPRs, -2 % time)
-#endif
-#ifndef AC_FACE_VALUE
-#define AC_FACE_VALUE 0     // fast precision: coarse-level features of the six offset points from bilinear face values (see coarse_finish_fv)
-#endif
-#ifndef AC_FV_SIGNS
-#define AC_FV_SIGNS 3       // (debug) bit 0: +eps, bit 1: -eps along z use the face-value form
-#endif
-#ifndef AC_FV_AXES
-#define AC_FV_AXES 7        // (debug) bit k: the face-value form is used for the offset points along axis k
-#endif
-#ifndef AC_SENTINEL_LOADS
-#define AC_SENTINEL_LOADS 0  // 1: lanes of a coarse level that need no new face send an out-of-range offset instead of being masked out (round 1 / 2; see coarse_issue)
-#endif
 #ifndef AC_ENC_ROUND
 #define AC_ENC_ROUND 2      // hash levels gathered per round per lane (registers vs loads in flight)
 #endif
@@ -132,7 +103,7 @@ struct RenderArgs {
     const float *near_m, *far_m;   // [N] mesh-guided range (+-inf where the ray misses the body) or NULL
     const float *ext_pts;          // MODE_UPSAMPLE: warped coarse points [N,T0,3]; MODE_FINAL: warped mid points [N,T,3]
     const uint8_t *mask;           // MODE_FINAL: [N,T] alpha mask
-    uint32_t *ray_counter;         // AC_DYNAMIC_RAYS: [8 XCDs][8 segments] work counters (zeroed before the launch): waves fetch their next (ray, segment) instead of owning fixed rays
+    uint32_t *ray_counter;         // [8 XCDs][8 segments] work counters (zeroed before the launch): waves fetch their next (ray, segment) instead of owning fixed rays
     uint32_t *seg_flags;           // [N] number of finished segments of each ray (zeroed before the launch), or NULL when seg_n == 1
     float *seg_state;              // [N][SEG_STATE] what a ray's next segment continues from: z values + running sums (library scratch)
     uint64_t seg_cb;               // first tile of segment s in bits 4s .. 4s+3, s = 0 .. seg_n
@@ -345,43 +316,10 @@ __device__ __forceinline__ void fill_lds_color_fast(float *lds, const RenderArgs
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32q __attribute__((ext_vector_type(4)));
-#ifndef AC_DENSE_PAIRS
-#define AC_DENSE_PAIRS 0    // 1: on dense levels the corners (x, x + 1) of a cell come through ONE 16-byte gather (round 4 experiment: bit-identical, 8.7 % fewer
-                            // gather instructions on the all-dense round, and NO gain -- render 0.7438 vs 0.7464 ms, the frozen SDS render 0.969 vs 0.959:
-                            // the texture-address path is paced by bytes per instruction, a 64-lane dwordx4 costs it what two dwordx2 cost; r04_experiments 7b)
-#endif
-
-#ifndef AC_PK_INTERP
-#define AC_PK_INTERP 0      // 1: the trilinear interpolation on the packed fp32 instructions (v_pk_mul_f32 / v_pk_fma_f32) -- round 6 experiment: bit-identical, 6.8 % fewer vector
-                            // instructions (6813 -> 6349 static, 10 spilled dwords fewer) and SLOWER: 0.746 -> 0.781 ms (profiles/r06_experiments.txt section 4d)
-#endif
-typedef float f32p __attribute__((ext_vector_type(2)));
+// dense levels' corner pairs through one 16-byte gather: bit-identical, no gain -- profiles/r04_experiments.txt section 7b
+// packed-fp32 interpolation (v_pk_mul_f32 / v_pk_fma_f32): bit-identical, slower -- profiles/r06_experiments.txt section 4d
 __device__ __forceinline__ void interp8(const u32x2 (&v)[8], float qx, float qy, float qz, bool oob, float &f0, float &f1)
 {
-#if AC_PK_INTERP
-    // The same 12 multiplications and 16 fused multiply-adds per level as below, in the same order per accumulator -- the same bits -- as 6 + 8 packed
-    // instructions: the weights of the corners (x, x + 1) travel as a pair, a corner's two channels are the pair the gather delivered, and a weight is
-    // broadcast to both channels by the instruction's operand selects (no move).
-    const f32p wx = { 1.0f - qx, qx };
-    const float wy0 = 1.0f - qy, wz0 = 1.0f - qz;
-    const f32p w0 = wx * f32p{ wy0, wy0 }, w1 = wx * f32p{ qy, qy };           // (w00, w10), (w01, w11)
-    f32p acc = { 0.0f, 0.0f };
-#pragma unroll
-    for (int c = 0; c < 8; c += 2) {
-        const float z = (c & 4) ? qz : wz0;
-        const f32p wp = ((c & 2) ? w1 : w0) * f32p{ z, z };
-        const f32p a = { __uint_as_float(v[c].x), __uint_as_float(v[c].y) }, b = { __uint_as_float(v[c + 1].x), __uint_as_float(v[c + 1].y) };
-#if AC_PK_INTERP == 2       // the weights packed, the accumulation as two independent scalar chains
-        acc[0] = fma_(wp[0], a[0], acc[0]); acc[1] = fma_(wp[0], a[1], acc[1]);
-        acc[0] = fma_(wp[1], b[0], acc[0]); acc[1] = fma_(wp[1], b[1], acc[1]);
-#else
-        acc = __builtin_elementwise_fma(__builtin_shufflevector(wp, wp, 0, 0), a, acc);
-        acc = __builtin_elementwise_fma(__builtin_shufflevector(wp, wp, 1, 1), b, acc);
-#endif
-    }
-    f0 = oob ? 0.0f : acc[0];
-    f1 = oob ? 0.0f : acc[1];
-#else
     const float wx0 = 1.0f - qx, wy0 = 1.0f - qy, wz0 = 1.0f - qz;
     const float w00 = wx0 * wy0, w10 = qx * wy0, w01 = wx0 * qy, w11 = qx * qy;
     float a0 = 0.0f, a1 = 0.0f;
@@ -394,7 +332,6 @@ __device__ __forceinline__ void interp8(const u32x2 (&v)[8], float qx, float qy,
     }
     f0 = oob ? 0.0f : a0;
     f1 = oob ? 0.0f : a1;
-#endif
 }
 template <int ROUND>
 __device__ __forceinline__ void encode4(const float *__restrict__ lds, rsrc_t table, int g, const int (&jmode)[4],
@@ -421,16 +358,6 @@ __device__ __forceinline__ void encode4(const float *__restrict__ lds, rsrc_t ta
             const uint32_t ax0 = gx, ax1 = gx + 1u, ay0 = gy * my, ay1 = ay0 + my, az0 = gz * mz, az1 = az0 + mz;
             const int mode = jmode[j];                      // wave-uniform: one code path per gather round
             uint32_t idx[8];
-#if AC_DENSE_PAIRS
-            if (mode == 0) {                                // all four levels of this round are dense: the corners (x, x + 1) are ADJACENT entries -- one
-#pragma unroll                                              // 16-byte gather per pair (the per-CU gather path is what the kernel is short of: r04_experiments 7)
-                for (int p = 0; p < 4; ++p) {
-                    const u32q w = __builtin_amdgcn_raw_buffer_load_b128(table, AC_GOFF((offset + (ax0 + ((p & 1) ? ay1 : ay0) + ((p & 2) ? az1 : az0))) * 8u), 0, 0);
-                    v[jj][2 * p] = u32x2{ w.x, w.y }; v[jj][2 * p + 1] = u32x2{ w.z, w.w };
-                }
-                continue;
-            }
-#endif
             if (mode == 0) {                                // all four levels of this round are dense
 #pragma unroll
                 for (int c = 0; c < 8; ++c) idx[c] = ((c & 1) ? ax1 : ax0) + ((c & 2) ? ay1 : ay0) + ((c & 4) ? az1 : az0);
@@ -445,7 +372,7 @@ __device__ __forceinline__ void encode4(const float *__restrict__ lds, rsrc_t ta
                 }
             }
 #pragma unroll
-            for (int c = 0; c < 8; ++c) v[jj][c] = __builtin_amdgcn_raw_buffer_load_b64(table, AC_GOFF((offset + idx[c]) * 8u), 0, 0);
+            for (int c = 0; c < 8; ++c) v[jj][c] = __builtin_amdgcn_raw_buffer_load_b64(table, (offset + idx[c]) * 8u, 0, 0);
         }
 #pragma unroll
         for (int jj = 0; jj < ROUND; ++jj)
@@ -536,13 +463,8 @@ __device__ __forceinline__ f32x4 sdf_l2(const float *__restrict__ lds, int lane,
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         float h[4];
-#ifdef AC_ABL_SOFTPLUS
-#pragma unroll
-        for (int r = 0; r < 4; ++r) h[r] = acc.a[t][r] * 0.5f;
-#else
         const float xin[4] = { acc.a[t][0], acc.a[t][1], acc.a[t][2], acc.a[t][3] };
         dv_softplus100_n<4>(lds + OFF_SPQ, xin, h);
-#endif
 #pragma unroll
         for (int r = 0; r < 4; ++r)
             o2 = __builtin_amdgcn_mfma_f32_16x16x4f32(lds[OFF_W2F + (4 * t + r) * 64 + lane], h[r], o2, 0, 0, 0);
@@ -574,12 +496,7 @@ __device__ __forceinline__ float sdf_l2_sdf(const float *__restrict__ lds, const
         float xin[NB_], h[NB_];
 #pragma unroll
         for (int i = 0; i < NB_; ++i) xin[i] = acc.a[t0 + (i >> 2)][i & 3];
-#ifdef AC_ABL_SOFTPLUS
-#pragma unroll
-        for (int i = 0; i < NB_; ++i) h[i] = xin[i] * 0.5f;
-#else
         dv_softplus100_n<NB_>(lds + OFF_SPQ, xin, h);
-#endif
 #pragma unroll
         for (int i = 0; i < NB_; ++i) p = fma_(w0.w[t0 + (i >> 2)][i & 3], h[i], p);
     }
@@ -623,7 +540,6 @@ template <int GM>
 __device__ __forceinline__ uint32_t gidx(const LvlC &L, uint32_t tx, uint32_t ty, uint32_t tz)
 {
     if constexpr (GM == 1) return (tx ^ ty ^ tz) & L.mask;
-    else if constexpr (GM == 0) return tx + ty + tz;                       // a dense round (every lane's level): index < level size by construction
     else return (L.hashed ? (tx ^ ty ^ tz) : (tx + ty + tz)) & L.mask;
 }
 // corner index (0..7) of the i-th corner (i = 0..3, other two axes in increasing order) on face b of axis K
@@ -634,8 +550,8 @@ template <int K> __device__ __forceinline__ constexpr int face_corner(int b, int
 
 // ---- coarse level (eps*scale < 1 cell): an offset point lies in the centre cell or in the adjacent one, so it needs at
 // most ONE face the centre does not have (coordinate g+2 for +eps, g-1 for -eps).  All 8 + 6*4 gathers of the level
-// are issued as one batch (lanes that need nothing send an out-of-range offset: dropped by the descriptor's bounds
-// check), then the 7 interpolations run from registers: one memory round trip per level instead of seven.  (As compiled, the compiler folds
+// are issued as one batch (lanes that need nothing are masked out; rounds 1 - 2 sent them an out-of-range offset instead), then the 7 interpolations
+// run from registers: one memory round trip per level instead of seven.  (As compiled, the compiler folds
 // coarse_finish's select into the offset points' loads -- register pre-set to the centre's corner, load under an exec mask, skipped when no lane of the
 // wave needs it -- so they leave after the centre's have returned: two round trips.  Forcing one batch was measured and changes nothing, the other wave
 // of the SIMD covers the second trip: profiles/r02_experiments.txt.)
@@ -656,30 +572,12 @@ __device__ __forceinline__ AxisGeo<K, SIGN> coarse_issue(rsrc_t table, const Lvl
     const uint32_t mk = K == 0 ? 1u : (K == 1 ? L.my : L.mz);
     const uint32_t base = K == 0 ? tx[0] : (K == 1 ? ty[0] : tz[0]);
     const uint32_t tk = SIGN == 0 ? base + 2u * mk : base - mk;   // coordinate g+2 / g-1 along K
-    if constexpr (GM == 0 && K != 0 && !AC_SENTINEL_LOADS) {      // dense round, a y- or z-face: its corners come in x-adjacent pairs
-#pragma unroll
-        for (int pp = 0; pp < 2; ++pp) {
-            const int c = face_corner<K>(0, 2 * pp);
-            const uint32_t ay = K == 1 ? tk : ty[(c >> 1) & 1], az = K == 2 ? tk : tz[(c >> 2) & 1];
-            w[2 * pp] = u32x2{ 0u, 0u }; w[2 * pp + 1] = u32x2{ 0u, 0u };
-            if (a.need) {
-                const u32q q = __builtin_amdgcn_raw_buffer_load_b128(table, AC_GOFF((L.offset + (tx[0] + ay + az)) * 8u), 0, 0);
-                w[2 * pp] = u32x2{ q.x, q.y }; w[2 * pp + 1] = u32x2{ q.z, q.w };
-            }
-        }
-        return a;
-    }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int c = face_corner<K>(0, i);
         const uint32_t ax = K == 0 ? tk : tx[c & 1], ay = K == 1 ? tk : ty[(c >> 1) & 1], az = K == 2 ? tk : tz[(c >> 2) & 1];
-#if AC_SENTINEL_LOADS
-        const uint32_t off = a.need ? (L.offset + gidx<GM>(L, ax, ay, az)) * 8u : 0xfffffff8u;
-        w[i] = __builtin_amdgcn_raw_buffer_load_b64(table, AC_GOFF(off), 0, 0);
-#else
         w[i] = u32x2{ 0u, 0u };
-        if (a.need) w[i] = __builtin_amdgcn_raw_buffer_load_b64(table, AC_GOFF((L.offset + gidx<GM>(L, ax, ay, az)) * 8u), 0, 0);
-#endif
+        if (a.need) w[i] = __builtin_amdgcn_raw_buffer_load_b64(table, (L.offset + gidx<GM>(L, ax, ay, az)) * 8u, 0, 0);
     }
     return a;
 }
@@ -700,40 +598,7 @@ __device__ __forceinline__ void coarse_finish(const AxisGeo<K, SIGN> &a, const u
     interp8(v2, K == 0 ? a.qk : qc[0], K == 1 ? a.qk : qc[1], K == 2 ? a.qk : qc[2], a.oob, f0, f1);
 }
 
-// ---- fast precision only (AC_FACE_VALUE): an offset point differs from the centre along ONE axis, so its feature is the linear
-// interpolation, along that axis, of two bilinear FACE values -- (A, B) of the centre cell, (B, N) one cell up, (N, A) one cell down, N = the
-// gathered face -- with the centre's weights for the other two axes: 4 + 3 x (4 + 4 x 8) + 6 x 11 vector instructions per level instead of
-// 7 full 8-corner interpolations and their corner selects.  Same function, different rounding (not the oracle's order): the offset features
-// only feed the split-bf16 correction of layer 1, whose own error is 2^-16 of the difference.
-template <int K> __device__ __forceinline__ void face_weights(const float (&qc)[3], float (&fw)[4])
-{
-    const float qa = K == 0 ? qc[1] : qc[0], qb = K == 2 ? qc[1] : qc[2];        // the two other axes, in increasing order
-    const float a0 = 1.0f - qa, b0 = 1.0f - qb;
-    fw[0] = a0 * b0; fw[1] = qa * b0; fw[2] = a0 * qb; fw[3] = qa * qb;
-}
-template <int K> __device__ __forceinline__ void face_value(const u32x2 (&vc)[8], int b, const float (&fw)[4], float (&f)[2])
-{
-    float s0 = fw[0] * __uint_as_float(vc[face_corner<K>(b, 0)].x), s1 = fw[0] * __uint_as_float(vc[face_corner<K>(b, 0)].y);
-#pragma unroll
-    for (int i = 1; i < 4; ++i) {
-        s0 = fma_(fw[i], __uint_as_float(vc[face_corner<K>(b, i)].x), s0);
-        s1 = fma_(fw[i], __uint_as_float(vc[face_corner<K>(b, i)].y), s1);
-    }
-    f[0] = s0; f[1] = s1;
-}
-template <int K, int SIGN>
-__device__ __forceinline__ void coarse_finish_fv(const AxisGeo<K, SIGN> &a, const float (&A)[2], const float (&B)[2], const u32x2 (&w)[4],
-                                                 const float (&fw)[4], float &f0, float &f1)
-{
-    float n0 = fw[0] * __uint_as_float(w[0].x), n1 = fw[0] * __uint_as_float(w[0].y);
-#pragma unroll
-    for (int i = 1; i < 4; ++i) { n0 = fma_(fw[i], __uint_as_float(w[i].x), n0); n1 = fma_(fw[i], __uint_as_float(w[i].y), n1); }
-    const float x0 = a.need ? (SIGN == 0 ? B[0] : n0) : A[0], x1 = a.need ? (SIGN == 0 ? B[1] : n1) : A[1];
-    const float y0 = a.need ? (SIGN == 0 ? n0 : A[0]) : B[0], y1 = a.need ? (SIGN == 0 ? n1 : A[1]) : B[1];
-    const float r0 = fma_(a.qk, y0 - x0, x0), r1 = fma_(a.qk, y1 - x1, x1);
-    f0 = a.oob ? 0.0f : r0;
-    f1 = a.oob ? 0.0f : r1;
-}
+// coarse offset points from bilinear face values (fast precision only): removed, the one run-to-run non-determinism ever seen -- DESIGN.md section 2.1
 
 // ---- fine level (eps spans one cell or more): every offset point gathers its own 8 corners ---------------------------
 template <int K, int GM>
@@ -750,17 +615,14 @@ __device__ __forceinline__ void fine_issue(rsrc_t table, const LvlC &L, const ui
     for (int c = 0; c < 8; ++c) {
         const uint32_t tk = ((c >> K) & 1) ? t1 : t0;
         const uint32_t ax = K == 0 ? tk : tx[c & 1], ay = K == 1 ? tk : ty[(c >> 1) & 1], az = K == 2 ? tk : tz[(c >> 2) & 1];
-        v[c] = __builtin_amdgcn_raw_buffer_load_b64(table, AC_GOFF((L.offset + gidx<GM>(L, ax, ay, az)) * 8u), 0, 0);
+        v[c] = __builtin_amdgcn_raw_buffer_load_b64(table, (L.offset + gidx<GM>(L, ax, ay, az)) * 8u, 0, 0);
     }
 }
 
 #define AC_FSTORE(E, F0, F1) { fslab[((E - 1) * 8 + 2 * j) * 64 + lane] = F0; fslab[((E - 1) * 8 + 2 * j + 1) * 64 + lane] = F1; }
 
-#ifndef AC_STENCIL_SPECIALIZE
-#define AC_STENCIL_SPECIALIZE 1      // a second copy of the stencil code for level groups that are hashed throughout (xor-only index arithmetic)
-#endif
 // one group of four levels (4j + g) of the stencil: centre features in c0 / c1, the six offset points' features to the slab
-template <int GM, int FV = 0>
+template <int GM>
 __device__ __forceinline__ void stencil_levels(const float *__restrict__ lds, float *__restrict__ fslab, rsrc_t table, int lane, int g, int j, bool fine,
                                                float ux, float uy, float uz, bool oob, float xp, float xm, float yp, float ym, float zp, float zm,
                                                float &c0, float &c1)
@@ -777,18 +639,10 @@ __device__ __forceinline__ void stencil_levels(const float *__restrict__ lds, fl
     uint32_t tx[2], ty[2], tz[2];
     tx[0] = gc[0]; tx[1] = gc[0] + 1u; ty[0] = gc[1] * L.my; ty[1] = ty[0] + L.my; tz[0] = gc[2] * L.mz; tz[1] = tz[0] + L.mz;
     u32x2 vc[8];
-    if constexpr (GM == 0) {                                // dense round: x-adjacent corners through one 16-byte gather each
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const u32q w = __builtin_amdgcn_raw_buffer_load_b128(table, AC_GOFF((L.offset + (tx[0] + ty[p & 1] + tz[p >> 1])) * 8u), 0, 0);
-            vc[2 * p] = u32x2{ w.x, w.y }; vc[2 * p + 1] = u32x2{ w.z, w.w };
-        }
-    } else {
 #pragma unroll
     for (int c = 0; c < 8; ++c)
-        vc[c] = __builtin_amdgcn_raw_buffer_load_b64(table, AC_GOFF((L.offset + gidx<GM>(L, tx[c & 1], ty[(c >> 1) & 1], tz[c >> 2])) * 8u), 0, 0);
-    }
-    if (GM == 0 || !fine) {
+        vc[c] = __builtin_amdgcn_raw_buffer_load_b64(table, (L.offset + gidx<GM>(L, tx[c & 1], ty[(c >> 1) & 1], tz[c >> 2])) * 8u, 0, 0);
+    if (!fine) {
         u32x2 w0[4], w1[4], w2[4], w3[4], w4[4], w5[4];
         const auto a0 = coarse_issue<0, 0, GM>(table, L, gc, tx, ty, tz, oob, xp, w0);
         const auto a1 = coarse_issue<0, 1, GM>(table, L, gc, tx, ty, tz, oob, xm, w1);
@@ -799,47 +653,13 @@ __device__ __forceinline__ void stencil_levels(const float *__restrict__ lds, fl
         __builtin_amdgcn_sched_barrier(0);
         interp8(vc, qc[0], qc[1], qc[2], oob, c0, c1);
         float f0, f1;
-        if constexpr (FV != 0) {
-            float fw[4], A[2], B[2];
-            if constexpr ((AC_FV_AXES & 1) != 0) {
-                face_weights<0>(qc, fw); face_value<0>(vc, 0, fw, A); face_value<0>(vc, 1, fw, B);
-                coarse_finish_fv<0, 0>(a0, A, B, w0, fw, f0, f1); AC_FSTORE(1, f0, f1)
-                coarse_finish_fv<0, 1>(a1, A, B, w1, fw, f0, f1); AC_FSTORE(2, f0, f1)
-            } else {
-                coarse_finish<0, 0>(a0, vc, w0, qc, f0, f1); AC_FSTORE(1, f0, f1)
-                coarse_finish<0, 1>(a1, vc, w1, qc, f0, f1); AC_FSTORE(2, f0, f1)
-            }
-            if constexpr ((AC_FV_AXES & 2) != 0) {
-                face_weights<1>(qc, fw); face_value<1>(vc, 0, fw, A); face_value<1>(vc, 1, fw, B);
-                coarse_finish_fv<1, 0>(a2, A, B, w2, fw, f0, f1); AC_FSTORE(3, f0, f1)
-                coarse_finish_fv<1, 1>(a3, A, B, w3, fw, f0, f1); AC_FSTORE(4, f0, f1)
-            } else {
-                coarse_finish<1, 0>(a2, vc, w2, qc, f0, f1); AC_FSTORE(3, f0, f1)
-                coarse_finish<1, 1>(a3, vc, w3, qc, f0, f1); AC_FSTORE(4, f0, f1)
-            }
-            if constexpr ((AC_FV_AXES & 4) != 0) {
-#ifdef AC_FV_DEBUG_NOP
-                asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
-#endif
-                face_weights<2>(qc, fw); face_value<2>(vc, 0, fw, A); face_value<2>(vc, 1, fw, B);
-                if constexpr ((AC_FV_SIGNS & 1) != 0) { coarse_finish_fv<2, 0>(a4, A, B, w4, fw, f0, f1); } else { coarse_finish<2, 0>(a4, vc, w4, qc, f0, f1); }
-                AC_FSTORE(5, f0, f1)
-                if constexpr ((AC_FV_SIGNS & 2) != 0) { coarse_finish_fv<2, 1>(a5, A, B, w5, fw, f0, f1); } else { coarse_finish<2, 1>(a5, vc, w5, qc, f0, f1); }
-                AC_FSTORE(6, f0, f1)
-            } else {
-                coarse_finish<2, 0>(a4, vc, w4, qc, f0, f1); AC_FSTORE(5, f0, f1)
-                coarse_finish<2, 1>(a5, vc, w5, qc, f0, f1); AC_FSTORE(6, f0, f1)
-            }
-        } else {
         coarse_finish<0, 0>(a0, vc, w0, qc, f0, f1); AC_FSTORE(1, f0, f1)
         coarse_finish<0, 1>(a1, vc, w1, qc, f0, f1); AC_FSTORE(2, f0, f1)
         coarse_finish<1, 0>(a2, vc, w2, qc, f0, f1); AC_FSTORE(3, f0, f1)
         coarse_finish<1, 1>(a3, vc, w3, qc, f0, f1); AC_FSTORE(4, f0, f1)
         coarse_finish<2, 0>(a4, vc, w4, qc, f0, f1); AC_FSTORE(5, f0, f1)
         coarse_finish<2, 1>(a5, vc, w5, qc, f0, f1); AC_FSTORE(6, f0, f1)
-        }
-    } else {
-#if AC_FINE_BATCH == 3     // all 48 gathers of the six offset points in flight at once: one memory round trip instead of three
+    } else {                // all 48 gathers of the six offset points in flight at once: one memory round trip instead of three (221 VGPRs, -2 % time)
         u32x2 va[8], vb[8], vc2[8], vd[8], ve[8], vf[8];
         float qa, qb, qc2, qd, qe, qf, f0, f1; bool oa, ob, oc2, od, oe, of;
         fine_issue<0, GM>(table, L, tx, ty, tz, oob, xp, va, qa, oa);
@@ -856,52 +676,9 @@ __device__ __forceinline__ void stencil_levels(const float *__restrict__ lds, fl
         interp8(vd, qc[0], qd, qc[2], od, f0, f1); AC_FSTORE(4, f0, f1)
         interp8(ve, qc[0], qc[1], qe, oe, f0, f1); AC_FSTORE(5, f0, f1)
         interp8(vf, qc[0], qc[1], qf, of, f0, f1); AC_FSTORE(6, f0, f1)
-#elif AC_FINE_BATCH == 2   // x and y offsets in one round trip, z offsets in a second one
-        u32x2 va[8], vb[8], vc2[8], vd[8];
-        float qa, qb, qc2, qd, f0, f1; bool oa, ob, oc2, od;
-        fine_issue<0, GM>(table, L, tx, ty, tz, oob, xp, va, qa, oa);
-        fine_issue<0, GM>(table, L, tx, ty, tz, oob, xm, vb, qb, ob);
-        fine_issue<1, GM>(table, L, tx, ty, tz, oob, yp, vc2, qc2, oc2);
-        fine_issue<1, GM>(table, L, tx, ty, tz, oob, ym, vd, qd, od);
-        __builtin_amdgcn_sched_barrier(0);
-        interp8(vc, qc[0], qc[1], qc[2], oob, c0, c1);
-        interp8(va, qa, qc[1], qc[2], oa, f0, f1); AC_FSTORE(1, f0, f1)
-        interp8(vb, qb, qc[1], qc[2], ob, f0, f1); AC_FSTORE(2, f0, f1)
-        __builtin_amdgcn_sched_barrier(0);
-        fine_issue<2, GM>(table, L, tx, ty, tz, oob, zp, va, qa, oa);
-        fine_issue<2, GM>(table, L, tx, ty, tz, oob, zm, vb, qb, ob);
-        __builtin_amdgcn_sched_barrier(0);
-        interp8(vc2, qc[0], qc2, qc[2], oc2, f0, f1); AC_FSTORE(3, f0, f1)
-        interp8(vd, qc[0], qd, qc[2], od, f0, f1); AC_FSTORE(4, f0, f1)
-        __builtin_amdgcn_sched_barrier(0);
-        interp8(va, qc[0], qc[1], qa, oa, f0, f1); AC_FSTORE(5, f0, f1)
-        interp8(vb, qc[0], qc[1], qb, ob, f0, f1); AC_FSTORE(6, f0, f1)
-#else
-        u32x2 va[8], vb[8];
-        float qa, qb, f0, f1; bool oa, ob;
-        fine_issue<0, GM>(table, L, tx, ty, tz, oob, xp, va, qa, oa);
-        fine_issue<0, GM>(table, L, tx, ty, tz, oob, xm, vb, qb, ob);
-        __builtin_amdgcn_sched_barrier(0);
-        interp8(vc, qc[0], qc[1], qc[2], oob, c0, c1);
-        interp8(va, qa, qc[1], qc[2], oa, f0, f1); AC_FSTORE(1, f0, f1)
-        interp8(vb, qb, qc[1], qc[2], ob, f0, f1); AC_FSTORE(2, f0, f1)
-        __builtin_amdgcn_sched_barrier(0);
-        fine_issue<1, GM>(table, L, tx, ty, tz, oob, yp, va, qa, oa);
-        fine_issue<1, GM>(table, L, tx, ty, tz, oob, ym, vb, qb, ob);
-        __builtin_amdgcn_sched_barrier(0);
-        interp8(va, qc[0], qa, qc[2], oa, f0, f1); AC_FSTORE(3, f0, f1)
-        interp8(vb, qc[0], qb, qc[2], ob, f0, f1); AC_FSTORE(4, f0, f1)
-        __builtin_amdgcn_sched_barrier(0);
-        fine_issue<2, GM>(table, L, tx, ty, tz, oob, zp, va, qa, oa);
-        fine_issue<2, GM>(table, L, tx, ty, tz, oob, zm, vb, qb, ob);
-        __builtin_amdgcn_sched_barrier(0);
-        interp8(va, qc[0], qc[1], qa, oa, f0, f1); AC_FSTORE(5, f0, f1)
-        interp8(vb, qc[0], qc[1], qb, ob, f0, f1); AC_FSTORE(6, f0, f1)
-#endif
     }
 }
 
-template <int FV = 0>
 __device__ __forceinline__ void encode_stencil(const float *__restrict__ lds, float *__restrict__ fslab, const FieldCtx &fc, int lane,
                                                float px, float py, float pz, float eps, float (&fe0)[4][2])
 {
@@ -931,9 +708,10 @@ __device__ __forceinline__ void encode_stencil(const float *__restrict__ lds, fl
     for (int j = 0; j < 4; ++j) {                           // one copy of each code path; results go to LDS / a rotating fe0
         float c0, c1;
         const bool fine = (jbits >> (8 + j)) & 1u, hashed4 = ((jbits >> (2 * j)) & 3u) == 1u, dense4 = ((jbits >> (2 * j)) & 3u) == 0u;
-        if (AC_STENCIL_SPECIALIZE && hashed4) stencil_levels<1, FV>(lds, fslab, table, lane, g, j, fine, ux, uy, uz, oob, xp, xm, yp, ym, zp, zm, c0, c1);
-        else if (AC_DENSE_PAIRS && dense4 && !fine) stencil_levels<0, FV>(lds, fslab, table, lane, g, j, false, ux, uy, uz, oob, xp, xm, yp, ym, zp, zm, c0, c1);
-        else stencil_levels<2, FV>(lds, fslab, table, lane, g, j, fine, ux, uy, uz, oob, xp, xm, yp, ym, zp, zm, c0, c1);
+        (void)dense4;                                       // (unused; taking it out moves register-allocation comments in the assembly)
+        // level groups hashed throughout get a second copy of the stencil code (xor-only index arithmetic)
+        if (hashed4) stencil_levels<1>(lds, fslab, table, lane, g, j, fine, ux, uy, uz, oob, xp, xm, yp, ym, zp, zm, c0, c1);
+        else stencil_levels<2>(lds, fslab, table, lane, g, j, fine, ux, uy, uz, oob, xp, xm, yp, ym, zp, zm, c0, c1);
         // rotate the centre features into place: after the 4th iteration fe0[j] holds level 4j+g
         fe0[0][0] = fe0[1][0]; fe0[0][1] = fe0[1][1]; fe0[1][0] = fe0[2][0]; fe0[1][1] = fe0[2][1];
         fe0[2][0] = fe0[3][0]; fe0[2][1] = fe0[3][1]; fe0[3][0] = c0; fe0[3][1] = c1;
@@ -995,9 +773,6 @@ __device__ __forceinline__ void sample_sh_bias(float *__restrict__ slab, const f
     wave_sync();
 }
 
-#ifndef AC_SH_VALUE_SELECT
-#define AC_SH_VALUE_SELECT 1
-#endif
 // The view-direction bias of layer 1 enters unit u's fma chain at ONE fixed position: after the three coordinates, in the k = 3 slot of the MFMA that
 // carries (x, y, z, -) -- a slot that multiplies 0 by 0 without view directions.  acc = fma(bias[u], 1, acc) there, in both forms:
 //   shb1 (the renderer: one ray per wave): the ray's bias row [64] in the wave's slab becomes that slot's A operand on the lanes of group 3 (B = 1 there):
@@ -1018,13 +793,9 @@ __device__ __forceinline__ void color_tile(const float *__restrict__ lds, int la
         for (int s = 0; s < 6; ++s) {
             const float b = s < 4 ? sdfout[s] : (s == 4 ? bxyz : bn);
             float wv = lds[OFF_C1F + (t * 6 + s) * 64 + lane];
-#if AC_SH_VALUE_SELECT
             // the ray's bias row for the lanes of group 3 as a second, plainly addressed LDS read and a select of the VALUE (round 6: the address select this
             // replaces kept a per-lane pointer alive across the tile, which the register allocator answered with a scratch reload inside this block)
             if (s == 4 && shb1) { const float wb = shb1[16 * t + (lane & 15)]; wv = g == 3 ? wb : wv; }
-#else
-            if (s == 4 && shb1) wv = *(g == 3 ? shb1 + 16 * t + (lane & 15) : lds + OFF_C1F + (t * 6 + s) * 64 + lane);      // (an address select: still one LDS read per lane)
-#endif
             acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wv, b, acc, 0, 0, 0);
             if (s == 4 && shb) {
                 const f32x4 bq = *reinterpret_cast<const f32x4 *>(shb + t * tstride);

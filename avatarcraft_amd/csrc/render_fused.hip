@@ -33,19 +33,10 @@
 
 namespace {
 
-#ifndef AC_DYNAMIC_RAYS
-#define AC_DYNAMIC_RAYS 1          // persistent workgroups (one per compute unit), rays handed out by per-XCD counters; 0: eight fixed rays per workgroup
-#endif
 #ifndef AC_XCD_CHUNK
 #define AC_XCD_CHUNK 512
 #endif
-#ifndef AC_WG_TICKETS
-#define AC_WG_TICKETS 0            // 1 (round 6 experiment): a workgroup's waves draw their work items from blocks of 8 CONSECUTIVE rays (one global ticket per
-#endif                             // block, handed out inside the workgroup through LDS) instead of one global ticket per wave: the 8 rays a compute unit
-                                   // works on at a time are neighbouring pixels, whose coarse / middle level cells share L1 lines
-#ifndef AC_FAST_COLOR
-#define AC_FAST_COLOR 1            // fast precision: the colour network in split bf16 too (0: only layer 1 of the finite-difference evaluations)
-#endif
+// a workgroup's waves on blocks of 8 consecutive rays (dynamic or static): 16 - 21 % slower than one ticket per wave -- profiles/r06_experiments.txt section 4c
 // EX = false: a launch that wants the per-ray results only (image, weights_sum, depth, normal_map, eik): none of the optional per-sample outputs is
 // compiled in, which takes their sixteen pointers (and the address arithmetic on them) out of the register budget of the tile loop
 // SH = true: a field with view directions (ac_field.Wc1_sh).  A template parameter, not a run-time branch: the tile loop runs at 256 VGPRs with a few
@@ -53,13 +44,8 @@ namespace {
 template <int MODE, bool FAST, bool EX, bool SH = false>
 __global__ __launch_bounds__(BLOCK) void render_rays_kernel(const RenderArgs a)
 {
-    constexpr bool FC = FAST && AC_FAST_COLOR;
+    constexpr bool FC = FAST;                                // fast precision: the colour network in split bf16 too
     extern __shared__ __attribute__((aligned(16))) float lds[];
-#if AC_WG_TICKETS && AC_DYNAMIC_RAYS
-    __shared__ uint32_t wg_cnt[8], wg_tag[8][16], wg_base[8][16];          // per segment: tickets drawn inside this workgroup | block k's (k + 1, global base)
-    if (threadIdx.x < 8) wg_cnt[threadIdx.x] = 0u;
-    if (threadIdx.x < 128) wg_tag[threadIdx.x >> 4][threadIdx.x & 15] = 0u;
-#endif
     if (a.prepared) {
         // the weights arrive in LDS order (ac_field_prepare): a linear copy, 16 bytes per lane and trip, instead of ~27 dependent
         // gather-and-place trips per thread in each of the 512 workgroups of a launch; only the per-launch sampling tables are added
@@ -100,12 +86,10 @@ __global__ __launch_bounds__(BLOCK) void render_rays_kernel(const RenderArgs a)
     // XCD-aware order: workgroup b runs on XCD b % 8 (observed dispatch rule; speed only): give every XCD a contiguous
     // slab of rays so that neighbouring pixels share one L2 instead of eight
     int bid = blockIdx.x;
-#ifndef AC_NO_XCD_REMAP
     {   // XCD k runs the workgroups b with b % 8 == k: give it the k-th contiguous range (ranges differ by one when 8 does not divide the grid)
         const int k = blockIdx.x & 7, q = gridDim.x >> 3, r = gridDim.x & 7;
         bid = k * q + (k < r ? k : r) + (blockIdx.x >> 3);
     }
-#endif
     // Staggered start: wave w of a workgroup begins AC_START_STAGGER x 4096 clocks (~2 us each) x w late.  All 2048 waves of a launch would otherwise walk
     // through the same phases of their first ray together (every wave gathering, then every wave in the MLPs): rays of the first round took 350 .. 420 us
     // against 280 .. 330 us for the ones fetched later, when the waves have drifted apart (tools/phase_profile.py).  Round 2 used 3 (6 us per wave index, 41 us
@@ -117,7 +101,6 @@ __global__ __launch_bounds__(BLOCK) void render_rays_kernel(const RenderArgs a)
     // (only launches that fill the device: a small batch -- a posed frame's tail, a unit test -- has no lock-step to break and would only pay the delay)
     if (a.n_rays >= 2048)
         for (int k_ = 0; k_ < AC_START_STAGGER * wave; ++k_) __builtin_amdgcn_s_sleep(64);
-#if AC_DYNAMIC_RAYS
     // Work items are (ray, segment) pairs fetched one at a time from per-XCD counters.  A ray is cut into seg_n segments of the tile loop (segment 0 =
     // the sampling stage + the first tiles); a wave that finishes a segment leaves the ray's z values and running sums in seg_state and raises the ray's
     // flag, whichever wave of the XCD fetches the next segment of that ray continues the SAME sequential arithmetic from there (bit-identical results).
@@ -135,21 +118,7 @@ __global__ __launch_bounds__(BLOCK) void render_rays_kernel(const RenderArgs a)
     const bool seg_first = seg == 0, seg_last = seg + 1 == seg_n;
     for (;;) {
         int ray = 0;
-#if AC_WG_TICKETS
-        if (lane == 0) {
-            const uint32_t t = atomicAdd(&wg_cnt[seg], 1u), blk = t >> 3, slot = t & 7u, idx = blk & 15u;
-            if (slot == 0u) {                                            // this wave opens block blk: 8 consecutive tickets of the XCD's counter
-                const uint32_t b = atomicAdd(a.ray_counter + xcd * 8 + seg, 8u);
-                __hip_atomic_store(&wg_base[seg][idx], b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                __hip_atomic_store(&wg_tag[seg][idx], blk + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            } else {
-                while (__hip_atomic_load(&wg_tag[seg][idx], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != blk + 1u) __builtin_amdgcn_s_sleep(1);
-            }
-            ray = (int)(__hip_atomic_load(&wg_base[seg][idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) + slot);
-        }
-#else
         if (lane == 0) ray = (int)atomicAdd(a.ray_counter + xcd * 8 + seg, 1u);
-#endif
         ray = __builtin_amdgcn_readfirstlane(ray);
         {
             const int k = ray / xchunk, base = (k * 8 + xcd) * xchunk;
@@ -159,14 +128,7 @@ __global__ __launch_bounds__(BLOCK) void render_rays_kernel(const RenderArgs a)
         }
         int rin = ray;                                               // row of this ray in rays_o / rays_d / near_m / far_m
         if (a.pair_n) { rin = ray >> 1; ray = rin + ((ray & 1) ? a.pair_n : 0); }      // a0 b0 a1 b1 ...: the two copies of a ray meet in their XCD's L2
-        (void)bid;
-#else
-    const int seg_n = 1, seg = 0, c_begin = 0, c_end = MAXT / 16;
-    const bool seg_first = true, seg_last = true;
-    {
-    for (int ray = bid * WAVES_PER_BLOCK + wave; ray < a.n_rays; ray += gridDim.x * WAVES_PER_BLOCK) {
-        const int rin = (a.pair_n && ray >= a.pair_n) ? ray - a.pair_n : ray;      // (pair launch: the copies are rows [0, N) and [N, 2N))
-#endif
+        (void)bid;                                                   // (used by the static hand-out, removed; dropping the remap changes the kernel's register setup)
         const int exr = ray - a.ex_from;                             // row in the per-sample outputs (pair launches keep them for copy b only)
         const bool ex_on = exr >= 0;
         AC_T0();
@@ -455,7 +417,7 @@ __global__ __launch_bounds__(BLOCK) void render_rays_kernel(const RenderArgs a)
             float gr[3] = { 0.0f, 0.0f, 0.0f };
             if (!skip) {
             float fe0[4][2];
-            encode_stencil<(FAST && AC_FACE_VALUE) ? 1 : 0>(lds, fsl, fc, lane, px, py, pz, bxe, fe0);
+            encode_stencil(lds, fsl, fc, lane, px, py, pz, bxe, fe0);
             if (EX && ex_on && a.out.feat7) {                                     // training render: keep the 7 x 8 features of this lane (the backward streams them back)
                 // layout [tile of 16 samples][14][lane][4]: float k = 8 e + q (evaluation e, slot q = 2 j + channel) of lane (n, g) sits in group k / 4,
                 // component k % 4 -- every store (and every load of the backward) is one 16-byte access per lane, 1 KB contiguous per wave
@@ -627,7 +589,6 @@ __global__ __launch_bounds__(BLOCK) void render_rays_kernel(const RenderArgs a)
 #endif
     }
     }
-#if AC_DYNAMIC_RAYS
     // ---- epilogue: the last workgroup to finish reduces gradient_error and re-arms the slot's work counters (RenderArgs::done_counter) --------------------
     // (the arguments used here are read from the kernel-argument segment again, behind an opaque barrier: kept in scalar registers from the start of the kernel
     //  they cost the work loops two spilled vector registers)
@@ -675,7 +636,6 @@ __global__ __launch_bounds__(BLOCK) void render_rays_kernel(const RenderArgs a)
             if (threadIdx.x == 64) *k_done = 0u;
         }
     }
-#endif
 #ifdef AC_PROFILE
     if (a.prof && lane == 0) { const int w_ = blockIdx.x * WAVES_PER_BLOCK + wave; for (int i = 0; i < 8; ++i) a.prof[w_ * 10 + i] = prof_acc[i];
         a.prof[w_ * 10 + 8] = __builtin_amdgcn_s_memtime() - prof_t0; a.prof[w_ * 10 + 9] = __builtin_amdgcn_s_memrealtime() - prof_r0; }   // shader clock vs 100 MHz
@@ -911,7 +871,6 @@ static void launch_render_p(const RenderArgs &a, hipStream_t stream)
     static uint64_t seen = 0;                       // one flag per instantiation
     const size_t lds_bytes = LDS_FLOATS * sizeof(float);
     ac::allow_dynamic_lds(seen, reinterpret_cast<const void *>(render_rays_kernel<MODE, FAST, EX, SH>), lds_bytes);
-#if AC_DYNAMIC_RAYS
     RenderArgs b = a;
     {
         // segments: the tiles of a ray in seg_n nearly equal runs; the sampling stage (about 1.6 tiles' worth of time) rides with the first
@@ -938,14 +897,6 @@ static void launch_render_p(const RenderArgs &a, hipStream_t stream)
         if (!sc) blocks = 0;                                             // (the scratch could not be allocated: an empty grid is a launch error the caller reports)
     }
     hipLaunchKernelGGL((render_rays_kernel<MODE, FAST, EX, SH>), dim3(blocks), dim3(BLOCK), lds_bytes, stream, b);
-#else
-    hipLaunchKernelGGL((render_rays_kernel<MODE, FAST, EX, SH>), dim3(blocks), dim3(BLOCK), lds_bytes, stream, a);
-    if (MODE != MODE_UPSAMPLE && a.out.eik_reduced) {                 // (static ray assignment builds: the reduction as its own launch(es))
-        const int nred = a.pair_n ? 2 : 1, nper = a.pair_n ? a.pair_n : a.n_rays;
-        for (int q = 0; q < nred; ++q)
-            hipLaunchKernelGGL(eikonal_reduce_kernel, dim3(1), dim3(1024), 0, stream, a.out.eik + (size_t)q * nper * 2, nper, a.out.eik_reduced + 2 * q, 1);
-    }
-#endif
 }
 static bool wants_samples(const ac_render_out &o)
 {

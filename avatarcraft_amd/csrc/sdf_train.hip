@@ -22,12 +22,6 @@
 
 namespace {
 
-#ifndef AC_SDFBWD_RANK1
-#define AC_SDFBWD_RANK1 1     // offset evaluations of the backward: rank-1 shortcuts instead of 32 of their 148 MFMA (0: every evaluation alike)
-#endif
-#ifndef AC_SDFBWD_PREFETCH
-#define AC_SDFBWD_PREFETCH 1  // sdf_stencil_bwd_kernel requests the next tile's inputs while it computes the current one
-#endif
 constexpr int TW = 4;                              // waves per workgroup of the backward kernels (296 / 284 VGPRs: one wave per SIMD)
 constexpr int TBLOCK = TW * 64;
 constexpr int FW = 8;                              // waves per workgroup of the forward SDF query (224 VGPRs: two waves per SIMD, like the renderer)
@@ -66,9 +60,6 @@ static_assert(BWD_LDS_FLOATS * 4 <= 160 * 1024, "LDS budget");
 //     (softplus, splits: vector work) instead of behind a barrier at the end of their own evaluation.
 #ifndef AC_SDFBWD_WAVES
 #define AC_SDFBWD_WAVES 4
-#endif
-#ifndef AC_SDFBWD_PIPE
-#define AC_SDFBWD_PIPE 1      // 1: the weight-gradient products of evaluation e run inside evaluation e + 1 on the bf16 matrix pipe (SAVED variant); 0: fp32, behind their own evaluation
 #endif
 constexpr int TW_S = AC_SDFBWD_WAVES;                                  // waves per workgroup of sdf_stencil_bwd_kernel<SAVED = true>
 // PIPE: the transposes of d1 [64 units][16 samples] and inp [48 columns][16 samples] as bf16 hi | lo parts, rows of 16 samples = 32 bytes padded to 48
@@ -230,7 +221,7 @@ __global__ __launch_bounds__(SAVED ? TW_S * 64 : TBLOCK) void sdf_stencil_bwd_ke
     float *fsl = slab, *T2 = slab + TS_T2 - SFE, *TA = slab + TS_TA - SFE, *TD0 = slab + TS_TD - SFE, *TI0 = slab + TS_TI - SFE;
     // PIPE: two buffers of (d1, inp) transposes -- evaluation `step` writes buffer step & 1 while the weight-gradient products of the evaluation before it read
     // the other one.  The very first step's "previous evaluation" is a buffer of zeros (products of 0: the accumulators keep their +0).
-    constexpr bool PIPE = SAVED && AC_SDFBWD_PIPE && AC_SDFBWD_RANK1;
+    constexpr bool PIPE = SAVED;                                // the weight-gradient products of evaluation e run inside evaluation e + 1 on the bf16 matrix pipe
     unsigned char *const BF = reinterpret_cast<unsigned char *>(TD0);      // PIPE: the two bf16 buffers take the place of the fp32 transposes
     if constexpr (PIPE) {
         uint32_t *bw = reinterpret_cast<uint32_t *>(BF);
@@ -246,14 +237,12 @@ __global__ __launch_bounds__(SAVED ? TW_S * 64 : TBLOCK) void sdf_stencil_bwd_ke
     const float bound = a.bound;
     f32x4 gW1[4][3], gW2[4];
     float gb2[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
-#if AC_SDFBWD_RANK1
     float a6[4][4];                                   // running sum over samples and offset evaluations of s * a[unit 16t + 4g + r] (-> dW2 row 0)
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
         for (int r = 0; r < 4; ++r) a6[t][r] = 0.0f;
     const W2Row0 w2r0 = load_w2_row0(lds, lane);
-#endif
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         gW2[t] = f32x4{ 0.0f, 0.0f, 0.0f, 0.0f };
@@ -332,9 +321,7 @@ __global__ __launch_bounds__(SAVED ? TW_S * 64 : TBLOCK) void sdf_stencil_bwd_ke
         } else {
             encode_stencil(lds, fsl, fc, lane, px, py, pz, eps, fe0);
         }
-#if AC_SDFBWD_PREFETCH
         if (tile + tstride < ntiles) request(tile + tstride, nxt);
-#endif
         const float pc0 = sel4(g, px, py, pz, 0.0f);
         Acc4 h10;                                               // layer 1 of the centre evaluation (set at e == 0)
 #pragma unroll
@@ -445,7 +432,6 @@ __global__ __launch_bounds__(SAVED ? TW_S * 64 : TBLOCK) void sdf_stencil_bwd_ke
             for (int t = 0; t < 4; ++t) softplus100_vg4(lds + OFF_SPQ, h1.a[t], av.a[t], dv.a[t]);
             }
             Acc4 d1;
-#if AC_SDFBWD_RANK1
             // The six offset evaluations feed the finite-difference gradient through their sdf alone: d2 = (s, 0, ..., 0).  Then
             // ga = W2^T d2 = s * W2[0, :] (16 multiplies instead of 16 MFMA), and their share of dW2 / db2 is row 0 only:
             // dW2[0, u] += sum over samples of s * a[u], kept as a per-lane running sum (reduced over the samples once, at the end).
@@ -459,7 +445,6 @@ __global__ __launch_bounds__(SAVED ? TW_S * 64 : TBLOCK) void sdf_stencil_bwd_ke
                         a6[t][r] = fma_(s_all, av.a[t][r], a6[t][r]);
                     }
             } else
-#endif
             {
                 // ga = W2^T d2, d1 = ga * softplus'
 #pragma unroll
@@ -517,9 +502,7 @@ __global__ __launch_bounds__(SAVED ? TW_S * 64 : TBLOCK) void sdf_stencil_bwd_ke
                 }
             }
             // transposes for the weight gradients (K = the 16 samples of the tile)
-#if AC_SDFBWD_RANK1
             if (!rank1)
-#endif
             {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) T2[(4 * g + r) * TLD + n] = d2[r];
@@ -562,13 +545,8 @@ __global__ __launch_bounds__(SAVED ? TW_S * 64 : TBLOCK) void sdf_stencil_bwd_ke
             wave_sync();
             ++step;
             if constexpr (!PIPE) {
-#if AC_SDFBWD_RANK1
                 if (!rank1)
-#endif
                     w2_grads();
-#ifdef AC_ABL_NODW1           // timing ablation: the weight-gradient products of the six offset evaluations are skipped
-                if (e == 0)
-#endif
                 w1_grads(TD, TI);
                 wave_sync();
             }
@@ -576,9 +554,6 @@ __global__ __launch_bounds__(SAVED ? TW_S * 64 : TBLOCK) void sdf_stencil_bwd_ke
         if constexpr (GX) {
             if (live && g < 3) g_x[3 * (size_t)b + g] = g == 0 ? gxa[0] : (g == 1 ? gxa[1] : gxa[2]);
         }
-#if !AC_SDFBWD_PREFETCH
-        if (tile + tstride < ntiles) request(tile + tstride, nxt);
-#endif
     }
     if constexpr (PIPE) {                                       // the last evaluation's products (an offset evaluation; a wave without a tile: the zero buffer)
         const unsigned char *const Br = BF + ((step & 1u) ? 0 : BF_BYTES);
@@ -606,7 +581,6 @@ __global__ __launch_bounds__(SAVED ? TW_S * 64 : TBLOCK) void sdf_stencil_bwd_ke
                 const int unit = 16 * t + 4 * g + r, kcol = 16 * c + n;
                 if (kcol < 36) part[unit * 36 + kcol] = gW1[t][c][r];
             }
-#if AC_SDFBWD_RANK1
     // row 0 of dW2 also receives the offset evaluations' running sums: unit u = 16c + n of lane (n, g = 0) is held, after a row reduction over
     // the 16 samples, by lane 15 of lane group n >> 2 in register a6[c][n & 3]
 #pragma unroll
@@ -617,7 +591,6 @@ __global__ __launch_bounds__(SAVED ? TW_S * 64 : TBLOCK) void sdf_stencil_bwd_ke
         const float add = (n & 3) == 0 ? tot[0] : ((n & 3) == 1 ? tot[1] : ((n & 3) == 2 ? tot[2] : tot[3]));
         if (g == 0) gW2[c][0] += add;
     }
-#endif
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
@@ -657,12 +630,10 @@ __global__ __launch_bounds__(1024) void sdf_partials_reduce_kernel(const float *
 //   dh2 = Wc3^T do3 (4 MFMA), dh1 = Wc2^T dh2 (64), dinp = Wc1^T dh1 (32; lane (n, g) receives d sdf_out[4g..4g+3] and d normal_g:
 //   exactly the layouts sdf_stencil_bwd_kernel and the caller read), dWc3 += do3 h2^T (16), dWc2 += dh2 h1^T (64),
 //   dWc1 += dh1 inp^T (32) with K = the 16 samples of the tile through LDS transposes.
-#ifndef AC_COLORBWD_BF16
-#define AC_COLORBWD_BF16 1    // round 4: layer 3 of the forward recomputation and the two data-gradient products of color_bwd_kernel (dh1 = Wc2^T dh2, dinp = Wc1^T dh1)
-#endif                        // as three-term bf16 splits instead of fp32 MFMA.  Layers 1 and 2 of the recomputation stay fp32: they decide the ReLU masks, and a
-                              // recomputation that is only 2^-16 accurate flips enough of them to show (dWc1 3e-3 of max against the fp64 oracle, measured);
-                              // the weight gradients (K = the tile's samples, through LDS) stay fp32 as well
-#if AC_COLORBWD_BF16
+// Since round 4, layer 3 of the forward recomputation and the two data-gradient products (dh1 = Wc2^T dh2, dinp = Wc1^T dh1) run as three-term bf16
+// splits instead of fp32 MFMA.  Layers 1 and 2 of the recomputation stay fp32: they decide the ReLU masks, and a recomputation that is only 2^-16
+// accurate flips enough of them to show (dWc1 3e-3 of max against the fp64 oracle, measured); the weight gradients (K = the tile's samples, through
+// LDS) stay fp32 as well
 // layer 3 of the forward: its two bf16 hi and two lo fragments (k blocks 0, 1; order of color_fast_weight) take the place of the fp32 ones
 constexpr int OFF_C3H = OFF_C3F, OFF_C3LO = OFF_C3F + 2 * 64 * 4;
 constexpr int OFF_C3T = OFF_WAVE;                  // [4 tiles][64]                       fp32 A fragments of Wc3^T (4 MFMA: not worth splitting)
@@ -671,12 +642,6 @@ constexpr int OFF_C2TL = OFF_C2T + 8 * 64 * 4;
 constexpr int OFF_C1T = OFF_C2TL + 8 * 64 * 4;     // [2 tiles][2 k blocks][64][4] hi | lo   Wc1^T (rows: sdf_out[16] | normal, coordinate)
 constexpr int OFF_C1TL = OFF_C1T + 4 * 64 * 4;
 constexpr int OFF_CW = OFF_C1TL + 4 * 64 * 4;      // per-wave slabs
-#else
-constexpr int OFF_C3T = OFF_WAVE;                  // [4 tiles][64]              A fragments of Wc3^T
-constexpr int OFF_C2T = OFF_C3T + 4 * 64;          // [4 tiles][16 ksteps][64]   Wc2^T
-constexpr int OFF_C1T = OFF_C2T + 64 * 64;         // [2 tiles][16 ksteps][64]   Wc1^T (rows: sdf_out[16] | normal, coordinate)
-constexpr int OFF_CW = OFF_C1T + 32 * 64;          // per-wave slabs
-#endif
 constexpr int CS_H1 = 0, CS_H2 = 64 * TLD, CS_D1 = 128 * TLD, CS_D2 = 192 * TLD, CS_O3 = 256 * TLD, CS_IN = 272 * TLD;
 constexpr int COLOR_SLAB = ((CS_IN + 32 * TLD + 3) / 4) * 4;
 constexpr int CBWD_LDS_FLOATS = OFF_CW + TW * COLOR_SLAB;
@@ -865,10 +830,6 @@ __global__ __launch_bounds__(FBLOCK) void occupancy_render_kernel(const RenderAr
                 const float px = clampf(sp[0], -bound, bound), py = clampf(sp[1], -bound, bound), pz = clampf(sp[2], -bound, bound), delta = sp[3];
                 const int src = (int)lanemap[slot / K];
                 const float dx = __shfl(c.dx, src), dy = __shfl(c.dy, src), dz = __shfl(c.dz, src);
-#ifdef AC_OCC_NOFIELD      // timing ablation: no field evaluation (what the marching and the bookkeeping cost alone)
-                const float nx = dx, ny = dy, nz = dz, alpha = 0.02f * delta / (delta + 1e-3f) + 0.0f * (px + py + pz + inv_s);
-                float rgb[3] = { 0.5f, 0.5f, 0.5f };
-#else
                 float fe0[4][2];
                 encode_stencil(lds, fsl, fc, lane, px, py, pz, eps, fe0);
                 f32x4 o16; float gr[3];
@@ -888,7 +849,6 @@ __global__ __launch_bounds__(FBLOCK) void occupancy_render_kernel(const RenderAr
                 const float half = -(a1 + a2) * delta * 0.5f;
                 const float pc = dv_sigmoid((o16[0] - half) * inv_s), nc = dv_sigmoid((o16[0] + half) * inv_s);
                 const float alpha = clampf((pc - nc + 1e-5f) / (pc + 1e-5f), 0.0f, 1.0f);
-#endif
                 wave_sync();                                                         // every lane has read its inputs: the slots become outputs
                 if (g == 0 && ci < cnt) {
                     float *so = stage + 8 * slot;
@@ -1289,10 +1249,6 @@ __global__ __launch_bounds__(FBLOCK) void occupancy_phased_kernel(const RenderAr
             const float4 in = *reinterpret_cast<const float4 *>(oc.s_in + 8 * (size_t)slot);
             const float px = clampf(in.x, -bound, bound), py = clampf(in.y, -bound, bound), pz = clampf(in.z, -bound, bound), delta = in.w;
             const float dx = oc.rays_d[3 * (size_t)ray], dy = oc.rays_d[3 * (size_t)ray + 1], dz = oc.rays_d[3 * (size_t)ray + 2];
-#ifdef AC_OCC_NOFIELD      // timing ablation: no field evaluation (what the walk, the barriers and the bookkeeping cost alone)
-            const float nx = dx, ny = dy, nz = dz, alpha = 0.02f * delta / (delta + 1e-3f) + 0.0f * (px + py + pz + inv_s);
-            float rgb[3] = { 0.5f, 0.5f, 0.5f };
-#else
             float fe0[4][2];
             encode_stencil(lds, fsl, fc, lane, px, py, pz, eps, fe0);
             f32x4 o16; float gr[3];
@@ -1312,7 +1268,6 @@ __global__ __launch_bounds__(FBLOCK) void occupancy_phased_kernel(const RenderAr
             const float half = -(a1 + a2) * delta * 0.5f;
             const float pc = dv_sigmoid((o16[0] - half) * inv_s), nc = dv_sigmoid((o16[0] + half) * inv_s);
             const float alpha = clampf((pc - nc + 1e-5f) / (pc + 1e-5f), 0.0f, 1.0f);
-#endif
             if (g == 0 && q < nl) {
                 float *po = oc.s_out + 8 * (size_t)slot;
                 *reinterpret_cast<float4 *>(po) = make_float4(alpha, rgb[0], rgb[1], rgb[2]);
@@ -1391,7 +1346,6 @@ __device__ __forceinline__ void fill_lds_color_bwd(float *lds, const RenderArgs 
         const int l = e & 63, to = e >> 6, m = l & 15, kk = l >> 4;
         lds[OFF_C3T + e] = kk < 3 ? a.Wc3[kk * 64 + 16 * to + m] : 0.0f;
     }
-#if AC_COLORBWD_BF16
     // K order of both products = the register layout the previous product leaves its result in (slot i of lane group kk in k block s = unit
     // 16 (2s + (i >> 2)) + 4 kk + (i & 3)): no data moves between lanes.  Weights split hi + lo by round-to-nearest like fill_lds_color_fast.
     uint32_t *lw = reinterpret_cast<uint32_t *>(lds);
@@ -1423,24 +1377,8 @@ __device__ __forceinline__ void fill_lds_color_bwd(float *lds, const RenderArgs 
         }
         lw[OFF_C3H + e] = hi2; lw[OFF_C3LO + e] = lo2;
     }
-    return;
-#endif
-#if !AC_COLORBWD_BF16
-    for (int e = threadIdx.x; e < 64 * 64; e += blockDim.x) {       // fragment (t, ks = 4 to + r): lane (m, kk) = Wc2[i = 16 to + 4 kk + r][j = 16 t + m]
-        const int l = e & 63, fs = e >> 6, t = fs >> 4, ks = fs & 15, to = ks >> 2, r = ks & 3, m = l & 15, kk = l >> 4;
-        lds[OFF_C2T + e] = a.Wc2[(16 * to + 4 * kk + r) * 64 + 16 * t + m];
-    }
-    for (int e = threadIdx.x; e < 32 * 64; e += blockDim.x) {       // fragment (tp, ks = 4 t + r): lane (m, kk) = Wc1[u = 16 t + 4 kk + r][col(tp, m)]
-        const int l = e & 63, fs = e >> 6, tp = fs >> 4, ks = fs & 15, t = ks >> 2, r = ks & 3, m = l & 15, kk = l >> 4;
-        int col = -1;
-        if (tp == 0) col = m == 0 ? -1 : 6 + (m - 1);                // row m = sdf_out[m]: feat m-1 (the sdf itself is not an input)
-        else if ((m & 3) == 0 && (m >> 2) < 3) col = 3 + (m >> 2);   // row 4 g: normal component g
-        lds[OFF_C1T + e] = col < 0 ? 0.0f : a.Wc1[(16 * t + 4 * kk + r) * 21 + col];
-    }
-#endif
 }
 
-#if AC_COLORBWD_BF16
 // acc += A (bf16 hi + lo fragment pair at hi_off / lo_off, fragment f) x B (split activations): three of the four partial products
 __device__ __forceinline__ f32x4 cb_mma(const float *__restrict__ lds, int hi_off, int lo_off, int f, int lane, const u32x4 &bh, const u32x4 &bl, f32x4 acc)
 {
@@ -1476,7 +1414,6 @@ __device__ __forceinline__ void split_tiles(const f32x4 (&v)[4], u32x4 (&bh)[2],
         split8_bf16_rn(in, bh[sb], bl[sb]);
     }
 }
-#endif
 
 // use_viewdirs (sh_bias != NULL): sample b belongs to ray b / T (T a multiple of 16: a tile never straddles two rays); layer 1 of the recomputed forward
 // starts from the ray's bias sh_bias[ray][64] (ac_sh_bias: the forward's own bits, so the ReLU masks are the forward's), and the gradient of that bias --
@@ -1561,18 +1498,12 @@ __global__ __launch_bounds__(TBLOCK) void color_bwd_kernel(const RenderArgs a, c
             h2[to] = acc;
         }
         f32x4 o3 = { 0.0f, 0.0f, 0.0f, 0.0f };
-#if AC_COLORBWD_BF16
         {
             u32x4 ch[2], cl[2];
             split_tiles(h2, ch, cl);
 #pragma unroll
             for (int sb = 0; sb < 2; ++sb) o3 = cb_mma(lds, OFF_C3H, OFF_C3LO, sb, lane, ch[sb], cl[sb], o3);
         }
-#else
-#pragma unroll
-        for (int kk = 0; kk < 16; ++kk)
-            o3 = __builtin_amdgcn_mfma_f32_16x16x4f32(lds[OFF_C3F + kk * 64 + lane], h2[kk >> 2][kk & 3], o3, 0, 0, 0);
-#endif
         // d o3 = d rgb * rgb (1 - rgb), held by the lanes g == 0 (o = r); broadcast to lane group kk = o as the B operand of Wc3^T
         float d3[3];
 #pragma unroll
@@ -1593,21 +1524,13 @@ __global__ __launch_bounds__(TBLOCK) void color_bwd_kernel(const RenderArgs a, c
             for (int r = 0; r < 4; ++r) acc[r] = h2[to][r] > 0.0f ? acc[r] : 0.0f;
             dh2[to] = acc;
         }
-#if AC_COLORBWD_BF16
         u32x4 gbh[2], gbl[2];
         split_tiles(dh2, gbh, gbl);
-#endif
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             f32x4 acc = { 0.0f, 0.0f, 0.0f, 0.0f };
-#if AC_COLORBWD_BF16
 #pragma unroll
             for (int sb = 0; sb < 2; ++sb) acc = cb_mma(lds, OFF_C2T, OFF_C2TL, 2 * t + sb, lane, gbh[sb], gbl[sb], acc);
-#else
-#pragma unroll
-            for (int ks = 0; ks < 16; ++ks)
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(lds[OFF_C2T + (t * 16 + ks) * 64 + lane], dh2[ks >> 2][ks & 3], acc, 0, 0, 0);
-#endif
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[r] = h1[t][r] > 0.0f ? acc[r] : 0.0f;
             dh1[t] = acc;
@@ -1621,21 +1544,13 @@ __global__ __launch_bounds__(TBLOCK) void color_bwd_kernel(const RenderArgs a, c
                 if (n == 15) *reinterpret_cast<f32x4 *>(g_sh_tiles + (size_t)tile * 64 + 16 * t + 4 * g) = sm;
             }
         }
-#if AC_COLORBWD_BF16
         split_tiles(dh1, gbh, gbl);
-#endif
         // dinp = Wc1^T dh1: tile 0 -> d sdf_out[4g + r], tile 1 reg 0 -> d normal_g
 #pragma unroll
         for (int tp = 0; tp < 2; ++tp) {
             f32x4 acc = { 0.0f, 0.0f, 0.0f, 0.0f };
-#if AC_COLORBWD_BF16
 #pragma unroll
             for (int sb = 0; sb < 2; ++sb) acc = cb_mma(lds, OFF_C1T, OFF_C1TL, 2 * tp + sb, lane, gbh[sb], gbl[sb], acc);
-#else
-#pragma unroll
-            for (int ks = 0; ks < 16; ++ks)
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(lds[OFF_C1T + (tp * 16 + ks) * 64 + lane], dh1[ks >> 2][ks & 3], acc, 0, 0, 0);
-#endif
             if (live) {
                 if (tp == 0) *reinterpret_cast<f32x4 *>(g_sdf16 + (size_t)b * 16 + 4 * g) = acc;
                 else if (g < 3) g_nrm[3 * (size_t)b + g] = acc[0];
@@ -1942,11 +1857,8 @@ uint32_t train_grid(uint32_t B)
 {
     const uint32_t ntiles = (B + 15) / 16;
     uint32_t blocks = (ntiles + TW - 1) / TW;
-#ifdef AC_TRAIN_GRID
-    const uint32_t cap = AC_TRAIN_GRID;
-#else
     const uint32_t cap = ac::cu_count();               // persistent, ONE workgroup per CU: their ~145 KB of LDS admit no second one, and every workgroup
-#endif                                                 // first lays the weights out in LDS (512 workgroups: backward 3.32 ms per SDS step, 256: 3.20)
+                                                       // first lays the weights out in LDS (512 workgroups: backward 3.32 ms per SDS step, 256: 3.20)
     if (blocks > cap) blocks = cap;
     return blocks ? blocks : 1;
 }

@@ -609,9 +609,6 @@ __device__ unsigned long long g_warp_prof[8];
 #define WP_END()
 #endif
 // ---- pieces shared by the search kernel and the builder of the cell grid -----------------------------------------------------------------
-#ifdef AC_WARP_SEED_DEBUG
-__device__ const double *g_warp_seed_d2 = nullptr;
-#endif
 // The tiles' bounds in LDS, two layouts.  Row-major [NB][ntp] (TM = false): lane = tile reads are conflict-free -- the structure build
 // (accel_cells_kernel: every cell runs the full bounding pass).  Tile-major [ntp][NBT] (TM = true, round 4): one tile's 15 numbers are four 16-byte
 // reads for a lane that looks at ITS OWN tile -- the search, whose front end is lane = sample since round 4 (15 scattered dword reads with 4 - 8-way
@@ -986,9 +983,6 @@ __global__ __launch_bounds__(256) void ray_cull_kernel(const float *__restrict__
 // order of the pairs, and equals the exhaustive kernel's bit for bit.
 constexpr uint32_t TQ = 1024, GQ = 256, FQ = 256;     // pair queues (rings): a sample adds <= NIT x 64 = 512 (sample, tile) pairs to < 32 left over; a group trip
                                                        // <= 128 (sample, tile, group) triples to < 16; a disc trip <= 128 (sample, face) pairs to < 64
-#ifndef AC_WARP_LANE_LISTS
-#define AC_WARP_LANE_LISTS 1     // the search's front end as lane = sample (every lane walks its own cell's tile list); 0: one sample at a time, lane = list entry
-#endif
 #ifndef AC_GSTEPS
 #define AC_GSTEPS 2
 #endif
@@ -1053,7 +1047,6 @@ __global__ __launch_bounds__(PK_WAVES * 64, AC_WARP_WAVES) void warp_samples_acc
     // masked out whatever its closest face is -- it is not searched at all (dead).  Outside both grids the mesh is >= the coarse margin away.
     bool dead = ray_dead ? ray_dead[ii / spr] != 0 : false;              // skip_masked: the sample's whole ray is provably masked out (ray_cull_kernel)
     if (!todo_lane) dead = true;                                         // fixup mode: already resolved (nothing is written for it below)
-#ifndef AC_ABL_NOGRID
     if (dead) mycnt = 0;
     else if (skip_thr >= 0.0f) {
         bool in_any = false;
@@ -1087,7 +1080,6 @@ __global__ __launch_bounds__(PK_WAVES * 64, AC_WARP_WAVES) void warp_samples_acc
             }
         }
     }
-#endif
     // TEMPORAL SEED (round 6): the caller keeps, per (ray, sample slot), the face the PREVIOUS frame's search found (tseeds; -1 = none) -- an animation's
     // body moves little between frames, so that face is usually the closest one again or next to it.  Its exact distance in THIS frame's pose is a real
     // face's distance, i.e. a valid first bound like the cell's seed face, and usually a much tighter one: the walk prunes against it from the first
@@ -1107,9 +1099,6 @@ __global__ __launch_bounds__(PK_WAVES * 64, AC_WARP_WAVES) void warp_samples_acc
         }
     }
     if (tseed < myseed && mycnt != CELL_OVERFLOW) myseed = tseed;
-#ifdef AC_WARP_SEED_DEBUG   // ceiling experiment (tools/warp_seed_probe.py): start every sample from its TRUE distance^2 (taken from a previous run)
-    if (g_warp_seed_d2 && live && mycnt != CELL_OVERFLOW) { const double t = g_warp_seed_d2[ii] * (1.0 + 1e-12); myseed = t < myseed ? t : myseed; }
-#endif
     // skip_thr >= 0 (round 5): the caller reads mask and the canonical points of UNMASKED samples only, i.e. a closest face matters only if it is closer than
     // the mask's threshold -- so the running bound never needs to start above it.  A sample whose seed face is farther away (the outer part of the
     // shell the cell grids cannot prove masked: the samples with the LONGEST candidate lists) walks its list against threshold (1 + 1e-6) instead; if no
@@ -1129,9 +1118,6 @@ __global__ __launch_bounds__(PK_WAVES * 64, AC_WARP_WAVES) void warp_samples_acc
     auto exact_batch = [&](uint32_t n) {
         wave_sync_lds();
         bool act = (uint32_t)lane < n;
-#ifdef AC_ABL_NOBATCH
-        act = false;
-#endif
         const uint32_t e = fq[(fh + (act ? (uint32_t)lane : 0u)) & (FQ - 1)];
         const uint32_t s = e >> 14, slot = e & 16383u;
         unsigned long long d2b = ~0ull;
@@ -1236,9 +1222,6 @@ __global__ __launch_bounds__(PK_WAVES * 64, AC_WARP_WAVES) void warp_samples_acc
             const float rr = (sp[u].w + __builtin_sqrtf(rem > 0.0f ? rem : 0.0f) * 1.000001f) + 1e-12f;
             const bool pass = have[u] && rem >= 0.0f && rho2 <= rr * rr * 1.000001f;
             const unsigned long long pm = __ballot(pass);
-#ifdef AC_COUNT_CAND
-            if (lane == 0) atomicAdd(reinterpret_cast<unsigned long long *>(av.hdr + 6), (unsigned long long)__builtin_popcountll(pm));
-#endif
             if (pass) fq[(ft + (uint32_t)__builtin_popcountll(pm & ((1ull << lane) - 1ull))) & (FQ - 1)] = (smp[u] << 14) | slot[u];
             ft += (uint32_t)__builtin_popcountll(pm);
         }
@@ -1248,9 +1231,6 @@ __global__ __launch_bounds__(PK_WAVES * 64, AC_WARP_WAVES) void warp_samples_acc
     auto push_tiles = [&](uint32_t j, unsigned long long cand, uint32_t tl) {
         if ((cand >> lane) & 1ull) tq[(tt + (uint32_t)__builtin_popcountll(cand & ((1ull << lane) - 1ull))) & (TQ - 1)] = (uint16_t)((j << 9) | tl);
         tt += (uint32_t)__builtin_popcountll(cand);
-#ifdef AC_COUNT_CAND
-        if (lane == 0) atomicAdd(reinterpret_cast<unsigned long long *>(av.hdr + 4), (unsigned long long)__builtin_popcountll(cand));
-#endif
     };
 
     // ONE inlined copy of each downstream stage; downstream first (that bounds the queues): full trips / batches while candidates are still coming, the
@@ -1267,7 +1247,6 @@ __global__ __launch_bounds__(PK_WAVES * 64, AC_WARP_WAVES) void warp_samples_acc
             else break;
         }
     };
-#if AC_WARP_LANE_LISTS
     // Round 4, the front end as lane = sample: every lane walks the tile list of ITS cell, four entries per trip -- the box test of an entry against the lane's
     // CURRENT bound (the running minimum the exact batches keep lowering, not only the seed), survivors compacted into the pair queue.  A trip costs what
     // one sample's step cost before (15 LDS reads + ~40 vector instructions) and serves up to 64 samples; the per-sample version broadcast the sample to
@@ -1300,24 +1279,17 @@ __global__ __launch_bounds__(PK_WAVES * 64, AC_WARP_WAVES) void warp_samples_acc
             drain(false);
         }
     }
-#endif
-    // the first 64 entries of a sample's list are requested PF samples ahead (a sample's front end is ~100 instructions: one sample of distance
-    // leaves the load's latency exposed); further chunks of a coarse-level list are requested together when the sample's turn comes
+    // the first 64 entries of a sample's list were requested PF samples ahead by the one-sample-at-a-time front end (round 3); the lane = sample front
+    // end above serves every sample with a list, so there is nothing left to request.  The (zero) queue stays: taking it out changes the generated code.
     constexpr int PF = 4;
     uint32_t tlq[PF];
-    auto list_head = [&](uint32_t jj) -> uint32_t {
-        if (AC_WARP_LANE_LISTS || jj >= npts) return 0u;
-        const uint32_t cn = (uint32_t)__builtin_amdgcn_readlane((int)mycnt, (int)jj);
-        return cn != CELL_OVERFLOW ? (uint32_t)av.ctl[(size_t)__builtin_amdgcn_readlane((int)mybase, (int)jj) + lane] : 0u;
-    };
+    auto list_head = [&](uint32_t) -> uint32_t { return 0u; };
 #pragma unroll
     for (int d = 0; d < PF; ++d) tlq[d] = list_head((uint32_t)d);
     for (uint32_t j = 0; j <= npts; ++j) {                                 // j == npts: drain the queues
         const bool last = j == npts;
-#if AC_WARP_LANE_LISTS
         // (samples with a list were served above: only the few without one -- outside both grids, an overflowing cell -- take a turn here)
         if (!last && (uint32_t)__builtin_amdgcn_readlane((int)mycnt, (int)j) != CELL_OVERFLOW) continue;
-#endif
         if (!last) {
         const float qf[3] = { lane_f32(pf[0], (int)j), lane_f32(pf[1], (int)j), lane_f32(pf[2], (int)j) };
         const uint32_t cnt = (uint32_t)__builtin_amdgcn_readlane((int)mycnt, (int)j);          // wave-uniform
@@ -1370,14 +1342,8 @@ __global__ __launch_bounds__(PK_WAVES * 64, AC_WARP_WAVES) void warp_samples_acc
             for (int it = 0; it < NIT; ++it) {
                 if ((uint32_t)it >= nit) break;                            // wave-uniform
                 unsigned long long cand = __ballot(lb[it] <= lim0f);       // fp32 compare against the bound rounded up: a superset
-#ifdef AC_ABL_NOCAND
-                cand = 0;
-#endif
                 push_tiles(j, cand, (uint32_t)(it * 64 + lane));
             }
-#ifdef AC_COUNT_CAND
-            if (lane == 0) atomicAdd(reinterpret_cast<unsigned long long *>(av.hdr + 4) + 1, 1ull << 40);      // samples through the full pass: high bits of counter 1
-#endif
             WP_TICK(3)
         }
         }
@@ -1540,14 +1506,6 @@ __global__ __launch_bounds__(256) void warp_samples_flist_kernel(const float *__
 }
 
 }  // namespace
-
-#ifdef AC_WARP_SEED_DEBUG
-AC_API void ac_debug_warp_seed(const double *d2)
-{
-    (void)hipDeviceSynchronize();
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_warp_seed_d2), &d2, sizeof(d2));
-}
-#endif
 
 #ifdef AC_PROFILE_WARP
 AC_API void ac_debug_warp_prof(unsigned long long *out, int reset)
