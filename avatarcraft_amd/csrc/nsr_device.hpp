@@ -19,7 +19,10 @@ namespace {
 #endif
 constexpr int WAVES_PER_BLOCK = AC_WPB;
 constexpr int BLOCK = WAVES_PER_BLOCK * 64;
-constexpr int MAXT = 128;
+#ifndef AC_MAXT
+#define AC_MAXT 128         // samples per ray a wave's LDS slab holds (render_long.hip: 512, at fewer waves per workgroup)
+#endif
+constexpr int MAXT = AC_MAXT;
 constexpr int SEG_STATE = MAXT + 16 + 64;   // floats per ray handed from one segment of a ray to the next: z [128] | cT, 10 running sums | pad | (view directions) the ray's layer-1 bias [64]
 #ifndef AC_ENC_ROUND
 #define AC_ENC_ROUND 2      // hash levels gathered per round per lane (registers vs loads in flight)

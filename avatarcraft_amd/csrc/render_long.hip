@@ -1,0 +1,479 @@
+// avatarcraft_amd/csrc/render_long.hip -- the fused Instant-NSR renderer for any sample count the reference accepts (ac_render_rays_long,
+// ac_sample_rays_long): num_steps >= 2 (not necessarily a multiple of 16), upsample_steps a multiple of 16, at most 512 samples per ray.
+//
+// The per-ray algorithm is render_rays_kernel's (render_fused.hip, MODE_FULL / MODE_UPSAMPLE) statement for statement: the same device blocks of
+// nsr_device.hpp, the same scans in the same order.  Where both renderers accept a sample count they agree bit for bit (tests/test_gpu_long_rays.py).
+// What differs:
+//   * a wave's LDS slab holds 512 samples (AC_MAXT), so a workgroup has 7 waves instead of 8: 13 540 + 7 x 3 680 floats = 153.5 KiB of the 160 KiB
+//     (8 waves would need 168 KiB);
+//   * num_steps need not be a multiple of 16: the last coarse tile and the last render tile are masked.  A masked lane still takes part in the
+//     field evaluation (the MFMA tiles need all 64 lanes; it evaluates the ray's last sample again) but contributes the identity to every scan
+//     and nothing to the cdf, the merges, the sums or the outputs;
+//   * lin_z is read from device memory (any length) instead of the 64-float LDS slot;
+//   * whole rays are the work items, dealt statically (no segment hand-off, no scratch): every ray costs the same number of tiles.
+#define AC_MAXT 512
+#ifndef AC_WPB
+#define AC_WPB 7
+#endif
+#include "nsr_device.hpp"
+
+namespace {
+
+constexpr int LONG_MAX_T = MAXT;
+constexpr int NCH = MAXT / 64;          // 64-lane chunks of the up-sampling scans
+
+template <int MODE, bool FAST, bool EX, bool SH>
+__global__ __launch_bounds__(BLOCK) void render_rays_long_kernel(const RenderArgs a)
+{
+    static_assert(MODE == MODE_FULL || MODE == MODE_UPSAMPLE, "canonical space only");
+    constexpr bool FC = FAST;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    if (a.prepared) {
+        const float4 *src = reinterpret_cast<const float4 *>(a.prepared);
+        float4 *dst = reinterpret_cast<float4 *>(lds);
+        for (int e = threadIdx.x; e < OFF_RWAVE / 4; e += blockDim.x)
+            dst[e] = src[(FC && 4 * e >= OFF_C1F && 4 * e < OFF_B1) ? e + (OFF_RWAVE - OFF_C1F) / 4 : e];
+        __syncthreads();
+        for (int e = threadIdx.x; e < 16; e += blockDim.x) lds[OFF_LIN + 64 + e] = a.lin_u ? a.lin_u[e] : 0.0f;
+    } else {
+        fill_lds_sdf(lds, a);
+        if constexpr (FAST) fill_lds_fast(lds, a);
+        if constexpr (FC) fill_lds_color_fast<true, true>(lds, a);
+        else fill_lds_color(lds, a);
+    }
+    __syncthreads();
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n = lane & 15, g = lane >> 4;
+    float *zs0 = lds + OFF_RWAVE + wave * WAVE_SLAB;    // final z values [512]
+    float *zs1 = zs0 + MAXT;                            // up-sampling state: zs1 [512], sd [2][512], cdf [512], znew [16] ...
+    float *sd = zs1 + MAXT;
+    float *cdf = sd + 2 * MAXT;
+    float *znl = cdf + MAXT;
+    float *fsl = zs1;                                   // ... then the finite-difference features [6][8][64]
+    const FieldCtx fc = make_ctx(a);
+    const W2Row0 w2r0 = load_w2_row0(lds, lane);
+    const float bound = a.bound;
+    const float inv_s_core = a.inv_s_dev ? *a.inv_s_dev : a.inv_s;
+    const int T0 = a.T0, nup = a.nup, T = T0 + 16 * nup;
+    const int ntile0 = (T0 + 15) / 16, ntile = (T + 15) / 16;
+
+    // static hand-out, XCD-aware like render_rays_kernel's counters: chunks of 512 consecutive rays, chunk c to XCD c % 8 (workgroup b runs on XCD
+    // b % 8; the grid is a multiple of 8); the waves of an XCD take its rays in turn
+    const int xper = ((a.n_rays + 7) / 8 + 7) & ~7, xchunk = xper < 512 ? xper : 512, xcd = blockIdx.x & 7;
+    const int kstride = (int)(gridDim.x >> 3) * WAVES_PER_BLOCK;
+    for (int k = (int)(blockIdx.x >> 3) * WAVES_PER_BLOCK + wave;; k += kstride) {
+        const int kc = k / xchunk, base = (kc * 8 + xcd) * xchunk;
+        if (base >= a.n_rays) break;
+        const int ray = base + (k - kc * xchunk);
+        if (ray >= a.n_rays) continue;
+        const float ox = a.rays_o[3 * ray], oy = a.rays_o[3 * ray + 1], oz = a.rays_o[3 * ray + 2];
+        const float dx = a.rays_d[3 * ray], dy = a.rays_d[3 * ray + 1], dz = a.rays_d[3 * ray + 2];
+        float near, far;
+        cube_near_far(ox, oy, oz, dx, dy, dz, bound, near, far);
+        if (a.near_m) {
+            const float nm = a.near_m[ray], fm = a.far_m[ray];
+            if (!is_inf(nm)) near = nm;
+            if (!is_inf(fm)) far = fm;
+        }
+        const float span = far - near;
+        const float sample_dist = span / (float)T0;
+        int cur = nup & 1, cnt = T0;
+        float *const zs_first = cur ? zs1 : zs0;
+
+        // ---- coarse samples (last tile masked when 16 does not divide num_steps) --------------------------------------------------
+        for (int c = 0; c < ntile0; ++c) {
+            const int i = 16 * c + n;
+            const bool valid = i < T0;
+            const int ic = valid ? i : T0 - 1;
+            float zi = near + span * a.lin_z[ic];
+            if (a.perturb) zi = zi + (a.noise[(size_t)ray * T0 + ic] - 0.5f) * sample_dist;
+            if (nup > 0) {
+                const float px = clampf(ox + dx * zi, -bound, bound), py = clampf(oy + dy * zi, -bound, bound), pz = clampf(oz + dz * zi, -bound, bound);
+                const f32x4 o2 = sdf_tile(lds, fc, lane, px, py, pz);
+                if (g == 0 && valid) sd[cur * MAXT + i] = o2[0];
+            }
+            if (g == 0 && valid) zs_first[i] = zi;
+        }
+        wave_sync();
+
+        // ---- NeuS up-sampling: chunks of 64 bins; chunks past the last bin are not visited (they would only scan identities) -----------
+        for (int it = 0; it < nup; ++it) {
+            const float *zc = cur ? zs1 : zs0, *sc = sd + cur * MAXT;
+            float *zn_ = cur ? zs0 : zs1, *sn_ = sd + (cur ^ 1) * MAXT;
+            const int m = cnt - 1;
+            const int nch_m = (m + 63) / 64, nch_c = (cnt + 63) / 64;
+            const float inv_s = __builtin_ldexpf(64.0f, it);        // 64 * 2^it (instant_nsr.py:183), exact; an int shift would overflow from it = 25 (up to 31 here)
+            float w[NCH];
+            float carry = 1.0f; bool first = true;
+#pragma unroll
+            for (int ch = 0; ch < NCH; ++ch) {
+                w[ch] = 0.0f;
+                if (ch >= nch_m) continue;
+                const int i = 64 * ch + lane;
+                float alpha = 0.0f, om = 1.0f;
+                if (i < m) {
+                    const float z0 = zc[i], z1 = zc[i + 1], s0 = sc[i], s1 = sc[i + 1];
+                    const float p0x = ox + dx * z0, p0y = oy + dy * z0, p0z = oz + dz * z0;
+                    const float p1x = ox + dx * z1, p1y = oy + dy * z1, p1z = oz + dz * z1;
+                    const float r0 = __builtin_sqrtf((p0x * p0x + p0y * p0y) + p0z * p0z);
+                    const float r1 = __builtin_sqrtf((p1x * p1x + p1y * p1y) + p1z * p1z);
+                    const bool inside = (r0 < 1.0f) | (r1 < 1.0f);
+                    const float mid = (s0 + s1) * 0.5f;
+                    const float dist = z1 - z0;
+                    const float cosv = (s1 - s0) / (dist + 1e-5f);
+                    float prev_cos = 0.0f;
+                    if (i > 0) { const float zm = zc[i - 1], sm = sc[i - 1]; prev_cos = (s0 - sm) / ((z0 - zm) + 1e-5f); }
+                    float cmin = prev_cos < cosv ? prev_cos : cosv;
+                    cmin = clampf(cmin, -1e3f, 0.0f) * (inside ? 1.0f : 0.0f);
+                    const float half = cmin * dist * 0.5f;
+                    const float pc = dv_sigmoid((mid - half) * inv_s), nc = dv_sigmoid((mid + half) * inv_s);
+                    alpha = (pc - nc + 1e-5f) / (pc + 1e-5f);
+                    om = 1.0f - alpha + 1e-7f;
+                }
+                float loc, row_in; bool row_first;
+                (void)chunk_scan<true>(om, lane, carry, first, loc, row_in, row_first);
+                const float sh = dpp_shr<1>(1.0f, loc);
+                float Tex;
+                if (n == 0) Tex = row_first ? 1.0f : row_in;
+                else Tex = row_first ? sh : row_in * sh;
+                w[ch] = (i < m) ? alpha * Tex + 1e-5f : 0.0f;
+            }
+            float total;
+            {
+                float c2 = 0.0f; bool f2 = true; float lc, ri; bool rf;
+                float last = 0.0f;
+#pragma unroll
+                for (int ch = 0; ch < NCH; ++ch) {
+                    if (ch >= nch_m) continue;
+                    const float incl = chunk_scan<false>(w[ch], lane, c2, f2, lc, ri, rf);
+                    const int il = m - 1 - 64 * ch;
+                    const float cand = __shfl(incl, il & 63);
+                    if (il >= 0 && il < 64) last = cand;
+                }
+                total = last;
+            }
+            {
+                float c3 = 0.0f; bool f3 = true; float lc, ri; bool rf;
+                if (lane == 0) cdf[0] = 0.0f;
+#pragma unroll
+                for (int ch = 0; ch < NCH; ++ch) {
+                    if (ch >= nch_m) continue;
+                    const int i = 64 * ch + lane;
+                    const float pdf = (i < m) ? w[ch] / total : 0.0f;
+                    const float incl = chunk_scan<false>(pdf, lane, c3, f3, lc, ri, rf);
+                    if (i < m) cdf[i + 1] = incl;
+                }
+            }
+            wave_sync();
+            float znew;
+            int ind;
+            {
+                const float u = lds[OFF_LIN + 64 + n];
+                int lo = 0, hi = cnt;
+                while (lo < hi) { const int md = (lo + hi) >> 1; if (cdf[md] <= u) lo = md + 1; else hi = md; }
+                ind = lo;
+                const int below = lo - 1 > 0 ? lo - 1 : 0;
+                const int above = lo < cnt - 1 ? lo : cnt - 1;
+                const float cb = cdf[below], ca = cdf[above];
+                float den = ca - cb;
+                if (den < 1e-5f) den = 1.0f;
+                const float t = (u - cb) / den;
+                const float zb = zc[below], za = zc[above];
+                znew = zb + t * (za - zb);
+            }
+            if (g == 0) {
+                znl[n] = znew;
+                if (EX && a.out.ss_inds) a.out.ss_inds[((size_t)ray * nup + it) * 16 + n] = ind;
+            }
+            const bool last_it = (it + 1 == nup);
+            float sdf_new = 0.0f;
+            if (!last_it) {
+                const float px = clampf(ox + dx * znew, -bound, bound), py = clampf(oy + dy * znew, -bound, bound),
+                            pz = clampf(oz + dz * znew, -bound, bound);
+                const f32x4 o2 = sdf_tile(lds, fc, lane, px, py, pz);
+                sdf_new = o2[0];
+            }
+            wave_sync();
+            // stable merge == torch.sort(cat([z, znew])); see render_rays_kernel for the unsorted first iteration of a ray that misses the cube
+            const bool old_sorted = !(it == 0 && span < 0.0f);
+            int32_t *sidx = (EX && a.out.sort_index) ? a.out.sort_index + ((size_t)ray * nup + it) * T : nullptr;     // [N, nup, T]
+#pragma unroll
+            for (int ch = 0; ch < NCH; ++ch) {
+                if (ch >= nch_c) continue;
+                const int i = 64 * ch + lane;
+                if (i < cnt) {
+                    const float zi = zc[i];
+                    int c = 0;
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) c += (znl[j] < zi) ? 1 : 0;
+                    int before = i;
+                    if (!old_sorted) {
+                        before = 0;
+                        for (int q = 0; q < cnt; ++q) { const float zk = zc[q]; before += ((zk < zi) || (zk == zi && q < i)) ? 1 : 0; }
+                    }
+                    zn_[before + c] = zi; sn_[before + c] = sc[i];
+                    if (sidx) sidx[before + c] = i;
+                }
+            }
+            if (sidx)
+                for (int i = cnt + 16 + lane; i < T; i += 64) sidx[i] = -1;
+            if (g == 0) {
+                int lo = 0, hi = cnt;
+                if (old_sorted) {
+                    while (lo < hi) { const int md = (lo + hi) >> 1; if (zc[md] <= znew) lo = md + 1; else hi = md; }
+                } else {
+                    for (int q = 0; q < cnt; ++q) lo += (zc[q] <= znew) ? 1 : 0;
+                }
+                int c = 0;
+#pragma unroll
+                for (int j = 0; j < 16; ++j) { const float zj = znl[j]; c += ((zj < znew) || (zj == znew && j < n)) ? 1 : 0; }
+                zn_[lo + c] = znew; sn_[lo + c] = sdf_new;
+                if (sidx) sidx[lo + c] = cnt + n;
+            }
+            cnt += 16; cur ^= 1;
+            wave_sync();
+        }
+
+        const float *zf = zs0;
+        if constexpr (MODE == MODE_UPSAMPLE) {
+            for (int i = lane; i < T; i += 64) a.zbuf[(size_t)ray * T + i] = zf[i];
+            wave_sync();
+            continue;
+        }
+
+        // ---- render core (last tile masked when 16 does not divide T) ------------------------------------------------------------------
+        float cT = 1.0f;
+        float *const accs = zs0 + SLAB_ACC;
+        if constexpr (SH) ray_sh_bias(zs0 + SLAB_SHB, a.Wsh, dx, dy, dz, lane);
+        const float bxe = a.eps;
+        for (int c = 0; c < ntile; ++c) {
+            const int i = 16 * c + n;
+            const bool valid = i < T;
+            const int ii = valid ? i : T - 1;
+            const float zi = zf[ii];
+            const float delta = (ii < T - 1) ? zf[ii + 1] - zi : sample_dist;
+            const float zmid = (ii < T - 1) ? zi + 0.5f * delta : zi;
+            const float px = clampf(ox + dx * zmid, -bound, bound), py = clampf(oy + dy * zmid, -bound, bound), pz = clampf(oz + dz * zmid, -bound, bound);
+            f32x4 oc = { 0.0f, 0.0f, 0.0f, 0.0f };
+            float gr[3] = { 0.0f, 0.0f, 0.0f };
+            {
+            float fe0[4][2];
+            encode_stencil(lds, fsl, fc, lane, px, py, pz, bxe, fe0);
+            const float pc0 = sel4(g, px, py, pz, 0.0f);
+            float spos = 0.0f;
+            if constexpr (FAST) {
+                const Acc4 acc0 = sdf_l1(lds, lane, pc0, fe0);
+                oc = sdf_l2(lds, lane, acc0);
+#pragma unroll 1
+                for (int e = 0; e < 6; ++e) {
+                    const int kn = e >> 1;
+                    float fe[4][2];
+#pragma unroll
+                    for (int q_ = 0; q_ < 8; ++q_) fe[q_ >> 1][q_ & 1] = fsl[(e * 8 + q_) * 64 + lane];
+                    const float pk = kn == 0 ? px : (kn == 1 ? py : pz);
+                    const float poff = clampf(pk + ((e & 1) ? -bxe : bxe), -bound, bound);
+                    const Acc4 acc = sdf_l1_delta(lds, lane, acc0, fe, fe0, kn, poff - pk);
+                    const float s_e = sdf_l2_sdf(lds, acc, w2r0);
+                    if (!(e & 1)) spos = s_e;
+                    else {
+                        const float gk = 0.5f * (spos - s_e) / bxe;
+                        if (kn == 0) gr[0] = gk; else if (kn == 1) gr[1] = gk; else gr[2] = gk;
+                    }
+                }
+            } else {
+            Acc4 acc = sdf_l1(lds, lane, pc0, fe0);
+#pragma unroll 1
+            for (int e = 0; e < 7; ++e) {
+                Acc4 accn = acc;
+                if (e < 6) {
+                    const int kn = e >> 1;
+                    float fe[4][2];
+#pragma unroll
+                    for (int q_ = 0; q_ < 8; ++q_) fe[q_ >> 1][q_ & 1] = fsl[(e * 8 + q_) * 64 + lane];
+                    const float pk = kn == 0 ? px : (kn == 1 ? py : pz);
+                    const float poff = clampf(pk + ((e & 1) ? -bxe : bxe), -bound, bound);
+                    accn = sdf_l1(lds, lane, g == kn ? poff : pc0, fe);
+                }
+                if (e == 0) oc = sdf_l2(lds, lane, acc);
+                else {
+                    const float s_e = sdf_l2_sdf(lds, acc, w2r0);
+                    const int kk = (e - 1) >> 1;
+                    if (e & 1) spos = s_e;
+                    else {
+                        const float gk = 0.5f * (spos - s_e) / bxe;
+                        if (kk == 0) gr[0] = gk; else if (kk == 1) gr[1] = gk; else gr[2] = gk;
+                    }
+                }
+                acc = accn;
+            }
+            }
+            }
+            const float gx = gr[0], gy = gr[1], gz = gr[2];
+            const float gn = __builtin_sqrtf((gx * gx + gy * gy) + gz * gz);
+            const float nx = gx / (1e-5f + gn), ny = gy / (1e-5f + gn), nz = gz / (1e-5f + gn);
+            float rgb[3] = { 0.0f, 0.0f, 0.0f };
+            if constexpr (FC) color_tile_fast(lds, lane, px, py, pz, nx, ny, nz, oc, rgb, nullptr, 16, SH ? zs0 + SLAB_SHB : nullptr);
+            else color_tile(lds, lane, px, py, pz, nx, ny, nz, oc, rgb, nullptr, 16, SH ? zs0 + SLAB_SHB : nullptr);
+            const float sdf0 = oc[0];
+            const float tc = (dx * nx + dy * ny) + dz * nz;
+            const float a1 = dv_softplus100(lds + OFF_SPQ, -tc * 0.5f + 0.5f) * a.one_m_car;
+            const float a2 = dv_softplus100(lds + OFF_SPQ, -tc) * a.car;
+            const float iter_cos = -(a1 + a2);
+            const float half = iter_cos * delta * 0.5f;
+            const float pc = dv_sigmoid((sdf0 - half) * inv_s_core), nc = dv_sigmoid((sdf0 + half) * inv_s_core);
+            const float alpha = valid ? clampf((pc - nc + 1e-5f) / (pc + 1e-5f), 0.0f, 1.0f) : 0.0f;
+            const float om = valid ? 1.0f - alpha + 1e-7f : 1.0f;              // masked lanes: the identity of the product scan
+            const float loc = row_scan<true>(om);
+            const float sh = dpp_shr<1>(1.0f, loc);
+            float Tex;
+            if (n == 0) Tex = (c == 0) ? 1.0f : cT;
+            else Tex = (c == 0) ? sh : cT * sh;
+            const float tot = lane_bcast(loc, 15);
+            cT = (c == 0) ? tot : cT * tot;
+            const float wgt = alpha * Tex;
+            const float zn01 = clampf((zi - near) / span, 0.0f, 1.0f);
+            const float pn = __builtin_sqrtf((px * px + py * py) + pz * pz);
+            const float relax = (pn < 1.2f && valid) ? 1.0f : 0.0f;
+            const float eerr = relax * ((gn - 1.0f) * (gn - 1.0f));
+            {
+                // masked lanes add exact zeros (x + 0 = x): wgt = 0 there, and every factor it meets is finite whenever the ray's own last
+                // sample is (a masked lane evaluates that very point again)
+                const float t1 = row_scan<false>(wgt), t2 = row_scan<false>(rgb[0] * wgt), t3 = row_scan<false>(rgb[1] * wgt), t4 = row_scan<false>(rgb[2] * wgt),
+                            t5 = row_scan<false>(nx * wgt), t6 = row_scan<false>(ny * wgt), t7 = row_scan<false>(nz * wgt), t8 = row_scan<false>(wgt * zn01),
+                            t9 = row_scan<false>(eerr), t10 = row_scan<false>(relax);
+                if (lane == 15) {
+#define AC_ACC(K, T_) accs[K] = (c == 0) ? T_ : accs[K] + T_;
+                    AC_ACC(1, t1) AC_ACC(2, t2) AC_ACC(3, t3) AC_ACC(4, t4) AC_ACC(5, t5) AC_ACC(6, t6) AC_ACC(7, t7) AC_ACC(8, t8) AC_ACC(9, t9) AC_ACC(10, t10)
+#undef AC_ACC
+                }
+            }
+            if (g == 0 && valid) {
+                const size_t si = (size_t)ray * T + i;
+                if (EX && a.out.z_vals) a.out.z_vals[si] = zi;
+                if (EX && a.out.weights) a.out.weights[si] = wgt;
+                if (EX && a.out.alpha) a.out.alpha[si] = alpha;
+                if (EX && a.out.sdf) a.out.sdf[si] = sdf0;
+                if (EX && a.out.color) { a.out.color[3 * si] = rgb[0]; a.out.color[3 * si + 1] = rgb[1]; a.out.color[3 * si + 2] = rgb[2]; }
+                if (EX && a.out.gradient) { a.out.gradient[3 * si] = gx; a.out.gradient[3 * si + 1] = gy; a.out.gradient[3 * si + 2] = gz; }
+                if (EX && a.out.pts) { a.out.pts[3 * si] = px; a.out.pts[3 * si + 1] = py; a.out.pts[3 * si + 2] = pz; }
+            }
+            if (EX && valid && a.out.sdf_out16)
+                *reinterpret_cast<f32x4 *>(a.out.sdf_out16 + ((size_t)ray * T + i) * 16 + 4 * g) = oc;
+        }
+        wave_sync();
+        if (lane == 0) {
+            const float s_w = accs[1], s_r = accs[2], s_g = accs[3], s_b = accs[4], s_nx = accs[5], s_ny = accs[6], s_nz = accs[7], s_d = accs[8], s_en = accs[9], s_ed = accs[10];
+            const float b0 = a.bg ? a.bg[3 * ray] : 1.0f, b1 = a.bg ? a.bg[3 * ray + 1] : 1.0f, b2 = a.bg ? a.bg[3 * ray + 2] : 1.0f;
+            a.out.image[3 * ray] = s_r + (1.0f - s_w) * b0;
+            a.out.image[3 * ray + 1] = s_g + (1.0f - s_w) * b1;
+            a.out.image[3 * ray + 2] = s_b + (1.0f - s_w) * b2;
+            a.out.normal_map[3 * ray] = s_nx; a.out.normal_map[3 * ray + 1] = s_ny; a.out.normal_map[3 * ray + 2] = s_nz;
+            a.out.weights_sum[ray] = s_w;
+            a.out.depth[ray] = s_d;
+            a.out.eik[2 * ray] = s_en; a.out.eik[2 * ray + 1] = s_ed;
+        }
+        wave_sync();
+    }
+}
+
+static int check_long_args(const char *who, const ac_render_opts *op, const float *rays_o, const float *rays_d, const float *noise,
+                           const float *lin_z, const float *lin_u)
+{
+    if (op->num_steps < 2 || op->upsample_steps < 0 || op->upsample_steps % 16 || op->num_steps + op->upsample_steps > LONG_MAX_T) {
+        ac::set_error("%s: num_steps=%d upsample_steps=%d unsupported (num_steps >= 2, upsample_steps >= 0 and a multiple of 16, "
+                      "num_steps + upsample_steps <= %d)", who, op->num_steps, op->upsample_steps, LONG_MAX_T);
+        return AC_ERR_BAD_ARG;
+    }
+    if (!(op->fd_eps > 0.0f)) {
+        ac::set_error("%s: fd_eps = %g (normal_epsilon_ratio >= 1): the finite-difference normals divide by it, it must be positive", who, (double)op->fd_eps);
+        return AC_ERR_BAD_ARG;
+    }
+    if (op->precision != 0 && op->precision != 1) { ac::set_error("%s: precision %d unknown (0 = exact, 1 = fast)", who, op->precision); return AC_ERR_BAD_ARG; }
+    if (op->opacity_only) { ac::set_error("%s: opacity_only is not supported by the long renderer", who); return AC_ERR_BAD_ARG; }
+    if (op->skip_masked) { ac::set_error("%s: skip_masked is a posed-space option; the long renderer is canonical only", who); return AC_ERR_BAD_ARG; }
+    if ((op->near_m != nullptr) != (op->far_m != nullptr)) { ac::set_error("%s: near_m and far_m go together", who); return AC_ERR_BAD_ARG; }
+    if (op->n_rays > 0 && (!rays_o || !rays_d || !lin_z || (op->upsample_steps && !lin_u) || (op->perturb && !noise))) {
+        ac::set_error("%s: NULL buffer", who); return AC_ERR_BAD_ARG;
+    }
+    return AC_OK;
+}
+
+static int fill_long_args(RenderArgs &a, const ac_field *field, const ac_render_opts *op, const float *rays_o, const float *rays_d,
+                          const float *bg, const float *noise, const float *lin_z, const float *lin_u)
+{
+    if (int rc = fill_args(a, field, op->bound)) return rc;
+    a.rays_o = rays_o; a.rays_d = rays_d; a.bg = bg; a.noise = noise; a.lin_z = lin_z; a.lin_u = lin_u;
+    a.n_rays = op->n_rays; a.T0 = op->num_steps; a.nup = op->upsample_steps / 16;
+    a.inv_s = op->inv_s; a.inv_s_dev = op->inv_s_dev; a.car = op->cos_anneal_ratio; a.one_m_car = (float)(1.0 - (double)op->cos_anneal_ratio);
+    a.eps = op->fd_eps; a.perturb = op->perturb; a.fast = op->precision;
+    a.near_m = op->near_m; a.far_m = op->far_m;
+    for (int j = 0; j < 4; ++j) {           // finite-difference reach in cells, per gather round (as fill_render_args)
+        a.jfine[j] = 0;
+        for (int g = 0; g < 4; ++g) {
+            const double cells = (double)op->fd_eps / (double)a.two_bound * (double)a.lvl[4 * j + g].scale;
+            if (!(cells * 1.001 + 1e-3 < 1.0)) a.jfine[j] = 1;
+        }
+    }
+    return AC_OK;
+}
+
+template <int MODE, bool FAST, bool EX, bool SH>
+static void launch_long_p(const RenderArgs &a, hipStream_t stream)
+{
+    static uint64_t seen = 0;
+    const size_t lds_bytes = LDS_FLOATS * sizeof(float);
+    ac::allow_dynamic_lds(seen, reinterpret_cast<const void *>(render_rays_long_kernel<MODE, FAST, EX, SH>), lds_bytes);
+    int blocks = (a.n_rays + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+    const int cus = (int)ac::cu_count();
+    if (blocks > cus) blocks = cus;
+    blocks = (blocks + 7) & ~7;                                      // the hand-out assumes every XCD has the same number of workgroups
+    hipLaunchKernelGGL((render_rays_long_kernel<MODE, FAST, EX, SH>), dim3(blocks), dim3(BLOCK), lds_bytes, stream, a);
+}
+
+static bool long_wants_samples(const ac_render_out &o)
+{
+    return o.z_vals || o.weights || o.alpha || o.color || o.sdf || o.gradient || o.ss_inds || o.sort_index || o.sdf_out16 || o.pts;
+}
+
+}  // namespace
+
+AC_API int ac_render_rays_long(const ac_field *field, const ac_render_opts *op, const float *rays_o, const float *rays_d,
+                               const float *bg, const float *noise, const float *lin_z, const float *lin_u,
+                               const ac_render_out *out, ac_stream_t stream)
+{
+    if (!op || !out) { ac::set_error("render_rays_long: NULL opts/out"); return AC_ERR_BAD_ARG; }
+    if (int rc = check_long_args("render_rays_long", op, rays_o, rays_d, noise, lin_z, lin_u)) return rc;
+    if (out->feat7) { ac::set_error("render_rays_long: feat7 (the fused training backward's features) is not produced by the long renderer"); return AC_ERR_BAD_ARG; }
+    if (op->n_rays <= 0) return AC_OK;
+    if (!out->image || !out->weights_sum || !out->depth || !out->normal_map || !out->eik) { ac::set_error("render_rays_long: NULL buffer"); return AC_ERR_BAD_ARG; }
+    RenderArgs a{};
+    if (int rc = fill_long_args(a, field, op, rays_o, rays_d, bg, noise, lin_z, lin_u)) return rc;
+    a.out = *out;
+    const hipStream_t st = (hipStream_t)stream;
+    const bool ex = long_wants_samples(a.out);
+    if (a.Wsh) {
+        if (a.fast) { if (ex) launch_long_p<MODE_FULL, true, true, true>(a, st); else launch_long_p<MODE_FULL, true, false, true>(a, st); }
+        else { if (ex) launch_long_p<MODE_FULL, false, true, true>(a, st); else launch_long_p<MODE_FULL, false, false, true>(a, st); }
+    } else {
+        if (a.fast) { if (ex) launch_long_p<MODE_FULL, true, true, false>(a, st); else launch_long_p<MODE_FULL, true, false, false>(a, st); }
+        else { if (ex) launch_long_p<MODE_FULL, false, true, false>(a, st); else launch_long_p<MODE_FULL, false, false, false>(a, st); }
+    }
+    if (int rc = ac::check_launch("render_rays_long")) return rc;
+    // gradient_error in the fixed order the other renderer's last workgroup uses (eikonal_reduce_kernel's): bit-identical
+    if (out->eik_reduced) return ac_eikonal_reduce2(out->eik, op->n_rays, out->eik_reduced, stream);
+    return AC_OK;
+}
+
+AC_API int ac_sample_rays_long(const ac_field *field, const ac_render_opts *op, const float *rays_o, const float *rays_d, const float *noise,
+                               const float *lin_z, const float *lin_u, float *z_vals, ac_stream_t stream)
+{
+    if (!op || !z_vals) { ac::set_error("sample_rays_long: NULL opts/z_vals"); return AC_ERR_BAD_ARG; }
+    if (int rc = check_long_args("sample_rays_long", op, rays_o, rays_d, noise, lin_z, lin_u)) return rc;
+    if (op->n_rays <= 0) return AC_OK;
+    RenderArgs a{};
+    if (int rc = fill_long_args(a, field, op, rays_o, rays_d, nullptr, noise, lin_z, lin_u)) return rc;
+    a.zbuf = z_vals;
+    launch_long_p<MODE_UPSAMPLE, false, false, false>(a, (hipStream_t)stream);
+    return ac::check_launch("sample_rays_long");
+}

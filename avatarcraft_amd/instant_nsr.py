@@ -425,6 +425,15 @@ class NeRFRenderer(nn.Module):
             raise NotImplementedError("the MI355X renderer needs the default SDF side of NeRFNetwork (16-level hash grid, include_input, "
                                       "SDF network 35-64-16); other widths / depths have no sampling kernel")
         full = self._fused_supported()
+        # counts outside the window of the fused renderer (multiples of 16, num_steps <= 64, at most 128 samples) go to the long renderer:
+        # canonical space only
+        long_counts = not nsr_ops.in_short_window(num_steps, upsample_steps)
+        if long_counts:
+            if not render_can:
+                raise NotImplementedError(f"posed-space rendering supports num_steps and upsample_steps that are multiples of 16 with "
+                                          f"16 <= num_steps <= 64 and num_steps + upsample_steps <= 128 only (got {num_steps} + {upsample_steps}); "
+                                          f"longer rays render in canonical space (render_can=True)")
+            nsr_ops.check_long_counts(num_steps, upsample_steps)
         B, N = rays_o.shape[:2]
         device = rays_o.device
         ro = rays_o.reshape(-1, 3).float().contiguous()
@@ -454,6 +463,19 @@ class NeRFRenderer(nn.Module):
             from .ray_utils import geometry_guided_near_far
             v = verts.verts if isinstance(verts, nsr_ops.WarpMesh) else verts
             near_far = geometry_guided_near_far(ro, rd, v, DEFAULT_GEO_THRESH)
+        if long_counts:
+            if needs_grad or not full:
+                # (the fused training operators -- fused_training = "core" and its manual backward -- stop at 128 samples: the long counts take the
+                # autograd render core, which handles any T)
+                z_vals = nsr_ops.sample_rays_long(self._field() if full else self._field_sdf_only(), ro, rd, num_steps, upsample_steps, bound,
+                                                  noise=noise, near_far=near_far)
+                return self._render_core_autograd(ro, rd, z_vals, num_steps, upsample_steps, bound, bg, cos_anneal_ratio, normal_epsilon_ratio, B, N,
+                                                  near_far=near_far)
+            out = nsr_ops.render_rays_long(self._field(), ro, rd, num_steps, upsample_steps, bound, inv_s_t, bg=bg, noise=noise,
+                                           cos_anneal_ratio=cos_anneal_ratio, normal_epsilon_ratio=normal_epsilon_ratio, extras=bool(per_sample),
+                                           near_far=near_far, precision=self.render_precision)
+            return (out["depth"].reshape(B, N), out.get("weights"), out["weights_sum"][:, None], out["image"].reshape(B, N, 3),
+                    out["normal_map"], out["gradient_error"], 0.0, out.get("color"), out.get("alpha"), out.get("z_vals"))
         if needs_grad and full and self.fused_training == "core" and near_far is None and self._manual_backward and warp is None:
             with torch.no_grad():
                 field, inv_s_ng = self._field(), self.forward_variance()

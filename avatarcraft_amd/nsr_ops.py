@@ -121,6 +121,44 @@ def render_rays(field, rays_o, rays_d, num_steps=64, upsample_steps=64, bound=1.
     skip_masked (posed space only): tiles of 16 samples that the warp masks out entirely are not evaluated (ac_render_opts.skip_masked): image,
     weights_sum, depth, normal_map, weights and alpha unchanged bit for bit; sdf / color / gradient of skipped samples 0, gradient_error over the
     evaluated samples."""
+    return _render(field, rays_o, rays_d, num_steps, upsample_steps, bound, inv_s, bg, noise, cos_anneal_ratio, normal_epsilon_ratio, extras,
+                   debug_indices, out, events, warp, train_extras, near_far, precision, skip_masked, opacity_only, long=False)
+
+
+LONG_MAX_SAMPLES = 512
+
+
+def check_long_counts(num_steps, upsample_steps):
+    """the envelope of the long renderer (ac_render_rays_long): RuntimeError naming the rule, before any device work"""
+    ns, us = int(num_steps), int(upsample_steps)
+    if ns < 2 or us < 0 or us % 16 or ns + us > LONG_MAX_SAMPLES:
+        raise RuntimeError(f"render_rays_long: num_steps={ns} upsample_steps={us} unsupported (num_steps >= 2, upsample_steps >= 0 and a multiple "
+                           f"of 16, num_steps + upsample_steps <= {LONG_MAX_SAMPLES})")
+
+
+def in_short_window(num_steps, upsample_steps):
+    """the counts render_rays / sample_rays accept (multiples of 16, 16 <= num_steps <= 64, sum <= 128)"""
+    ns, us = int(num_steps), int(upsample_steps)
+    return ns % 16 == 0 and us % 16 == 0 and 16 <= ns <= 64 and us >= 0 and ns + us <= 128
+
+
+def render_rays_long(field, rays_o, rays_d, num_steps=64, upsample_steps=64, bound=1.6, inv_s=1.0, bg=None, noise=None,
+                     cos_anneal_ratio=1.0, normal_epsilon_ratio=0.0, extras=False, debug_indices=False, out=None, events=None, warp=None,
+                     train_extras=False, near_far=None, precision="exact", skip_masked=False, opacity_only=False):
+    """render_rays for any sample count the reference accepts (ac_render_rays_long): num_steps >= 2, upsample_steps >= 0 a multiple of 16, at most
+    512 samples per ray.  Same arguments and result dict as render_rays; bit-identical to it where both accept the counts.  Canonical space only
+    (warp, skip_masked and opacity_only are rejected); train_extras gives sdf_out16 / pts but no stencil features; sort_index is [N, nup, T]."""
+    check_long_counts(num_steps, upsample_steps)
+    if warp is not None:
+        raise RuntimeError("render_rays_long: canonical space only (posed rendering at long counts is not supported)")
+    if skip_masked or opacity_only:
+        raise RuntimeError("render_rays_long: skip_masked and opacity_only are not supported")
+    return _render(field, rays_o, rays_d, num_steps, upsample_steps, bound, inv_s, bg, noise, cos_anneal_ratio, normal_epsilon_ratio, extras,
+                   debug_indices, out, events, None, train_extras, near_far, precision, False, False, long=True)
+
+
+def _render(field, rays_o, rays_d, num_steps, upsample_steps, bound, inv_s, bg, noise, cos_anneal_ratio, normal_epsilon_ratio, extras,
+            debug_indices, out, events, warp, train_extras, near_far, precision, skip_masked, opacity_only, long):
     rays_o = _chk(rays_o.reshape(-1, 3), "rays_o")
     rays_d = _chk(rays_d.reshape(-1, 3), "rays_d")
     N = rays_o.shape[0]
@@ -157,10 +195,11 @@ def render_rays(field, rays_o, rays_d, num_steps=64, upsample_steps=64, bound=1.
         o.sdf_out16 = buf("sdf_out16", (N, T, 16)).data_ptr()
         o.pts = buf("pts", (N, T, 3)).data_ptr()
         if SAVE_STENCIL_FEATURES:
-            o.feat7 = buf("feat7", (N * T // 16, 14, 64, 4)).data_ptr()
+            if not long:
+                o.feat7 = buf("feat7", (N * T // 16, 14, 64, 4)).data_ptr()
     if debug_indices:
         o.ss_inds = buf("ss_inds", (N, max(nup, 1), 16), torch.int32).data_ptr()
-        o.sort_index = buf("sort_index", (N, max(nup, 1), 128), torch.int32).data_ptr()
+        o.sort_index = buf("sort_index", (N, max(nup, 1), T if long else 128), torch.int32).data_ptr()
     if bg is not None:
         bg = _chk(bg.reshape(-1, 3), "bg_color", (N, 3))
     if noise is not None:
@@ -178,7 +217,10 @@ def render_rays(field, rays_o, rays_d, num_steps=64, upsample_steps=64, bound=1.
     st = L.current_stream(dev)
     if events is not None:          # (start, end) torch.cuda.Event pair around the render kernel only (bench.py roofline)
         events[0].record()
-    if warp is None:
+    if long:
+        L.check(L.lib().ac_render_rays_long(C.byref(field.c), C.byref(op), rays_o.data_ptr(), rays_d.data_ptr(), L.ptr(bg), L.ptr(noise),
+                                            lin_z.data_ptr(), lin_u.data_ptr(), C.byref(o), st), "render_rays_long")
+    elif warp is None:
         L.check(L.lib().ac_render_rays(C.byref(field.c), C.byref(op), rays_o.data_ptr(), rays_d.data_ptr(), L.ptr(bg), L.ptr(noise),
                                        lin_z.data_ptr(), lin_u.data_ptr(), C.byref(o), st), "render_rays")
     else:
@@ -273,6 +315,17 @@ def render_rays_pair(field, rays_o, rays_d, noise2, num_steps=64, upsample_steps
 
 def sample_rays(field, rays_o, rays_d, num_steps=64, upsample_steps=64, bound=1.6, noise=None, near_far=None):
     """the no-grad sampling stage of run() only -> z_vals [N, num_steps + upsample_steps] (identical to render_rays' z_vals)"""
+    return _sample(field, rays_o, rays_d, num_steps, upsample_steps, bound, noise, near_far, long=False)
+
+
+def sample_rays_long(field, rays_o, rays_d, num_steps=64, upsample_steps=64, bound=1.6, noise=None, near_far=None):
+    """sample_rays for any count render_rays_long accepts (ac_sample_rays_long) -> z_vals [N, num_steps + upsample_steps], identical to
+    render_rays_long's z_vals (and to sample_rays' where both accept the counts)"""
+    check_long_counts(num_steps, upsample_steps)
+    return _sample(field, rays_o, rays_d, num_steps, upsample_steps, bound, noise, near_far, long=True)
+
+
+def _sample(field, rays_o, rays_d, num_steps, upsample_steps, bound, noise, near_far, long):
     rays_o = _chk(rays_o.reshape(-1, 3), "rays_o")
     rays_d = _chk(rays_d.reshape(-1, 3), "rays_d")
     N, dev = rays_o.shape[0], rays_o.device
@@ -284,8 +337,9 @@ def sample_rays(field, rays_o, rays_d, num_steps=64, upsample_steps=64, bound=1.
     if near_far is not None:
         nm, fm = _chk(near_far[0].reshape(-1), "near", (N,)), _chk(near_far[1].reshape(-1), "far", (N,))
     op = L.ac_render_opts(N, int(num_steps), int(upsample_steps), float(bound), 1.0, 1.0, 0.005, int(noise is not None), None, L.ptr(nm), L.ptr(fm), 0, 0)
-    L.check(L.lib().ac_sample_rays(C.byref(field.c), C.byref(op), rays_o.data_ptr(), rays_d.data_ptr(), L.ptr(noise), lin_z.data_ptr(),
-                                   lin_u.data_ptr(), z.data_ptr(), L.current_stream(dev)), "sample_rays")
+    name = "sample_rays_long" if long else "sample_rays"
+    L.check(getattr(L.lib(), "ac_" + name)(C.byref(field.c), C.byref(op), rays_o.data_ptr(), rays_d.data_ptr(), L.ptr(noise), lin_z.data_ptr(),
+                                           lin_u.data_ptr(), z.data_ptr(), L.current_stream(dev)), name)
     return z
 
 

@@ -259,6 +259,18 @@ int ac_render_rays_pair(const ac_field *field, const ac_render_opts *opts, const
                         const float *bg2, const float *noise2, const float *lin_z, const float *lin_u,
                         const ac_render_out *out, ac_stream_t stream);
 
+/* ac_render_rays for any sample count the reference accepts: num_steps >= 2 (any value, not only multiples of 16), upsample_steps >= 0 and a
+ * multiple of 16, num_steps + upsample_steps <= 512 (anything else: AC_ERR_BAD_ARG naming the rule).  Canonical space only; same arguments and
+ * outputs as ac_render_rays (lin_z [num_steps]), except: sort_index is [N, upsample_steps/16, T] (T = num_steps + upsample_steps, -1 pad),
+ * feat7 must be NULL and opts->opacity_only / skip_masked must be 0.  Where both accept the counts, every output is bit-identical to
+ * ac_render_rays'.  Needs no scratch; gradient_error (eik_reduced) is formed by ac_eikonal_reduce2 on the same stream. */
+int ac_render_rays_long(const ac_field *field, const ac_render_opts *opts, const float *rays_o, const float *rays_d,
+                        const float *bg, const float *noise, const float *lin_z, const float *lin_u,
+                        const ac_render_out *out, ac_stream_t stream);
+/* the sampling stage of ac_render_rays_long alone -> z_vals [N, num_steps + upsample_steps]: the long counterpart of ac_sample_rays */
+int ac_sample_rays_long(const ac_field *field, const ac_render_opts *opts, const float *rays_o, const float *rays_d, const float *noise,
+                        const float *lin_z, const float *lin_u, float *z_vals, ac_stream_t stream);
+
 /* gradient_error = sum(relax*err) / (sum(relax) + 1e-5) over the per-ray partials, fixed order
  * (instant_nsr.py:270-272); result: 1 float (device) */
 int ac_eikonal_reduce(const float *eik, int32_t n_rays, float *result, ac_stream_t stream);
