@@ -7,6 +7,7 @@
 #include "ac_devmath.hpp"
 #include "ac_sp_table.hpp"
 #include "ac_sh16.hpp"
+#include <type_traits>
 
 using namespace acdev;
 
@@ -723,6 +724,25 @@ __device__ __forceinline__ void encode_stencil(const float *__restrict__ lds, fl
 }
 #undef AC_FSTORE
 
+// the normal from the finite-difference gradient: |g| (eikonal term) and g / (1e-5 + |g|)
+struct FdNormal { float gn, nx, ny, nz; };
+__device__ __forceinline__ FdNormal fd_normal(float gx, float gy, float gz)
+{
+    const float gn = __builtin_sqrtf((gx * gx + gy * gy) + gz * gz);
+    return FdNormal{ gn, gx / (1e-5f + gn), gy / (1e-5f + gn), gz / (1e-5f + gn) };
+}
+
+// NeuS alpha (instant_nsr.py:219-248) of a section of length delta at sdf value sdf0: tc = dot(ray direction, normal), inv_s = forward_variance()
+__device__ __forceinline__ float neus_alpha(const float *__restrict__ lds, const RenderArgs &a, float tc, float sdf0, float delta, float inv_s)
+{
+    const float a1 = dv_softplus100(lds + OFF_SPQ, -tc * 0.5f + 0.5f) * a.one_m_car;
+    const float a2 = dv_softplus100(lds + OFF_SPQ, -tc) * a.car;
+    const float iter_cos = -(a1 + a2);
+    const float half = iter_cos * delta * 0.5f;
+    const float pc = dv_sigmoid((sdf0 - half) * inv_s), nc = dv_sigmoid((sdf0 + half) * inv_s);
+    return clampf((pc - nc + 1e-5f) / (pc + 1e-5f), 0.0f, 1.0f);
+}
+
 // ---- forward_color for a tile: rgb (post-sigmoid) valid in lanes g==0 ---------------------------------
 // ---- use_viewdirs = True (models/instant_nsr.py:565-569, 644-653): h = cat[x, sh(d), n, geo_feat] ----------------------------------------
 // The 16 spherical harmonics (degree 4, encoder/shencoder) of the RAW ray direction enter layer 1 of the colour network only.  The direction is constant
@@ -949,6 +969,43 @@ int fill_args(RenderArgs &a, const ac_field *f, float bound)
     a.bound = bound; a.two_bound = (float)(2.0 * (double)bound);
     a.inv_tb = ac::verified_reciprocal(a.two_bound);
     return AC_OK;
+}
+
+// the finite-difference step, and per gather round of encode_stencil whether one of its levels reaches past the neighbouring cell (jfine)
+void set_fd_eps(RenderArgs &a, float eps)
+{
+    a.eps = eps;
+    for (int j = 0; j < 4; ++j) {
+        a.jfine[j] = 0;
+        for (int g = 0; g < 4; ++g) {
+            const double cells = (double)eps / (double)a.two_bound * (double)a.lvl[4 * j + g].scale;
+            if (!(cells * 1.001 + 1e-3 < 1.0)) a.jfine[j] = 1;
+        }
+    }
+}
+
+// what both renderers (render_fused.hip, render_long.hip) take from ac_render_opts; each checks the options its own window accepts
+int fill_render_common(RenderArgs &a, const ac_field *field, const ac_render_opts *op, const float *rays_o, const float *rays_d,
+                       const float *bg, const float *noise, const float *lin_z, const float *lin_u)
+{
+    if (int rc = fill_args(a, field, op->bound)) return rc;
+    a.rays_o = rays_o; a.rays_d = rays_d; a.bg = bg; a.noise = noise; a.lin_z = lin_z; a.lin_u = lin_u;
+    a.n_rays = op->n_rays; a.T0 = op->num_steps; a.nup = op->upsample_steps / 16;
+    a.inv_s = op->inv_s; a.inv_s_dev = op->inv_s_dev; a.car = op->cos_anneal_ratio; a.one_m_car = (float)(1.0 - (double)op->cos_anneal_ratio);
+    a.perturb = op->perturb; a.fast = op->precision;
+    a.near_m = op->near_m; a.far_m = op->far_m;
+    set_fd_eps(a, op->fd_eps);
+    return AC_OK;
+}
+
+// launch(FAST, EX, SH) with the three run-time switches as std::bool_constant: one kernel instantiation per combination
+template <class L>
+void dispatch_variants(bool fast, bool ex, bool sh, L &&launch)
+{
+    using T = std::true_type;
+    using F = std::false_type;
+    if (sh) { if (fast) { if (ex) launch(T{}, T{}, T{}); else launch(T{}, F{}, T{}); } else if (ex) launch(F{}, T{}, T{}); else launch(F{}, F{}, T{}); }
+    else { if (fast) { if (ex) launch(T{}, T{}, F{}); else launch(T{}, F{}, F{}); } else if (ex) launch(F{}, T{}, F{}); else launch(F{}, F{}, F{}); }
 }
 
 

@@ -436,6 +436,7 @@ __global__ __launch_bounds__(BLOCK) void render_rays_kernel(const RenderArgs a)
                 }
             }
             AC_TICK(3)
+            // (the stencil stays inline here, in render_long.hip and in sdf_train.hip's fd_forward: as one shared helper it changes the generated code)
             const float pc0 = sel4(g, px, py, pz, 0.0f);
             float spos = 0.0f;
             if constexpr (FAST) {
@@ -491,8 +492,8 @@ __global__ __launch_bounds__(BLOCK) void render_rays_kernel(const RenderArgs a)
             }
             AC_TICK(4)
             const float gx = gr[0], gy = gr[1], gz = gr[2];        // every lane of a sample holds the same finite-difference gradient
-            const float gn = __builtin_sqrtf((gx * gx + gy * gy) + gz * gz);
-            const float nx = gx / (1e-5f + gn), ny = gy / (1e-5f + gn), nz = gz / (1e-5f + gn);
+            const FdNormal nrm = fd_normal(gx, gy, gz);
+            const float gn = nrm.gn, nx = nrm.nx, ny = nrm.ny, nz = nrm.nz;
             float rgb[3] = { 0.0f, 0.0f, 0.0f };
             if (!skip && !a.opacity_only) {                      // (wave-uniform)
                 if constexpr (FC) color_tile_fast(lds, lane, px, py, pz, nx, ny, nz, oc, rgb, nullptr, 16, SH ? zs0 + SLAB_SHB : nullptr);
@@ -501,13 +502,7 @@ __global__ __launch_bounds__(BLOCK) void render_rays_kernel(const RenderArgs a)
             AC_TICK(5)
             // NeuS alpha :219-248
             const float sdf0 = oc[0];
-            const float tc = (dx * nx + dy * ny) + dz * nz;
-            const float a1 = dv_softplus100(lds + OFF_SPQ, -tc * 0.5f + 0.5f) * a.one_m_car;
-            const float a2 = dv_softplus100(lds + OFF_SPQ, -tc) * a.car;
-            const float iter_cos = -(a1 + a2);
-            const float half = iter_cos * delta * 0.5f;
-            const float pc = dv_sigmoid((sdf0 - half) * inv_s_core), nc = dv_sigmoid((sdf0 + half) * inv_s_core);
-            float alpha = clampf((pc - nc + 1e-5f) / (pc + 1e-5f), 0.0f, 1.0f);
+            float alpha = neus_alpha(lds, a, (dx * nx + dy * ny) + dz * nz, sdf0, delta, inv_s_core);
             if constexpr (MODE == MODE_FINAL) alpha = alpha * (a.mask[(size_t)ray * T + i] ? 1.0f : 0.0f);      // :246-249
             const float om = 1.0f - alpha + 1e-7f;
             // transmittance: exclusive tile scan with carry  :250
@@ -772,28 +767,15 @@ static int check_render_args(const char *who, const ac_render_opts *op, const fl
 static int fill_render_args(RenderArgs &a, const ac_field *field, const ac_render_opts *op, const float *rays_o, const float *rays_d,
                             const float *bg, const float *noise, const float *lin_z, const float *lin_u, const ac_render_out *out)
 {
-    if (int rc = fill_args(a, field, op->bound)) return rc;
-    a.rays_o = rays_o; a.rays_d = rays_d; a.bg = bg; a.noise = noise; a.lin_z = lin_z; a.lin_u = lin_u;
+    if (int rc = fill_render_common(a, field, op, rays_o, rays_d, bg, noise, lin_z, lin_u)) return rc;
     a.out = *out;
-    a.n_rays = op->n_rays; a.T0 = op->num_steps; a.nup = op->upsample_steps / 16;
     a.pair_n = 0; a.ex_from = 0; a.ex_rows = op->n_rays;
-    a.inv_s = op->inv_s; a.inv_s_dev = op->inv_s_dev; a.car = op->cos_anneal_ratio; a.one_m_car = (float)(1.0 - (double)op->cos_anneal_ratio);
-    a.eps = op->fd_eps; a.perturb = op->perturb;
     if (op->precision != 0 && op->precision != 1) { ac::set_error("ac_render_opts: precision %d unknown (0 = exact, 1 = fast)", op->precision); return AC_ERR_BAD_ARG; }
-    a.fast = op->precision;
     if (op->skip_masked != 0 && op->skip_masked != 1) { ac::set_error("ac_render_opts: skip_masked must be 0 or 1"); return AC_ERR_BAD_ARG; }
     a.skip_masked = op->skip_masked;
     if (op->opacity_only != 0 && op->opacity_only != 1) { ac::set_error("ac_render_opts: opacity_only must be 0 or 1"); return AC_ERR_BAD_ARG; }
     a.opacity_only = op->opacity_only;
     if ((op->near_m != nullptr) != (op->far_m != nullptr)) { ac::set_error("ac_render_opts: near_m and far_m go together"); return AC_ERR_BAD_ARG; }
-    a.near_m = op->near_m; a.far_m = op->far_m;
-    for (int j = 0; j < 4; ++j) {           // finite-difference reach in cells, per gather round (see encode_stencil)
-        a.jfine[j] = 0;
-        for (int g = 0; g < 4; ++g) {
-            const double cells = (double)op->fd_eps / (double)a.two_bound * (double)a.lvl[4 * j + g].scale;
-            if (!(cells * 1.001 + 1e-3 < 1.0)) a.jfine[j] = 1;
-        }
-    }
     return AC_OK;
 }
 
@@ -907,13 +889,10 @@ static void launch_render(const RenderArgs &a, hipStream_t stream)
 {
     const bool ex = wants_samples(a.out);
     if constexpr (MODE != MODE_UPSAMPLE) {          // (the sampling-only launch has no finite-difference stage)
-        if (a.Wsh) {                                // a field with view directions: its own instantiations (see the kernel's SH parameter)
-            if (a.fast) { if (ex) launch_render_p<MODE, true, true, true>(a, stream); else launch_render_p<MODE, true, false, true>(a, stream); return; }
-            if (ex) launch_render_p<MODE, false, true, true>(a, stream); else launch_render_p<MODE, false, false, true>(a, stream);
-            return;
-        }
-        if (a.fast) { if (ex) launch_render_p<MODE, true, true>(a, stream); else launch_render_p<MODE, true, false>(a, stream); return; }
-        if (ex) launch_render_p<MODE, false, true>(a, stream); else launch_render_p<MODE, false, false>(a, stream);
+        // a field with view directions has its own instantiations (see the kernel's SH parameter)
+        dispatch_variants(a.fast, ex, a.Wsh != nullptr, [&](auto fast, auto ex_, auto sh) {
+            launch_render_p<MODE, decltype(fast)::value, decltype(ex_)::value, decltype(sh)::value>(a, stream);
+        });
         return;
     }
     if (a.out.ss_inds || a.out.sort_index) launch_render_p<MODE, false, true>(a, stream);      // (the sampling-only launch can export the sample indices)

@@ -1,8 +1,9 @@
 // avatarcraft_amd/csrc/render_long.hip -- the fused Instant-NSR renderer for any sample count the reference accepts (ac_render_rays_long,
 // ac_sample_rays_long): num_steps >= 2 (not necessarily a multiple of 16), upsample_steps a multiple of 16, at most 512 samples per ray.
 //
-// The per-ray algorithm is render_rays_kernel's (render_fused.hip, MODE_FULL / MODE_UPSAMPLE) statement for statement: the same device blocks of
-// nsr_device.hpp, the same scans in the same order.  Where both renderers accept a sample count they agree bit for bit (tests/test_gpu_long_rays.py).
+// The per-ray algorithm is render_rays_kernel's (render_fused.hip, MODE_FULL / MODE_UPSAMPLE): the same device blocks of nsr_device.hpp
+// (fd_normal among them), the same scans in the same order; the blocks still written out in both kernels are marked where they stand.
+// Where both renderers accept a sample count they agree bit for bit (tests/test_gpu_long_rays.py).
 // What differs:
 //   * a wave's LDS slab holds 512 samples (AC_MAXT), so a workgroup has 7 waves instead of 8: 13 540 + 7 x 3 680 floats = 153.5 KiB of the 160 KiB
 //     (8 waves would need 168 KiB);
@@ -260,6 +261,7 @@ __global__ __launch_bounds__(BLOCK) void render_rays_long_kernel(const RenderArg
             {
             float fe0[4][2];
             encode_stencil(lds, fsl, fc, lane, px, py, pz, bxe, fe0);
+            // (render_rays_kernel's stencil, kept inline: as a shared helper it changes both renderers' code)
             const float pc0 = sel4(g, px, py, pz, 0.0f);
             float spos = 0.0f;
             if constexpr (FAST) {
@@ -310,12 +312,13 @@ __global__ __launch_bounds__(BLOCK) void render_rays_long_kernel(const RenderArg
             }
             }
             const float gx = gr[0], gy = gr[1], gz = gr[2];
-            const float gn = __builtin_sqrtf((gx * gx + gy * gy) + gz * gz);
-            const float nx = gx / (1e-5f + gn), ny = gy / (1e-5f + gn), nz = gz / (1e-5f + gn);
+            const FdNormal nrm = fd_normal(gx, gy, gz);
+            const float gn = nrm.gn, nx = nrm.nx, ny = nrm.ny, nz = nrm.nz;
             float rgb[3] = { 0.0f, 0.0f, 0.0f };
             if constexpr (FC) color_tile_fast(lds, lane, px, py, pz, nx, ny, nz, oc, rgb, nullptr, 16, SH ? zs0 + SLAB_SHB : nullptr);
             else color_tile(lds, lane, px, py, pz, nx, ny, nz, oc, rgb, nullptr, 16, SH ? zs0 + SLAB_SHB : nullptr);
             const float sdf0 = oc[0];
+            // (neus_alpha's arithmetic, inline: through the helper this kernel's code changes)
             const float tc = (dx * nx + dy * ny) + dz * nz;
             const float a1 = dv_softplus100(lds + OFF_SPQ, -tc * 0.5f + 0.5f) * a.one_m_car;
             const float a2 = dv_softplus100(lds + OFF_SPQ, -tc) * a.car;
@@ -399,25 +402,6 @@ static int check_long_args(const char *who, const ac_render_opts *op, const floa
     return AC_OK;
 }
 
-static int fill_long_args(RenderArgs &a, const ac_field *field, const ac_render_opts *op, const float *rays_o, const float *rays_d,
-                          const float *bg, const float *noise, const float *lin_z, const float *lin_u)
-{
-    if (int rc = fill_args(a, field, op->bound)) return rc;
-    a.rays_o = rays_o; a.rays_d = rays_d; a.bg = bg; a.noise = noise; a.lin_z = lin_z; a.lin_u = lin_u;
-    a.n_rays = op->n_rays; a.T0 = op->num_steps; a.nup = op->upsample_steps / 16;
-    a.inv_s = op->inv_s; a.inv_s_dev = op->inv_s_dev; a.car = op->cos_anneal_ratio; a.one_m_car = (float)(1.0 - (double)op->cos_anneal_ratio);
-    a.eps = op->fd_eps; a.perturb = op->perturb; a.fast = op->precision;
-    a.near_m = op->near_m; a.far_m = op->far_m;
-    for (int j = 0; j < 4; ++j) {           // finite-difference reach in cells, per gather round (as fill_render_args)
-        a.jfine[j] = 0;
-        for (int g = 0; g < 4; ++g) {
-            const double cells = (double)op->fd_eps / (double)a.two_bound * (double)a.lvl[4 * j + g].scale;
-            if (!(cells * 1.001 + 1e-3 < 1.0)) a.jfine[j] = 1;
-        }
-    }
-    return AC_OK;
-}
-
 template <int MODE, bool FAST, bool EX, bool SH>
 static void launch_long_p(const RenderArgs &a, hipStream_t stream)
 {
@@ -448,17 +432,12 @@ AC_API int ac_render_rays_long(const ac_field *field, const ac_render_opts *op, 
     if (op->n_rays <= 0) return AC_OK;
     if (!out->image || !out->weights_sum || !out->depth || !out->normal_map || !out->eik) { ac::set_error("render_rays_long: NULL buffer"); return AC_ERR_BAD_ARG; }
     RenderArgs a{};
-    if (int rc = fill_long_args(a, field, op, rays_o, rays_d, bg, noise, lin_z, lin_u)) return rc;
+    if (int rc = fill_render_common(a, field, op, rays_o, rays_d, bg, noise, lin_z, lin_u)) return rc;
     a.out = *out;
     const hipStream_t st = (hipStream_t)stream;
-    const bool ex = long_wants_samples(a.out);
-    if (a.Wsh) {
-        if (a.fast) { if (ex) launch_long_p<MODE_FULL, true, true, true>(a, st); else launch_long_p<MODE_FULL, true, false, true>(a, st); }
-        else { if (ex) launch_long_p<MODE_FULL, false, true, true>(a, st); else launch_long_p<MODE_FULL, false, false, true>(a, st); }
-    } else {
-        if (a.fast) { if (ex) launch_long_p<MODE_FULL, true, true, false>(a, st); else launch_long_p<MODE_FULL, true, false, false>(a, st); }
-        else { if (ex) launch_long_p<MODE_FULL, false, true, false>(a, st); else launch_long_p<MODE_FULL, false, false, false>(a, st); }
-    }
+    dispatch_variants(a.fast, long_wants_samples(a.out), a.Wsh != nullptr, [&](auto fast, auto ex, auto sh) {
+        launch_long_p<MODE_FULL, decltype(fast)::value, decltype(ex)::value, decltype(sh)::value>(a, st);
+    });
     if (int rc = ac::check_launch("render_rays_long")) return rc;
     // gradient_error in the fixed order the other renderer's last workgroup uses (eikonal_reduce_kernel's): bit-identical
     if (out->eik_reduced) return ac_eikonal_reduce2(out->eik, op->n_rays, out->eik_reduced, stream);
@@ -472,7 +451,7 @@ AC_API int ac_sample_rays_long(const ac_field *field, const ac_render_opts *op, 
     if (int rc = check_long_args("sample_rays_long", op, rays_o, rays_d, noise, lin_z, lin_u)) return rc;
     if (op->n_rays <= 0) return AC_OK;
     RenderArgs a{};
-    if (int rc = fill_long_args(a, field, op, rays_o, rays_d, nullptr, noise, lin_z, lin_u)) return rc;
+    if (int rc = fill_render_common(a, field, op, rays_o, rays_d, nullptr, noise, lin_z, lin_u)) return rc;
     a.zbuf = z_vals;
     launch_long_p<MODE_UPSAMPLE, false, false, false>(a, (hipStream_t)stream);
     return ac::check_launch("sample_rays_long");

@@ -112,6 +112,7 @@ __device__ __forceinline__ void softplus100_vg4(const float *__restrict__ spg, c
 }
 
 // the 7 evaluations of one tile: centre outputs (o = 4g + r) and the finite-difference gradient (the same in all four lanes of a sample)
+// (the renderers' exact stencil; they keep their own copy inline, because one helper shared with them changes the generated code)
 __device__ __forceinline__ void fd_forward(const float *__restrict__ lds, const float *__restrict__ fsl, int lane, float px, float py, float pz,
                                            float eps, float bound, const float (&fe0)[4][2], f32x4 &oc, float (&gr)[3])
 {
@@ -699,8 +700,8 @@ __global__ __launch_bounds__(FBLOCK) void field_samples_kernel(const RenderArgs 
         f32x4 oc; float gr[3];
         fd_forward(lds, fsl, lane, px, py, pz, eps, bound, fe0, oc, gr);
         const float gx = gr[0], gy = gr[1], gz = gr[2];
-        const float gn = __builtin_sqrtf((gx * gx + gy * gy) + gz * gz);
-        const float nx = gx / (1e-5f + gn), ny = gy / (1e-5f + gn), nz = gz / (1e-5f + gn);
+        const FdNormal nrm = fd_normal(gx, gy, gz);
+        const float gn = nrm.gn, nx = nrm.nx, ny = nrm.ny, nz = nrm.nz;
         float rgb[3];
         if (a.Wsh) {                                                 // use_viewdirs: the layer-1 bias of THIS sample's direction (wave-uniform branch)
             wave_sync();                                             // (every lane is done with the feature slab)
@@ -709,6 +710,7 @@ __global__ __launch_bounds__(FBLOCK) void field_samples_kernel(const RenderArgs 
         } else color_tile(lds, lane, px, py, pz, nx, ny, nz, oc, rgb);
         // NeuS alpha, instant_nsr.py:219-243 with the marcher's step as the section length
         const float sdf0 = oc[0];
+        // (neus_alpha's arithmetic, inline: through the helper these kernels' code changes)
         const float tc = (dx * nx + dy * ny) + dz * nz;
         const float a1 = dv_softplus100(lds + OFF_SPQ, -tc * 0.5f + 0.5f) * a.one_m_car;
         const float a2 = dv_softplus100(lds + OFF_SPQ, -tc) * a.car;
@@ -835,8 +837,8 @@ __global__ __launch_bounds__(FBLOCK) void occupancy_render_kernel(const RenderAr
                 f32x4 o16; float gr[3];
                 fd_forward(lds, fsl, lane, px, py, pz, eps, bound, fe0, o16, gr);
                 const float gx = gr[0], gy = gr[1], gz = gr[2];
-                const float gn = __builtin_sqrtf((gx * gx + gy * gy) + gz * gz);
-                const float nx = gx / (1e-5f + gn), ny = gy / (1e-5f + gn), nz = gz / (1e-5f + gn);
+                const FdNormal nrm = fd_normal(gx, gy, gz);
+                const float gn = nrm.gn, nx = nrm.nx, ny = nrm.ny, nz = nrm.nz;
                 float rgb[3];
                 if (a.Wsh) {
                     wave_sync();
@@ -844,11 +846,11 @@ __global__ __launch_bounds__(FBLOCK) void occupancy_render_kernel(const RenderAr
                     color_tile(lds, lane, px, py, pz, nx, ny, nz, o16, rgb, fsl + 4 * lane, 256);
                 } else color_tile(lds, lane, px, py, pz, nx, ny, nz, o16, rgb);
                 const float tcos = (dx * nx + dy * ny) + dz * nz;
-                const float a1 = dv_softplus100(lds + OFF_SPQ, -tcos * 0.5f + 0.5f) * a.one_m_car;
-                const float a2 = dv_softplus100(lds + OFF_SPQ, -tcos) * a.car;
-                const float half = -(a1 + a2) * delta * 0.5f;
-                const float pc = dv_sigmoid((o16[0] - half) * inv_s), nc = dv_sigmoid((o16[0] + half) * inv_s);
-                const float alpha = clampf((pc - nc + 1e-5f) / (pc + 1e-5f), 0.0f, 1.0f);
+            const float a1 = dv_softplus100(lds + OFF_SPQ, -tcos * 0.5f + 0.5f) * a.one_m_car;
+            const float a2 = dv_softplus100(lds + OFF_SPQ, -tcos) * a.car;
+            const float half = -(a1 + a2) * delta * 0.5f;
+            const float pc = dv_sigmoid((o16[0] - half) * inv_s), nc = dv_sigmoid((o16[0] + half) * inv_s);
+            const float alpha = clampf((pc - nc + 1e-5f) / (pc + 1e-5f), 0.0f, 1.0f);
                 wave_sync();                                                         // every lane has read its inputs: the slots become outputs
                 if (g == 0 && ci < cnt) {
                     float *so = stage + 8 * slot;
@@ -1047,8 +1049,8 @@ __global__ __launch_bounds__(FBLOCK) void occupancy_train_kernel(const RenderArg
             f32x4 o16; float gr[3];
             fd_forward(lds, fsl, lane, px, py, pz, eps, bound, fe0, o16, gr);
             const float gx = gr[0], gy = gr[1], gz = gr[2];
-            const float gn = __builtin_sqrtf((gx * gx + gy * gy) + gz * gz);
-            const float nx = gx / (1e-5f + gn), ny = gy / (1e-5f + gn), nz = gz / (1e-5f + gn);
+            const FdNormal nrm = fd_normal(gx, gy, gz);
+            const float gn = nrm.gn, nx = nrm.nx, ny = nrm.ny, nz = nrm.nz;
             float rgb[3];
             if (a.Wsh) {
                 wave_sync();
@@ -1254,8 +1256,8 @@ __global__ __launch_bounds__(FBLOCK) void occupancy_phased_kernel(const RenderAr
             f32x4 o16; float gr[3];
             fd_forward(lds, fsl, lane, px, py, pz, eps, bound, fe0, o16, gr);
             const float gx = gr[0], gy = gr[1], gz = gr[2];
-            const float gn = __builtin_sqrtf((gx * gx + gy * gy) + gz * gz);
-            const float nx = gx / (1e-5f + gn), ny = gy / (1e-5f + gn), nz = gz / (1e-5f + gn);
+            const FdNormal nrm = fd_normal(gx, gy, gz);
+            const float gn = nrm.gn, nx = nrm.nx, ny = nrm.ny, nz = nrm.nz;
             float rgb[3];
             if (a.Wsh) {
                 wave_sync();
@@ -1866,14 +1868,7 @@ uint32_t train_grid(uint32_t B)
 int prep_args(RenderArgs &a, const ac_field *field, float bound, float eps)
 {
     if (int rc = fill_args(a, field, bound)) return rc;
-    a.eps = eps;
-    for (int j = 0; j < 4; ++j) {
-        a.jfine[j] = 0;
-        for (int g = 0; g < 4; ++g) {
-            const double cells = (double)eps / (double)a.two_bound * (double)a.lvl[4 * j + g].scale;
-            if (!(cells * 1.001 + 1e-3 < 1.0)) a.jfine[j] = 1;
-        }
-    }
+    set_fd_eps(a, eps);
     return AC_OK;
 }
 
