@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the AvatarCraft hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -12,16 +12,22 @@ reduce) over one 4096-ray batch; step k renders batch k % 16 of the view.  Input
 MLP weights) are resident in HBM before the timed region.  value = rays / s over all ranks (weak scaling:
 every rank renders its own view, no data-path collective -- rays are independent).
 
-Printed JSON (rank 0, one line) carries the contract fields plus
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: nothing else runs on the GPU or the
+CPU.  Printed JSON (rank 0, one line) carries the contract fields plus
   roofline     : dominant kernel (render_rays_kernel) against the HBM roofline with the ALGORITHMIC bytes of
                  SURVEY 8(d): 1 032 192 gather bytes per ray (1008 hash evals x 1024 B) x 4096 rays per launch,
-                 divided by the mean launch duration measured with HIP events on the launch stream.
+                 divided by the mean launch duration measured with HIP events on the launch stream (the timed steps' own).
+--full adds everything that takes runs of its own:
+  roofline.other_precision, roofline.whole_view_in_one_launch : the same kernel in the other arithmetic mode, and on the whole view
+                 in one launch.
   cpu_baseline : the CPU oracle (oracle/, a port of the reference algorithm; OpenMP over rays) timed on this
                  host on a bounded sample of the same workload.  A reported baseline, not the target.
+  the further workloads (sds_step, sds_view_fine, posed_frame, viewdirs, mesh_export_512, density_grid_update, occupancy_render,
+                 the guidance stand-in, real_sd) and, on N > 1, same_job_solo.  The options that choose or skip
+                 them (--sds-steps, --posed-frames, --no-* ...) take effect only with --full.
 
 This file holds the contract: arguments, the timed region of the headline metric, the JSON line.  Every further workload
-the line reports (sds_step, sds_view_fine, posed_frame, viewdirs, mesh_export_512, density_grid_update, occupancy_render,
-the guidance stand-in, the CPU baselines) and the `--gpus N` self-launcher live in bench_legs/, one module each.
+and the `--gpus N` self-launcher live in bench_legs/, one module each.
 """
 import argparse
 import json
@@ -93,6 +99,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=8)
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure everything else the line can report: the other precision, the "
+                                                        "whole view in one launch, the SDS step, the bench_legs/ workloads, the CPU baselines, the real-SD "
+                                                        "probe and, on N > 1, the same-job solo figures (the options below that choose or skip them act "
+                                                        "only with --full)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-prepared-field", action="store_true", help="A/B: every render workgroup derives the LDS weight layout itself (no ac_field_prepare)")
     ap.add_argument("--precision", choices=["fast", "exact"], default="exact",
@@ -104,7 +114,7 @@ def main():
                                                            "eik_res, gradient_error of the 4096-ray batch) as DIR/<name>.npy in float32; rank 0 only")
     ap.add_argument("--sds-steps", type=int, default=8, help="also time this many 4096-ray SDS steps (secondary metric); 0 = skip")
     ap.add_argument("--real-sd", action="store_true", help="time one SDS step with the real Stable-Diffusion guidance if diffusers + the weights are on this "
-                                                           "machine (the line's real_sd field says why not otherwise; the probe itself always runs)")
+                                                           "machine (the line's real_sd field says why not otherwise; the probe itself runs in every --full run)")
     ap.add_argument("--sd-arch-steps", type=int, default=2, help="time this many SDS steps with a guidance of Stable-Diffusion 1.5's architecture (random weights: "
                                                                   "what the step costs once the real UNet is in it); 0 = skip")
     ap.add_argument("--no-occupancy", action="store_true", help="skip the occupancy-grid render leg (render(cuda_ray=True): a separate figure beside the headline)")
@@ -143,7 +153,7 @@ def main():
     if not a.no_prepared_field:
         field.prepare()                 # the weights in LDS order, once (like NeRFRenderer does per parameter version)
     solo = None
-    if world > 1:
+    if world > 1 and a.full:
         # BEFORE the process group exists: what this very GPU does on its own in this very job (the same launches as the timed region below, the same SDS
         # steps without a collective) -- the N = 1 reference of an N > 1 line measured on the same box, clocks and build (`same_job_solo`; the driver
         # computes the scaling efficiency it reports from its own separate N = 1 run)
@@ -204,30 +214,31 @@ def main():
         dump_outputs(outs[(a.steps - 1) % nb], a.dump_outputs)
     order = sorted(range(len(regions)), key=lambda i: regions[i][0])
     dt, dt_rank_min, kern_ms = regions[order[len(order) // 2]]
-    # the same launches in the OTHER arithmetic mode, outside the timed region (rank 0 reports it next to the headline: `exact` is bit-identical to the
-    # CPU oracle, `fast` keeps sample positions / indices / sdf bit-identical and moves pixels by ~1e-6)
     other = "exact" if a.precision == "fast" else "fast"
-    ev2 = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.steps)]
-    for k in range(min(a.warmup, 2)):
-        nsr_ops.render_rays(field, ro_t[:RAYS_PER_BATCH], rd_t[:RAYS_PER_BATCH], NUM_STEPS, UPSAMPLE_STEPS, 1.6, inv_s, out=outs[0], precision=other)
-    for k in range(a.steps):
-        b = k % nb
-        sl = slice(b * RAYS_PER_BATCH, (b + 1) * RAYS_PER_BATCH)
-        nsr_ops.render_rays(field, ro_t[sl], rd_t[sl], NUM_STEPS, UPSAMPLE_STEPS, 1.6, inv_s, out=outs[b], events=ev2[k], precision=other)
-    torch.cuda.synchronize()
-    other_ms = float(np.mean([s.elapsed_time(e) for s, e in ev2]))
-    # informational: the same 65 536 rays of the view in ONE launch (the interface takes any ray count; the reference batches by 4096 to bound its
-    # memory).  A 4096-ray launch is two rays per wave slot and ends with its slowest pair; sixteen times more rays per launch average that out.
-    view_out = {}
-    wev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(3)]
-    for k in range(4):
-        nsr_ops.render_rays(field, ro_t, rd_t, NUM_STEPS, UPSAMPLE_STEPS, 1.6, inv_s, out=view_out, events=wev[k - 1] if k else None, precision=a.precision)
-    torch.cuda.synchronize()
-    view_ms = float(np.mean([s.elapsed_time(e) for s, e in wev]))
-    del view_out
+    if a.full:
+        # the same launches in the OTHER arithmetic mode, outside the timed region (rank 0 reports it next to the headline: `exact` is bit-identical to the
+        # CPU oracle, `fast` keeps sample positions / indices / sdf bit-identical and moves pixels by ~1e-6)
+        ev2 = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.steps)]
+        for k in range(min(a.warmup, 2)):
+            nsr_ops.render_rays(field, ro_t[:RAYS_PER_BATCH], rd_t[:RAYS_PER_BATCH], NUM_STEPS, UPSAMPLE_STEPS, 1.6, inv_s, out=outs[0], precision=other)
+        for k in range(a.steps):
+            b = k % nb
+            sl = slice(b * RAYS_PER_BATCH, (b + 1) * RAYS_PER_BATCH)
+            nsr_ops.render_rays(field, ro_t[sl], rd_t[sl], NUM_STEPS, UPSAMPLE_STEPS, 1.6, inv_s, out=outs[b], events=ev2[k], precision=other)
+        torch.cuda.synchronize()
+        other_ms = float(np.mean([s.elapsed_time(e) for s, e in ev2]))
+        # informational: the same 65 536 rays of the view in ONE launch (the interface takes any ray count; the reference batches by 4096 to bound its
+        # memory).  A 4096-ray launch is two rays per wave slot and ends with its slowest pair; sixteen times more rays per launch average that out.
+        view_out = {}
+        wev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(3)]
+        for k in range(4):
+            nsr_ops.render_rays(field, ro_t, rd_t, NUM_STEPS, UPSAMPLE_STEPS, 1.6, inv_s, out=view_out, events=wev[k - 1] if k else None, precision=a.precision)
+        torch.cuda.synchronize()
+        view_ms = float(np.mean([s.elapsed_time(e) for s, e in wev]))
+        del view_out
 
     sds = None
-    if a.sds_steps > 0:
+    if a.full and a.sds_steps > 0:
         try:                                   # secondary metric: never let it take the headline line down with it
             sds, _nets = time_sds_step(dev, p, table, rank, world, dist, a.sds_steps)
             del _nets
@@ -272,7 +283,7 @@ def main():
                                           "bit for bit; fast (opt-in): fp32 everywhere except layer 1 of the six finite-difference SDF evaluations (a split-bf16, "
                                           "hi + lo, 3-product correction of the exact fp32 centre evaluation) and the colour network (split-bf16 x 3); sample "
                                           "positions, indices and sdf bit-identical to exact mode, pixels within 4e-6; the other mode's timing is in "
-                                          "roofline.other_precision")},
+                                          "roofline.other_precision (--full)")},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                          "traffic": traffic, "traffic_source": "rocprofv3 --pmc FETCH_SIZE pass of this command at the commit named in profiles/traffic.json (not re-measured in this run)",
                          "traffic_note": traffic_note, "kernel": "render_rays_kernel", "kernel_ms": kern_ms,
@@ -288,63 +299,65 @@ def main():
                          # committed PMC pass of this workload (tools/collect_profiles.py: busy_objects), not re-measured in this run
                          "issue": (dict(binding["issue"], source=binding_src) if binding and "issue" in binding else None),
                          "gather": (dict(binding["gather"], l2_sector_bytes_per_launch=binding.get("l2_sector_bytes_per_launch"), source=binding_src)
-                                    if binding and "gather" in binding else None),
-                         "other_precision": {"precision": other, "kernel_ms": other_ms, "rays_per_s_per_gpu": RAYS_PER_BATCH / (other_ms * 1e-3),
-                                             "frac": BYTES_PER_RAY * RAYS_PER_BATCH / (other_ms * 1e-3) / 1e9 / HBM_PEAK_GBS},
-                         "whole_view_in_one_launch": {"rays": H * W, "kernel_ms": view_ms, "rays_per_s_per_gpu": H * W / (view_ms * 1e-3),
-                                                      "frac": BYTES_PER_RAY * H * W / (view_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                                      "note": "informational, not the metric's 4096-ray batch"}},
+                                    if binding and "gather" in binding else None)},
         }
+        if a.full:
+            res["roofline"]["other_precision"] = {"precision": other, "kernel_ms": other_ms, "rays_per_s_per_gpu": RAYS_PER_BATCH / (other_ms * 1e-3),
+                                                  "frac": BYTES_PER_RAY * RAYS_PER_BATCH / (other_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
+            res["roofline"]["whole_view_in_one_launch"] = {"rays": H * W, "kernel_ms": view_ms, "rays_per_s_per_gpu": H * W / (view_ms * 1e-3),
+                                                           "frac": BYTES_PER_RAY * H * W / (view_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                                           "note": "informational, not the metric's 4096-ray batch"}
         if sds is not None:
             res["sds_step"] = sds
             if world == 1 and not a.no_fp32_records:
                 fr = time_sds_step_fp32_records(a.sds_steps)
                 sds["ms_per_step_fp32_records"] = fr.get("ms_per_step")
                 sds["fp32_records"] = fr
-        # the further workloads of the line (bench_legs/): each in its own try -- a failing leg reports its error in place and the line is still printed --
-        # and with its wall time in leg_seconds (what the default run spends where: VERDICT round 5, What's weak 6)
-        leg_s = {}
+        if a.full:
+            # the further workloads of the line (bench_legs/): each in its own try -- a failing leg reports its error in place and the line is still printed --
+            # and with its wall time in leg_seconds (what a --full run spends where: VERDICT round 5, What's weak 6)
+            leg_s = {}
 
-        def leg(name, fn, trace=500):
-            t_leg = time.perf_counter()
+            def leg(name, fn, trace=500):
+                t_leg = time.perf_counter()
+                try:
+                    out = fn()
+                except Exception as e:             # noqa: BLE001
+                    import traceback
+                    out = {"error": f"{type(e).__name__}: {e}", "trace": traceback.format_exc()[-trace:]}
+                leg_s[name] = round(time.perf_counter() - t_leg, 2)
+                return out
+            if sds is not None and "fp32_records" in sds:
+                leg_s["sds_step_fp32_records (child process)"] = sds["fp32_records"].pop("seconds", None)
+            if world == 1 and a.posed_frames > 0:
+                res["posed_frame"] = leg("posed_frame", lambda: time_posed_frame(dev, p, table, a.posed_frames, cpu=not a.no_cpu_baseline))
+            if world == 1 and not a.no_cpu_baseline:
+                res["cpu_baseline"] = leg("cpu_baseline", lambda: cpu_baseline(p, table, ro, rd))
+            if world == 1 and not a.no_occupancy:
+                res["occupancy_render"] = leg("occupancy_render", lambda: time_occupancy_render(dev, p, table, ro_t, rd_t))
+            if world == 1 and a.sds_steps > 0 and not a.no_fine_view:
+                res["sds_view_fine"] = leg("sds_view_fine", lambda: time_sds_fine_view(dev, p, table, whole_view_backward=a.whole_view_backward), 600)
+            if world == 1 and not a.no_viewdirs:
+                def _vd():
+                    v = time_viewdirs(dev, p, table, ro_t, rd_t)
+                    v["render_vs_default"] = v["render_kernel_ms_per_4096_rays"] / kern_ms
+                    if sds is not None and "error" not in sds:
+                        v["sds_step_vs_default"] = v["sds_step_ms"] / sds["ms_per_step"]
+                    return v
+                res["viewdirs"] = leg("viewdirs", _vd, 600)
+            if world == 1 and not a.no_geometry:
+                g = leg("geometry", lambda: time_geometry(dev, p, table), 600)
+                res.update(g if "error" not in g else {"mesh_export_512": g})
+            if world == 1 and a.sd_arch_steps > 0:
+                res["sds_step_sd_arch_standin"] = leg("sds_step_sd_arch_standin", lambda: time_sd_arch_step(dev, p, table, a.sd_arch_steps, variants=a.sd_arch_variants))
+            res["leg_seconds"] = leg_s
             try:
-                out = fn()
-            except Exception as e:             # noqa: BLE001
-                import traceback
-                out = {"error": f"{type(e).__name__}: {e}", "trace": traceback.format_exc()[-trace:]}
-            leg_s[name] = round(time.perf_counter() - t_leg, 2)
-            return out
-        if sds is not None and "fp32_records" in sds:
-            leg_s["sds_step_fp32_records (child process)"] = sds["fp32_records"].pop("seconds", None)
-        if world == 1 and a.posed_frames > 0:
-            res["posed_frame"] = leg("posed_frame", lambda: time_posed_frame(dev, p, table, a.posed_frames, cpu=not a.no_cpu_baseline))
-        if world == 1 and not a.no_cpu_baseline:
-            res["cpu_baseline"] = leg("cpu_baseline", lambda: cpu_baseline(p, table, ro, rd))
-        if world == 1 and not a.no_occupancy:
-            res["occupancy_render"] = leg("occupancy_render", lambda: time_occupancy_render(dev, p, table, ro_t, rd_t))
-        if world == 1 and a.sds_steps > 0 and not a.no_fine_view:
-            res["sds_view_fine"] = leg("sds_view_fine", lambda: time_sds_fine_view(dev, p, table, whole_view_backward=a.whole_view_backward), 600)
-        if world == 1 and not a.no_viewdirs:
-            def _vd():
-                v = time_viewdirs(dev, p, table, ro_t, rd_t)
-                v["render_vs_default"] = v["render_kernel_ms_per_4096_rays"] / kern_ms
-                if sds is not None and "error" not in sds:
-                    v["sds_step_vs_default"] = v["sds_step_ms"] / sds["ms_per_step"]
-                return v
-            res["viewdirs"] = leg("viewdirs", _vd, 600)
-        if world == 1 and not a.no_geometry:
-            g = leg("geometry", lambda: time_geometry(dev, p, table), 600)
-            res.update(g if "error" not in g else {"mesh_export_512": g})
-        if world == 1 and a.sd_arch_steps > 0:
-            res["sds_step_sd_arch_standin"] = leg("sds_step_sd_arch_standin", lambda: time_sd_arch_step(dev, p, table, a.sd_arch_steps, variants=a.sd_arch_variants))
-        res["leg_seconds"] = leg_s
-        try:
-            from avatarcraft_amd.guidance import real_sd_probe
-            ok_sd, why_sd = real_sd_probe("1.5")
-            res["real_sd"] = (time_real_sd_step(dev, p, table) if (ok_sd and a.real_sd) else
-                              (f"available ({why_sd}); pass --real-sd to time it" if ok_sd else f"absent: {why_sd}"))
-        except Exception as e:                 # noqa: BLE001
-            res["real_sd"] = f"error: {type(e).__name__}: {e}"
+                from avatarcraft_amd.guidance import real_sd_probe
+                ok_sd, why_sd = real_sd_probe("1.5")
+                res["real_sd"] = (time_real_sd_step(dev, p, table) if (ok_sd and a.real_sd) else
+                                  (f"available ({why_sd}); pass --real-sd to time it" if ok_sd else f"absent: {why_sd}"))
+            except Exception as e:                 # noqa: BLE001
+                res["real_sd"] = f"error: {type(e).__name__}: {e}"
         res["hsa_ipc_mode_legacy"] = {"value": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY"),
                                       "set_by": os.environ.get("AC_BENCH_IPC_NOTE", "the environment of this process (not bench.py's launcher)")}
         if solo is not None:

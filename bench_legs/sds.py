@@ -136,7 +136,7 @@ def time_sds_step_fp32_records(steps):
     env = dict(os.environ, AC_LIB_PATH=so)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--repeat", "1", "--sds-steps", str(int(steps)), "--posed-frames", "0",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "4", "--warmup", "2", "--repeat", "1", "--sds-steps", str(int(steps)), "--posed-frames", "0",
            "--no-cpu-baseline", "--no-occupancy", "--sd-arch-steps", "0", "--no-fine-view", "--no-viewdirs", "--no-geometry", "--no-fp32-records"]
     t0 = time.perf_counter()
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)

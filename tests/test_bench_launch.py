@@ -88,7 +88,7 @@ def test_gpus_without_world_size_goes_to_the_launcher(monkeypatch):
 def test_bench_gpus_2_self_launched_over_gloo_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env["AC_DIST_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--repeat", "1", "--sds-steps", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--repeat", "1", "--sds-steps", "1",
                         "--posed-frames", "0"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     rec = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
@@ -124,7 +124,7 @@ def test_bench_line_names_its_binding_resources_and_no_frac_exceeds_one():
     """the driver's line carries roofline.issue (VALU + fp32-MFMA issue busy fraction) and roofline.gather (per-CU texture-address
     path) from the committed counter pass, the regular-grid kernels' fraction is taken against the 64-byte sectors actually requested of L2, and no `frac`
     anywhere in the record exceeds 1"""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--repeat", "1", "--sds-steps", "1", "--posed-frames", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "4", "--warmup", "2", "--repeat", "1", "--sds-steps", "1", "--posed-frames", "0",
                         "--no-cpu-baseline", "--no-occupancy", "--no-viewdirs", "--no-fine-view", "--sd-arch-steps", "0"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -136,3 +136,22 @@ def test_bench_line_names_its_binding_resources_and_no_frac_exceeds_one():
     assert not over, over
     m = rec["mesh_export_512"]["roofline"]
     assert m["frac"] <= 1.0 and m["request_rate_vs_hbm_peak"] > 0 and "issue" in m
+
+
+@pytest.mark.gpu
+def test_plain_bench_runs_only_the_headline(tmp_path):
+    """without --full the run sets up, warms up, times the steps, dumps the outputs and prints the contract line; nothing that takes runs of its own"""
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--dump-outputs", str(out)],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    rec = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
+    assert rec["unit"] == "rays/s" and rec["higher_is_better"] is True and rec["dtype"] == "f32" and rec["metric"].startswith("rays/sec, 4096-ray batch")
+    assert rec["steps"] == 4 and rec["warmup"] == 2 and rec["repeat"] == 5 and rec["n_gpus"] == 1
+    assert rec["ms_per_step"] > 0 and rec["value"] == pytest.approx(4096 / (rec["ms_per_step"] * 1e-3), rel=1e-9)
+    assert rec["roofline"]["kernel_ms"] > 0 and 0 < rec["roofline"]["frac"] <= 1
+    full_only = {"sds_step", "posed_frame", "cpu_baseline", "occupancy_render", "sds_view_fine", "viewdirs", "mesh_export_512", "density_grid_update",
+                 "sds_step_sd_arch_standin", "leg_seconds", "real_sd", "same_job_solo"}
+    assert not full_only & set(rec), full_only & set(rec)
+    assert "other_precision" not in rec["roofline"] and "whole_view_in_one_launch" not in rec["roofline"]
+    assert "image.npy" in os.listdir(out)

@@ -3,7 +3,7 @@ profiles/traffic.json from its PMC passes.
 
     python tools/collect_profiles.py r02a [--round r02]
 
-Writes profiles/<round>_kernel_stats.csv (rocprofv3 --kernel-trace --stats of the default `python bench.py --steps 20 --warmup 5`),
+Writes profiles/<round>_kernel_stats.csv (rocprofv3 --kernel-trace --stats of `python bench.py --full --steps 20 --warmup 5`),
 <round>_kernel_stats_by_workload.json (the same trace split by the bench's three workloads: the render kernel serves all of them),
 <round>_pmc_summary.json (per-kernel means of every PMC group), <round>_bench.json (the JSON line printed under the profiler)
 and traffic.json."""
@@ -188,12 +188,12 @@ def main():
         "sds_step_hbm_bytes_per_step": int(sum(parts.values())),
         "sds_step_by_kernel": {k: int(v) for k, v in parts.items()},
         "commit": head, "profile": f"tools/prof_{rnd}.sh {tag} -> profiles/{rnd}_pmc_summary.json",
-        "command": f"bench.py --steps {pb['steps']} --warmup {pb['warmup']} --sds-steps 2 --posed-frames 1 --repeat 1 under rocprofv3 --pmc (one pass per counter group)",
+        "command": f"bench.py --full --steps {pb['steps']} --warmup {pb['warmup']} --sds-steps 2 --posed-frames 1 --repeat 1 under rocprofv3 --pmc (one pass per counter group)",
         "render_rays_kernel_mfma_busy_frac": mfma_busy,
         "fetch_size_note": ("FETCH_SIZE = TCC_EA0_RDREQ x 64 B on gfx950; calibrated for THIS access pattern (8-byte gathers, one 64-byte sector per L2 miss: "
                             "profiles/r01_fetch_calibration.txt) -> factor 1.0 used; the guide's x2 correction applies to wide coalesced streaming reads "
                             "(128-byte requests tallied at 64 B), which this kernel does not issue -- with x2 the figure would still be below the algorithmic bytes"),
-        "_note": (f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (one pass each) on `bench.py --steps {pb['steps']} --warmup {pb['warmup']} --sds-steps 2 "
+        "_note": (f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (one pass each) on `bench.py --full --steps {pb['steps']} --warmup {pb['warmup']} --sds-steps 2 "
                   f"--posed-frames 1`. render: mean FETCH_SIZE of the {n_main} main-bench dispatches of {rk} (KB x 1024; WRITE_SIZE "
                   f"{mean(write[rk][:n_main]):.0f} KB). sds_step: FETCH_SIZE + WRITE_SIZE of the HIP kernels of one step (three renders of the training "
                   "view + the kernels of ac_render_core_backward); torch's Adam / loss kernels (~0.4 GB) not included. Calibration as in round 1 "

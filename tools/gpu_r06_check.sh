@@ -3,7 +3,7 @@ cd $GRAFT_REPO_ROOT; O=gpurun_out/r06_${1:-check}; mkdir -p $O
 timeout 1500 python -m pytest tests -m gpu -q --maxfail=15 -p no:cacheprovider -rs ${2:+-k "$2"} > $O/pytest.log 2>&1; echo "pytest rc $?" | tee $O/pytest.rc
 grep -n "passed\|failed\|SKIPPED" $O/pytest.log | tail -5; grep -n "^E  " $O/pytest.log | cut -c1-300 | head -30
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc $?"; tail -c 300 $O/bench.err
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc $?"; tail -c 300 $O/bench.err
 python - <<PY
 import json
 r=json.loads(open("$O/bench.json").read().strip().splitlines()[-1])

@@ -1,7 +1,7 @@
 # instruction-cache counters of the big kernels (separate --pmc pass, kernel trace off)
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_icache; rm -rf $O; mkdir -p $O
-B="python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --sds-steps 2 --posed-frames 0"
+B="python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --sds-steps 2 --posed-frames 0"
 rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE --output-format csv -d $O/a -o p -- $B > $O/a.log 2>&1
 rocprofv3 --pmc SQ_IFETCH SQ_IFETCH_LEVEL SQ_WAIT_INST_ANY SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_WAIT_ANY SQ_ACTIVE_INST_ANY --output-format csv -d $O/b -o p -- $B > $O/b.log 2>&1
 python - <<PY

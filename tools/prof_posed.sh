@@ -1,7 +1,7 @@
 # rocprofv3 kernel stats of posed frames (render_warp configuration)
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_posed; rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o p -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --sds-steps 0 --posed-frames 3 > $O/kt.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o p -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --sds-steps 0 --posed-frames 3 > $O/kt.log 2>&1
 tail -1 $O/kt.log | python -c "import sys,json; print(json.loads(sys.stdin.read())['posed_frame'])"
 python - <<PY
 import csv

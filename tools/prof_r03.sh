@@ -2,8 +2,8 @@
 #   bash tools/prof_r03.sh <tag>      -> gpurun_out/prof_<tag>/{kt,...}/, summary.json, traffic.json
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_$1; rm -rf $O; mkdir -p $O
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o p -- python $R/bench.py --steps 20 --warmup 5 > $O/kt_bench.json 2> $O/kt.log
-B="python $R/bench.py --steps 8 --warmup 2 --no-cpu-baseline --sds-steps 2 --posed-frames 1 --repeat 1"
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o p -- python $R/bench.py --full --steps 20 --warmup 5 > $O/kt_bench.json 2> $O/kt.log
+B="python $R/bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --sds-steps 2 --posed-frames 1 --repeat 1"
 i=0
 for grp in "FETCH_SIZE" "WRITE_SIZE" \
            "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY" \

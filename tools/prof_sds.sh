@@ -2,7 +2,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_sds; rm -rf $O; mkdir -p $O
 N=${1:-4}
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o p -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --sds-steps $N --posed-frames 0 > $O/kt.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o p -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --sds-steps $N --posed-frames 0 > $O/kt.log 2>&1
 python - <<PY
 import csv
 rows=list(csv.DictReader(open("$O/kt/p_kernel_stats.csv")))

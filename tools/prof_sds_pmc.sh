@@ -1,7 +1,7 @@
 # PMC counters of the training kernels (own passes, kernel-trace separate): tools/prof_sds_pmc.sh
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_sds_pmc; rm -rf $O; mkdir -p $O
-B="python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --sds-steps 2 --posed-frames 0"
+B="python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --sds-steps 2 --posed-frames 0"
 rocprofv3 --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --output-format csv -d $O/sq -o p -- $B > $O/sq.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -o p -- $B > $O/fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -o p -- $B > $O/write.log 2>&1

@@ -7,7 +7,7 @@ KERNELS=${KERNELS:-binned|bucket_acc|sdf_stencil_bwd|color_bwd|render_rays}
 for n in "$@"; do
   lib=$R/tools/_bin/lib_$n.so; [ "$n" = "head" ] && lib=$R/avatarcraft_amd/libavatarcraft_hip.so
   rm -rf $O/kt_$n
-  AC_LIB_PATH=$lib timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$n -o p -- python $R/bench.py $BENCH_ARGS > $O/kt_$n.log 2>&1
+  AC_LIB_PATH=$lib timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$n -o p -- python $R/bench.py --full $BENCH_ARGS > $O/kt_$n.log 2>&1
   python - "$n" "$O/kt_$n" "$KERNELS" "$O/kt_$n.log" <<'PY'
 import csv, re, sys, glob, json
 n, d, pat, log = sys.argv[1:5]

@@ -1,7 +1,7 @@
 # wait-state / issue counters of the hot kernels (each --pmc group is its own pass): tools/prof_waits.sh <tag>
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/waits_$1; rm -rf $O; mkdir -p $O
-B="python $R/bench.py --steps 4 --warmup 1 --no-cpu-baseline --sds-steps 2 --posed-frames 1"
+B="python $R/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --sds-steps 2 --posed-frames 1"
 i=0
 for grp in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS" \
            "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA" \

@@ -5,7 +5,7 @@ BENCH_ARGS=${BENCH_ARGS:---steps 64 --warmup 8 --no-cpu-baseline --sds-steps 6 -
 for n in "$@"; do
   lib=$R/tools/_bin/lib_$n.so; [ "$n" = "head" ] && lib=$R/avatarcraft_amd/libavatarcraft_hip.so
   for i in 1 2; do
-    AC_LIB_PATH=$lib timeout 300 python $R/bench.py $BENCH_ARGS 2>$O/err_$n.log | tail -1 > $O/line_$n_$i.json
+    AC_LIB_PATH=$lib timeout 300 python $R/bench.py --full $BENCH_ARGS 2>$O/err_$n.log | tail -1 > $O/line_$n_$i.json
     python - "$n" $O/line_$n_$i.json <<'PY'
 import sys, json
 n, f = sys.argv[1], sys.argv[2]
