@@ -52,9 +52,10 @@ inline uint32_t cu_count()
 // Persistent kernels that synchronise their grid with barriers in global memory need EVERY workgroup resident (VERDICT / ADVICE round 5): the grid is
 // sized from what the runtime says fits (hipOccupancyMaxActiveBlocksPerMultiprocessor x compute units -- registers, LDS and workgroup size of THIS kernel,
 // not an assumption about them) and the launch goes through hipLaunchCooperativeKernel, which refuses a grid that cannot be co-resident at launch time
-// instead of letting it dead-lock.  (What neither can rule out -- a foreign kernel of another stream or process that HOLDS compute units for longer than
-// the barriers' bounded spin -- is caught behind the launch: the kernels count a timed-out barrier in their scratch's sticky word and the host wrappers
-// re-render through the barrier-free path; nsr_ops.render_rays_occupancy / instant_nsr.run_cuda.)  AC_COOP_LAUNCH=0: plain launch of the same grid.
+// instead of letting it dead-lock (a device without cooperative launches gets a plain launch of the same grid).  (What neither can rule out -- a foreign
+// kernel of another stream or process that HOLDS compute units for longer than the barriers' bounded spin -- is caught behind the launch: the kernels
+// count a timed-out barrier in their scratch's sticky word and the host wrappers re-render through the barrier-free path; nsr_ops.render_rays_occupancy /
+// instant_nsr.run_cuda.)
 // blocks: in = the grid the work wants, out = min(that, resident capacity).
 inline int launch_resident(const char *what, const void *kernel, uint32_t &blocks, uint32_t threads, size_t lds_bytes, hipStream_t st, void **params)
 {
@@ -66,13 +67,12 @@ inline int launch_resident(const char *what, const void *kernel, uint32_t &block
     }
     const uint32_t cap = (uint32_t)per_cu * cu_count();
     if (blocks > cap) blocks = cap;
-    static const int coop_env = []() { const char *e = getenv("AC_COOP_LAUNCH"); return (e && e[0] == '0' && !e[1]) ? 0 : 1; }();
     int dev = 0, coop = 0;
-    if (coop_env && hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, dev);
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, dev);
     hipError_t e;
-    if (coop_env && coop) e = hipLaunchCooperativeKernel(kernel, dim3(blocks), dim3(threads), params, (unsigned int)lds_bytes, st);
+    if (coop) e = hipLaunchCooperativeKernel(kernel, dim3(blocks), dim3(threads), params, (unsigned int)lds_bytes, st);
     else e = hipLaunchKernel(kernel, dim3(blocks), dim3(threads), params, lds_bytes, st);
-    if (e != hipSuccess) { (void)hipGetLastError(); set_error("%s: %s (grid %u x %u, %zu bytes of LDS, %s launch)", what, hipGetErrorString(e), blocks, threads, lds_bytes, (coop_env && coop) ? "cooperative" : "plain"); return AC_ERR_LAUNCH; }
+    if (e != hipSuccess) { (void)hipGetLastError(); set_error("%s: %s (grid %u x %u, %zu bytes of LDS, %s launch)", what, hipGetErrorString(e), blocks, threads, lds_bytes, coop ? "cooperative" : "plain"); return AC_ERR_LAUNCH; }
     return check_launch(what);
 }
 

@@ -20,31 +20,12 @@
 // index, z fastest) then by axis x, y, z; triangles by cell (linear index) then by table position.
 #include "nsr_device.hpp"
 
-#include <stdlib.h>
-#ifndef AC_GRID_ORDER_DEFAULT
-#define AC_GRID_ORDER_DEFAULT 1
-#endif
-#ifndef AC_GRID_ROUND_DEFAULT
-#define AC_GRID_ROUND_DEFAULT 2
-#endif
 #define AC_MC_CONST static __constant__ const
 #include "ac_mc_table.hpp"
 
 namespace {
 
 // ---------------------------------------------------------------------------------------------------------------- SDF on a regular grid
-// sdf_tile (nsr_device.hpp) with the number of hash levels a lane requests per memory round trip as a parameter: the same arithmetic in the same order
-// (bit-identical values), more gathers in flight per wave
-template <int ROUND>
-__device__ __forceinline__ f32x4 sdf_tile_r(const float *__restrict__ lds, const FieldCtx &fc, int lane, float px, float py, float pz)
-{
-    const int g = lane >> 4;
-    float f[4][2];
-    encode4<ROUND>(lds, fc.table, g, fc.jmode, px, py, pz, fc.bound, fc.two_bound, f, fc.inv_tb);
-    __builtin_amdgcn_sched_barrier(0);
-    return sdf_mlp(lds, lane, sel4(g, px, py, pz, 0.0f), f);
-}
-
 // update_extra_state's density (:331-337): inv_s e^(-inv_s sdf) / (1 + e^(-inv_s sdf)) for sdf > 0, the mirrored form for sdf <= 0 -- the two
 // overflow-free branches, every operation in the reference's order (mul, exp, mul | add, div) in fp32
 __device__ __forceinline__ float dg_density(float sdf, float inv_s)
@@ -55,15 +36,13 @@ __device__ __forceinline__ float dg_density(float sdf, float inv_s)
 
 constexpr uint32_t GB_X = 16, GB_Y = 4, GB_Z = 16;           // a brick of grid points: 64 tiles of 16 points along X
 
-// BRICK = false: tiles of 16 consecutive points in the volume's linear order (z fastest), dealt to the waves round robin (round 5's first version).
-// BRICK = true : the volume is cut into bricks of 16 x 4 x 16 points; a workgroup evaluates one brick at a time, its 8 waves take 8 tiles each, and a
+// The volume is cut into bricks of 16 x 4 x 16 points; a workgroup evaluates one brick at a time, its 8 waves take 8 tiles each, and a
 //   tile is 16 consecutive points ALONG X.  Why x: the spatial hash of the fine levels is x ^ y P1 ^ z P2 (hashencoder.cu:54-70) -- linear in x, so the eight cells
 //   x in [8k, 8k + 8) of one (y, z) row are the eight entries of ONE 64-byte sector of the table (and consecutive entries on the dense levels).  A gather
 //   instruction serves one corner of the 16 points of a tile: along x those 16 entries sit in 2 .. 9 sectors, along y or z in 16 (the primes scatter them
 //   over the level's 4 MB).  The per-CU gather path and the fabric behind L2 -- what this kernel is short of -- see a fraction of the requests.
 //   The results are staged in LDS and written with z fastest (64-byte runs) -- the volume keeps the reference's [x][y][z] layout.
 //   Every XCD (workgroup index mod 8) walks through its own contiguous eighth of the bricks: coarse and middle levels are re-used from its L2.
-template <int ROUND, bool BRICK>
 __global__ __launch_bounds__(BLOCK) void field_sdf_grid_kernel(const RenderArgs a, const float *__restrict__ ax, const float *__restrict__ ay,
                                                                const float *__restrict__ az, uint32_t nx, uint32_t ny, uint32_t nz, int mode, float inv_s,
                                                                float *__restrict__ vol)
@@ -75,40 +54,30 @@ __global__ __launch_bounds__(BLOCK) void field_sdf_grid_kernel(const RenderArgs 
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
     const FieldCtx fc = make_ctx(a);
-    if constexpr (!BRICK) {
-        const uint32_t B = nx * ny * nz, ntiles = (B + 15u) / 16u;
-        for (uint32_t tile = blockIdx.x * WAVES_PER_BLOCK + wave; tile < ntiles; tile += gridDim.x * WAVES_PER_BLOCK) {
-            const uint32_t b = tile * 16u + (uint32_t)n, bb = b < B ? b : B - 1u;
-            const uint32_t iz = bb % nz, t = bb / nz, iy = t % ny, ix = t / ny;
-            const f32x4 o = sdf_tile_r<ROUND>(lds, fc, lane, ax[ix], ay[iy], az[iz]);
-            if (b < B && g == 0) vol[b] = value(o[0]);
-        }
-    } else {
-        float *stage = lds + OFF_WAVE;                                                               // [GB_X][GB_Y][GB_Z]
-        const uint32_t nbz = (nz + GB_Z - 1) / GB_Z, nby = (ny + GB_Y - 1) / GB_Y, nbx = (nx + GB_X - 1) / GB_X;
-        const uint32_t nbricks = nbx * nby * nbz, per_xcd = (nbricks + 7u) / 8u;
-        const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3, slots = gridDim.x >> 3;        // (the grid is a multiple of 8 workgroups)
-        for (uint32_t bi = slot; bi < per_xcd; bi += slots) {
-            const uint32_t brick = xcd * per_xcd + bi;
-            if (brick >= nbricks) break;                                                             // (workgroup-uniform)
-            const uint32_t bz = brick % nbz, bt = brick / nbz, by = bt % nby, bx = bt / nby;
+    float *stage = lds + OFF_WAVE;                                                               // [GB_X][GB_Y][GB_Z]
+    const uint32_t nbz = (nz + GB_Z - 1) / GB_Z, nby = (ny + GB_Y - 1) / GB_Y, nbx = (nx + GB_X - 1) / GB_X;
+    const uint32_t nbricks = nbx * nby * nbz, per_xcd = (nbricks + 7u) / 8u;
+    const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3, slots = gridDim.x >> 3;        // (the grid is a multiple of 8 workgroups)
+    for (uint32_t bi = slot; bi < per_xcd; bi += slots) {
+        const uint32_t brick = xcd * per_xcd + bi;
+        if (brick >= nbricks) break;                                                             // (workgroup-uniform)
+        const uint32_t bz = brick % nbz, bt = brick / nbz, by = bt % nby, bx = bt / nby;
 #pragma unroll 1
-            for (uint32_t t = (uint32_t)wave; t < GB_Y * GB_Z; t += WAVES_PER_BLOCK) {
-                const uint32_t ly = t >> 4, lz = t & 15u;
-                const uint32_t ix = bx * GB_X + (uint32_t)n, iy = by * GB_Y + ly, iz = bz * GB_Z + lz;
-                if (iy >= ny || iz >= nz) continue;                                                  // (wave-uniform)
-                const uint32_t cx = ix < nx ? ix : nx - 1u;
-                const f32x4 o = sdf_tile_r<ROUND>(lds, fc, lane, ax[cx], ay[iy], az[iz]);
-                if (g == 0) stage[((uint32_t)n * GB_Y + ly) * GB_Z + lz] = value(o[0]);
-            }
-            __syncthreads();
-            for (uint32_t o = threadIdx.x; o < GB_X * GB_Y * GB_Z; o += BLOCK) {
-                const uint32_t lz = o & 15u, ly = (o >> 4) & 3u, lx = o >> 6;
-                const uint32_t ix = bx * GB_X + lx, iy = by * GB_Y + ly, iz = bz * GB_Z + lz;
-                if (ix < nx && iy < ny && iz < nz) vol[((size_t)ix * ny + iy) * nz + iz] = stage[o];
-            }
-            __syncthreads();
+        for (uint32_t t = (uint32_t)wave; t < GB_Y * GB_Z; t += WAVES_PER_BLOCK) {
+            const uint32_t ly = t >> 4, lz = t & 15u;
+            const uint32_t ix = bx * GB_X + (uint32_t)n, iy = by * GB_Y + ly, iz = bz * GB_Z + lz;
+            if (iy >= ny || iz >= nz) continue;                                                  // (wave-uniform)
+            const uint32_t cx = ix < nx ? ix : nx - 1u;
+            const f32x4 o = sdf_tile(lds, fc, lane, ax[cx], ay[iy], az[iz]);
+            if (g == 0) stage[((uint32_t)n * GB_Y + ly) * GB_Z + lz] = value(o[0]);
         }
+        __syncthreads();
+        for (uint32_t o = threadIdx.x; o < GB_X * GB_Y * GB_Z; o += BLOCK) {
+            const uint32_t lz = o & 15u, ly = (o >> 4) & 3u, lx = o >> 6;
+            const uint32_t ix = bx * GB_X + lx, iy = by * GB_Y + ly, iz = bz * GB_Z + lz;
+            if (ix < nx && iy < ny && iz < nz) vol[((size_t)ix * ny + iy) * nz + iz] = stage[o];
+        }
+        __syncthreads();
     }
 }
 
@@ -422,27 +391,19 @@ int launch_grid(const RenderArgs &a, const float *axis_x, const float *axis_y, c
                 float *volume, hipStream_t stream, const char *what)
 {
     const size_t lds_bytes = (OFF_WAVE + GB_X * GB_Y * GB_Z) * sizeof(float);
-    const uint32_t B = nx * ny * nz, ntiles = (B + 15u) / 16u;
-    // experiment switches (same values whatever they say): AC_GRID_ORDER = 0 linear tiles | 1 bricks per XCD; AC_GRID_ROUND = 2 | 4 levels per gather round
-    static const int order = []() { const char *e = getenv("AC_GRID_ORDER"); return e ? atoi(e) : AC_GRID_ORDER_DEFAULT; }();
-    static const int round_ = []() { const char *e = getenv("AC_GRID_ROUND"); return (e && atoi(e) == 4) ? 4 : (e && atoi(e) == 2 ? 2 : AC_GRID_ROUND_DEFAULT); }();
-    using kern_t = void (*)(const RenderArgs, const float *, const float *, const float *, uint32_t, uint32_t, uint32_t, int, float, float *);
-    const kern_t kern = order ? (round_ == 4 ? (kern_t)field_sdf_grid_kernel<4, true> : (kern_t)field_sdf_grid_kernel<2, true>)
-                              : (round_ == 4 ? (kern_t)field_sdf_grid_kernel<4, false> : (kern_t)field_sdf_grid_kernel<2, false>);
-    uint32_t blocks = order ? ((nx + GB_X - 1) / GB_X) * ((ny + GB_Y - 1) / GB_Y) * ((nz + GB_Z - 1) / GB_Z) : (ntiles + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+    uint32_t blocks = ((nx + GB_X - 1) / GB_X) * ((ny + GB_Y - 1) / GB_Y) * ((nz + GB_Z - 1) / GB_Z);
     // persistent workgroups, exactly as many as the device keeps resident at once (43 KB of LDS each; the registers decide): a workgroup that had to
     // wait for a slot would start its share of the tiles when the others are done
-    static int per_cu[4] = { 0, 0, 0, 0 };
-    int &pc = per_cu[(order ? 2 : 0) + (round_ == 4 ? 1 : 0)];
-    if (!pc) {
+    static int per_cu = 0;
+    if (!per_cu) {
         int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, BLOCK, lds_bytes) != hipSuccess || n < 1) n = 1;
-        pc = n;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, field_sdf_grid_kernel, BLOCK, lds_bytes) != hipSuccess || n < 1) n = 1;
+        per_cu = n;
     }
-    const uint32_t cap = (uint32_t)pc * ac::cu_count();
+    const uint32_t cap = (uint32_t)per_cu * ac::cu_count();
     if (blocks > cap) blocks = cap;
-    if (order) blocks = (blocks + 7u) & ~7u;                          // every XCD the same number of workgroups
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(BLOCK), lds_bytes, stream, a, axis_x, axis_y, axis_z, nx, ny, nz, mode, inv_s, volume);
+    blocks = (blocks + 7u) & ~7u;                                     // every XCD the same number of workgroups
+    hipLaunchKernelGGL(field_sdf_grid_kernel, dim3(blocks), dim3(BLOCK), lds_bytes, stream, a, axis_x, axis_y, axis_z, nx, ny, nz, mode, inv_s, volume);
     return ac::check_launch(what);
 }
 

@@ -1938,9 +1938,8 @@ static int render_rays_occupancy_impl(const ac_field *field, const float *rays_o
     const uint32_t cus = ac::cu_count();
     // rays per wave (2^glog): 16 for whole views, 8 for small batches (more waves in flight: the march is a chain of ~200 dependent grid look-ups per ray,
     // 0.26 ms end to end, and only concurrency hides it).  Measured on the 256 x 256 bench view (profiles/r04_experiments.txt section 11): 65 536 rays in one
-    // launch 2.67 / 2.37 / 2.92 / 3.26 ms for 8 / 16 / 32 / 64 rays per wave; in 4096-ray launches 12.1 / 15.6 / 20.0 / 23.4 ms.  AC_OCC_GLOG = 2 .. 6 overrides.
-    static const int env_glog = []() { const char *e = getenv("AC_OCC_GLOG"); return (e && e[0] >= '2' && e[0] <= '6' && !e[1]) ? e[0] - '0' : -1; }();
-    const uint32_t glog = env_glog >= 0 ? (uint32_t)env_glog : (N >= 32768u ? 4u : 3u);
+    // launch 2.67 / 2.37 / 2.92 / 3.26 ms for 8 / 16 / 32 / 64 rays per wave; in 4096-ray launches 12.1 / 15.6 / 20.0 / 23.4 ms.
+    const uint32_t glog = N >= 32768u ? 4u : 3u;
     const uint32_t gsz = 1u << glog;
     // the voxel faces as a table behind the stages when H + 1 floats still fit the compute unit's LDS (H = 128: 516 of the 1.9 KB left)
     const bool tab = (OCC_LDS_FLOATS + (size_t)H + 1) * sizeof(float) + 64 <= 160 * 1024;
@@ -2036,15 +2035,12 @@ AC_API uint32_t ac_set_occupancy_barrier_ms(uint32_t ms)
 
 // scratch of ac_render_rays_occupancy_phased: [16] sync words | alive lists [2][N] | per-ray state [N][4] | per-entry counts [N] | tile list [N << nlog] |
 // sample slots in / out [N << nlog][8] each.  ZERO-FILLED by the caller once (the sync words; every call leaves them zero again); any call with the same or a
-// smaller N (and the same n_step) may reuse it on the same stream.
+// smaller N may reuse it on the same stream.
 struct OccPhLayout { size_t alive, st, cnt, list, s_in, s_out, total; };
-static uint32_t occ_phased_nlog()
+constexpr uint32_t OCC_PHASED_NLOG = 4;          // log2 of n_step, the samples per ray and round
+static OccPhLayout occ_phased_layout(uint32_t N)
 {
-    static const int env = []() { const char *e = getenv("AC_OCC_NLOG"); return (e && e[0] >= '1' && e[0] <= '6' && !e[1]) ? e[0] - '0' : -1; }();
-    return env >= 0 ? (uint32_t)env : 4u;
-}
-static OccPhLayout occ_phased_layout(uint32_t N, uint32_t nlog)
-{
+    constexpr uint32_t nlog = OCC_PHASED_NLOG;
     OccPhLayout l{};
     size_t o = 16 * sizeof(uint32_t);
     l.alive = o; o += 2 * (size_t)N * sizeof(int32_t);
@@ -2058,7 +2054,7 @@ static OccPhLayout occ_phased_layout(uint32_t N, uint32_t nlog)
     l.total = o;
     return l;
 }
-AC_API size_t ac_render_rays_occupancy_phased_scratch(uint32_t N) { return occ_phased_layout(N, occ_phased_nlog()).total; }
+AC_API size_t ac_render_rays_occupancy_phased_scratch(uint32_t N) { return occ_phased_layout(N).total; }
 
 AC_API int ac_render_rays_occupancy_phased(const ac_field *field, const float *rays_o, const float *rays_d, uint32_t N, const float *grid, uint32_t H,
                                            float mean_density, float bound, float eps, float inv_s, const float *inv_s_dev, float cos_anneal_ratio,
@@ -2069,9 +2065,9 @@ AC_API int ac_render_rays_occupancy_phased(const ac_field *field, const float *r
     if (!rays_o || !rays_d || !grid || !weights_sum || !depth || !image || !normal_map || !scratch || H < 2 || !(eps > 0.0f)) {
         ac::set_error("render_rays_occupancy_phased: NULL buffer, H < 2 or eps <= 0"); return AC_ERR_BAD_ARG;
     }
-    const uint32_t nlog = occ_phased_nlog();
+    const uint32_t nlog = OCC_PHASED_NLOG;
     if (((uint64_t)N << nlog) >= (1ull << 31)) { ac::set_error("render_rays_occupancy_phased: too many rays for 32-bit slot ids"); return AC_ERR_BAD_ARG; }
-    const OccPhLayout l = occ_phased_layout(N, nlog);
+    const OccPhLayout l = occ_phased_layout(N);
     if (scratch_bytes < l.total) { ac::set_error("render_rays_occupancy_phased: scratch of %zu bytes needed, %zu given", l.total, scratch_bytes); return AC_ERR_BAD_ARG; }
     RenderArgs a{};
     if (int rc = prep_args(a, field, bound, eps)) return rc;

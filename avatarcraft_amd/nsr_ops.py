@@ -194,9 +194,8 @@ def _render(field, rays_o, rays_d, num_steps, upsample_steps, bound, inv_s, bg, 
     if train_extras:
         o.sdf_out16 = buf("sdf_out16", (N, T, 16)).data_ptr()
         o.pts = buf("pts", (N, T, 3)).data_ptr()
-        if SAVE_STENCIL_FEATURES:
-            if not long:
-                o.feat7 = buf("feat7", (N * T // 16, 14, 64, 4)).data_ptr()
+        if not long:        # the hash features of every sample's 7-point stencil (0.9 KB per sample): the backward streams them back instead of gathering them again
+            o.feat7 = buf("feat7", (N * T // 16, 14, 64, 4)).data_ptr()
     if debug_indices:
         o.ss_inds = buf("ss_inds", (N, max(nup, 1), 16), torch.int32).data_ptr()
         o.sort_index = buf("sort_index", (N, max(nup, 1), T if long else 128), torch.int32).data_ptr()
@@ -282,8 +281,7 @@ def render_rays_pair(field, rays_o, rays_d, noise2, num_steps=64, upsample_steps
     per_sample = {"z_vals": (N, T), "color": (N, T, 3), "sdf": (N, T), "gradient": (N, T, 3), "sdf_out16": (N, T, 16), "pts": (N, T, 3)}      # what the backward reads
     if keep_weights:
         per_sample.update({"weights": (N, T), "alpha": (N, T)})
-    if SAVE_STENCIL_FEATURES:
-        per_sample["feat7"] = (N * T // 16, 14, 64, 4)
+    per_sample["feat7"] = (N * T // 16, 14, 64, 4)
     for k, shp in per_sample.items():
         setattr(o, k, buf(k, shp).data_ptr())
     noise2 = _chk(noise2.reshape(2 * N, num_steps), "noise2")
@@ -473,11 +471,6 @@ def free_scratch():
     _CORE_SCRATCH.clear()
     from .encoder.hashencoder import backend as BK
     BK._SCRATCH.clear()
-
-
-# a training render keeps the hash features of every sample's 7-point stencil (0.9 KB per sample) so that the backward streams them back instead of
-# gathering them again; AC_NO_FEAT7=1 restores the re-gathering backward (A/B timing)
-SAVE_STENCIL_FEATURES = os.environ.get("AC_NO_FEAT7", "0") != "1"
 
 
 # see _RenderCore.backward: False = the table gradient goes through autograd (default); True = accumulated into table.grad in place
@@ -976,7 +969,7 @@ def field_samples(field, xyzs, dirs, deltas, bound, eps, inv_s, cos_anneal_ratio
 
 # from this ray count on the inference launch runs in phases (same bits): 1.01 against 1.94 ms on a 256 x 256 view, 0.54 against 0.87 ms on a 4096-ray batch of
 # its middle rows; a few dozen rays are quicker through the one-wave-per-group kernel (no grid barriers)
-OCCUPANCY_PHASED_MIN_RAYS = int(os.environ.get("AC_OCC_PHASED_MIN_RAYS", "2048"))
+OCCUPANCY_PHASED_MIN_RAYS = 2048
 _OP_SCRATCH = {}
 
 # The phased kernels (inference and training form) synchronise their grid with barriers in global memory.  The launch is sized and checked for co-residency

@@ -422,11 +422,11 @@ int ac_render_rays_occupancy(const ac_field *field, const float *rays_o, const f
 /* The same inference render, the same bits, as rounds of march | field | composite INSIDE one launch with grid barriers between the phases (ABI 7): every lane
  * walks a ray, the samples of a round are evaluated on tiles dealt to all waves, and the rays that go on (not at `far`, T >= 1e-2, below max_steps) form the
  * next round's list -- the reference's loop without its host read-backs; faster than ac_render_rays_occupancy on whole views, where that kernel keeps a
- * quarter of a wave's lanes walking and every wave evaluating its own tiles one after the other.  n_step = 16 samples per ray and round (AC_OCC_NLOG = 1 .. 6
- * overrides its log2); results do not depend on it.  scratch: ac_render_rays_occupancy_phased_scratch(N) bytes (64 B per ray and round sample: 67 MB for a
+ * quarter of a wave's lanes walking and every wave evaluating its own tiles one after the other.  n_step = 16 samples per ray and round; results do not
+ * depend on it.  scratch: ac_render_rays_occupancy_phased_scratch(N) bytes (64 B per ray and round sample: 67 MB for a
  * 256 x 256 view), ZERO-FILLED by the caller before its first use, re-armed by every call, one buffer per stream; a call with fewer rays may reuse it.
  * A launch needs every workgroup resident: the grid is min(what the rays want, hipOccupancyMaxActiveBlocksPerMultiprocessor x compute units) and goes
- * through hipLaunchCooperativeKernel where the device supports it (AC_COOP_LAUNCH=0: a plain launch of the same grid) -- a grid that cannot be co-resident is
+ * through hipLaunchCooperativeKernel where the device supports it (a plain launch of the same grid where it does not) -- a grid that cannot be co-resident is
  * refused AT LAUNCH (AC_ERR_LAUNCH).  What remains: a foreign kernel holding compute units for longer than a barrier's bounded spin (two seconds;
  * ac_set_occupancy_barrier_ms / AC_OCC_BARRIER_MS override) -- then the phased kernel gives up, counts itself in the scratch's 32-bit word 8 (sticky) and sets
  * the launch's verdict word 9; the call has ALREADY queued the barrier-free kernel of ac_render_rays_occupancy behind it, conditional on that word: it
