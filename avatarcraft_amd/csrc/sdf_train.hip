@@ -1615,6 +1615,12 @@ __global__ __launch_bounds__(TBLOCK) void color_bwd_kernel(const RenderArgs a, c
 // forward is the renderer's own arithmetic (16-sample tile scans with sequential carry), the backward recomputes it.
 //   forward : (z, sdf, normal, colour, ray) -> image, weights_sum, depth, normal_map, weights, alpha
 //   backward: (d image, d weights_sum, d depth, d normal_map) -> d sdf, d normal, d colour, per-ray partial of d inv_s
+// Two instantiations each way, chosen by comp_launch:
+//   CAP = 128, RAGGED = false: the short window (T a multiple of 16, at most 128), render_rays_kernel's tiles;
+//   CAP = 512, RAGGED = true : the long renderer's envelope (any T up to 512), render_rays_long_kernel's tiles -- ceil(T / 16) of them, the last one
+//     masked by that kernel's rules (render_long.hip): a masked lane evaluates the ray's last sample again, contributes the identity (1, not 1 + 1e-7)
+//     to the transmittance scan and exact zeros (weight 0) to every sum, and writes nothing.  The weights and transmittances it recomputes are
+//     therefore the long forward's bit for bit.
 struct CompArgs {
     const float *rays_o, *rays_d, *z, *sdf, *nrm, *col, *bg;
     int n_rays, T0, T;
@@ -1646,6 +1652,7 @@ __device__ __forceinline__ CompSample comp_sample(const float *__restrict__ spg,
     return s;
 }
 
+template <int CAP, bool RAGGED>
 __global__ __launch_bounds__(256) void composite_fwd_kernel(const CompArgs a_in, float *__restrict__ image, float *__restrict__ wsum,
                                                             float *__restrict__ depth, float *__restrict__ nmap, float *__restrict__ weights,
                                                             float *__restrict__ alpha_out)
@@ -1653,7 +1660,7 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(const CompArgs a_in,
     CompArgs a = a_in;
     if (a.inv_s_dev) a.inv_s = *a.inv_s_dev;
     __shared__ float spg[SPQ_FLOATS];
-    __shared__ float zsh[4][128];
+    __shared__ float zsh[4][CAP];
     for (int e = threadIdx.x; e < SPQ_FLOATS; e += blockDim.x) spg[e] = AC_SP_G[e >> 2][e & 3];
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 15;
@@ -1672,12 +1679,15 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(const CompArgs a_in,
         for (int i = lane; i < a.T; i += 64) zr[i] = a.z[(size_t)ray * a.T + i];
         wave_sync();
         float cT = 1.0f, s_w = 0.0f, s_r = 0.0f, s_g = 0.0f, s_b = 0.0f, s_nx = 0.0f, s_ny = 0.0f, s_nz = 0.0f, s_d = 0.0f;
-        for (int c = 0; c < a.T / 16; ++c) {
-            const int i = 16 * c + n;
+        for (int c = 0; c < (RAGGED ? (a.T + 15) / 16 : a.T / 16); ++c) {
+            int i = 16 * c + n;
+            const bool valid = !RAGGED || i < a.T;
+            if (!valid) i = a.T - 1;                                                            // a masked lane: the ray's last sample again
             const size_t si = (size_t)ray * a.T + i;
             const float nx = a.nrm[3 * si], ny = a.nrm[3 * si + 1], nz = a.nrm[3 * si + 2];
             CompSample s = comp_sample(spg, a, zr, i, a.sdf[si], nx, ny, nz, dx, dy, dz, near, span, sample_dist);
             if (a.mask && !a.mask[si]) { s.alpha = 0.0f; s.om = 1.0f + 1e-7f; }                 // alpha * 0; the factor 1 - 0 + 1e-7 stays in the product
+            if (!valid) { s.alpha = 0.0f; s.om = 1.0f; }                                        // the identity of the product scan, weight 0
             const float loc = row_scan<true>(s.om);
             const float sh = dpp_shr<1>(1.0f, loc);
             float Tex;
@@ -1694,7 +1704,7 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(const CompArgs a_in,
             AC_ACC(s_b, b * wgt) AC_ACC(s_nz, nz * wgt)
             AC_ACC(s_d, wgt * s.zn)
 #undef AC_ACC
-            if (lane < 16) { weights[si] = wgt; alpha_out[si] = s.alpha; }
+            if (lane < 16 && valid) { weights[si] = wgt; alpha_out[si] = s.alpha; }
         }
         if (lane == 0) {
             const float b0 = a.bg ? a.bg[3 * ray] : 1.0f, b1 = a.bg ? a.bg[3 * ray + 1] : 1.0f, b2 = a.bg ? a.bg[3 * ray + 2] : 1.0f;
@@ -1706,6 +1716,7 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(const CompArgs a_in,
     }
 }
 
+template <int CAP, bool RAGGED>
 __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompArgs a_in, const float *__restrict__ g_image, const float *__restrict__ g_wsum,
                                                             const float *__restrict__ g_depth, const float *__restrict__ g_nmap,
                                                             float *__restrict__ g_sdf, float *__restrict__ g_nrm, float *__restrict__ g_col,
@@ -1714,7 +1725,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompArgs a_in,
     CompArgs a = a_in;
     if (a.inv_s_dev) a.inv_s = *a.inv_s_dev;
     __shared__ float spg[SPQ_FLOATS];
-    __shared__ float zsh[4][128], tex[4][128], wq[4][128], psum[4][128];
+    __shared__ float zsh[4][CAP], tex[4][CAP], wq[4][CAP], psum[4][CAP];
     for (int e = threadIdx.x; e < SPQ_FLOATS; e += blockDim.x) spg[e] = AC_SP_G[e >> 2][e & 3];
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 15;
@@ -1738,12 +1749,15 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompArgs a_in,
         const float b0 = a.bg ? a.bg[3 * ray] : 1.0f, b1 = a.bg ? a.bg[3 * ray + 1] : 1.0f, b2 = a.bg ? a.bg[3 * ray + 2] : 1.0f;
         // pass A: transmittance, weights, d loss / d w_i, prefix sums of dw_i w_i
         float cT = 1.0f, run = 0.0f;
-        for (int c = 0; c < a.T / 16; ++c) {
-            const int i = 16 * c + n;
+        for (int c = 0; c < (RAGGED ? (a.T + 15) / 16 : a.T / 16); ++c) {
+            int i = 16 * c + n;
+            const bool valid = !RAGGED || i < a.T;
+            if (!valid) i = a.T - 1;                                                            // as in the forward
             const size_t si = (size_t)ray * a.T + i;
             const float nx = a.nrm[3 * si], ny = a.nrm[3 * si + 1], nz = a.nrm[3 * si + 2];
             CompSample s = comp_sample(spg, a, zr, i, a.sdf[si], nx, ny, nz, dx, dy, dz, near, span, sample_dist);
             if (a.mask && !a.mask[si]) { s.alpha = 0.0f; s.om = 1.0f + 1e-7f; }                 // alpha * 0; the factor 1 - 0 + 1e-7 stays in the product
+            if (!valid) { s.alpha = 0.0f; s.om = 1.0f; }                                        // weight 0: dw * 0 adds an exact zero to the prefix sums
             const float loc = row_scan<true>(s.om);
             const float sh = dpp_shr<1>(1.0f, loc);
             float Tex;
@@ -1756,7 +1770,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompArgs a_in,
             const float dw = ((gi0 * (r - b0) + gi1 * (g - b1)) + gi2 * (b - b2)) + gws + gdp * s.zn + ((gn0 * nx + gn1 * ny) + gn2 * nz);
             const float incl = row_scan<false>(dw * wgt) + run;
             run = lane_bcast(incl, 15);
-            if (lane < 16) { tex[wave][i] = Tex; wq[wave][i] = dw; psum[wave][i] = incl; }
+            if (lane < 16 && valid) { tex[wave][i] = Tex; wq[wave][i] = dw; psum[wave][i] = incl; }
         }
         const float total = run;
         wave_sync();
@@ -2330,11 +2344,21 @@ static int color_backward_impl(const ac_field *field, const float *x, const floa
     return ac::check_launch("color_backward");
 }
 
+constexpr int COMP_LONG_MAX_T = 512;
+
+// the long instantiation (composite_*_kernel<512, true>) where the short one does not apply
+static bool comp_long(const CompArgs &a) { return a.T > 128 || a.T % 16; }
+
 static int comp_args(CompArgs &a, const char *who, const float *rays_o, const float *rays_d, const float *z, const float *sdf, const float *nrm,
                      const float *col, const float *bg, int32_t n_rays, int32_t T0, int32_t T, float bound, float inv_s, float car)
 {
     if (!rays_o || !rays_d || !z || !sdf || !nrm || !col) { ac::set_error("%s: NULL buffer", who); return AC_ERR_BAD_ARG; }
-    if (T0 <= 0 || T % 16 || T < T0 || T > 128) { ac::set_error("%s: T0=%d T=%d unsupported (T a multiple of 16, <= 128)", who, T0, T); return AC_ERR_BAD_ARG; }
+    const bool short_ok = T0 > 0 && T % 16 == 0 && T >= T0 && T <= 128;
+    const bool long_ok = T0 >= 2 && T >= T0 && (T - T0) % 16 == 0 && T <= COMP_LONG_MAX_T;          // ac_render_rays_long's counts
+    if (!short_ok && !long_ok) {
+        ac::set_error("%s: T0=%d T=%d unsupported (T a multiple of 16, <= 128; or T0 >= 2, T - T0 >= 0 a multiple of 16, T <= %d)", who, T0, T, COMP_LONG_MAX_T);
+        return AC_ERR_BAD_ARG;
+    }
     a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.sdf = sdf; a.nrm = nrm; a.col = col; a.bg = bg;
     a.n_rays = n_rays; a.T0 = T0; a.T = T; a.bound = bound; a.inv_s = inv_s; a.car = car; a.one_m_car = (float)(1.0 - (double)car);
     a.inv_s_dev = nullptr;
@@ -2351,7 +2375,10 @@ AC_API int ac_composite_forward(const float *rays_o, const float *rays_d, const 
     if (int rc = comp_args(a, "composite_forward", rays_o, rays_d, z_vals, sdf, normal, color, bg, n_rays, num_steps, T, bound, inv_s, cos_anneal_ratio)) return rc;
     if (!image || !weights_sum || !depth || !normal_map || !weights || !alpha) { ac::set_error("composite_forward: NULL output"); return AC_ERR_BAD_ARG; }
     int blocks = (n_rays + 3) / 4; if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(composite_fwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, image, weights_sum, depth, normal_map, weights, alpha);
+    if (comp_long(a))
+        hipLaunchKernelGGL((composite_fwd_kernel<COMP_LONG_MAX_T, true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, image, weights_sum, depth, normal_map, weights, alpha);
+    else
+        hipLaunchKernelGGL((composite_fwd_kernel<128, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, image, weights_sum, depth, normal_map, weights, alpha);
     return ac::check_launch("composite_forward");
 }
 
@@ -2367,8 +2394,12 @@ AC_API int ac_composite_backward(const float *rays_o, const float *rays_d, const
         ac::set_error("composite_backward: NULL buffer"); return AC_ERR_BAD_ARG;
     }
     int blocks = (n_rays + 3) / 4; if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(composite_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, g_image, g_weights_sum, g_depth, g_normal_map, g_sdf,
-                       g_normal, g_color, g_inv_s_per_ray);
+    if (comp_long(a))
+        hipLaunchKernelGGL((composite_bwd_kernel<COMP_LONG_MAX_T, true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, g_image, g_weights_sum, g_depth,
+                           g_normal_map, g_sdf, g_normal, g_color, g_inv_s_per_ray);
+    else
+        hipLaunchKernelGGL((composite_bwd_kernel<128, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, g_image, g_weights_sum, g_depth,
+                           g_normal_map, g_sdf, g_normal, g_color, g_inv_s_per_ray);
     return ac::check_launch("composite_backward");
 }
 
@@ -2414,6 +2445,17 @@ AC_API int ac_render_core_backward(const ac_field *field, const ac_render_opts *
         ac::set_error("render_core_backward: NULL buffer"); return AC_ERR_BAD_ARG;
     }
     if (!(op->fd_eps > 0.0f)) { ac::set_error("render_core_backward: fd_eps must be positive"); return AC_ERR_BAD_ARG; }
+    // at a count that 16 does not divide (the long renderer's), a 16-sample tile of the flat samples straddles two rays
+    if (T % 16 && sv->feat7) {
+        ac::set_error("render_core_backward: feat7 needs T a multiple of 16 (T=%d): its tiles are one ray's 16 samples; the long renderer's outputs "
+                      "take the re-gathering backward (feat7 = NULL)", T);
+        return AC_ERR_BAD_ARG;
+    }
+    if (T % 16 && field->Wc1_sh) {
+        ac::set_error("render_core_backward: a field with view directions needs T a multiple of 16 (T=%d): the colour backward takes a 16-sample tile "
+                      "as one ray's", T);
+        return AC_ERR_BAD_ARG;
+    }
     const uint32_t B = (uint32_t)N * (uint32_t)T;
     const CoreLayout l = core_layout(field, B);
     if (!scratch || scratch_bytes < l.total) { ac::set_error("render_core_backward: scratch of %zu bytes needed, %zu given", l.total, scratch_bytes); return AC_ERR_BAD_ARG; }
@@ -2431,8 +2473,12 @@ AC_API int ac_render_core_backward(const ac_field *field, const ac_render_opts *
         if ((op->near_m != nullptr) != (op->far_m != nullptr)) { ac::set_error("render_core_backward: near_m and far_m go together"); return AC_ERR_BAD_ARG; }
         a.near_m = op->near_m; a.far_m = op->far_m; a.mask = sv->mask;          // posed space: the range and the alpha mask of the forward
         int blocks = (N + 3) / 4; if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(composite_bwd_kernel, dim3(blocks), dim3(256), 0, st, a, up->g_image, up->g_weights_sum, up->g_depth, up->g_normal_map, g_sdf,
-                           g_nrm_a, g_col, gr->g_inv_s_per_ray);
+        if (comp_long(a))
+            hipLaunchKernelGGL((composite_bwd_kernel<COMP_LONG_MAX_T, true>), dim3(blocks), dim3(256), 0, st, a, up->g_image, up->g_weights_sum, up->g_depth,
+                               up->g_normal_map, g_sdf, g_nrm_a, g_col, gr->g_inv_s_per_ray);
+        else
+            hipLaunchKernelGGL((composite_bwd_kernel<128, false>), dim3(blocks), dim3(256), 0, st, a, up->g_image, up->g_weights_sum, up->g_depth,
+                               up->g_normal_map, g_sdf, g_nrm_a, g_col, gr->g_inv_s_per_ray);
     }
     if ((field->Wc1_sh != nullptr) != (sv->sh_bias != nullptr) || (field->Wc1_sh != nullptr) != (gr->g_sh_tiles != nullptr)) {
         ac::set_error("render_core_backward: a field with view directions (ac_field.Wc1_sh) needs ac_core_saved.sh_bias and ac_core_grads.g_sh_tiles, one without takes neither");

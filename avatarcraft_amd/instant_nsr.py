@@ -180,10 +180,15 @@ class NeRFRenderer(nn.Module):
     # gradients of (image, weights_sum, gradient_error) into parameter gradients: ac_render_core_backward + ac_param_grads, accumulated into .grad
     _manual_backward = False
 
-    def manual_backward_supported(self):
+    def manual_backward_supported(self, num_steps=None, upsample_steps=None):
         # (not for cuda_ray nets: their render() is run_cuda's occupancy march -- the fixed-step pair / whole-view launches and backward_last() would render
         #  different samples than render_instantnsr_naive does for the same net; ADVICE round 5.  They train through run_cuda under autograd.)
-        return self.fused_training == "core" and self._fused_supported() and self.encoder.embeddings.is_cuda and not getattr(self, "cuda_ray", False)
+        # With the counts: False also where the fused backward does not reach -- a field with view directions at a count that 16 does not divide (the
+        # colour backward takes a tile of 16 samples as one ray's); such a step trains through autograd.
+        ok = self.fused_training == "core" and self._fused_supported() and self.encoder.embeddings.is_cuda and not getattr(self, "cuda_ray", False)
+        if ok and num_steps is not None and upsample_steps is not None and self.use_viewdirs:
+            ok = (int(num_steps) + int(upsample_steps)) % 16 == 0
+        return ok
 
     def render_step_pair(self, rays_o, rays_d, num_steps, upsample_steps, bound, bkg_fn, cos_anneal_ratio=1.0, normal_epsilon_ratio=0.0):
         """The two renders of net_style in one stylisation step (stylize.py:98-116 render_val, :143-152 the differentiable render of the same rays) as
@@ -193,7 +198,7 @@ class NeRFRenderer(nn.Module):
         stylize.sds_step pairs the renders only for a guidance with `private_rng = True`.
         Returns (rgb_val [N,3], rgb [N,3], gradient_error, weight_sum [N,1]) of which the last three belong to the training render, whose
         per-sample outputs are kept for backward_last().  Every value equals what the two separate renders give, bit for bit."""
-        if not (self.training and self.manual_backward_supported()):
+        if not (self.training and self.manual_backward_supported(num_steps, upsample_steps)):
             raise RuntimeError("render_step_pair: needs the default model in train mode on the GPU")
         ro = rays_o.reshape(-1, 3).float().contiguous()
         rd = rays_d.reshape(-1, 3).float().contiguous()
@@ -225,8 +230,14 @@ class NeRFRenderer(nn.Module):
             bg2 = torch.cat([bg_a, bg_b]).contiguous()
         with torch.no_grad():
             field, inv_s = self._field(), self.forward_variance()
-            ra, rb = nsr_ops.render_rays_pair(field, ro, rd, noise2, num_steps, upsample_steps, bound, inv_s, bg2=bg2,
-                                              cos_anneal_ratio=cos_anneal_ratio, normal_epsilon_ratio=normal_epsilon_ratio, precision=self.render_precision)
+            if nsr_ops.in_short_window(num_steps, upsample_steps):
+                ra, rb = nsr_ops.render_rays_pair(field, ro, rd, noise2, num_steps, upsample_steps, bound, inv_s, bg2=bg2,
+                                                  cos_anneal_ratio=cos_anneal_ratio, normal_epsilon_ratio=normal_epsilon_ratio, precision=self.render_precision)
+            else:           # (the pair launch is the short window's): two launches of the long renderer, the same draws
+                kw = dict(cos_anneal_ratio=cos_anneal_ratio, normal_epsilon_ratio=normal_epsilon_ratio, precision=self.render_precision)
+                ra = nsr_ops.render_rays_long(field, ro, rd, num_steps, upsample_steps, bound, inv_s, bg=bg2[:N], noise=noise2[:N], **kw)
+                rb = nsr_ops.render_rays_long(field, ro, rd, num_steps, upsample_steps, bound, inv_s, bg=bg2[N:], noise=noise2[N:], extras=True,
+                                              train_extras=True, **kw)
         self._last_train = (rb, ro, rd, bg2[N:], field)
         self._guard_finite(rb["eik_res"][0])
         return ra["image"], rb["image"], rb["eik_res"][0], rb["weights_sum"][:, None]
@@ -263,10 +274,12 @@ class NeRFRenderer(nn.Module):
         else:
             bg = torch.cat([b if b is not None else torch.ones((min(batch_size, N - k * batch_size), 3), dtype=torch.float32, device=device)
                             for k, b in enumerate(bgs)]).contiguous()
+        # (at the long renderer's counts opacity_only renders the colour too: weight_sum is the same bits either way)
+        short = nsr_ops.in_short_window(num_steps, upsample_steps)
+        render, kw = (nsr_ops.render_rays, dict(opacity_only=bool(opacity_only))) if short else (nsr_ops.render_rays_long, {})
         with torch.no_grad():
-            out = nsr_ops.render_rays(self._field(), ro, rd, num_steps, upsample_steps, bound, self.forward_variance(), bg=bg, noise=noise,
-                                      cos_anneal_ratio=cos_anneal_ratio, normal_epsilon_ratio=normal_epsilon_ratio, extras=False,
-                                      precision=self.render_precision, opacity_only=bool(opacity_only))
+            out = render(self._field(), ro, rd, num_steps, upsample_steps, bound, self.forward_variance(), bg=bg, noise=noise,
+                         cos_anneal_ratio=cos_anneal_ratio, normal_epsilon_ratio=normal_epsilon_ratio, extras=False, precision=self.render_precision, **kw)
         return out["image"], out["weights_sum"][:, None]
 
     def render_view_train(self, rays_o, rays_d, num_steps, upsample_steps, bound, draw_fn, batch_size, cos_anneal_ratio=1.0, normal_epsilon_ratio=0.0):
@@ -276,7 +289,7 @@ class NeRFRenderer(nn.Module):
         further draws of its own there, e.g. the frozen avatar's background), then the jitter noise of those rays.  The eikonal term stays a ratio PER PATCH
         (instant_nsr.py:266-272): eik [P] are the patches' gradient_errors (the bits a launch of the patch alone reports), and backward_last takes one g_eik
         per patch.  -> (rgb [N,3], eik [P], weight_sum [N,1]); pixels equal the patch-by-patch renders bit for bit."""
-        if not (self.training and self.manual_backward_supported()):
+        if not (self.training and self.manual_backward_supported(num_steps, upsample_steps)):
             raise RuntimeError("render_view_train: needs the default model in train mode on the GPU")
         ro = rays_o.reshape(-1, 3).float().contiguous()
         rd = rays_d.reshape(-1, 3).float().contiguous()
@@ -294,10 +307,11 @@ class NeRFRenderer(nn.Module):
             if r.data_ptr() != dst.data_ptr():                   # (a replaced torch.rand that ignores `out`: tests replaying recorded draws)
                 dst.copy_(r)
         bg = torch.cat(bgs).contiguous() if len(bgs) > 1 else bgs[0].contiguous()
+        render = nsr_ops.render_rays if nsr_ops.in_short_window(num_steps, upsample_steps) else nsr_ops.render_rays_long
         with torch.no_grad():
             field, inv_s = self._field(), self.forward_variance()
-            out = nsr_ops.render_rays(field, ro, rd, num_steps, upsample_steps, bound, inv_s, bg=bg, noise=noise, cos_anneal_ratio=cos_anneal_ratio,
-                                      normal_epsilon_ratio=normal_epsilon_ratio, extras=True, train_extras=True, precision=self.render_precision)
+            out = render(field, ro, rd, num_steps, upsample_steps, bound, inv_s, bg=bg, noise=noise, cos_anneal_ratio=cos_anneal_ratio,
+                         normal_epsilon_ratio=normal_epsilon_ratio, extras=True, train_extras=True, precision=self.render_precision)
             groups = nsr_ops.eikonal_groups(out["eik"], int(batch_size))
         self._last_train = (out, ro, rd, bg, field)
         self._last_train_groups = (int(batch_size), groups)
@@ -458,10 +472,21 @@ class NeRFRenderer(nn.Module):
             from .ray_utils import geometry_guided_near_far
             v = verts.verts if isinstance(verts, nsr_ops.WarpMesh) else verts
             near_far = geometry_guided_near_far(ro, rd, v, DEFAULT_GEO_THRESH)
+        if needs_grad and full and self.fused_training == "core" and near_far is None and self._manual_backward and warp is None:
+            # (at the long counts the long renderer's launch: ac_render_core_backward takes its outputs as well)
+            render = nsr_ops.render_rays_long if long_counts else nsr_ops.render_rays
+            with torch.no_grad():
+                field, inv_s_ng = self._field(), self.forward_variance()
+                out = render(field, ro, rd, num_steps, upsample_steps, bound, inv_s_ng, bg=bg, noise=noise, cos_anneal_ratio=cos_anneal_ratio,
+                             normal_epsilon_ratio=normal_epsilon_ratio, extras=True, train_extras=True, precision=self.render_precision)
+            self._last_train = (out, ro, rd, bg, field)
+            self._guard_finite(out["eik_res"][0])
+            return (out["depth"].reshape(B, N), out["weights"], out["weights_sum"][:, None], out["image"].reshape(B, N, 3), out["normal_map"],
+                    out["eik_res"][0], 0.0, out["color"], out["alpha"], out["z_vals"])
         if long_counts:
             if needs_grad or not full:
-                # (the fused training operators -- fused_training = "core" and its manual backward -- stop at 128 samples: the long counts take the
-                # autograd render core, which handles any T)
+                # (the fused training operator -- fused_training = "core" under autograd -- stops at 128 samples: the long counts take the autograd
+                # render core, which handles any T)
                 z_vals = nsr_ops.sample_rays_long(self._field() if full else self._field_sdf_only(), ro, rd, num_steps, upsample_steps, bound,
                                                   noise=noise, near_far=near_far)
                 return self._render_core_autograd(ro, rd, z_vals, num_steps, upsample_steps, bound, bg, cos_anneal_ratio, normal_epsilon_ratio, B, N,
@@ -471,15 +496,6 @@ class NeRFRenderer(nn.Module):
                                            near_far=near_far, precision=self.render_precision)
             return (out["depth"].reshape(B, N), out.get("weights"), out["weights_sum"][:, None], out["image"].reshape(B, N, 3),
                     out["normal_map"], out["gradient_error"], 0.0, out.get("color"), out.get("alpha"), out.get("z_vals"))
-        if needs_grad and full and self.fused_training == "core" and near_far is None and self._manual_backward and warp is None:
-            with torch.no_grad():
-                field, inv_s_ng = self._field(), self.forward_variance()
-                out = nsr_ops.render_rays(field, ro, rd, num_steps, upsample_steps, bound, inv_s_ng, bg=bg, noise=noise, cos_anneal_ratio=cos_anneal_ratio,
-                                          normal_epsilon_ratio=normal_epsilon_ratio, extras=True, train_extras=True, precision=self.render_precision)
-            self._last_train = (out, ro, rd, bg, field)
-            self._guard_finite(out["eik_res"][0])
-            return (out["depth"].reshape(B, N), out["weights"], out["weights_sum"][:, None], out["image"].reshape(B, N, 3), out["normal_map"],
-                    out["eik_res"][0], 0.0, out["color"], out["alpha"], out["z_vals"])
         if needs_grad and full and self.fused_training == "core" and near_far is None:
             W = nsr_ops.weight_norm_all(list(self.sdf_net) + list(self.color_net))
             enc = self.encoder

@@ -196,6 +196,8 @@ def _render(field, rays_o, rays_d, num_steps, upsample_steps, bound, inv_s, bg, 
         o.pts = buf("pts", (N, T, 3)).data_ptr()
         if not long:        # the hash features of every sample's 7-point stencil (0.9 KB per sample): the backward streams them back instead of gathering them again
             o.feat7 = buf("feat7", (N * T // 16, 14, 64, 4)).data_ptr()
+        else:               # (none from the long renderer: render_core_backward gathers again; a reused result dict must not hand on another launch's)
+            res.pop("feat7", None)
     if debug_indices:
         o.ss_inds = buf("ss_inds", (N, max(nup, 1), 16), torch.int32).data_ptr()
         o.sort_index = buf("sort_index", (N, max(nup, 1), T if long else 128), torch.int32).data_ptr()

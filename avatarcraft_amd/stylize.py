@@ -212,6 +212,15 @@ def sds_step(net_style, net_gt, rays_o, rays_d, hw, optimizer, guidance, batch_s
                          num_steps, upsample_steps, timers, overlap_allreduce, grad_divisor, verdict)
 
 
+def _manual_supported(net, num_steps, upsample_steps):
+    """net.manual_backward_supported, told the counts where they matter: outside the fused renderer's window (the long renderer's counts) the
+    fused backward does not reach every model (NeRFNetwork.manual_backward_supported)"""
+    f = getattr(net, "manual_backward_supported", None)
+    if f is None:
+        return False
+    return f() if nsr_ops.in_short_window(num_steps, upsample_steps) else f(num_steps, upsample_steps)
+
+
 def _sds_step(net_style, net_gt, rays_o, rays_d, hw, optimizer, guidance, batch_size, w_eikonal, use_opacity, bkg_key, flat_grad, process_group, num_steps,
               upsample_steps, timers, overlap_allreduce, grad_divisor, verdict):
     h, w = hw
@@ -221,7 +230,7 @@ def _sds_step(net_style, net_gt, rays_o, rays_d, hw, optimizer, guidance, batch_
         if timers is not None:
             ev = torch.cuda.Event(enable_timing=True); ev.record(); timers.append((name, ev))
     mark("start")
-    manual = rays_o.is_cuda and getattr(net_style, "manual_backward_supported", lambda: False)()
+    manual = rays_o.is_cuda and _manual_supported(net_style, num_steps, upsample_steps)
     # One patch covers the view (the coarse stage: 64 x 64 rays): render_val and the training render of the patch are the same rays with two
     # noise draws -- one launch renders both (NeRFNetwork.render_step_pair); the training render does not depend on the guidance, only its
     # backward does.  Larger views keep the reference's order (render_val of the whole view first, then patch by patch).

@@ -537,7 +537,9 @@ int ac_color_backward(const ac_field *field, const float *x, const float *normal
  * (near/far of the cube and sample_dist = (far - near) / num_steps are recomputed), optional background [N,3] (NULL = white).
  * forward : image [N,3], weights_sum [N], depth [N], normal_map [N,3], weights [N,T], alpha [N,T] -- the arithmetic of ac_render_rays.
  * backward: (d image, d weights_sum, d depth, d normal_map) -> d sdf [N,T], d normal [N,T,3], d colour [N,T,3] and the per-ray partial
- *           sums of d inv_s [N] (the caller adds them up).  T = num_steps + upsample_steps, a multiple of 16, <= 128. */
+ *           sums of d inv_s [N] (the caller adds them up).  T = num_steps + upsample_steps: a multiple of 16, <= 128 (ac_render_rays' counts), or
+ *           ac_render_rays_long's: num_steps >= 2, upsample_steps >= 0 a multiple of 16, T <= 512 -- the weights are then that renderer's, bit for bit
+ *           (its last tile of 16 samples masked when 16 does not divide T). */
 int ac_composite_forward(const float *rays_o, const float *rays_d, const float *z_vals, const float *sdf, const float *normal, const float *color,
                          const float *bg, int32_t n_rays, int32_t num_steps, int32_t T, float bound, float inv_s, float cos_anneal_ratio,
                          float *image, float *weights_sum, float *depth, float *normal_map, float *weights, float *alpha, ac_stream_t stream);
@@ -549,6 +551,9 @@ int ac_composite_backward(const float *rays_o, const float *rays_d, const float 
 /* ---- the whole differentiable render core (models/instant_nsr.py:190-299) backward in one call (training path).
  * The forward is ac_render_rays itself with the per-sample outputs kept (z_vals, pts, sdf, sdf_out16, gradient, color and the
  * eikonal denominator of ac_eikonal_reduce2): the training render and the inference render are the same launch, bit for bit.
+ * At the long renderer's counts (T = num_steps + upsample_steps > 128 or not a multiple of 16; the envelope of ac_composite_forward) the forward is
+ * ac_render_rays_long with the same outputs; saved->feat7 must then be NULL when 16 does not divide T (that renderer does not write it: the stencil
+ * features are gathered again), and a field with view directions needs T a multiple of 16 (AC_ERR_BAD_ARG naming the rule otherwise).
  * The backward chains, on `stream`: normals from the finite-difference gradients -> NeuS alpha / compositing backward ->
  * colour MLP backward -> normalisation + eikonal backward -> fused SDF-query backward -> table-gradient scatter.
  *   upstream: d image [N,3], d weights_sum [N], d depth [N], d normal_map [N,3] (any may be NULL = 0), d gradient_error (1 float, device, or NULL)
