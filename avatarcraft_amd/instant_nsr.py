@@ -485,7 +485,7 @@ class NeRFRenderer(nn.Module):
                     out["eik_res"][0], 0.0, out["color"], out["alpha"], out["z_vals"])
         if long_counts:
             if needs_grad or not full:
-                # (the fused training operator -- fused_training = "core" under autograd -- stops at 128 samples: the long counts take the autograd
+                # (the fused training operator -- fused_training = "core" under autograd -- takes at most 128 samples: the long counts take the autograd
                 # render core, which handles any T)
                 z_vals = nsr_ops.sample_rays_long(self._field() if full else self._field_sdf_only(), ro, rd, num_steps, upsample_steps, bound,
                                                   noise=noise, near_far=near_far)

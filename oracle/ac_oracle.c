@@ -484,8 +484,11 @@ ORC_API float orc_test_sigmoid(float x) { return orc_sigmoid(x); }
 /* per-ray scans                                                        */
 /* ------------------------------------------------------------------ */
 /* inclusive scan of x[0..m) in tiles of 16: Kogge-Stone inside a tile (pad = identity),
- * sequential carry across tiles.  op: 0 = add, 1 = mul. */
-static void orc_tilescan(int op, const float *x, int m, float *out)
+ * sequential carry across tiles.  op: 0 = add, 1 = mul.  Returns the carry after the last tile: the
+ * reduction of whole tiles, pad included, which is how the renderers form the per-ray sums (a row's
+ * last lane).  It equals out[m-1] when 16 divides m; in a ragged last tile of r = m % 16 elements it
+ * is a different association unless r is a power of two (r = 3: (v0 + v1) + v2, not v0 + (v1 + v2)). */
+static float orc_tilescan(int op, const float *x, int m, float *out)
 {
     float carry = 0.0f;
     for (int t0 = 0; t0 < m; t0 += 16) {
@@ -500,6 +503,7 @@ static void orc_tilescan(int op, const float *x, int m, float *out)
             out[t0 + i] = (t0 == 0) ? v[i] : (op ? carry * v[i] : carry + v[i]);
         carry = (t0 == 0) ? v[15] : (op ? carry * v[15] : carry + v[15]);
     }
+    return carry;
 }
 
 /* ------------------------------------------------------------------ */
@@ -521,10 +525,14 @@ typedef struct {
     float *sdf;          /* [N,T]  sdf at the final mid points */
     float *gradient;     /* [N,T,3] FD gradient */
     int32_t *ss_inds;    /* [N, up/16, 16] searchsorted indices of sample_pdf */
-    int32_t *sort_index; /* [N, up/16, 128] torch.sort permutation of cat_z_vals (pad -1) */
+    int32_t *sort_index; /* [N, up/16, sort_stride] torch.sort permutation of cat_z_vals (pad -1); sort_stride >= T is an argument of the entry
+                          * point: 128 (the fused renderer's layout) or T (the long renderer's).  This struct and the entry points' signatures
+                          * are the library's ABI, which earlier callers pass as they are: they only gain new entry points, never fields */
 } orc_render_out;
 
-#define ORC_MAXT 128
+/* ORC_MAXT: ac_oracle.h.  orc_render_rays and orc_render_rays_warped keep the fused renderer's window (the long renderer is canonical
+ * only); orc_render_rays_long takes the long renderer's. */
+#define ORC_SHORT_MAXT 128
 
 /* sample_pdf(det=True) + up_sample (instant_nsr.py:21-55,410-459).  lin_u[16] is the
  * host-made torch.linspace(0.5/16, 1-0.5/16, 16). */
@@ -553,7 +561,7 @@ static void orc_up_sample(const float o[3], const float d[3], const float *z, co
         alpha[i] = (pc - nc + 1e-5f) / (pc + 1e-5f);
         om[i] = 1.0f - alpha[i] + 1e-7f;
     }
-    orc_tilescan(1, om, m, cp);                      /* inclusive cumprod */
+    orc_tilescan(1, om, m, cp);                      /* inclusive cumprod (the total is read at m - 1 below, as the kernels do) */
     for (int i = 0; i < m; i++) w[i] = alpha[i] * (i == 0 ? 1.0f : cp[i - 1]) + 1e-5f;
     float cs[ORC_MAXT];
     orc_tilescan(0, w, m, cs);
@@ -629,9 +637,10 @@ static void warp_clamp(const orc_warp_ctx *wc, const float *pts, int n, float bo
     }
 }
 
+/* range: NULL, or this ray's given (near, far) -- the near_far argument of the long renderer (render_long.hip:74-79) */
 static void render_one_ray(const orc_field *f, const orc_render_opts *op, const float *o, const float *d,
                            const float *bg, const float *noise, const float *lin_z, const float *lin_u,
-                           int r, const orc_render_out *out, const orc_warp_ctx *wc)
+                           int r, const orc_render_out *out, int sort_stride, const orc_warp_ctx *wc, const float *range)
 {
     const float bound = op->bound;
     const int T0 = op->num_steps, nup = op->upsample_steps / 16, T = T0 + 16 * nup;
@@ -645,11 +654,14 @@ static void render_one_ray(const orc_field *f, const orc_render_opts *op, const 
         if (k == 0 || hi < far) far = hi;
     }
     if (near < 0.05f) near = 0.05f;
+    float mesh_range[2];
     if (wc && wc->use_mesh_guide) {                  /* :148-153: mesh-guided range where the ray passes the body */
-        float nm, fm;
-        orc_mesh_near_far(o, d, wc->verts, 1, wc->V, wc->geo_threshold, &nm, &fm);
-        if (!isinf(nm)) near = nm;
-        if (!isinf(fm)) far = fm;
+        orc_mesh_near_far(o, d, wc->verts, 1, wc->V, wc->geo_threshold, &mesh_range[0], &mesh_range[1]);
+        range = mesh_range;
+    }
+    if (range) {                                     /* a finite value replaces the cube's (after its 0.05 clamp), +-inf keeps it */
+        if (!isinf(range[0])) near = range[0];
+        if (!isinf(range[1])) far = range[1];
     }
     const float span = far - near;
     const float sample_dist = span / (float)T0;      /* instant_nsr.py:160 */
@@ -674,7 +686,7 @@ static void render_one_ray(const orc_field *f, const orc_render_opts *op, const 
         }
         for (int it = 0; it < nup; it++) {           /* :182-184 */
             float znew[16], sdfnew[16];
-            float inv_s = (float)(64 << it);
+            float inv_s = ldexpf(64.0f, it);         /* 64 * 2^it, exact for all 31 passes (an int shift overflows from it = 25) */
             orc_up_sample(o, d, z, sdf, n, inv_s, lin_u, znew,
                           out->ss_inds ? out->ss_inds + ((size_t)r * nup + it) * 16 : NULL);
             int last = (it + 1 == nup);
@@ -692,8 +704,8 @@ static void render_one_ray(const orc_field *f, const orc_render_opts *op, const 
             for (int i = 0; i < n; i++) { z2[pos_old[i]] = z[i]; s2[pos_old[i]] = sdf[i]; }
             for (int j = 0; j < 16; j++) { z2[pos_new[j]] = znew[j]; s2[pos_new[j]] = last ? 0.0f : sdfnew[j]; }
             if (out->sort_index) {
-                int32_t *si = out->sort_index + ((size_t)r * nup + it) * 128;
-                for (int i = 0; i < 128; i++) si[i] = -1;
+                int32_t *si = out->sort_index + ((size_t)r * nup + it) * sort_stride;
+                for (int i = 0; i < sort_stride; i++) si[i] = -1;
                 for (int i = 0; i < n; i++) si[pos_old[i]] = i;
                 for (int j = 0; j < 16; j++) si[pos_new[j]] = n + j;
             }
@@ -756,20 +768,20 @@ static void render_one_ray(const orc_field *f, const orc_render_opts *op, const 
     }
     orc_tilescan(1, om, T, cp);
     for (int i = 0; i < T; i++) wgt[i] = alpha[i] * (i == 0 ? 1.0f : cp[i - 1]);   /* :250 */
-    /* reductions: tile-scan sums (last element of the inclusive add scan) */
+    /* reductions: tile-scan sums over whole tiles (orc_tilescan's total: a ragged last tile is padded with zeros, render_long.hip) */
     float tmp[ORC_MAXT], sc[ORC_MAXT];
-    orc_tilescan(0, wgt, T, sc); float wsum = sc[T - 1];
+    float wsum = orc_tilescan(0, wgt, T, sc);
     float img[3], nm[3];
     for (int k = 0; k < 3; k++) {
         for (int i = 0; i < T; i++) tmp[i] = col[i][k] * wgt[i];
-        orc_tilescan(0, tmp, T, sc); img[k] = sc[T - 1];
+        img[k] = orc_tilescan(0, tmp, T, sc);
         for (int i = 0; i < T; i++) tmp[i] = nrm[i][k] * wgt[i];
-        orc_tilescan(0, tmp, T, sc); nm[k] = sc[T - 1];
+        nm[k] = orc_tilescan(0, tmp, T, sc);
     }
     for (int i = 0; i < T; i++) tmp[i] = wgt[i] * zn[i];
-    orc_tilescan(0, tmp, T, sc); float depth = sc[T - 1];
-    orc_tilescan(0, eerr, T, sc); float e_num = sc[T - 1];
-    orc_tilescan(0, erelax, T, sc); float e_den = sc[T - 1];
+    float depth = orc_tilescan(0, tmp, T, sc);
+    float e_num = orc_tilescan(0, eerr, T, sc);
+    float e_den = orc_tilescan(0, erelax, T, sc);
     for (int k = 0; k < 3; k++) {
         float b = bg ? bg[k] : 1.0f;
         out->image[(size_t)r * 3 + k] = img[k] + (1.0f - wsum) * b;    /* :294 */
@@ -788,18 +800,35 @@ static void render_one_ray(const orc_field *f, const orc_render_opts *op, const 
 
 /* lin_z[T0] = torch.linspace(0,1,T0); lin_u[16] = torch.linspace(0.5/16, 1-0.5/16, 16)
  * (made by the host exactly as the reference does, instant_nsr.py:155,34);
- * bg may be NULL (bg_color = 1); noise [N,T0] U[0,1) only read when opts->perturb. */
+ * bg may be NULL (bg_color = 1); noise [N,T0] U[0,1) only read when opts->perturb;
+ * near_m / far_m [N] may be NULL (both or neither): per-ray sampling range, a finite value overrides the cube's;
+ * sort_stride >= T: the last dimension of out->sort_index.
+ * The envelope is the long renderer's: num_steps >= 2, upsample_steps a multiple of 16, T <= ORC_MAXT. */
+ORC_API int orc_render_rays_long(const orc_field *f, const orc_render_opts *op, const float *rays_o,
+                                 const float *rays_d, const float *bg, const float *noise,
+                                 const float *lin_z, const float *lin_u, const float *near_m, const float *far_m,
+                                 int32_t sort_stride, const orc_render_out *out)
+{
+    const int T = op->num_steps + op->upsample_steps;
+    if (op->num_steps < 2 || op->upsample_steps < 0 || op->upsample_steps % 16 || T > ORC_MAXT ||
+        (out->sort_index && sort_stride < T) || (!near_m != !far_m)) return 1;
+    #pragma omp parallel for schedule(dynamic, 4)
+    for (int64_t r = 0; r < (int64_t)op->n_rays; r++) {
+        const float range[2] = { near_m ? near_m[r] : 0.0f, far_m ? far_m[r] : 0.0f };
+        render_one_ray(f, op, rays_o + 3 * r, rays_d + 3 * r, bg ? bg + 3 * r : NULL,
+                       noise ? noise + (size_t)r * op->num_steps : NULL, lin_z, lin_u, (int)r, out, sort_stride, NULL, near_m ? range : NULL);
+    }
+    return 0;
+}
+
+/* the fused renderer's window (multiples of 16, 16 <= num_steps, at most 128 samples), sort_index [N, up/16, 128], the cube's range */
 ORC_API int orc_render_rays(const orc_field *f, const orc_render_opts *op, const float *rays_o,
                             const float *rays_d, const float *bg, const float *noise,
                             const float *lin_z, const float *lin_u, const orc_render_out *out)
 {
     if (op->num_steps % 16 || op->upsample_steps % 16 || op->num_steps < 16 ||
-        op->num_steps + op->upsample_steps > ORC_MAXT) return 1;
-    #pragma omp parallel for schedule(dynamic, 4)
-    for (int64_t r = 0; r < (int64_t)op->n_rays; r++)
-        render_one_ray(f, op, rays_o + 3 * r, rays_d + 3 * r, bg ? bg + 3 * r : NULL,
-                       noise ? noise + (size_t)r * op->num_steps : NULL, lin_z, lin_u, (int)r, out, NULL);
-    return 0;
+        op->num_steps + op->upsample_steps > ORC_SHORT_MAXT) return 1;
+    return orc_render_rays_long(f, op, rays_o, rays_d, bg, noise, lin_z, lin_u, NULL, NULL, ORC_SHORT_MAXT, out);
 }
 
 /* NeRFRenderer.run(render_can=False, verts, faces, Ts, use_mesh_guide) */
@@ -808,11 +837,11 @@ ORC_API int orc_render_rays_warped(const orc_field *f, const orc_render_opts *op
                                    const float *lin_z, const float *lin_u, const orc_warp_ctx *wc, const orc_render_out *out)
 {
     if (op->num_steps % 16 || op->upsample_steps % 16 || op->num_steps < 16 || op->num_steps > 64 ||
-        op->num_steps + op->upsample_steps > ORC_MAXT || !wc) return 1;
+        op->num_steps + op->upsample_steps > ORC_SHORT_MAXT || !wc) return 1;
     #pragma omp parallel for schedule(dynamic, 1)
     for (int64_t r = 0; r < (int64_t)op->n_rays; r++)
         render_one_ray(f, op, rays_o + 3 * r, rays_d + 3 * r, bg ? bg + 3 * r : NULL,
-                       noise ? noise + (size_t)r * op->num_steps : NULL, lin_z, lin_u, (int)r, out, wc);
+                       noise ? noise + (size_t)r * op->num_steps : NULL, lin_z, lin_u, (int)r, out, ORC_SHORT_MAXT, wc, NULL);
     return 0;
 }
 

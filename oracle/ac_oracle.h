@@ -8,6 +8,12 @@
 
 #define ORC_API __attribute__((visibility("default")))
 
+/* samples per ray the render forward (orc_render_rays_long) and the render-core backward accept: the long renderer's envelope
+ * (avatarcraft_amd/csrc/render_long.hip, AC_MAXT).  The per-ray arrays sized by it live on the stack: a frame of about 55 KB in the forward and
+ * 120 KB in the backward (gcc -fstack-usage), a few percent of the smallest stack an OpenMP worker gets (libgomp: OMP_STACKSIZE, else the pthread
+ * default -- the stack rlimit, or 2 MiB where that is unlimited). */
+#define ORC_MAXT 512
+
 /* effective (weight-normed) parameters of the default NeRFNetwork (models/instant_nsr.py:478-591) */
 typedef struct {
     const float *table;        /* embeddings [n_entries, 2] */
@@ -30,8 +36,8 @@ void orc_sh16(const float d[3], float sh[16]);
 /* NeRFRenderer.run options (models/instant_nsr.py:133-299) */
 typedef struct {
     int32_t n_rays;
-    int32_t num_steps;        /* coarse samples T0: multiple of 16, 16..64  */
-    int32_t upsample_steps;   /* multiple of 16, T0+up <= 128 */
+    int32_t num_steps;        /* coarse samples T0 >= 2 (orc_render_rays: a multiple of 16, >= 16; orc_render_rays_warped: 16..64 too) */
+    int32_t upsample_steps;   /* multiple of 16, T0+up <= ORC_MAXT (orc_render_rays, orc_render_rays_warped: <= 128) */
     float bound;
     float inv_s;              /* forward_variance(): exp(10*variance).clip(1e-6,1e6) */
     float cos_anneal_ratio;

@@ -43,7 +43,7 @@
 #define OFF_C1 (OFF_B2 + 16)
 #define OFF_C2 (OFF_C1 + NC1)
 #define OFF_C3 (OFF_C2 + NC2)
-#define BWD_MAXT 128
+#define BWD_MAXT ORC_MAXT
 
 typedef struct {
     double *g_table;     /* [n_entries * 2], accumulated into (caller zero-fills) */

@@ -468,14 +468,24 @@ class _WarpCtx(C.Structure):
                 ("can_mid", f32p), ("mask", C.POINTER(C.c_uint8))]
 
 
+MAX_SAMPLES = 512         # ORC_MAXT (ac_oracle.h): the long renderer's envelope
+
+
 def render_rays(field, rays_o, rays_d, num_steps=64, upsample_steps=64, bound=1.6, inv_s=None, bg=None, noise=None,
-                cos_anneal_ratio=1.0, normal_epsilon_ratio=0.0, extras=True, warp=None):
+                cos_anneal_ratio=1.0, normal_epsilon_ratio=0.0, extras=True, warp=None, near_far=None):
     """NeRFRenderer.run (models/instant_nsr.py:133-299).  render_can=True unless warp = dict(verts, faces, Ts[, threshold,
-    use_mesh_guide]) is given (render_can=False: SMPL-guided inverse warp of the samples).  Returns a dict."""
+    use_mesh_guide]) is given (render_can=False: SMPL-guided inverse warp of the samples).  Returns a dict.
+    Canonical space: num_steps >= 2, upsample_steps a multiple of 16, num_steps + upsample_steps <= MAX_SAMPLES (the long renderer's envelope);
+    near_far = (near [N], far [N]) overrides the cube's range where finite (+-inf keeps it), as the renderers' near_far argument does.
+    Posed space: the fused renderer's window (multiples of 16, 16 <= num_steps <= 64, at most 128 samples).
+    sort_index is [N, nup, 128] up to 128 samples (the fused renderer's layout), [N, nup, T] above (the long renderer's)."""
     rays_o = _f(rays_o).reshape(-1, 3); rays_d = _f(rays_d).reshape(-1, 3)
     N = rays_o.shape[0]
     T = num_steps + upsample_steps
     nup = upsample_steps // 16
+    if near_far is not None and warp is not None:
+        raise RuntimeError("render_rays: near_far is a canonical-space argument (posed space takes the mesh-guided range)")
+    stride = max(T, 128)
     lin_z, lin_u = linspace_tables(num_steps)
     op = _Opts(N, num_steps, upsample_steps, bound, float(inv_s), float(cos_anneal_ratio),
                float(np.float32(0.005 * (1.0 - normal_epsilon_ratio))), int(noise is not None))
@@ -485,15 +495,16 @@ def render_rays(field, rays_o, rays_d, num_steps=64, upsample_steps=64, bound=1.
         res.update(z_vals=np.empty((N, T), np.float32), weights=np.empty((N, T), np.float32),
                    alpha=np.empty((N, T), np.float32), color=np.empty((N, T, 3), np.float32),
                    sdf=np.empty((N, T), np.float32), gradient=np.empty((N, T, 3), np.float32),
-                   ss_inds=np.empty((N, max(nup, 1), 16), np.int32), sort_index=np.empty((N, max(nup, 1), 128), np.int32))
+                   ss_inds=np.empty((N, max(nup, 1), 16), np.int32), sort_index=np.empty((N, max(nup, 1), stride), np.int32))
     o = _Out()
     for k, v in res.items():
         setattr(o, k, _p(v, i32p if v.dtype == np.int32 else f32p))
     bgc = _f(bg).reshape(-1, 3) if bg is not None else None
     nz = _f(noise).reshape(N, num_steps) if noise is not None else None
     if warp is None:
-        rc = lib().orc_render_rays(C.byref(field.c), C.byref(op), _p(rays_o), _p(rays_d), _p(bgc), _p(nz), _p(lin_z), _p(lin_u),
-                                   C.byref(o))
+        nm, fm = (None, None) if near_far is None else (_f(near_far[0]).reshape(N), _f(near_far[1]).reshape(N))
+        rc = lib().orc_render_rays_long(C.byref(field.c), C.byref(op), _p(rays_o), _p(rays_d), _p(bgc), _p(nz), _p(lin_z), _p(lin_u),
+                                        _p(nm), _p(fm), C.c_int32(stride), C.byref(o))
     else:
         verts = _f(warp["verts"]).reshape(-1, 3)
         faces = np.ascontiguousarray(np.asarray(warp["faces"])[:, :3], np.int32)
@@ -506,7 +517,9 @@ def render_rays(field, rays_o, rays_d, num_steps=64, upsample_steps=64, bound=1.
         rc = lib().orc_render_rays_warped(C.byref(field.c), C.byref(op), _p(rays_o), _p(rays_d), _p(bgc), _p(nz), _p(lin_z), _p(lin_u),
                                           C.byref(wc), C.byref(o))
     if rc:
-        raise RuntimeError("render_rays: unsupported num_steps/upsample_steps")
+        rule = ("posed space: multiples of 16, 16 <= num_steps <= 64, at most 128 samples" if warp is not None else
+                f"num_steps >= 2, upsample_steps a multiple of 16, at most {MAX_SAMPLES} samples")
+        raise RuntimeError(f"render_rays: num_steps={num_steps} upsample_steps={upsample_steps} unsupported ({rule})")
     res["gradient_error"] = float(lib().orc_eikonal_reduce(_p(res["eik"]), C.c_int32(N)))
     return res
 

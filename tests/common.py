@@ -32,3 +32,34 @@ def edge_case_rays():
                    [0.0, 0.0, 1.0], [0.0, -1.0, 0.0], [1.0, 1e-9, -1e-9], [1e-4, -1e-4, -1.0], [0.0, 0.0, -3.0], [0.0, 0.0, -1.0]], np.float32)
     nrm = np.linalg.norm(rd, axis=1, keepdims=True); nrm[10] = 1.0              # ray 10 keeps its unnormalised direction
     return ro, (rd / nrm).astype(np.float32)
+
+
+# up-sampling passes whose sample indices are compared with the reference's at long counts (all passes of a case not listed).  16 + 496 runs 31
+# passes with inv_s = 64 * 2^i up to 6.9e10: from the sixth on (inv_s >= 2048) the cdf is a step function and sample_pdf's index is decided by
+# last-ulp differences between two fp32 implementations.  There a case pins what such a render is for -- pixels within 1e-3 and the final z values
+# within 2e-3 -- the indices of its first five passes exactly, and the number of indices that differ over all passes (LONG_INDEX_DIFFS: the
+# oracle's count, which the GPU shares bit for bit), so that it cannot drift silently.
+LONG_INDEX_PASSES = {"eval_16_496": 5}
+LONG_INDEX_DIFFS = {"eval_16_496": 1328}
+
+
+def sort_orders_match_up_to_ties(srt, srt_ref, flips):
+    """Sort permutations on every ray without a recorded flip: identical, except that the order may differ inside a window of differing
+    positions (neighbours at most 16 apart: the samples one pass adds) that holds the same set of indices on both sides.  From the fifth
+    up-sampling iteration on (inv_s >= 1024) sample_pdf places new samples exactly on existing z values: the renderers' merge keeps the old
+    sample first (a stable sort), torch.sort (not stable) may not -- a tie of three can even keep its middle element in place; the sorted z
+    values are the same either way."""
+    rays_ok = np.ones(srt.shape[0], bool)
+    rays_ok[flips[:, 0]] = False
+    for r in np.flatnonzero(rays_ok):
+        for it in range(srt.shape[1]):
+            a, b = srt[r, it], srt_ref[r, it]
+            d = np.flatnonzero(a != b)
+            i = 0
+            while i < len(d):                       # windows of differing positions
+                j = i
+                while j + 1 < len(d) and d[j + 1] - d[j] <= 16:
+                    j += 1
+                run = slice(d[i], d[j] + 1)
+                assert j > i and sorted(a[run]) == sorted(b[run]), (r, it, d[i:j + 1].tolist(), a[run].tolist(), b[run].tolist())
+                i = j + 1

@@ -8,10 +8,11 @@ served by oracle/.  The field is nsr_params.npz's (make_golden.build_reference_n
 Cases, 32 rays each (keys prefixed "<case>/"): eval (128, 128), (100, 64), (256, 0), (96, 32), (40, 16), (16, 496) (31 up-sampling passes,
 inv_s up to 64 * 2^30) and one train case (96, 32) with its
 recorded jitter noise and the gradients of image.sum() + gradient_error w.r.t. the table (a sample of rows) and the MLP parameters.
-RECORDED_FLIPS comes from the code under test, not from an independent oracle: oracle/ stops at 128 samples, so the positions (ray, pass, sample)
-where the searchsorted index differs from the reference's were measured by running the long renderer itself (ac_render_rays_long) on the GPU
-against this fixture.  They are the kind of ill-conditioned comparison tests/test_oracle_golden.py:_indices_match describes.  The GPU test asserts
-exactly these and no others, each off by at most 1.  16 + 496 has none in the passes the test compares (the first five, see INDEX_PASSES there).
+RECORDED_FLIPS are the CPU oracle's: the positions (ray, pass, sample) where oracle/'s restatement of run() (whose envelope is the long
+renderer's, up to 512 samples) picks a different searchsorted index than the reference, each off by exactly 1.  tests/test_oracle_long.py
+asserts that the oracle reproduces exactly these and no others, and that at 16 + 496 its indices differ in no pass the tests compare (the first
+five, tests/common.py:LONG_INDEX_PASSES) and in 1 328 over all 31; the GPU tests assert the same of the long renderer, which equals the oracle
+bit for bit (tests/test_gpu_long_oracle.py).  They are the kind of ill-conditioned comparison tests/test_oracle_golden.py:_indices_match describes.
 """
 import os
 import sys

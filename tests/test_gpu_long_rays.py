@@ -1,11 +1,14 @@
 """-m gpu: the long renderer (ac_render_rays_long / ac_sample_rays_long: any num_steps >= 2, upsample_steps a multiple of 16, at most 512 samples).
-Pinned two ways: bit for bit against the fused renderer (render_rays / sample_rays) where both accept the counts, and against the reference's own
-run() beyond that (tests/golden/run_long.npz, tests/golden/make_long_golden.py)."""
+Pinned three ways: bit for bit against the fused renderer (render_rays / sample_rays) where both accept the counts, bit for bit against the CPU
+oracle over the whole envelope (tests/test_gpu_long_oracle.py), and against the reference's own run() (tests/golden/run_long.npz,
+tests/golden/make_long_golden.py).  The searchsorted flips that comparison accepts are the oracle's (tests/test_oracle_long.py asserts that the
+oracle reproduces them), which this file asserts the GPU shares."""
 import numpy as np
 import pytest
 import torch
 
-from tests.common import load_golden, make_rays, edge_case_rays
+from tests.common import load_golden, make_rays, edge_case_rays, sort_orders_match_up_to_ties, LONG_INDEX_DIFFS, \
+    LONG_INDEX_PASSES as INDEX_PASSES
 from tests.gpu_common import device_field, assert_bitwise
 
 pytestmark = pytest.mark.gpu
@@ -14,11 +17,8 @@ DEV = "cuda:0"
 OVERLAP = [(16, 0), (32, 32), (64, 0), (64, 64), (16, 112)]
 OUT_KEYS = ["image", "weights_sum", "depth", "normal_map", "eik", "z_vals", "weights", "alpha", "color", "sdf", "gradient", "sdf_out16", "pts"]
 EVAL_CASES = ["eval_128_128", "eval_100_64", "eval_256_0", "eval_96_32", "eval_40_16", "eval_16_496"]
-# up-sampling passes whose sample indices are compared with the reference's (all passes of a case not listed).  16 + 496 runs 31 passes with
-# inv_s = 64 * 2^i up to 6.9e10: from the sixth on (inv_s >= 2048) the cdf is a step function and sample_pdf's index is decided by last-ulp
-# differences between two fp32 implementations (measured: 1 328 differing indices over passes 5 - 30, none before).  There the case pins
-# what such a render is for -- pixels within 1e-3 and the final z values within 2e-3 -- and the indices of its first five passes exactly.
-INDEX_PASSES = {"eval_16_496": 5}
+# INDEX_PASSES (tests/common.py): the up-sampling passes whose sample indices are compared with the reference's; at 16 + 496 the later passes hold
+# 1 328 differing indices, the oracle's count (tests/test_oracle_long.py), which the GPU shares bit for bit (tests/test_gpu_long_oracle.py)
 
 
 def t(a):
@@ -104,30 +104,10 @@ def test_long_vs_reference_golden(env, name):
         bad = ss != ss_ref
         assert np.array_equal(np.argwhere(bad).astype(np.int32).reshape(-1, 3), flips), f"searchsorted flips {np.argwhere(bad).tolist()} != recorded {flips.tolist()}"
         assert np.abs(ss.astype(np.int64) - ss_ref)[bad].max(initial=0) <= 1
-        _sort_orders_match_up_to_ties(h("sort_index")[:, :nup], c["sort_index"][:, :nup], flips)
+        sort_orders_match_up_to_ties(h("sort_index")[:, :nup], c["sort_index"][:, :nup], flips)
         assert np.abs(h("z_vals") - c["z_vals"]).max() <= 2e-3
-
-
-def _sort_orders_match_up_to_ties(srt, srt_ref, flips):
-    """Sort permutations on every ray without a recorded flip: identical, except that the order may differ inside a window of differing
-    positions (neighbours at most 16 apart: the samples one pass adds) that holds the same set of indices on both sides.  From the fifth
-    up-sampling iteration on (inv_s >= 1024) sample_pdf places new samples exactly on existing z values: the kernel's merge keeps the old sample
-    first (a stable sort), torch.sort (not stable) may not -- a tie of three can even keep its middle element in place; the sorted z values
-    are the same either way."""
-    rays_ok = np.ones(srt.shape[0], bool)
-    rays_ok[flips[:, 0]] = False
-    for r in np.flatnonzero(rays_ok):
-        for it in range(srt.shape[1]):
-            a, b = srt[r, it], srt_ref[r, it]
-            d = np.flatnonzero(a != b)
-            i = 0
-            while i < len(d):                       # windows of differing positions
-                j = i
-                while j + 1 < len(d) and d[j + 1] - d[j] <= 16:
-                    j += 1
-                run = slice(d[i], d[j] + 1)
-                assert j > i and sorted(a[run]) == sorted(b[run]), (r, it, d[i:j + 1].tolist(), a[run].tolist(), b[run].tolist())
-                i = j + 1
+        if name in LONG_INDEX_DIFFS:
+            assert int((h("ss_inds") != c["ss_inds"]).sum()) == LONG_INDEX_DIFFS[name]
 
 
 def _golden_net(train=False):

@@ -82,8 +82,8 @@ def test_long_backward_matches_reference_gradients(name):
         assert k == "z_off" or e <= tol, (k, e, worst)
 
 
-# ---- 2. the fp64 oracle at ragged counts ------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("T0,up", [(100, 16), (40, 16), (70, 48), (96, 32)])
+# ---- 2. the fp64 oracle at ragged and long counts --------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("T0,up", [(100, 16), (40, 16), (70, 48), (96, 32), (100, 64), (128, 128), (256, 0), (2, 496)])
 def test_long_backward_matches_oracle_fp64(T0, up):
     from avatarcraft_amd import nsr_ops
     from oracle import oracle as O
@@ -92,6 +92,11 @@ def test_long_backward_matches_oracle_fp64(T0, up):
     f, table = device_field(p, device=DEV)
     of = oracle_field(p, table)
     ro, rd = bench.sds_view(0)                      # test_oracle_backward.py's 4096-ray patch
+    if (T0, up) == (128, 128):
+        # its first 1024 rays: with this case's upstream draws, d loss / d inv_s over the whole patch is a cancellation -- +0.168 on these rays,
+        # -0.167 on the rest, a total of 1.4e-3 against 21.6 summed over the per-ray magnitudes -- so the relative bound below would measure
+        # the cancellation (4.9e-3), not the backward (measured per part: 3.3e-5 and 7.4e-5 of the oracle's value)
+        ro, rd = ro[:1024], rd[:1024]
     N = ro.shape[0]
     rs = np.random.RandomState(T0 * 1000 + up)
     noise = rs.uniform(0, 1, (N, T0)).astype(np.float32)
