@@ -144,6 +144,8 @@ _SIGS = {
     "ac_render_rays_warped_scratch": ([i32, i32, C.POINTER(C.c_size_t)], C.c_size_t),
     "ac_render_rays_warped": ([C.POINTER(ac_field), C.POINTER(ac_render_opts), vp, vp, vp, vp, vp, vp, C.POINTER(ac_warp_mesh), vp, C.c_size_t,
                                C.POINTER(ac_render_out), vp], C.c_int),
+    "ac_render_rays_long_warped": ([C.POINTER(ac_field), C.POINTER(ac_render_opts), vp, vp, vp, vp, vp, vp, C.POINTER(ac_warp_mesh), vp, C.c_size_t,
+                                    C.POINTER(ac_render_out), vp], C.c_int),
     "ac_warp_samples": ([vp, vp, vp, vp, u32, u32, u32, C.c_double, vp, vp, vp, vp, vp, vp, vp], C.c_int),
     "ac_sh_bias": ([C.POINTER(ac_field), vp, u32, vp, vp, vp], C.c_int),
     "ac_field_color_dirs": ([C.POINTER(ac_field), vp, vp, vp, vp, u32, vp, vp], C.c_int),

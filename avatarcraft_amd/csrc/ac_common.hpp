@@ -21,6 +21,17 @@ int warp_samples_accel_impl(const float *pts, const float *verts, const int32_t 
 // skip_masked rendering: ray_dead[r] = 1 if no sample of ray r (coarse samples coarse_pts [N, T0, 3] and everything between them) can be unmasked
 int warp_ray_cull(const float *coarse_pts, uint32_t N, uint32_t T0, double threshold, const void *accel, uint8_t *ray_dead, ac_stream_t stream);
 
+// the steps of a posed-space render that ac_render_rays_warped and ac_render_rays_long_warped share (render_fused.hip):
+//   warped_coarse_pts: pts[n, i] = o + d * z_i of the coarse samples (unclamped), the input of the first closest-face search; `who` names the launch in an error;
+//   warp_any: one closest-face search + inverse warp of P points through the mesh's culling structure (or the exhaustive search without one);
+//             spr / seed_off: this search's columns [seed_off, seed_off + spr) of ac_warp_mesh.seed_faces;
+//   warped_phase_mark: phase boundary k (0 .. 5) of ac_debug_warped_phases
+int warped_coarse_pts(const char *who, const float *rays_o, const float *rays_d, const float *near_m, const float *far_m, const float *lin_z, const float *noise,
+                      int n_rays, int T0, float bound, int perturb, float *pts, hipStream_t st);
+int warp_any(const ac_warp_mesh *m, const float *pts, uint32_t P, float *can, uint8_t *mask, ac_stream_t stream, int skip_far = 0,
+             const uint8_t *ray_dead = nullptr, uint32_t spr = 1, uint32_t seed_off = 0);
+void warped_phase_mark(int k, hipStream_t st);
+
 inline int check_launch(const char *what)
 {
     hipError_t e = hipGetLastError();

@@ -970,8 +970,16 @@ AC_API size_t ac_render_rays_warped_scratch(int32_t n_rays, int32_t T, size_t of
     return o + ((N + 255) & ~(size_t)255);                     // + ray_dead [N] u8 (skip_masked), behind the six documented segments
 }
 
-static int warp_any(const ac_warp_mesh *m, const float *pts, uint32_t P, float *can, uint8_t *mask, ac_stream_t stream, int skip_far = 0,
-                    const uint8_t *ray_dead = nullptr, uint32_t spr = 1, uint32_t seed_off = 0)
+// the helpers of the posed sequence below; ac:: linkage (ac_common.hpp) because ac_render_rays_long_warped (render_long.hip) chains the same steps
+int ac::warped_coarse_pts(const char *who, const float *rays_o, const float *rays_d, const float *near_m, const float *far_m, const float *lin_z, const float *noise,
+                          int n_rays, int T0, float bound, int perturb, float *pts, hipStream_t st)
+{
+    hipLaunchKernelGGL(coarse_pts_kernel, dim3((n_rays * T0 + 255) / 256), dim3(256), 0, st, rays_o, rays_d, near_m, far_m, lin_z, noise, n_rays, T0, bound, perturb, pts);
+    return ac::check_launch(who);
+}
+
+int ac::warp_any(const ac_warp_mesh *m, const float *pts, uint32_t P, float *can, uint8_t *mask, ac_stream_t stream, int skip_far,
+                 const uint8_t *ray_dead, uint32_t spr, uint32_t seed_off)
 {
     if (m->accel) {
         // temporal seeds (ac_warp_mesh.seed_faces): this search's columns [seed_off, seed_off + spr) of the caller's per-ray rows
@@ -985,11 +993,12 @@ static int warp_any(const ac_warp_mesh *m, const float *pts, uint32_t P, float *
 // Measurement hook (bench.py's posed-frame roofline): with ac_debug_warped_phases(1) every ac_render_rays_warped call records HIP events on its stream
 // at the phase boundaries -- [0] start, [1] near / far + coarse points + ray cull, [2] first warp search, [3] up-sampling pass, [4] second warp search,
 // [5] final pass -- and ac_debug_warped_phase_ms() returns the five intervals of the LAST call in ms (it waits for that call).  Off by default.
+// (ac_render_rays_long_warped marks the same boundaries.)
 namespace {
 hipEvent_t g_phase_ev[6];
 int g_phase_on = 0, g_phase_have = 0;
-void phase_mark(int k, hipStream_t st) { if (g_phase_on) { (void)hipEventRecord(g_phase_ev[k], st); if (k == 5) g_phase_have = 1; } }
 }
+void ac::warped_phase_mark(int k, hipStream_t st) { if (g_phase_on) { (void)hipEventRecord(g_phase_ev[k], st); if (k == 5) g_phase_have = 1; } }
 AC_API void ac_debug_warped_phases(int enable)
 {
     if (enable && !g_phase_on) for (auto &e : g_phase_ev) (void)hipEventCreate(&e);
@@ -1030,36 +1039,35 @@ AC_API int ac_render_rays_warped(const ac_field *field, const ac_render_opts *op
     hipStream_t st = (hipStream_t)stream;
     RenderArgs a{};
     if (int rc = fill_render_args(a, field, op, rays_o, rays_d, bg, noise, lin_z, lin_u, out)) return rc;
-    phase_mark(0, st);
+    ac::warped_phase_mark(0, st);
     if (mesh->use_mesh_guide) {
         if (int rc = ac_mesh_near_far(rays_o, rays_d, mesh->verts, (uint32_t)N, mesh->V, mesh->geo_threshold, near_m, far_m, stream)) return rc;
         a.near_m = near_m; a.far_m = far_m;
     }
     a.zbuf = zbuf; a.mid_pts = pts;
     if (op->upsample_steps > 0) {                                 // coarse samples -> canonical space (:166-172)
-        hipLaunchKernelGGL(coarse_pts_kernel, dim3((N * T0 + 255) / 256), dim3(256), 0, st, rays_o, rays_d, a.near_m, a.far_m, lin_z, noise, N, T0,
-                           op->bound, op->perturb, pts);
-        if (int rc = ac::check_launch("render_rays_warped (coarse points)")) return rc;
+        if (int rc = ac::warped_coarse_pts("render_rays_warped (coarse points)", rays_o, rays_d, a.near_m, a.far_m, lin_z, noise, N, T0, op->bound, op->perturb, pts, st))
+            return rc;
         if (op->skip_masked && mesh->accel) {                     // rays that cannot hold an unmasked sample: no search, no field evaluation
             uint8_t *rdead = reinterpret_cast<uint8_t *>(sc + ac_render_rays_warped_scratch(N, T, nullptr) - (((size_t)N + 255) & ~(size_t)255));
             if (int rc = ac::warp_ray_cull(pts, (uint32_t)N, (uint32_t)T0, mesh->threshold, mesh->accel, rdead, stream)) return rc;
             ray_dead = rdead;
         }
-        phase_mark(1, st);
-        if (int rc = warp_any(mesh, pts, (uint32_t)(N * T0), can, mask, stream, 0, ray_dead, (uint32_t)T0, 0u)) return rc;
-    } else phase_mark(1, st);
-    phase_mark(2, st);
+        ac::warped_phase_mark(1, st);
+        if (int rc = ac::warp_any(mesh, pts, (uint32_t)(N * T0), can, mask, stream, 0, ray_dead, (uint32_t)T0, 0u)) return rc;
+    } else ac::warped_phase_mark(1, st);
+    ac::warped_phase_mark(2, st);
     a.ext_pts = can;
     a.ray_dead = ray_dead;
     launch_render<MODE_UPSAMPLE>(a, st);                          // coarse sdf, up-sampling, mid points (posed space)
     if (int rc = ac::check_launch("render_rays_warped (up-sampling)")) return rc;
-    phase_mark(3, st);
+    ac::warped_phase_mark(3, st);
     // (skip_masked: the final pass does not evaluate masked-out samples, so the search may leave out those the cell grids prove masked)
-    if (int rc = warp_any(mesh, pts, (uint32_t)(N * T), can, mask, stream, op->skip_masked, ray_dead, (uint32_t)T, (uint32_t)T0)) return rc;     // :198-203
-    phase_mark(4, st);
+    if (int rc = ac::warp_any(mesh, pts, (uint32_t)(N * T), can, mask, stream, op->skip_masked, ray_dead, (uint32_t)T, (uint32_t)T0)) return rc;     // :198-203
+    ac::warped_phase_mark(4, st);
     a.mask = mask;
     launch_render<MODE_FINAL>(a, st);
-    phase_mark(5, st);
+    ac::warped_phase_mark(5, st);
     return ac::check_launch("render_rays_warped");
 }
 

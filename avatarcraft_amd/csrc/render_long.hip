@@ -12,6 +12,8 @@
 //     and nothing to the cdf, the merges, the sums or the outputs;
 //   * lin_z is read from device memory (any length) instead of the 64-float LDS slot;
 //   * whole rays are the work items, dealt statically (no segment hand-off, no scratch): every ray costs the same number of tiles.
+// Posed space (ac_render_rays_long_warped) is the sequence of ac_render_rays_warped on this kernel: MODE_UPSAMPLE takes the warped coarse points
+// and writes z and the posed mid points, MODE_FINAL runs the render core at the warped mid points with alpha * mask.
 #define AC_MAXT 512
 #ifndef AC_WPB
 #define AC_WPB 7
@@ -26,7 +28,6 @@ constexpr int NCH = MAXT / 64;          // 64-lane chunks of the up-sampling sca
 template <int MODE, bool FAST, bool EX, bool SH>
 __global__ __launch_bounds__(BLOCK) void render_rays_long_kernel(const RenderArgs a)
 {
-    static_assert(MODE == MODE_FULL || MODE == MODE_UPSAMPLE, "canonical space only");
     constexpr bool FC = FAST;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if (a.prepared) {
@@ -79,18 +80,42 @@ __global__ __launch_bounds__(BLOCK) void render_rays_long_kernel(const RenderArg
         }
         const float span = far - near;
         const float sample_dist = span / (float)T0;
-        int cur = nup & 1, cnt = T0;
+        int cur = (MODE == MODE_FINAL) ? 0 : (nup & 1), cnt = T0;
         float *const zs_first = cur ? zs1 : zs0;
 
+        if constexpr (MODE == MODE_UPSAMPLE) {
+            // skip_masked: a ray that cannot hold an unmasked sample (ray_cull) is not evaluated; its z array is the coarse one padded with its last value
+            if (a.ray_dead && a.ray_dead[ray]) {
+                for (int i = lane; i < T; i += 64) {
+                    const int ic = i < T0 ? i : T0 - 1;
+                    float zi = near + span * a.lin_z[ic];
+                    if (a.perturb) zi = zi + (a.noise[(size_t)ray * T0 + ic] - 0.5f) * sample_dist;
+                    const size_t si = (size_t)ray * T + i;
+                    a.zbuf[si] = zi;
+                    if (a.mid_pts) { a.mid_pts[3 * si] = ox + dx * zi; a.mid_pts[3 * si + 1] = oy + dy * zi; a.mid_pts[3 * si + 2] = oz + dz * zi; }
+                }
+                wave_sync();
+                continue;
+            }
+        }
         // ---- coarse samples (last tile masked when 16 does not divide num_steps) --------------------------------------------------
-        for (int c = 0; c < ntile0; ++c) {
+        if constexpr (MODE == MODE_FINAL) {
+            for (int i = lane; i < T; i += 64) zs0[i] = a.zbuf[(size_t)ray * T + i];
+        }
+        for (int c = 0; c < (MODE == MODE_FINAL ? 0 : ntile0); ++c) {
             const int i = 16 * c + n;
             const bool valid = i < T0;
             const int ic = valid ? i : T0 - 1;
             float zi = near + span * a.lin_z[ic];
             if (a.perturb) zi = zi + (a.noise[(size_t)ray * T0 + ic] - 0.5f) * sample_dist;
             if (nup > 0) {
-                const float px = clampf(ox + dx * zi, -bound, bound), py = clampf(oy + dy * zi, -bound, bound), pz = clampf(oz + dz * zi, -bound, bound);
+                float px = clampf(ox + dx * zi, -bound, bound), py = clampf(oy + dy * zi, -bound, bound), pz = clampf(oz + dz * zi, -bound, bound);
+                if constexpr (MODE == MODE_UPSAMPLE) {
+                    if (a.ext_pts) {                                // posed space: the warped coarse points
+                        const float *e = a.ext_pts + ((size_t)ray * T0 + ic) * 3;
+                        px = clampf(e[0], -bound, bound); py = clampf(e[1], -bound, bound); pz = clampf(e[2], -bound, bound);
+                    }
+                }
                 const f32x4 o2 = sdf_tile(lds, fc, lane, px, py, pz);
                 if (g == 0 && valid) sd[cur * MAXT + i] = o2[0];
             }
@@ -99,7 +124,7 @@ __global__ __launch_bounds__(BLOCK) void render_rays_long_kernel(const RenderArg
         wave_sync();
 
         // ---- NeuS up-sampling: chunks of 64 bins; chunks past the last bin are not visited (they would only scan identities) -----------
-        for (int it = 0; it < nup; ++it) {
+        for (int it = 0; it < (MODE == MODE_FINAL ? 0 : nup); ++it) {
             const float *zc = cur ? zs1 : zs0, *sc = sd + cur * MAXT;
             float *zn_ = cur ? zs0 : zs1, *sn_ = sd + (cur ^ 1) * MAXT;
             const int m = cnt - 1;
@@ -238,7 +263,16 @@ __global__ __launch_bounds__(BLOCK) void render_rays_long_kernel(const RenderArg
 
         const float *zf = zs0;
         if constexpr (MODE == MODE_UPSAMPLE) {
-            for (int i = lane; i < T; i += 64) a.zbuf[(size_t)ray * T + i] = zf[i];
+            for (int i = lane; i < T; i += 64) {
+                const size_t si = (size_t)ray * T + i;
+                const float zi = zf[i];
+                a.zbuf[si] = zi;
+                if (a.mid_pts) {                                    // posed space: the mid points o + d * zmid (before the clamp) go to the second search
+                    const float delta = (i < T - 1) ? zf[i + 1] - zi : sample_dist;
+                    const float zmid = (i < T - 1) ? zi + 0.5f * delta : zi;
+                    a.mid_pts[3 * si] = ox + dx * zmid; a.mid_pts[3 * si + 1] = oy + dy * zmid; a.mid_pts[3 * si + 2] = oz + dz * zmid;
+                }
+            }
             wave_sync();
             continue;
         }
@@ -255,10 +289,23 @@ __global__ __launch_bounds__(BLOCK) void render_rays_long_kernel(const RenderArg
             const float zi = zf[ii];
             const float delta = (ii < T - 1) ? zf[ii + 1] - zi : sample_dist;
             const float zmid = (ii < T - 1) ? zi + 0.5f * delta : zi;
-            const float px = clampf(ox + dx * zmid, -bound, bound), py = clampf(oy + dy * zmid, -bound, bound), pz = clampf(oz + dz * zmid, -bound, bound);
+            float px, py, pz;
+            // posed space: the warp's mask of this sample, and (skip_masked) a tile whose 16 samples are all masked out is not evaluated: it contributes
+            // alpha * 0 whatever the field says there (wave-uniform; lanes past T count as masked)
+            float mk = 1.0f;
+            bool skip = false;
+            if constexpr (MODE == MODE_FINAL) {
+                const float *e = a.ext_pts + ((size_t)ray * T + ii) * 3;
+                px = clampf(e[0], -bound, bound); py = clampf(e[1], -bound, bound); pz = clampf(e[2], -bound, bound);
+                const bool live = a.mask[(size_t)ray * T + ii] != 0;
+                mk = live ? 1.0f : 0.0f;
+                if (a.skip_masked) skip = __ballot(valid && live) == 0ull;
+            } else {
+                px = clampf(ox + dx * zmid, -bound, bound); py = clampf(oy + dy * zmid, -bound, bound); pz = clampf(oz + dz * zmid, -bound, bound);
+            }
             f32x4 oc = { 0.0f, 0.0f, 0.0f, 0.0f };
             float gr[3] = { 0.0f, 0.0f, 0.0f };
-            {
+            if (MODE != MODE_FINAL || !skip) {
             float fe0[4][2];
             encode_stencil(lds, fsl, fc, lane, px, py, pz, bxe, fe0);
             // (render_rays_kernel's stencil, kept inline: as a shared helper it changes both renderers' code)
@@ -315,8 +362,10 @@ __global__ __launch_bounds__(BLOCK) void render_rays_long_kernel(const RenderArg
             const FdNormal nrm = fd_normal(gx, gy, gz);
             const float gn = nrm.gn, nx = nrm.nx, ny = nrm.ny, nz = nrm.nz;
             float rgb[3] = { 0.0f, 0.0f, 0.0f };
+            if (MODE != MODE_FINAL || !skip) {
             if constexpr (FC) color_tile_fast(lds, lane, px, py, pz, nx, ny, nz, oc, rgb, nullptr, 16, SH ? zs0 + SLAB_SHB : nullptr);
             else color_tile(lds, lane, px, py, pz, nx, ny, nz, oc, rgb, nullptr, 16, SH ? zs0 + SLAB_SHB : nullptr);
+            }
             const float sdf0 = oc[0];
             // (neus_alpha's arithmetic, inline: through the helper this kernel's code changes)
             const float tc = (dx * nx + dy * ny) + dz * nz;
@@ -325,7 +374,8 @@ __global__ __launch_bounds__(BLOCK) void render_rays_long_kernel(const RenderArg
             const float iter_cos = -(a1 + a2);
             const float half = iter_cos * delta * 0.5f;
             const float pc = dv_sigmoid((sdf0 - half) * inv_s_core), nc = dv_sigmoid((sdf0 + half) * inv_s_core);
-            const float alpha = valid ? clampf((pc - nc + 1e-5f) / (pc + 1e-5f), 0.0f, 1.0f) : 0.0f;
+            float alpha = valid ? clampf((pc - nc + 1e-5f) / (pc + 1e-5f), 0.0f, 1.0f) : 0.0f;
+            if constexpr (MODE == MODE_FINAL) alpha = alpha * mk;
             const float om = valid ? 1.0f - alpha + 1e-7f : 1.0f;              // masked lanes: the identity of the product scan
             const float loc = row_scan<true>(om);
             const float sh = dpp_shr<1>(1.0f, loc);
@@ -337,7 +387,7 @@ __global__ __launch_bounds__(BLOCK) void render_rays_long_kernel(const RenderArg
             const float wgt = alpha * Tex;
             const float zn01 = clampf((zi - near) / span, 0.0f, 1.0f);
             const float pn = __builtin_sqrtf((px * px + py * py) + pz * pz);
-            const float relax = (pn < 1.2f && valid) ? 1.0f : 0.0f;
+            const float relax = (pn < 1.2f && valid && !(MODE == MODE_FINAL && skip)) ? 1.0f : 0.0f;
             const float eerr = relax * ((gn - 1.0f) * (gn - 1.0f));
             {
                 // masked lanes add exact zeros (x + 0 = x): wgt = 0 there, and every factor it meets is finite whenever the ray's own last
@@ -381,7 +431,7 @@ __global__ __launch_bounds__(BLOCK) void render_rays_long_kernel(const RenderArg
 }
 
 static int check_long_args(const char *who, const ac_render_opts *op, const float *rays_o, const float *rays_d, const float *noise,
-                           const float *lin_z, const float *lin_u)
+                           const float *lin_z, const float *lin_u, bool posed = false)
 {
     if (op->num_steps < 2 || op->upsample_steps < 0 || op->upsample_steps % 16 || op->num_steps + op->upsample_steps > LONG_MAX_T) {
         ac::set_error("%s: num_steps=%d upsample_steps=%d unsupported (num_steps >= 2, upsample_steps >= 0 and a multiple of 16, "
@@ -394,7 +444,10 @@ static int check_long_args(const char *who, const ac_render_opts *op, const floa
     }
     if (op->precision != 0 && op->precision != 1) { ac::set_error("%s: precision %d unknown (0 = exact, 1 = fast)", who, op->precision); return AC_ERR_BAD_ARG; }
     if (op->opacity_only) { ac::set_error("%s: opacity_only is not supported by the long renderer", who); return AC_ERR_BAD_ARG; }
-    if (op->skip_masked) { ac::set_error("%s: skip_masked is a posed-space option; the long renderer is canonical only", who); return AC_ERR_BAD_ARG; }
+    if (op->skip_masked != 0 && op->skip_masked != 1) { ac::set_error("%s: skip_masked must be 0 or 1", who); return AC_ERR_BAD_ARG; }
+    if (op->skip_masked && !posed) {
+        ac::set_error("%s: skip_masked is a posed-space option; this entry is canonical (posed: ac_render_rays_long_warped)", who); return AC_ERR_BAD_ARG;
+    }
     if ((op->near_m != nullptr) != (op->far_m != nullptr)) { ac::set_error("%s: near_m and far_m go together", who); return AC_ERR_BAD_ARG; }
     if (op->n_rays > 0 && (!rays_o || !rays_d || !lin_z || (op->upsample_steps && !lin_u) || (op->perturb && !noise))) {
         ac::set_error("%s: NULL buffer", who); return AC_ERR_BAD_ARG;
@@ -455,4 +508,71 @@ AC_API int ac_sample_rays_long(const ac_field *field, const ac_render_opts *op, 
     a.zbuf = z_vals;
     launch_long_p<MODE_UPSAMPLE, false, false, false>(a, (hipStream_t)stream);
     return ac::check_launch("sample_rays_long");
+}
+
+// Posed space at the long counts: ac_render_rays_warped's sequence (render_fused.hip) on this kernel -- mesh near / far -> coarse posed points -> (ray cull)
+// -> first closest-face search -> MODE_UPSAMPLE (coarse sdf at the warped coarse points, up-sampling, z and the posed mid points) -> second search ->
+// MODE_FINAL (field at the warped mid points, alpha * mask, optional skipping of fully masked tiles).  Scratch: ac_render_rays_warped_scratch(n_rays, T, offs).
+AC_API int ac_render_rays_long_warped(const ac_field *field, const ac_render_opts *op, const float *rays_o, const float *rays_d,
+                                      const float *bg, const float *noise, const float *lin_z, const float *lin_u,
+                                      const ac_warp_mesh *mesh, void *scratch, size_t scratch_bytes, const ac_render_out *out,
+                                      ac_stream_t stream)
+{
+    const char *who = "render_rays_long_warped";
+    if (!op || !out || !mesh) { ac::set_error("%s: NULL opts/out/mesh", who); return AC_ERR_BAD_ARG; }
+    if (int rc = check_long_args(who, op, rays_o, rays_d, noise, lin_z, lin_u, true)) return rc;
+    if (out->feat7) { ac::set_error("%s: feat7 (the fused training backward's features) is not produced by the long renderer", who); return AC_ERR_BAD_ARG; }
+    if (op->n_rays <= 0) return AC_OK;
+    if (!out->image || !out->weights_sum || !out->depth || !out->normal_map || !out->eik) { ac::set_error("%s: NULL buffer", who); return AC_ERR_BAD_ARG; }
+    if (!mesh->verts || !mesh->faces || !mesh->T || mesh->V == 0 || mesh->F == 0) { ac::set_error("%s: NULL mesh buffer or empty mesh", who); return AC_ERR_BAD_ARG; }
+    const int N = op->n_rays, T0 = op->num_steps, T = T0 + op->upsample_steps;
+    if ((size_t)N * (size_t)T > 0x7fffffffu) { ac::set_error("%s: %d rays x %d samples: too many samples for one launch", who, N, T); return AC_ERR_BAD_ARG; }
+    size_t offs[6];
+    const size_t need = ac_render_rays_warped_scratch(N, T, offs);
+    if (!scratch || scratch_bytes < need) { ac::set_error("%s: scratch of %zu bytes needed, %zu given", who, need, scratch_bytes); return AC_ERR_BAD_ARG; }
+    char *sc = static_cast<char *>(scratch);
+    float *near_m = reinterpret_cast<float *>(sc + offs[0]), *far_m = reinterpret_cast<float *>(sc + offs[1]);
+    float *pts = reinterpret_cast<float *>(sc + offs[2]), *can = reinterpret_cast<float *>(sc + offs[3]);
+    uint8_t *mask = reinterpret_cast<uint8_t *>(sc + offs[4]);
+    float *zbuf = reinterpret_cast<float *>(sc + offs[5]);
+    const uint8_t *ray_dead = nullptr;
+    const hipStream_t st = (hipStream_t)stream;
+    RenderArgs a{};
+    if (int rc = fill_render_common(a, field, op, rays_o, rays_d, bg, noise, lin_z, lin_u)) return rc;
+    a.out = *out;
+    a.skip_masked = op->skip_masked;
+    ac::warped_phase_mark(0, st);
+    if (mesh->use_mesh_guide) {
+        if (int rc = ac_mesh_near_far(rays_o, rays_d, mesh->verts, (uint32_t)N, mesh->V, mesh->geo_threshold, near_m, far_m, stream)) return rc;
+        a.near_m = near_m; a.far_m = far_m;
+    }
+    a.zbuf = zbuf; a.mid_pts = pts;
+    if (op->upsample_steps > 0) {
+        if (int rc = ac::warped_coarse_pts("render_rays_long_warped (coarse points)", rays_o, rays_d, a.near_m, a.far_m, lin_z, noise, N, T0, op->bound, op->perturb, pts, st))
+            return rc;
+        if (op->skip_masked && mesh->accel) {                     // rays that cannot hold an unmasked sample: no search, no field evaluation
+            uint8_t *rdead = reinterpret_cast<uint8_t *>(sc + need - (((size_t)N + 255) & ~(size_t)255));
+            if (int rc = ac::warp_ray_cull(pts, (uint32_t)N, (uint32_t)T0, mesh->threshold, mesh->accel, rdead, stream)) return rc;
+            ray_dead = rdead;
+        }
+        ac::warped_phase_mark(1, st);
+        if (int rc = ac::warp_any(mesh, pts, (uint32_t)(N * T0), can, mask, stream, 0, ray_dead, (uint32_t)T0, 0u)) return rc;
+    } else ac::warped_phase_mark(1, st);
+    ac::warped_phase_mark(2, st);
+    a.ext_pts = can;
+    a.ray_dead = ray_dead;
+    if (a.out.ss_inds || a.out.sort_index) launch_long_p<MODE_UPSAMPLE, false, true, false>(a, st);      // (the sampling launch can export the sample indices)
+    else launch_long_p<MODE_UPSAMPLE, false, false, false>(a, st);
+    if (int rc = ac::check_launch("render_rays_long_warped (up-sampling)")) return rc;
+    ac::warped_phase_mark(3, st);
+    if (int rc = ac::warp_any(mesh, pts, (uint32_t)(N * T), can, mask, stream, op->skip_masked, ray_dead, (uint32_t)T, (uint32_t)T0)) return rc;
+    ac::warped_phase_mark(4, st);
+    a.mask = mask;
+    dispatch_variants(a.fast, long_wants_samples(a.out), a.Wsh != nullptr, [&](auto fast, auto ex, auto sh) {
+        launch_long_p<MODE_FINAL, decltype(fast)::value, decltype(ex)::value, decltype(sh)::value>(a, st);
+    });
+    ac::warped_phase_mark(5, st);
+    if (int rc = ac::check_launch(who)) return rc;
+    if (out->eik_reduced) return ac_eikonal_reduce2(out->eik, op->n_rays, out->eik_reduced, stream);
+    return AC_OK;
 }

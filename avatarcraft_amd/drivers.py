@@ -72,9 +72,12 @@ def render_canonical_360(net, n_views=100, render_hw=(256, 256), center=(0.0, 0.
 
 
 def render_animation(net, body_model, cam_pose, poses=None, render_type="animate", shape_from=None, shape_to=None, resolution=256, max_frames=100,
-                     white_bkg=True, rays_per_batch=None, device="cuda", rank=None, world=None):
+                     white_bkg=True, rays_per_batch=None, device="cuda", rank=None, world=None, num_steps=32, upsample_steps=32):
     """yields (frame index, rgb [res,res,3]) for an SMPL pose sequence (render_type "animate", poses [F,72]) or a shape interpolation
     ("interp_shape", shape_from / shape_to [1,10]), seen from the dataset camera `cam_pose` [4,4]; 32 + 32 samples per ray like the reference.
+    num_steps / upsample_steps: render_warp.py's two command-line counts; outside the fused renderer's window (multiples of 16, num_steps <= 64, at most 128
+    samples) the frames go to the long posed renderer (num_steps >= 2, upsample_steps a multiple of 16, at most 512 samples): net.posed_long_rays is
+    switched on for the duration, like skip_masked_samples.
     rays_per_batch: the reference cuts a frame into 64 * 128 = 8192-ray batches (render_warp.py) to bound its memory; the default here is the whole
     frame in one batch (0.13 GB of scratch at 256 x 256): same pixels, and the launches are full when the body covers a fraction of the image.
     rank / world: this process renders the frames shard_indices(n_frames, rank, world) (default: its rank in the default process group; without one,
@@ -97,14 +100,19 @@ def render_animation(net, body_model, cam_pose, poses=None, render_type="animate
         # the loop keeps rgb only: samples the warp masks out (alpha * 0) need no field evaluation (bit-identical pixels).  The switch is set around
         # each frame's render and restored (also when the consumer abandons the generator): the caller's net keeps its documented default
         prev = getattr(net, "skip_masked_samples", None)
+        prev_long = getattr(net, "posed_long_rays", None)
         if prev is not None:
             net.skip_masked_samples = True
+        if prev_long is not None:
+            net.posed_long_rays = True
         try:
             rgb, _, _ = render_instantnsr_naive(net, ro, rd, rays_per_batch, requires_grad=False, bkg_key=WHITE_BKG if white_bkg else BLACK_BKG,
                                                 return_torch=True, perturb=False, return_raw=True, render_can=False,
-                                                verts=mesh if mesh is not None else world_verts[i], faces=faces, Ts=Ts[i], num_steps=32, upsample_steps=32,
-                                                bound=NSR_BOUND)
+                                                verts=mesh if mesh is not None else world_verts[i], faces=faces, Ts=Ts[i], num_steps=num_steps,
+                                                upsample_steps=upsample_steps, bound=NSR_BOUND)
         finally:
             if prev is not None:
                 net.skip_masked_samples = prev
+            if prev_long is not None:
+                net.posed_long_rays = prev_long
         yield i, rgb.reshape(resolution, resolution, 3)

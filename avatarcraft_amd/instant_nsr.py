@@ -11,7 +11,8 @@ Where the work happens:
   * rendering with gradients (stylize / reconstruct) takes the sample positions from the fused kernel (the reference
     computes them under no_grad, :176-184) and evaluates the differentiable "render core" (:190-299) with autograd
     over the HIP hash encoder; a fused backward kernel is the next step.
-  * render_can=False (SMPL inverse warp, :166-172,198-203): no-grad only (render_warp.py), ac_render_rays_warped.
+  * render_can=False (SMPL inverse warp, :166-172,198-203): no-grad only (render_warp.py), ac_render_rays_warped; at sample counts
+    outside the fused renderer's window ac_render_rays_long_warped (opt-in: posed_long_rays).
 """
 import numpy as np
 import math
@@ -373,6 +374,10 @@ class NeRFRenderer(nn.Module):
     # which no inference driver reads, covers the evaluated samples only).  False (default): every output as the reference computes it.
     # drivers.render_animation (render_warp.py's loop, which keeps rgb only) switches it on.
     skip_masked_samples = False
+    # posed-space inference at the sample counts outside the fused renderer's window (nsr_ops.in_short_window): False (default) = run(render_can=False)
+    # raises NotImplementedError there; True = a no-grad posed render goes to the long renderer (nsr_ops.render_rays_long(warp=...): any num_steps >= 2,
+    # upsample_steps a multiple of 16, at most 512 samples).  drivers.render_animation switches it on for its duration.
+    posed_long_rays = False
     # posed-space inference through the harness (render_utils.render_instantnsr_naive): the closest-face searches of a frame start from the faces the previous
     # frame found for the same (ray, sample slot) -- an upper bound from a real face, so the same pixels bit for bit, with tighter culling (ac_warp_mesh.seed_faces)
     warp_temporal_seeds = True
@@ -435,13 +440,14 @@ class NeRFRenderer(nn.Module):
                                       "SDF network 35-64-16); other widths / depths have no sampling kernel")
         full = self._fused_supported()
         # counts outside the window of the fused renderer (multiples of 16, num_steps <= 64, at most 128 samples) go to the long renderer:
-        # canonical space only
+        # canonical space, and posed space without gradients when posed_long_rays is on
         long_counts = not nsr_ops.in_short_window(num_steps, upsample_steps)
         if long_counts:
-            if not render_can:
+            if not render_can and not self.posed_long_rays:
                 raise NotImplementedError(f"posed-space rendering supports num_steps and upsample_steps that are multiples of 16 with "
                                           f"16 <= num_steps <= 64 and num_steps + upsample_steps <= 128 only (got {num_steps} + {upsample_steps}); "
-                                          f"longer rays render in canonical space (render_can=True)")
+                                          f"longer rays render in canonical space (render_can=True), or in posed space without gradients with "
+                                          f"posed_long_rays = True")
             nsr_ops.check_long_counts(num_steps, upsample_steps)
         B, N = rays_o.shape[:2]
         device = rays_o.device
@@ -460,6 +466,11 @@ class NeRFRenderer(nn.Module):
         warp = None
         near_far = None
         if not render_can:                                       # SMPL inverse warp :166-172,198-203 (inference path of render_warp.py)
+            if long_counts and needs_grad:
+                raise NotImplementedError(f"posed-space training is built for the short window only (multiples of 16, 16 <= num_steps <= 64, at most 128 "
+                                          f"samples; got {num_steps} + {upsample_steps}): the long posed renderer (posed_long_rays) runs under no_grad")
+            if long_counts and opacity_only:
+                raise NotImplementedError("opacity_only is not supported by the long renderer")
             if needs_grad and self.fused_training != "core":
                 raise NotImplementedError("posed-space rendering under autograd runs through the fused operator only (fused_training = 'core')")
             if not full:
@@ -484,7 +495,7 @@ class NeRFRenderer(nn.Module):
             return (out["depth"].reshape(B, N), out["weights"], out["weights_sum"][:, None], out["image"].reshape(B, N, 3), out["normal_map"],
                     out["eik_res"][0], 0.0, out["color"], out["alpha"], out["z_vals"])
         if long_counts:
-            if needs_grad or not full:
+            if warp is None and (needs_grad or not full):
                 # (the fused training operator -- fused_training = "core" under autograd -- takes at most 128 samples: the long counts take the autograd
                 # render core, which handles any T)
                 z_vals = nsr_ops.sample_rays_long(self._field() if full else self._field_sdf_only(), ro, rd, num_steps, upsample_steps, bound,
@@ -493,7 +504,8 @@ class NeRFRenderer(nn.Module):
                                                   near_far=near_far)
             out = nsr_ops.render_rays_long(self._field(), ro, rd, num_steps, upsample_steps, bound, inv_s_t, bg=bg, noise=noise,
                                            cos_anneal_ratio=cos_anneal_ratio, normal_epsilon_ratio=normal_epsilon_ratio, extras=bool(per_sample),
-                                           near_far=near_far, precision=self.render_precision)
+                                           warp=warp, near_far=near_far, precision=self.render_precision,
+                                           skip_masked=self.skip_masked_samples and warp is not None)
             return (out["depth"].reshape(B, N), out.get("weights"), out["weights_sum"][:, None], out["image"].reshape(B, N, 3),
                     out["normal_map"], out["gradient_error"], 0.0, out.get("color"), out.get("alpha"), out.get("z_vals"))
         if needs_grad and full and self.fused_training == "core" and near_far is None:

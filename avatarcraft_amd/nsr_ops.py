@@ -146,15 +146,17 @@ def render_rays_long(field, rays_o, rays_d, num_steps=64, upsample_steps=64, bou
                      cos_anneal_ratio=1.0, normal_epsilon_ratio=0.0, extras=False, debug_indices=False, out=None, events=None, warp=None,
                      train_extras=False, near_far=None, precision="exact", skip_masked=False, opacity_only=False):
     """render_rays for any sample count the reference accepts (ac_render_rays_long): num_steps >= 2, upsample_steps >= 0 a multiple of 16, at most
-    512 samples per ray.  Same arguments and result dict as render_rays; bit-identical to it where both accept the counts.  Canonical space only
-    (warp, skip_masked and opacity_only are rejected); train_extras gives sdf_out16 / pts but no stencil features; sort_index is [N, nup, T]."""
+    512 samples per ray.  Same arguments and result dict as render_rays; bit-identical to it where both accept the counts.  train_extras gives
+    sdf_out16 / pts but no stencil features; sort_index is [N, nup, T].  opacity_only is rejected.
+    warp = WarpMesh(...) renders in posed space (ac_render_rays_long_warped): + can_mid [N,T,3], mask [N,T] views of the scratch as from
+    render_rays(warp=...), with skip_masked as there; without a warp skip_masked is rejected (a posed-space option)."""
     check_long_counts(num_steps, upsample_steps)
-    if warp is not None:
-        raise RuntimeError("render_rays_long: canonical space only (posed rendering at long counts is not supported)")
-    if skip_masked or opacity_only:
-        raise RuntimeError("render_rays_long: skip_masked and opacity_only are not supported")
+    if opacity_only:
+        raise RuntimeError("render_rays_long: opacity_only is not supported")
+    if skip_masked and warp is None:
+        raise RuntimeError("render_rays_long: skip_masked is a posed-space option (pass warp=WarpMesh(...))")
     return _render(field, rays_o, rays_d, num_steps, upsample_steps, bound, inv_s, bg, noise, cos_anneal_ratio, normal_epsilon_ratio, extras,
-                   debug_indices, out, events, None, train_extras, near_far, precision, False, False, long=True)
+                   debug_indices, out, events, warp, train_extras, near_far, precision, skip_masked, False, long=True)
 
 
 def _render(field, rays_o, rays_d, num_steps, upsample_steps, bound, inv_s, bg, noise, cos_anneal_ratio, normal_epsilon_ratio, extras,
@@ -218,7 +220,7 @@ def _render(field, rays_o, rays_d, num_steps, upsample_steps, bound, inv_s, bg, 
     st = L.current_stream(dev)
     if events is not None:          # (start, end) torch.cuda.Event pair around the render kernel only (bench.py roofline)
         events[0].record()
-    if long:
+    if long and warp is None:
         L.check(L.lib().ac_render_rays_long(C.byref(field.c), C.byref(op), rays_o.data_ptr(), rays_d.data_ptr(), L.ptr(bg), L.ptr(noise),
                                             lin_z.data_ptr(), lin_u.data_ptr(), C.byref(o), st), "render_rays_long")
     elif warp is None:
@@ -228,9 +230,9 @@ def _render(field, rays_o, rays_d, num_steps, upsample_steps, bound, inv_s, bg, 
         offs = (C.c_size_t * 6)()
         nbytes = L.lib().ac_render_rays_warped_scratch(N, T, offs)
         scratch = buf("_warp_scratch", (max(int(nbytes), 1),), torch.uint8)
-        L.check(L.lib().ac_render_rays_warped(C.byref(field.c), C.byref(op), rays_o.data_ptr(), rays_d.data_ptr(), L.ptr(bg), L.ptr(noise),
-                                              lin_z.data_ptr(), lin_u.data_ptr(), C.byref(warp.c), scratch.data_ptr(), int(nbytes), C.byref(o), st),
-                "render_rays_warped")
+        entry, who = (L.lib().ac_render_rays_long_warped, "render_rays_long_warped") if long else (L.lib().ac_render_rays_warped, "render_rays_warped")
+        L.check(entry(C.byref(field.c), C.byref(op), rays_o.data_ptr(), rays_d.data_ptr(), L.ptr(bg), L.ptr(noise),
+                      lin_z.data_ptr(), lin_u.data_ptr(), C.byref(warp.c), scratch.data_ptr(), int(nbytes), C.byref(o), st), who)
         res["can_mid"] = scratch[offs[3]:offs[3] + N * T * 12].view(_F32).view(N, T, 3)
         res["mask"] = scratch[offs[4]:offs[4] + N * T].view(N, T)
         if skip_masked and warp.accel is not None and upsample_steps > 0:      # rays the cell grids proved masked out (never sampled): the scratch's last segment

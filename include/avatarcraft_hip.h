@@ -260,7 +260,7 @@ int ac_render_rays_pair(const ac_field *field, const ac_render_opts *opts, const
                         const ac_render_out *out, ac_stream_t stream);
 
 /* ac_render_rays for any sample count the reference accepts: num_steps >= 2 (any value, not only multiples of 16), upsample_steps >= 0 and a
- * multiple of 16, num_steps + upsample_steps <= 512 (anything else: AC_ERR_BAD_ARG naming the rule).  Canonical space only; same arguments and
+ * multiple of 16, num_steps + upsample_steps <= 512 (anything else: AC_ERR_BAD_ARG naming the rule).  Canonical space (posed: ac_render_rays_long_warped); same arguments and
  * outputs as ac_render_rays (lin_z [num_steps]), except: sort_index is [N, upsample_steps/16, T] (T = num_steps + upsample_steps, -1 pad),
  * feat7 must be NULL and opts->opacity_only / skip_masked must be 0.  Where both accept the counts, every output is bit-identical to
  * ac_render_rays'.  Needs no scratch; gradient_error (eik_reduced) is formed by ac_eikonal_reduce2 on the same stream. */
@@ -665,6 +665,17 @@ int ac_render_rays_warped(const ac_field *field, const ac_render_opts *opts, con
                           const float *bg, const float *noise, const float *lin_z, const float *lin_u,
                           const ac_warp_mesh *mesh, void *scratch, size_t scratch_bytes, const ac_render_out *out,
                           ac_stream_t stream);
+
+/* ac_render_rays_warped for the sample counts of ac_render_rays_long (num_steps >= 2, upsample_steps >= 0 and a multiple of 16, at most 512 samples): the
+ * same sequence -- mesh near / far, coarse points, first closest-face search, up-sampling at the warped coarse points, second search, render core at the
+ * warped mid points with alpha * mask -- on the long renderer's kernel.  Same arguments, outputs and scratch (ac_render_rays_warped_scratch(n_rays, T, offs))
+ * as ac_render_rays_warped; honours opts->skip_masked, mesh->accel, mesh->seed_faces and mesh->use_mesh_guide; sort_index is [N, upsample_steps/16, T];
+ * gradient_error (eik_reduced) is formed by ac_eikonal_reduce2 on the same stream.  feat7 must be NULL and opts->opacity_only 0 (AC_ERR_BAD_ARG).  Where
+ * both accept the counts, every output is bit-identical to ac_render_rays_warped's. */
+int ac_render_rays_long_warped(const ac_field *field, const ac_render_opts *opts, const float *rays_o, const float *rays_d,
+                               const float *bg, const float *noise, const float *lin_z, const float *lin_u,
+                               const ac_warp_mesh *mesh, void *scratch, size_t scratch_bytes, const ac_render_out *out,
+                               ac_stream_t stream);
 
 #ifdef __cplusplus
 }
