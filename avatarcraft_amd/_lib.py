@@ -155,6 +155,10 @@ _SIGS = {
     "ac_marching_cubes_emit": ([vp, u32, u32, u32, f32, vp, C.c_size_t, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, u32, vp, u32, vp], C.c_int),
     "ac_density_grid_update_scratch": ([u32], C.c_size_t),
     "ac_density_grid_update": ([C.POINTER(ac_field), vp, u32, f32, f32, f32, vp, vp, vp, C.c_size_t, vp], C.c_int),
+    "ac_table_to_half": ([vp, u32, vp, vp, vp], C.c_int),
+    "ac_render_rays_h16": ([C.POINTER(ac_field), vp, C.POINTER(ac_render_opts), vp, vp, vp, vp, vp, vp, C.POINTER(ac_render_out), vp], C.c_int),
+    "ac_render_rays_warped_h16": ([C.POINTER(ac_field), vp, C.POINTER(ac_render_opts), vp, vp, vp, vp, vp, vp, C.POINTER(ac_warp_mesh), vp, C.c_size_t,
+                                   C.POINTER(ac_render_out), vp], C.c_int),
 }
 EXPORTS = tuple(_SIGS)
 FIELD_PREPARED_BYTES = 98304          # AC_FIELD_PREPARED_BYTES of include/avatarcraft_hip.h

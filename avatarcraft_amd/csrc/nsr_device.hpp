@@ -337,7 +337,19 @@ __device__ __forceinline__ void interp8(const u32x2 (&v)[8], float qx, float qy,
     f0 = oob ? 0.0f : a0;
     f1 = oob ? 0.0f : a1;
 }
-template <int ROUND>
+// one table entry = the bit patterns of its two fp32 features.  H16 = false: the fp32 table, one 8-byte gather.  H16 = true: the half table of
+// ac_table_to_half (one dword per entry, channel 0 in the low half; descriptor of n_entries x 4 bytes): one 4-byte gather, widened by two f16 -> f32
+// conversions (exact, subnormals included) into the registers the fp32 path fills -- everything behind the load is the same code in both forms
+template <bool H16>
+__device__ __forceinline__ u32x2 table_entry(rsrc_t table, uint32_t idx)
+{
+    if constexpr (H16) {
+        const uint32_t d = __builtin_amdgcn_raw_buffer_load_b32(table, idx * 4u, 0, 0);
+        const float c0 = (float)__builtin_bit_cast(_Float16, (unsigned short)(d & 0xffffu)), c1 = (float)__builtin_bit_cast(_Float16, (unsigned short)(d >> 16));
+        return u32x2{ __float_as_uint(c0), __float_as_uint(c1) };
+    } else return __builtin_amdgcn_raw_buffer_load_b64(table, idx * 8u, 0, 0);
+}
+template <int ROUND, bool H16 = false>
 __device__ __forceinline__ void encode4(const float *__restrict__ lds, rsrc_t table, int g, const int (&jmode)[4],
                                         float px, float py, float pz, float bound, float two_bound, float (&f)[4][2], float inv_tb = 0.0f)
 {
@@ -376,7 +388,7 @@ __device__ __forceinline__ void encode4(const float *__restrict__ lds, rsrc_t ta
                 }
             }
 #pragma unroll
-            for (int c = 0; c < 8; ++c) v[jj][c] = __builtin_amdgcn_raw_buffer_load_b64(table, (offset + idx[c]) * 8u, 0, 0);
+            for (int c = 0; c < 8; ++c) v[jj][c] = table_entry<H16>(table, offset + idx[c]);
         }
 #pragma unroll
         for (int jj = 0; jj < ROUND; ++jj)
@@ -520,11 +532,12 @@ __device__ __forceinline__ f32x4 sdf_mlp(const float *__restrict__ lds, int lane
     return sdf_l2(lds, lane, acc);
 }
 
+template <bool H16 = false>
 __device__ __forceinline__ f32x4 sdf_tile(const float *__restrict__ lds, const FieldCtx &fc, int lane, float px, float py, float pz)
 {
     const int g = lane >> 4;
     float f[4][2];
-    encode4<AC_ENC_ROUND>(lds, fc.table, g, fc.jmode, px, py, pz, fc.bound, fc.two_bound, f, fc.inv_tb);
+    encode4<AC_ENC_ROUND, H16>(lds, fc.table, g, fc.jmode, px, py, pz, fc.bound, fc.two_bound, f, fc.inv_tb);
     __builtin_amdgcn_sched_barrier(0);
     return sdf_mlp(lds, lane, sel4(g, px, py, pz, 0.0f), f);
 }
@@ -562,7 +575,7 @@ template <int K> __device__ __forceinline__ constexpr int face_corner(int b, int
 template <int K, int SIGN>   // SIGN 0: +eps, 1: -eps
 struct AxisGeo { float qk; bool need, oob; };
 
-template <int K, int SIGN, int GM>
+template <int K, int SIGN, int GM, bool H16>
 __device__ __forceinline__ AxisGeo<K, SIGN> coarse_issue(rsrc_t table, const LvlC &L, const uint32_t (&gc)[3], const uint32_t (&tx)[2],
                                                        const uint32_t (&ty)[2], const uint32_t (&tz)[2], bool oob_c, float u,
                                                        u32x2 (&w)[4])
@@ -581,7 +594,7 @@ __device__ __forceinline__ AxisGeo<K, SIGN> coarse_issue(rsrc_t table, const Lvl
         const int c = face_corner<K>(0, i);
         const uint32_t ax = K == 0 ? tk : tx[c & 1], ay = K == 1 ? tk : ty[(c >> 1) & 1], az = K == 2 ? tk : tz[(c >> 2) & 1];
         w[i] = u32x2{ 0u, 0u };
-        if (a.need) w[i] = __builtin_amdgcn_raw_buffer_load_b64(table, (L.offset + gidx<GM>(L, ax, ay, az)) * 8u, 0, 0);
+        if (a.need) w[i] = table_entry<H16>(table, L.offset + gidx<GM>(L, ax, ay, az));
     }
     return a;
 }
@@ -605,7 +618,7 @@ __device__ __forceinline__ void coarse_finish(const AxisGeo<K, SIGN> &a, const u
 // coarse offset points from bilinear face values (fast precision only): removed, the one run-to-run non-determinism ever seen -- DESIGN.md section 2.1
 
 // ---- fine level (eps spans one cell or more): every offset point gathers its own 8 corners ---------------------------
-template <int K, int GM>
+template <int K, int GM, bool H16>
 __device__ __forceinline__ void fine_issue(rsrc_t table, const LvlC &L, const uint32_t (&tx)[2], const uint32_t (&ty)[2],
                                            const uint32_t (&tz)[2], bool oob_c, float u, u32x2 (&v)[8], float &qk, bool &oob)
 {
@@ -619,14 +632,14 @@ __device__ __forceinline__ void fine_issue(rsrc_t table, const LvlC &L, const ui
     for (int c = 0; c < 8; ++c) {
         const uint32_t tk = ((c >> K) & 1) ? t1 : t0;
         const uint32_t ax = K == 0 ? tk : tx[c & 1], ay = K == 1 ? tk : ty[(c >> 1) & 1], az = K == 2 ? tk : tz[(c >> 2) & 1];
-        v[c] = __builtin_amdgcn_raw_buffer_load_b64(table, (L.offset + gidx<GM>(L, ax, ay, az)) * 8u, 0, 0);
+        v[c] = table_entry<H16>(table, L.offset + gidx<GM>(L, ax, ay, az));
     }
 }
 
 #define AC_FSTORE(E, F0, F1) { fslab[((E - 1) * 8 + 2 * j) * 64 + lane] = F0; fslab[((E - 1) * 8 + 2 * j + 1) * 64 + lane] = F1; }
 
 // one group of four levels (4j + g) of the stencil: centre features in c0 / c1, the six offset points' features to the slab
-template <int GM>
+template <int GM, bool H16>
 __device__ __forceinline__ void stencil_levels(const float *__restrict__ lds, float *__restrict__ fslab, rsrc_t table, int lane, int g, int j, bool fine,
                                                float ux, float uy, float uz, bool oob, float xp, float xm, float yp, float ym, float zp, float zm,
                                                float &c0, float &c1)
@@ -645,15 +658,15 @@ __device__ __forceinline__ void stencil_levels(const float *__restrict__ lds, fl
     u32x2 vc[8];
 #pragma unroll
     for (int c = 0; c < 8; ++c)
-        vc[c] = __builtin_amdgcn_raw_buffer_load_b64(table, (L.offset + gidx<GM>(L, tx[c & 1], ty[(c >> 1) & 1], tz[c >> 2])) * 8u, 0, 0);
+        vc[c] = table_entry<H16>(table, L.offset + gidx<GM>(L, tx[c & 1], ty[(c >> 1) & 1], tz[c >> 2]));
     if (!fine) {
         u32x2 w0[4], w1[4], w2[4], w3[4], w4[4], w5[4];
-        const auto a0 = coarse_issue<0, 0, GM>(table, L, gc, tx, ty, tz, oob, xp, w0);
-        const auto a1 = coarse_issue<0, 1, GM>(table, L, gc, tx, ty, tz, oob, xm, w1);
-        const auto a2 = coarse_issue<1, 0, GM>(table, L, gc, tx, ty, tz, oob, yp, w2);
-        const auto a3 = coarse_issue<1, 1, GM>(table, L, gc, tx, ty, tz, oob, ym, w3);
-        const auto a4 = coarse_issue<2, 0, GM>(table, L, gc, tx, ty, tz, oob, zp, w4);
-        const auto a5 = coarse_issue<2, 1, GM>(table, L, gc, tx, ty, tz, oob, zm, w5);
+        const auto a0 = coarse_issue<0, 0, GM, H16>(table, L, gc, tx, ty, tz, oob, xp, w0);
+        const auto a1 = coarse_issue<0, 1, GM, H16>(table, L, gc, tx, ty, tz, oob, xm, w1);
+        const auto a2 = coarse_issue<1, 0, GM, H16>(table, L, gc, tx, ty, tz, oob, yp, w2);
+        const auto a3 = coarse_issue<1, 1, GM, H16>(table, L, gc, tx, ty, tz, oob, ym, w3);
+        const auto a4 = coarse_issue<2, 0, GM, H16>(table, L, gc, tx, ty, tz, oob, zp, w4);
+        const auto a5 = coarse_issue<2, 1, GM, H16>(table, L, gc, tx, ty, tz, oob, zm, w5);
         __builtin_amdgcn_sched_barrier(0);
         interp8(vc, qc[0], qc[1], qc[2], oob, c0, c1);
         float f0, f1;
@@ -666,12 +679,12 @@ __device__ __forceinline__ void stencil_levels(const float *__restrict__ lds, fl
     } else {                // all 48 gathers of the six offset points in flight at once: one memory round trip instead of three (221 VGPRs, -2 % time)
         u32x2 va[8], vb[8], vc2[8], vd[8], ve[8], vf[8];
         float qa, qb, qc2, qd, qe, qf, f0, f1; bool oa, ob, oc2, od, oe, of;
-        fine_issue<0, GM>(table, L, tx, ty, tz, oob, xp, va, qa, oa);
-        fine_issue<0, GM>(table, L, tx, ty, tz, oob, xm, vb, qb, ob);
-        fine_issue<1, GM>(table, L, tx, ty, tz, oob, yp, vc2, qc2, oc2);
-        fine_issue<1, GM>(table, L, tx, ty, tz, oob, ym, vd, qd, od);
-        fine_issue<2, GM>(table, L, tx, ty, tz, oob, zp, ve, qe, oe);
-        fine_issue<2, GM>(table, L, tx, ty, tz, oob, zm, vf, qf, of);
+        fine_issue<0, GM, H16>(table, L, tx, ty, tz, oob, xp, va, qa, oa);
+        fine_issue<0, GM, H16>(table, L, tx, ty, tz, oob, xm, vb, qb, ob);
+        fine_issue<1, GM, H16>(table, L, tx, ty, tz, oob, yp, vc2, qc2, oc2);
+        fine_issue<1, GM, H16>(table, L, tx, ty, tz, oob, ym, vd, qd, od);
+        fine_issue<2, GM, H16>(table, L, tx, ty, tz, oob, zp, ve, qe, oe);
+        fine_issue<2, GM, H16>(table, L, tx, ty, tz, oob, zm, vf, qf, of);
         __builtin_amdgcn_sched_barrier(0);
         interp8(vc, qc[0], qc[1], qc[2], oob, c0, c1);
         interp8(va, qa, qc[1], qc[2], oa, f0, f1); AC_FSTORE(1, f0, f1)
@@ -683,6 +696,7 @@ __device__ __forceinline__ void stencil_levels(const float *__restrict__ lds, fl
     }
 }
 
+template <bool H16 = false>
 __device__ __forceinline__ void encode_stencil(const float *__restrict__ lds, float *__restrict__ fslab, const FieldCtx &fc, int lane,
                                                float px, float py, float pz, float eps, float (&fe0)[4][2])
 {
@@ -714,8 +728,8 @@ __device__ __forceinline__ void encode_stencil(const float *__restrict__ lds, fl
         const bool fine = (jbits >> (8 + j)) & 1u, hashed4 = ((jbits >> (2 * j)) & 3u) == 1u, dense4 = ((jbits >> (2 * j)) & 3u) == 0u;
         (void)dense4;                                       // (unused; taking it out moves register-allocation comments in the assembly)
         // level groups hashed throughout get a second copy of the stencil code (xor-only index arithmetic)
-        if (hashed4) stencil_levels<1>(lds, fslab, table, lane, g, j, fine, ux, uy, uz, oob, xp, xm, yp, ym, zp, zm, c0, c1);
-        else stencil_levels<2>(lds, fslab, table, lane, g, j, fine, ux, uy, uz, oob, xp, xm, yp, ym, zp, zm, c0, c1);
+        if (hashed4) stencil_levels<1, H16>(lds, fslab, table, lane, g, j, fine, ux, uy, uz, oob, xp, xm, yp, ym, zp, zm, c0, c1);
+        else stencil_levels<2, H16>(lds, fslab, table, lane, g, j, fine, ux, uy, uz, oob, xp, xm, yp, ym, zp, zm, c0, c1);
         // rotate the centre features into place: after the 4th iteration fe0[j] holds level 4j+g
         fe0[0][0] = fe0[1][0]; fe0[0][1] = fe0[1][1]; fe0[1][0] = fe0[2][0]; fe0[1][1] = fe0[2][1];
         fe0[2][0] = fe0[3][0]; fe0[2][1] = fe0[3][1]; fe0[3][0] = c0; fe0[3][1] = c1;

@@ -51,8 +51,10 @@ def shard_indices(n, rank=None, world=None):
 
 
 def render_canonical_360(net, n_views=100, render_hw=(256, 256), center=(0.0, 0.0, 0.0), up=(0.0, 1.0, 0.0), white_bkg=True, with_head=True,
-                         rays_per_batch=4096, device="cuda", rank=None, world=None):
+                         rays_per_batch=4096, device="cuda", rank=None, world=None, table_dtype=None):
     """yields (ring name, view index, rgb [H,W,3] float32 in [0,1], depth [H,W]) for the body ring and, with_head, the head ring.
+    table_dtype: None (default) leaves net.render_table_dtype as the caller set it; "float" / "half" sets it around each view's render and restores it
+    (also when the consumer abandons the generator).  "half" takes effect for a net in eval() mode (NeRFNetwork.render_table_dtype).
     rank / world: this process renders the views shard_indices(n_views, rank, world) of every ring (default: its rank in the default process group;
     without one, all views) -- the view index yielded is the GLOBAL one, so the ranks' outputs interleave into the reference's file sequence."""
     center, up = np.asarray(center, dtype=np.float64), np.asarray(up, dtype=np.float64)
@@ -66,18 +68,27 @@ def render_canonical_360(net, n_views=100, render_hw=(256, 256), center=(0.0, 0.
             if i not in mine:
                 continue
             ro, rd = cap2rays(pose2cap([h, w], pose), device=device)
-            rgb, _, extra = render_instantnsr_naive(net, ro, rd, rays_per_batch, requires_grad=False, bkg_key=WHITE_BKG if white_bkg else BLACK_BKG,
-                                                    return_torch=True, perturb=False, return_raw=True, render_can=True)
+            prev_table = getattr(net, "render_table_dtype", None)
+            if table_dtype is not None and prev_table is not None:
+                net.render_table_dtype = table_dtype
+            try:
+                rgb, _, extra = render_instantnsr_naive(net, ro, rd, rays_per_batch, requires_grad=False, bkg_key=WHITE_BKG if white_bkg else BLACK_BKG,
+                                                        return_torch=True, perturb=False, return_raw=True, render_can=True)
+            finally:
+                if table_dtype is not None and prev_table is not None:
+                    net.render_table_dtype = prev_table
             yield name, i, rgb.reshape(h, w, 3), extra["depth"].reshape(h, w)
 
 
 def render_animation(net, body_model, cam_pose, poses=None, render_type="animate", shape_from=None, shape_to=None, resolution=256, max_frames=100,
-                     white_bkg=True, rays_per_batch=None, device="cuda", rank=None, world=None, num_steps=32, upsample_steps=32):
+                     white_bkg=True, rays_per_batch=None, device="cuda", rank=None, world=None, num_steps=32, upsample_steps=32, table_dtype=None):
     """yields (frame index, rgb [res,res,3]) for an SMPL pose sequence (render_type "animate", poses [F,72]) or a shape interpolation
     ("interp_shape", shape_from / shape_to [1,10]), seen from the dataset camera `cam_pose` [4,4]; 32 + 32 samples per ray like the reference.
     num_steps / upsample_steps: render_warp.py's two command-line counts; outside the fused renderer's window (multiples of 16, num_steps <= 64, at most 128
     samples) the frames go to the long posed renderer (num_steps >= 2, upsample_steps a multiple of 16, at most 512 samples): net.posed_long_rays is
     switched on for the duration, like skip_masked_samples.
+    table_dtype: None (default) leaves net.render_table_dtype alone; "float" / "half" sets it around each frame's render and restores it, like the two
+    switches above ("half": a net in eval() mode, counts inside the fused renderer's window -- NeRFNetwork.render_table_dtype).
     rays_per_batch: the reference cuts a frame into 64 * 128 = 8192-ray batches (render_warp.py) to bound its memory; the default here is the whole
     frame in one batch (0.13 GB of scratch at 256 x 256): same pixels, and the launches are full when the body covers a fraction of the image.
     rank / world: this process renders the frames shard_indices(n_frames, rank, world) (default: its rank in the default process group; without one,
@@ -105,6 +116,9 @@ def render_animation(net, body_model, cam_pose, poses=None, render_type="animate
             net.skip_masked_samples = True
         if prev_long is not None:
             net.posed_long_rays = True
+        prev_table = getattr(net, "render_table_dtype", None)
+        if table_dtype is not None and prev_table is not None:
+            net.render_table_dtype = table_dtype
         try:
             rgb, _, _ = render_instantnsr_naive(net, ro, rd, rays_per_batch, requires_grad=False, bkg_key=WHITE_BKG if white_bkg else BLACK_BKG,
                                                 return_torch=True, perturb=False, return_raw=True, render_can=False,
@@ -115,4 +129,6 @@ def render_animation(net, body_model, cam_pose, poses=None, render_type="animate
                 net.skip_masked_samples = prev
             if prev_long is not None:
                 net.posed_long_rays = prev_long
+            if table_dtype is not None and prev_table is not None:
+                net.render_table_dtype = prev_table
         yield i, rgb.reshape(resolution, resolution, 3)

@@ -369,6 +369,12 @@ class NeRFRenderer(nn.Module):
     # split-bf16 corrections of the centre's layer 1 and the colour network in split bf16 (normals within 6e-5 of "exact", sample positions /
     # indices / sdf bit-identical).  A training render's backward differentiates the formulation its forward ran.
     render_precision = "exact"
+    # the hash table the fused renderer gathers from in inference: "float" (default) = the fp32 parameters; "half" (opt-in) = their fp16 copy
+    # (nsr_ops.Field.half_table: 4 bytes per entry instead of 8, made once per parameter version), bit-identical to a render of a model whose table is
+    # embeddings.half().float().  "half" applies to run() only in eval() mode and when no gradient is wanted -- canonical and posed renders inside the
+    # fused renderer's window; there a long sample count raises NotImplementedError (the long renderer has no half-table form: no silent mix of
+    # tables).  Training mode, renders under autograd, run_cuda and everything else read the fp32 table whatever this says.
+    render_table_dtype = "float"
     # posed-space inference (render_can=False): samples the SMPL warp masks out contribute alpha * 0 = nothing.  True: tiles of 16 such samples are
     # not evaluated (pixels, depth, normals, weights unchanged bit for bit; the per-sample sdf / colour of skipped samples are 0 and gradient_error,
     # which no inference driver reads, covers the evaluated samples only).  False (default): every output as the reference computes it.
@@ -463,6 +469,13 @@ class NeRFRenderer(nn.Module):
             bg = bg.reshape(-1, 3) if bg.numel() >= 3 else bg.reshape(1, 1).expand(1, 3)
             bg = bg.expand(N, 3).contiguous() if bg.shape[0] == 1 else bg.contiguous()
         needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        half = self.render_table_dtype == "half" and not needs_grad and not self.training and full
+        if self.render_table_dtype not in nsr_ops.TABLE_DTYPES:
+            raise RuntimeError(f"render_table_dtype must be one of {nsr_ops.TABLE_DTYPES}, got {self.render_table_dtype!r}")
+        if half and long_counts:
+            raise NotImplementedError(f"render_table_dtype = 'half' renders inside the fused renderer's window only (multiples of 16, 16 <= num_steps <= 64, "
+                                      f"at most 128 samples; got {num_steps} + {upsample_steps}): the long renderer reads the fp32 table, and an inference "
+                                      f"render does not switch tables silently")
         warp = None
         near_far = None
         if not render_can:                                       # SMPL inverse warp :166-172,198-203 (inference path of render_warp.py)
@@ -525,7 +538,8 @@ class NeRFRenderer(nn.Module):
                                               near_far=near_far)
         out = nsr_ops.render_rays(self._field(), ro, rd, num_steps, upsample_steps, bound, inv_s_t, bg=bg, noise=noise, cos_anneal_ratio=cos_anneal_ratio,
                                   normal_epsilon_ratio=normal_epsilon_ratio, extras=bool(per_sample), warp=warp, near_far=near_far,
-                                  precision=self.render_precision, skip_masked=self.skip_masked_samples, opacity_only=bool(opacity_only))
+                                  precision=self.render_precision, skip_masked=self.skip_masked_samples, opacity_only=bool(opacity_only),
+                                  table_dtype="half" if half else "float")
         return (out["depth"].reshape(B, N), out.get("weights"), out["weights_sum"][:, None], out["image"].reshape(B, N, 3),
                 out["normal_map"], out["gradient_error"], 0.0, out.get("color"), out.get("alpha"), out.get("z_vals"))
 

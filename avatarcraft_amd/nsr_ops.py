@@ -60,6 +60,24 @@ class Field:
         self.c = f
         self.device = table.device
         self.prepared = None
+        self._half = None
+
+    def half_table(self):
+        """the hash table in half precision (ac_table_to_half): an int32 [n_entries] device tensor, one dword per entry (channel 0 in the low half), 4
+        bytes per entry instead of 8.  Made once per Field -- a Field is a snapshot of the parameters, a changed table gets a new Field -- and what
+        render_rays(table_dtype="half") gathers from.  RuntimeError if a finite value of the table does not fit fp16 (it would render as inf)."""
+        if self._half is None:
+            table = self.t["table"]
+            n = table.shape[0]
+            h = torch.empty((n,), dtype=torch.int32, device=self.device)
+            n_bad = torch.zeros((1,), dtype=torch.int32, device=self.device)
+            L.check(L.lib().ac_table_to_half(table.data_ptr(), n, h.data_ptr(), n_bad.data_ptr(), L.current_stream(self.device)), "table_to_half")
+            bad = int(n_bad.item())
+            if bad:
+                raise RuntimeError(f"half_table: {bad} of {n} table entries hold a finite value beyond the fp16 range (|v| > 65504 becomes inf): "
+                                   f"this field cannot be rendered from a half-precision table")
+            self._half = h
+        return self._half
 
     def prepare(self):
         """ac_field_prepare: lay the weights out once in the order the renderer keeps them in LDS (its 512 workgroups per launch then copy
@@ -87,6 +105,23 @@ def linspace_tables(num_steps, device):
 
 
 PRECISIONS = {"exact": 0, "fast": 1}
+TABLE_DTYPES = ("float", "half")
+
+
+def check_table_dtype(who, table_dtype, long=False, pair=False, train_extras=False, opacity_only=False):
+    """the rules of table_dtype (RuntimeError naming the rule, before any device work): "half" is the fused renderer's inference launch only"""
+    if table_dtype not in TABLE_DTYPES:
+        raise RuntimeError(f"{who}: table_dtype must be one of {TABLE_DTYPES}, got {table_dtype!r}")
+    if table_dtype != "half":
+        return
+    if long:
+        raise RuntimeError(f"{who}: table_dtype='half' is built for the fused renderer's window only (render_rays); the long renderer reads the fp32 table")
+    if pair:
+        raise RuntimeError(f"{who}: table_dtype='half' is not built for the pair launch (a training step's renders share the fp32 table)")
+    if train_extras:
+        raise RuntimeError(f"{who}: table_dtype='half' with train_extras: nothing trains from the half table (an inference option)")
+    if opacity_only:
+        raise RuntimeError(f"{who}: table_dtype='half' with opacity_only is not built (opacity_only serves the frozen avatar of a training step: fp32 table)")
 
 
 class RenderResult(dict):
@@ -107,7 +142,7 @@ def _inv_s_arg(inv_s):
 
 def render_rays(field, rays_o, rays_d, num_steps=64, upsample_steps=64, bound=1.6, inv_s=1.0, bg=None, noise=None,
                 cos_anneal_ratio=1.0, normal_epsilon_ratio=0.0, extras=False, debug_indices=False, out=None, events=None, warp=None,
-                train_extras=False, near_far=None, precision="exact", skip_masked=False, opacity_only=False):
+                train_extras=False, near_far=None, precision="exact", skip_masked=False, opacity_only=False, table_dtype="float"):
     """One launch of the fused renderer for N rays.  Returns a dict of CUDA tensors:
     image[N,3] weights_sum[N] depth[N] normal_map[N,3] eik[N,2] gradient_error[] (+ z_vals, weights,
     alpha, color, sdf, gradient when extras; + ss_inds, sort_index when debug_indices; + sdf_out16 [N,T,16], pts [N,T,3] and
@@ -120,9 +155,14 @@ def render_rays(field, rays_o, rays_d, num_steps=64, upsample_steps=64, bound=1.
     opacity_only: the colour network is not evaluated (image = background over a black body); weights_sum, depth, normal_map, gradient_error unchanged.
     skip_masked (posed space only): tiles of 16 samples that the warp masks out entirely are not evaluated (ac_render_opts.skip_masked): image,
     weights_sum, depth, normal_map, weights and alpha unchanged bit for bit; sdf / color / gradient of skipped samples 0, gradient_error over the
-    evaluated samples."""
+    evaluated samples.
+    table_dtype: "float" (default: the field's fp32 table) or "half" (opt-in, inference): the launch gathers from field.half_table() -- 4 bytes per
+    entry instead of 8 -- through ac_render_rays_h16 / ac_render_rays_warped_h16; every output is bit-identical to this call on a field whose table is
+    table.half().float().  "half" with train_extras or opacity_only raises RuntimeError."""
+    check_table_dtype("render_rays", table_dtype, train_extras=train_extras, opacity_only=opacity_only)
     return _render(field, rays_o, rays_d, num_steps, upsample_steps, bound, inv_s, bg, noise, cos_anneal_ratio, normal_epsilon_ratio, extras,
-                   debug_indices, out, events, warp, train_extras, near_far, precision, skip_masked, opacity_only, long=False)
+                   debug_indices, out, events, warp, train_extras, near_far, precision, skip_masked, opacity_only, long=False,
+                   half=table_dtype == "half")
 
 
 LONG_MAX_SAMPLES = 512
@@ -144,12 +184,14 @@ def in_short_window(num_steps, upsample_steps):
 
 def render_rays_long(field, rays_o, rays_d, num_steps=64, upsample_steps=64, bound=1.6, inv_s=1.0, bg=None, noise=None,
                      cos_anneal_ratio=1.0, normal_epsilon_ratio=0.0, extras=False, debug_indices=False, out=None, events=None, warp=None,
-                     train_extras=False, near_far=None, precision="exact", skip_masked=False, opacity_only=False):
+                     train_extras=False, near_far=None, precision="exact", skip_masked=False, opacity_only=False, table_dtype="float"):
     """render_rays for any sample count the reference accepts (ac_render_rays_long): num_steps >= 2, upsample_steps >= 0 a multiple of 16, at most
     512 samples per ray.  Same arguments and result dict as render_rays; bit-identical to it where both accept the counts.  train_extras gives
     sdf_out16 / pts but no stencil features; sort_index is [N, nup, T].  opacity_only is rejected.
     warp = WarpMesh(...) renders in posed space (ac_render_rays_long_warped): + can_mid [N,T,3], mask [N,T] views of the scratch as from
-    render_rays(warp=...), with skip_masked as there; without a warp skip_masked is rejected (a posed-space option)."""
+    render_rays(warp=...), with skip_masked as there; without a warp skip_masked is rejected (a posed-space option).
+    table_dtype: "float" only ("half" raises: the long renderer has no half-table form)."""
+    check_table_dtype("render_rays_long", table_dtype, long=True)
     check_long_counts(num_steps, upsample_steps)
     if opacity_only:
         raise RuntimeError("render_rays_long: opacity_only is not supported")
@@ -160,7 +202,7 @@ def render_rays_long(field, rays_o, rays_d, num_steps=64, upsample_steps=64, bou
 
 
 def _render(field, rays_o, rays_d, num_steps, upsample_steps, bound, inv_s, bg, noise, cos_anneal_ratio, normal_epsilon_ratio, extras,
-            debug_indices, out, events, warp, train_extras, near_far, precision, skip_masked, opacity_only, long):
+            debug_indices, out, events, warp, train_extras, near_far, precision, skip_masked, opacity_only, long, half=False):
     rays_o = _chk(rays_o.reshape(-1, 3), "rays_o")
     rays_d = _chk(rays_d.reshape(-1, 3), "rays_d")
     N = rays_o.shape[0]
@@ -218,9 +260,13 @@ def _render(field, rays_o, rays_d, num_steps, upsample_steps, bound, inv_s, bg, 
     if isinstance(res, RenderResult):
         res.opts = (op, inv_s_t, nm, fm)
     st = L.current_stream(dev)
+    h16 = field.half_table().data_ptr() if half else None          # (converted once per Field; before the events: not part of the render's time)
     if events is not None:          # (start, end) torch.cuda.Event pair around the render kernel only (bench.py roofline)
         events[0].record()
-    if long and warp is None:
+    if half and warp is None:
+        L.check(L.lib().ac_render_rays_h16(C.byref(field.c), h16, C.byref(op), rays_o.data_ptr(), rays_d.data_ptr(), L.ptr(bg), L.ptr(noise),
+                                           lin_z.data_ptr(), lin_u.data_ptr(), C.byref(o), st), "render_rays_h16")
+    elif long and warp is None:
         L.check(L.lib().ac_render_rays_long(C.byref(field.c), C.byref(op), rays_o.data_ptr(), rays_d.data_ptr(), L.ptr(bg), L.ptr(noise),
                                             lin_z.data_ptr(), lin_u.data_ptr(), C.byref(o), st), "render_rays_long")
     elif warp is None:
@@ -231,8 +277,12 @@ def _render(field, rays_o, rays_d, num_steps, upsample_steps, bound, inv_s, bg, 
         nbytes = L.lib().ac_render_rays_warped_scratch(N, T, offs)
         scratch = buf("_warp_scratch", (max(int(nbytes), 1),), torch.uint8)
         entry, who = (L.lib().ac_render_rays_long_warped, "render_rays_long_warped") if long else (L.lib().ac_render_rays_warped, "render_rays_warped")
-        L.check(entry(C.byref(field.c), C.byref(op), rays_o.data_ptr(), rays_d.data_ptr(), L.ptr(bg), L.ptr(noise),
-                      lin_z.data_ptr(), lin_u.data_ptr(), C.byref(warp.c), scratch.data_ptr(), int(nbytes), C.byref(o), st), who)
+        rest = (C.byref(op), rays_o.data_ptr(), rays_d.data_ptr(), L.ptr(bg), L.ptr(noise), lin_z.data_ptr(), lin_u.data_ptr(), C.byref(warp.c),
+                scratch.data_ptr(), int(nbytes), C.byref(o), st)
+        if half:
+            L.check(L.lib().ac_render_rays_warped_h16(C.byref(field.c), h16, *rest), "render_rays_warped_h16")
+        else:
+            L.check(entry(C.byref(field.c), *rest), who)
         res["can_mid"] = scratch[offs[3]:offs[3] + N * T * 12].view(_F32).view(N, T, 3)
         res["mask"] = scratch[offs[4]:offs[4] + N * T].view(N, T)
         if skip_masked and warp.accel is not None and upsample_steps > 0:      # rays the cell grids proved masked out (never sampled): the scratch's last segment
@@ -257,11 +307,13 @@ def handoff_timeouts(device=None):
 
 
 def render_rays_pair(field, rays_o, rays_d, noise2, num_steps=64, upsample_steps=64, bound=1.6, inv_s=1.0, bg2=None, cos_anneal_ratio=1.0,
-                     normal_epsilon_ratio=0.0, precision="exact", out=None, events=None, keep_weights=False):
+                     normal_epsilon_ratio=0.0, precision="exact", out=None, events=None, keep_weights=False, table_dtype="float"):
     """ac_render_rays_pair: the same N rays rendered twice in ONE launch -- copy a with noise2[0] / bg2[0] (per-ray outputs only), copy b with
     noise2[1] / bg2[1] (+ everything the render-core backward needs: the training forward).  Returns (a, b): two RenderResult dicts whose tensors are
     the two halves of shared [2N, ...] buffers; b.opts is the N-ray ac_render_opts the backward takes.  Bit-identical to
-    render_rays(..., noise=noise2[0]) and render_rays(..., noise=noise2[1], extras=True, train_extras=True)."""
+    render_rays(..., noise=noise2[0]) and render_rays(..., noise=noise2[1], extras=True, train_extras=True).
+    table_dtype: "float" only ("half" raises: the pair launch is a training launch)."""
+    check_table_dtype("render_rays_pair", table_dtype, pair=True)
     rays_o = _chk(rays_o.reshape(-1, 3), "rays_o")
     rays_d = _chk(rays_d.reshape(-1, 3), "rays_d")
     N, dev, T = rays_o.shape[0], rays_o.device, num_steps + upsample_steps

@@ -677,6 +677,29 @@ int ac_render_rays_long_warped(const ac_field *field, const ac_render_opts *opts
                                const ac_warp_mesh *mesh, void *scratch, size_t scratch_bytes, const ac_render_out *out,
                                ac_stream_t stream);
 
+/* ---- rendering from a half-precision hash table (opt-in, inference only) ----------------------------------------------------------------------------
+ * The half table holds ONE dword per entry of the fp32 table [n_entries][2] (n_entries = field->offsets[16]): channel 0 as an IEEE binary16 in the low
+ * half, channel 1 in the high half -- 4 bytes per entry instead of 8, the same level offsets.  ac_table_to_half makes it: every value is rounded to
+ * nearest even, subnormals are kept, NaN stays NaN, |v| > 65504 that rounds up becomes +-inf.  *n_bad (a device word the caller zeroes; the call adds
+ * to it) counts the entries in which a FINITE fp32 value became +-inf: a field that does not fit binary16 must not be rendered from the half table.
+ *
+ * ac_render_rays_h16 / ac_render_rays_warped_h16 are ac_render_rays / ac_render_rays_warped with every table gather one dword from table_h16, widened to
+ * fp32 exactly (binary16 -> binary32 loses nothing); all other arithmetic is the same code.  Contract: every output is BIT-IDENTICAL to the fp32 entry
+ * given the widened table (each half converted back to fp32) as field->table.  How close that is to a render from the unrounded table is a property
+ * of the field, not of these entries.  field->table is not read (it may be NULL); the other members of the field, the options,
+ * the trailing arguments, the outputs and the scratch (ac_render_rays_warped_scratch) are those of the fp32 entries.
+ * AC_ERR_BAD_ARG, with the rule in the message: table_h16 NULL; opts->opacity_only; out->feat7, out->sdf_out16 or out->pts (the training extras: nothing
+ * trains from the half table); sample counts outside the window of ac_render_rays.  There is no half-table form of the pair launch, the long renderer,
+ * the occupancy, geometry or training entries. */
+int ac_table_to_half(const float *table, uint32_t n_entries, void *table_h16, uint32_t *n_bad, ac_stream_t stream);
+int ac_render_rays_h16(const ac_field *field, const void *table_h16, const ac_render_opts *opts, const float *rays_o, const float *rays_d,
+                       const float *bg, const float *noise, const float *lin_z, const float *lin_u,
+                       const ac_render_out *out, ac_stream_t stream);
+int ac_render_rays_warped_h16(const ac_field *field, const void *table_h16, const ac_render_opts *opts, const float *rays_o, const float *rays_d,
+                              const float *bg, const float *noise, const float *lin_z, const float *lin_u,
+                              const ac_warp_mesh *mesh, void *scratch, size_t scratch_bytes, const ac_render_out *out,
+                              ac_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
