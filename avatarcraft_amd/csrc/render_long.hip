@@ -1,5 +1,5 @@
 // avatarcraft_amd/csrc/render_long.hip -- the fused Instant-NSR renderer for any sample count the reference accepts (ac_render_rays_long,
-// ac_sample_rays_long): num_steps >= 2 (not necessarily a multiple of 16), upsample_steps a multiple of 16, at most 512 samples per ray.
+// ac_render_rays_long_pair, ac_sample_rays_long): num_steps >= 2 (not necessarily a multiple of 16), upsample_steps a multiple of 16, at most 512 samples per ray.
 //
 // The per-ray algorithm is render_rays_kernel's (render_fused.hip, MODE_FULL / MODE_UPSAMPLE): the same device blocks of nsr_device.hpp
 // (fd_normal among them), the same scans in the same order; the blocks still written out in both kernels are marked where they stand.
@@ -29,6 +29,9 @@ template <int MODE, bool FAST, bool EX, bool SH>
 __global__ __launch_bounds__(BLOCK) void render_rays_long_kernel(const RenderArgs a)
 {
     constexpr bool FC = FAST;
+    // the training options of the canonical entry (pair launch, opacity_only, the stencil features feat7) live in the <MODE_FULL, *, EX = true, *> instantiations
+    // only, behind run-time tests: a launch that asks for one of them takes such an instantiation, every other instantiation compiles as if they did not exist
+    constexpr bool TR = EX && MODE == MODE_FULL;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if (a.prepared) {
         const float4 *src = reinterpret_cast<const float4 *>(a.prepared);
@@ -67,14 +70,25 @@ __global__ __launch_bounds__(BLOCK) void render_rays_long_kernel(const RenderArg
     for (int k = (int)(blockIdx.x >> 3) * WAVES_PER_BLOCK + wave;; k += kstride) {
         const int kc = k / xchunk, base = (kc * 8 + xcd) * xchunk;
         if (base >= a.n_rays) break;
-        const int ray = base + (k - kc * xchunk);
+        int ray = base + (k - kc * xchunk);
         if (ray >= a.n_rays) continue;
-        const float ox = a.rays_o[3 * ray], oy = a.rays_o[3 * ray + 1], oz = a.rays_o[3 * ray + 2];
-        const float dx = a.rays_d[3 * ray], dy = a.rays_d[3 * ray + 1], dz = a.rays_d[3 * ray + 2];
+        int rin = ray;                                              // row of this ray in rays_o / rays_d / near_m / far_m
+        int exr = ray;                                              // row in the per-sample outputs
+        bool ex_on = true;
+        if constexpr (TR) {
+            // pair launch (ac_render_rays_long_pair): the 2 pair_n work items are a0 b0 a1 b1 ...; a chunk holds an even number of them, so the two copies
+            // of a ray are consecutive items of one chunk = of one XCD, taken by neighbouring waves at the same time: they meet in that XCD's L2.
+            // Copy b = rows [pair_n, 2 pair_n) of noise, bg and the per-ray outputs; the per-sample outputs are kept for copy b only (ex_from = pair_n)
+            if (a.pair_n) { rin = ray >> 1; ray = rin + ((ray & 1) ? a.pair_n : 0); }
+            exr = ray - a.ex_from;
+            ex_on = exr >= 0;
+        }
+        const float ox = a.rays_o[3 * rin], oy = a.rays_o[3 * rin + 1], oz = a.rays_o[3 * rin + 2];
+        const float dx = a.rays_d[3 * rin], dy = a.rays_d[3 * rin + 1], dz = a.rays_d[3 * rin + 2];
         float near, far;
         cube_near_far(ox, oy, oz, dx, dy, dz, bound, near, far);
         if (a.near_m) {
-            const float nm = a.near_m[ray], fm = a.far_m[ray];
+            const float nm = a.near_m[rin], fm = a.far_m[rin];
             if (!is_inf(nm)) near = nm;
             if (!is_inf(fm)) far = fm;
         }
@@ -210,7 +224,7 @@ __global__ __launch_bounds__(BLOCK) void render_rays_long_kernel(const RenderArg
             }
             if (g == 0) {
                 znl[n] = znew;
-                if (EX && a.out.ss_inds) a.out.ss_inds[((size_t)ray * nup + it) * 16 + n] = ind;
+                if (EX && ex_on && a.out.ss_inds) a.out.ss_inds[((size_t)exr * nup + it) * 16 + n] = ind;
             }
             const bool last_it = (it + 1 == nup);
             float sdf_new = 0.0f;
@@ -223,7 +237,7 @@ __global__ __launch_bounds__(BLOCK) void render_rays_long_kernel(const RenderArg
             wave_sync();
             // stable merge == torch.sort(cat([z, znew])); see render_rays_kernel for the unsorted first iteration of a ray that misses the cube
             const bool old_sorted = !(it == 0 && span < 0.0f);
-            int32_t *sidx = (EX && a.out.sort_index) ? a.out.sort_index + ((size_t)ray * nup + it) * T : nullptr;     // [N, nup, T]
+            int32_t *sidx = (EX && ex_on && a.out.sort_index) ? a.out.sort_index + ((size_t)exr * nup + it) * T : nullptr;     // [N, nup, T]
 #pragma unroll
             for (int ch = 0; ch < NCH; ++ch) {
                 if (ch >= nch_c) continue;
@@ -280,7 +294,7 @@ __global__ __launch_bounds__(BLOCK) void render_rays_long_kernel(const RenderArg
         // ---- render core (last tile masked when 16 does not divide T) ------------------------------------------------------------------
         float cT = 1.0f;
         float *const accs = zs0 + SLAB_ACC;
-        if constexpr (SH) ray_sh_bias(zs0 + SLAB_SHB, a.Wsh, dx, dy, dz, lane);
+        if constexpr (SH) { if (!(TR && a.opacity_only)) ray_sh_bias(zs0 + SLAB_SHB, a.Wsh, dx, dy, dz, lane); }
         const float bxe = a.eps;
         for (int c = 0; c < ntile; ++c) {
             const int i = 16 * c + n;
@@ -308,6 +322,23 @@ __global__ __launch_bounds__(BLOCK) void render_rays_long_kernel(const RenderArg
             if (MODE != MODE_FINAL || !skip) {
             float fe0[4][2];
             encode_stencil(lds, fsl, fc, lane, px, py, pz, bxe, fe0);
+            if constexpr (TR) {
+                if (ex_on && a.out.feat7) {
+                    // training render: keep the 7 x 8 features of this lane, in render_rays_kernel's layout [tile of 16 samples][14][lane][4] (the host admits
+                    // feat7 only when 16 divides T: every tile is whole); the lane term enters through an opaque copy, as there
+                    int lane_x = lane;
+                    asm volatile("" : "+v"(lane_x));
+                    f32x4 *dst = reinterpret_cast<f32x4 *>(a.out.feat7) + (((size_t)exr * (T / 16) + c) * 14) * 64 + lane_x;
+                    dst[0] = f32x4{ fe0[0][0], fe0[0][1], fe0[1][0], fe0[1][1] };
+                    dst[64] = f32x4{ fe0[2][0], fe0[2][1], fe0[3][0], fe0[3][1] };
+#pragma unroll 1
+                    for (int e = 0; e < 6; ++e) {
+                        const float *sp = fsl + (e * 8) * 64 + lane;
+                        dst[(2 * e + 2) * 64] = f32x4{ sp[0], sp[64], sp[128], sp[192] };
+                        dst[(2 * e + 3) * 64] = f32x4{ sp[256], sp[320], sp[384], sp[448] };
+                    }
+                }
+            }
             // (render_rays_kernel's stencil, kept inline: as a shared helper it changes both renderers' code)
             const float pc0 = sel4(g, px, py, pz, 0.0f);
             float spos = 0.0f;
@@ -362,7 +393,7 @@ __global__ __launch_bounds__(BLOCK) void render_rays_long_kernel(const RenderArg
             const FdNormal nrm = fd_normal(gx, gy, gz);
             const float gn = nrm.gn, nx = nrm.nx, ny = nrm.ny, nz = nrm.nz;
             float rgb[3] = { 0.0f, 0.0f, 0.0f };
-            if (MODE != MODE_FINAL || !skip) {
+            if ((MODE != MODE_FINAL || !skip) && !(TR && a.opacity_only)) {       // (wave-uniform; opacity_only: a black body)
             if constexpr (FC) color_tile_fast(lds, lane, px, py, pz, nx, ny, nz, oc, rgb, nullptr, 16, SH ? zs0 + SLAB_SHB : nullptr);
             else color_tile(lds, lane, px, py, pz, nx, ny, nz, oc, rgb, nullptr, 16, SH ? zs0 + SLAB_SHB : nullptr);
             }
@@ -401,8 +432,8 @@ __global__ __launch_bounds__(BLOCK) void render_rays_long_kernel(const RenderArg
 #undef AC_ACC
                 }
             }
-            if (g == 0 && valid) {
-                const size_t si = (size_t)ray * T + i;
+            if (g == 0 && valid && ex_on) {
+                const size_t si = (size_t)exr * T + i;
                 if (EX && a.out.z_vals) a.out.z_vals[si] = zi;
                 if (EX && a.out.weights) a.out.weights[si] = wgt;
                 if (EX && a.out.alpha) a.out.alpha[si] = alpha;
@@ -411,8 +442,8 @@ __global__ __launch_bounds__(BLOCK) void render_rays_long_kernel(const RenderArg
                 if (EX && a.out.gradient) { a.out.gradient[3 * si] = gx; a.out.gradient[3 * si + 1] = gy; a.out.gradient[3 * si + 2] = gz; }
                 if (EX && a.out.pts) { a.out.pts[3 * si] = px; a.out.pts[3 * si + 1] = py; a.out.pts[3 * si + 2] = pz; }
             }
-            if (EX && valid && a.out.sdf_out16)
-                *reinterpret_cast<f32x4 *>(a.out.sdf_out16 + ((size_t)ray * T + i) * 16 + 4 * g) = oc;
+            if (EX && valid && ex_on && a.out.sdf_out16)
+                *reinterpret_cast<f32x4 *>(a.out.sdf_out16 + ((size_t)exr * T + i) * 16 + 4 * g) = oc;
         }
         wave_sync();
         if (lane == 0) {
@@ -443,7 +474,11 @@ static int check_long_args(const char *who, const ac_render_opts *op, const floa
         return AC_ERR_BAD_ARG;
     }
     if (op->precision != 0 && op->precision != 1) { ac::set_error("%s: precision %d unknown (0 = exact, 1 = fast)", who, op->precision); return AC_ERR_BAD_ARG; }
-    if (op->opacity_only) { ac::set_error("%s: opacity_only is not supported by the long renderer", who); return AC_ERR_BAD_ARG; }
+    if (op->opacity_only != 0 && op->opacity_only != 1) { ac::set_error("%s: opacity_only must be 0 or 1", who); return AC_ERR_BAD_ARG; }
+    if (op->opacity_only && posed) {
+        ac::set_error("%s: opacity_only is a canonical-space option of the long renderer (ac_render_rays_long); the posed entry evaluates the colour network", who);
+        return AC_ERR_BAD_ARG;
+    }
     if (op->skip_masked != 0 && op->skip_masked != 1) { ac::set_error("%s: skip_masked must be 0 or 1", who); return AC_ERR_BAD_ARG; }
     if (op->skip_masked && !posed) {
         ac::set_error("%s: skip_masked is a posed-space option; this entry is canonical (posed: ac_render_rays_long_warped)", who); return AC_ERR_BAD_ARG;
@@ -473,6 +508,29 @@ static bool long_wants_samples(const ac_render_out &o)
     return o.z_vals || o.weights || o.alpha || o.color || o.sdf || o.gradient || o.ss_inds || o.sort_index || o.sdf_out16 || o.pts;
 }
 
+// the stencil features exist per tile of 16 samples of one ray: only a count 16 divides has them (other counts gather again in the backward)
+static int check_long_feat7(const char *who, const ac_render_opts *op, const ac_render_out *out)
+{
+    const int T = op->num_steps + op->upsample_steps;
+    if (out->feat7 && T % 16) {
+        ac::set_error("%s: feat7 needs T = num_steps + upsample_steps a multiple of 16 (T = %d); at other counts pass NULL: ac_render_core_backward gathers again", who, T);
+        return AC_ERR_BAD_ARG;
+    }
+    return AC_OK;
+}
+
+// the canonical launch: the training options (pair launch, opacity_only, feat7) are compiled into the EX instantiations only
+static int launch_long_full(const char *who, RenderArgs &a, const ac_render_opts *op, const ac_render_out *out, hipStream_t st)
+{
+    a.out = *out;
+    a.opacity_only = op->opacity_only;
+    const bool ex = long_wants_samples(a.out) || a.out.feat7 || a.pair_n || a.opacity_only;
+    dispatch_variants(a.fast, ex, a.Wsh != nullptr, [&](auto fast, auto ex_, auto sh) {
+        launch_long_p<MODE_FULL, decltype(fast)::value, decltype(ex_)::value, decltype(sh)::value>(a, st);
+    });
+    return ac::check_launch(who);
+}
+
 }  // namespace
 
 AC_API int ac_render_rays_long(const ac_field *field, const ac_render_opts *op, const float *rays_o, const float *rays_d,
@@ -481,19 +539,39 @@ AC_API int ac_render_rays_long(const ac_field *field, const ac_render_opts *op, 
 {
     if (!op || !out) { ac::set_error("render_rays_long: NULL opts/out"); return AC_ERR_BAD_ARG; }
     if (int rc = check_long_args("render_rays_long", op, rays_o, rays_d, noise, lin_z, lin_u)) return rc;
-    if (out->feat7) { ac::set_error("render_rays_long: feat7 (the fused training backward's features) is not produced by the long renderer"); return AC_ERR_BAD_ARG; }
+    if (int rc = check_long_feat7("render_rays_long", op, out)) return rc;
     if (op->n_rays <= 0) return AC_OK;
     if (!out->image || !out->weights_sum || !out->depth || !out->normal_map || !out->eik) { ac::set_error("render_rays_long: NULL buffer"); return AC_ERR_BAD_ARG; }
     RenderArgs a{};
     if (int rc = fill_render_common(a, field, op, rays_o, rays_d, bg, noise, lin_z, lin_u)) return rc;
-    a.out = *out;
-    const hipStream_t st = (hipStream_t)stream;
-    dispatch_variants(a.fast, long_wants_samples(a.out), a.Wsh != nullptr, [&](auto fast, auto ex, auto sh) {
-        launch_long_p<MODE_FULL, decltype(fast)::value, decltype(ex)::value, decltype(sh)::value>(a, st);
-    });
-    if (int rc = ac::check_launch("render_rays_long")) return rc;
+    if (int rc = launch_long_full("render_rays_long", a, op, out, (hipStream_t)stream)) return rc;
     // gradient_error in the fixed order the other renderer's last workgroup uses (eikonal_reduce_kernel's): bit-identical
     if (out->eik_reduced) return ac_eikonal_reduce2(out->eik, op->n_rays, out->eik_reduced, stream);
+    return AC_OK;
+}
+
+// ac_render_rays_pair at the long counts: the same N rays twice in one launch (two noise draws, two backgrounds).  The 2N work items go through the static
+// hand-out unchanged (chunks of 512 items, chunk c to XCD c % 8), the two copies of a ray as consecutive items of one chunk; no scratch, no counters, no
+// hand-off.  The rays are independent: every value equals two ac_render_rays_long calls bit for bit.  gradient_error of each copy: ac_eikonal_reduce2.
+AC_API int ac_render_rays_long_pair(const ac_field *field, const ac_render_opts *op, const float *rays_o, const float *rays_d,
+                                    const float *bg2, const float *noise2, const float *lin_z, const float *lin_u,
+                                    const ac_render_out *out, ac_stream_t stream)
+{
+    const char *who = "render_rays_long_pair";
+    if (!op || !out) { ac::set_error("%s: NULL opts/out", who); return AC_ERR_BAD_ARG; }
+    if (int rc = check_long_args(who, op, rays_o, rays_d, noise2, lin_z, lin_u)) return rc;
+    if (int rc = check_long_feat7(who, op, out)) return rc;
+    if (op->n_rays <= 0) return AC_OK;
+    if (op->n_rays > (1 << 29)) { ac::set_error("%s: too many rays", who); return AC_ERR_BAD_ARG; }
+    if (!out->image || !out->weights_sum || !out->depth || !out->normal_map || !out->eik) { ac::set_error("%s: NULL buffer", who); return AC_ERR_BAD_ARG; }
+    RenderArgs a{};
+    if (int rc = fill_render_common(a, field, op, rays_o, rays_d, bg2, noise2, lin_z, lin_u)) return rc;
+    a.pair_n = op->n_rays; a.n_rays = 2 * op->n_rays; a.ex_from = op->n_rays; a.ex_rows = op->n_rays;
+    if (int rc = launch_long_full(who, a, op, out, (hipStream_t)stream)) return rc;
+    if (out->eik_reduced) {
+        if (int rc = ac_eikonal_reduce2(out->eik, op->n_rays, out->eik_reduced, stream)) return rc;
+        return ac_eikonal_reduce2(out->eik + 2 * (size_t)op->n_rays, op->n_rays, out->eik_reduced + 2, stream);
+    }
     return AC_OK;
 }
 

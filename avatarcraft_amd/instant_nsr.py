@@ -191,6 +191,10 @@ class NeRFRenderer(nn.Module):
             ok = (int(num_steps) + int(upsample_steps)) % 16 == 0
         return ok
 
+    def _long_save_stencil(self, num_steps, upsample_steps):
+        """a training render at a long count keeps the stencil features: long_step_extras, and a count 16 divides"""
+        return bool(self.long_step_extras) and (int(num_steps) + int(upsample_steps)) % 16 == 0
+
     def render_step_pair(self, rays_o, rays_d, num_steps, upsample_steps, bound, bkg_fn, cos_anneal_ratio=1.0, normal_epsilon_ratio=0.0):
         """The two renders of net_style in one stylisation step (stylize.py:98-116 render_val, :143-152 the differentiable render of the same rays) as
         ONE launch (ac_render_rays_pair): the two copies of a ray share most table sectors and meet in L2.  Random draws, in the order the two renders
@@ -234,7 +238,11 @@ class NeRFRenderer(nn.Module):
             if nsr_ops.in_short_window(num_steps, upsample_steps):
                 ra, rb = nsr_ops.render_rays_pair(field, ro, rd, noise2, num_steps, upsample_steps, bound, inv_s, bg2=bg2,
                                                   cos_anneal_ratio=cos_anneal_ratio, normal_epsilon_ratio=normal_epsilon_ratio, precision=self.render_precision)
-            else:           # (the pair launch is the short window's): two launches of the long renderer, the same draws
+            elif self.long_step_extras:     # the long pair launch; the stencil features where 16 divides the count
+                ra, rb = nsr_ops.render_rays_long_pair(field, ro, rd, noise2, num_steps, upsample_steps, bound, inv_s, bg2=bg2,
+                                                       cos_anneal_ratio=cos_anneal_ratio, normal_epsilon_ratio=normal_epsilon_ratio,
+                                                       precision=self.render_precision, save_stencil=self._long_save_stencil(num_steps, upsample_steps))
+            else:           # (long_step_extras off): two launches of the long renderer, the same draws
                 kw = dict(cos_anneal_ratio=cos_anneal_ratio, normal_epsilon_ratio=normal_epsilon_ratio, precision=self.render_precision)
                 ra = nsr_ops.render_rays_long(field, ro, rd, num_steps, upsample_steps, bound, inv_s, bg=bg2[:N], noise=noise2[:N], **kw)
                 rb = nsr_ops.render_rays_long(field, ro, rd, num_steps, upsample_steps, bound, inv_s, bg=bg2[N:], noise=noise2[N:], extras=True,
@@ -275,9 +283,12 @@ class NeRFRenderer(nn.Module):
         else:
             bg = torch.cat([b if b is not None else torch.ones((min(batch_size, N - k * batch_size), 3), dtype=torch.float32, device=device)
                             for k, b in enumerate(bgs)]).contiguous()
-        # (at the long renderer's counts opacity_only renders the colour too: weight_sum is the same bits either way)
+        # (at the long renderer's counts opacity_only renders the colour too unless long_step_extras is on: weight_sum is the same bits either way)
         short = nsr_ops.in_short_window(num_steps, upsample_steps)
-        render, kw = (nsr_ops.render_rays, dict(opacity_only=bool(opacity_only))) if short else (nsr_ops.render_rays_long, {})
+        if short:
+            render, kw = nsr_ops.render_rays, dict(opacity_only=bool(opacity_only))
+        else:
+            render, kw = nsr_ops.render_rays_long, (dict(opacity_only=bool(opacity_only)) if self.long_step_extras else {})
         with torch.no_grad():
             out = render(self._field(), ro, rd, num_steps, upsample_steps, bound, self.forward_variance(), bg=bg, noise=noise,
                          cos_anneal_ratio=cos_anneal_ratio, normal_epsilon_ratio=normal_epsilon_ratio, extras=False, precision=self.render_precision, **kw)
@@ -384,6 +395,15 @@ class NeRFRenderer(nn.Module):
     # raises NotImplementedError there; True = a no-grad posed render goes to the long renderer (nsr_ops.render_rays_long(warp=...): any num_steps >= 2,
     # upsample_steps a multiple of 16, at most 512 samples).  drivers.render_animation switches it on for its duration.
     posed_long_rays = False
+    # the stylisation step without autograd (stylize.sds_step) at the sample counts outside the fused renderer's window, canonical space.  False (default):
+    # every route is what it was -- two launches of the long renderer on the one-patch route, no stencil features (ac_render_core_backward gathers the table
+    # again), the frozen avatar of the opacity loss renders its colours.  True (opt-in; set it on net_style AND on the frozen net_gt): the step structure of
+    # the window -- the one-patch route is ONE launch (nsr_ops.render_rays_long_pair); the one-patch and patch-by-patch training renders keep the stencil
+    # features (feat7) where 16 divides num_steps + upsample_steps (other counts keep re-gathering); no-grad renders asked for opacity_only (the frozen
+    # avatar: run(), render_view_nograd) skip the colour network.  The whole-view training render (render_view_train) keeps re-gathering either way: 0.9 KB
+    # of features per sample is 15 GB for 65 536 rays x 256 samples.  Results: the pair launch and opacity_only change no bit; the saved features change the
+    # SDF-network gradient by what the two forms of its backward differ.
+    long_step_extras = False
     # posed-space inference through the harness (render_utils.render_instantnsr_naive): the closest-face searches of a frame start from the faces the previous
     # frame found for the same (ray, sample slot) -- an upper bound from a real face, so the same pixels bit for bit, with tighter culling (ac_warp_mesh.seed_faces)
     warp_temporal_seeds = True
@@ -499,10 +519,11 @@ class NeRFRenderer(nn.Module):
         if needs_grad and full and self.fused_training == "core" and near_far is None and self._manual_backward and warp is None:
             # (at the long counts the long renderer's launch: ac_render_core_backward takes its outputs as well)
             render = nsr_ops.render_rays_long if long_counts else nsr_ops.render_rays
+            kw = dict(save_stencil=True) if long_counts and self._long_save_stencil(num_steps, upsample_steps) else {}
             with torch.no_grad():
                 field, inv_s_ng = self._field(), self.forward_variance()
                 out = render(field, ro, rd, num_steps, upsample_steps, bound, inv_s_ng, bg=bg, noise=noise, cos_anneal_ratio=cos_anneal_ratio,
-                             normal_epsilon_ratio=normal_epsilon_ratio, extras=True, train_extras=True, precision=self.render_precision)
+                             normal_epsilon_ratio=normal_epsilon_ratio, extras=True, train_extras=True, precision=self.render_precision, **kw)
             self._last_train = (out, ro, rd, bg, field)
             self._guard_finite(out["eik_res"][0])
             return (out["depth"].reshape(B, N), out["weights"], out["weights_sum"][:, None], out["image"].reshape(B, N, 3), out["normal_map"],
@@ -518,7 +539,8 @@ class NeRFRenderer(nn.Module):
             out = nsr_ops.render_rays_long(self._field(), ro, rd, num_steps, upsample_steps, bound, inv_s_t, bg=bg, noise=noise,
                                            cos_anneal_ratio=cos_anneal_ratio, normal_epsilon_ratio=normal_epsilon_ratio, extras=bool(per_sample),
                                            warp=warp, near_far=near_far, precision=self.render_precision,
-                                           skip_masked=self.skip_masked_samples and warp is not None)
+                                           skip_masked=self.skip_masked_samples and warp is not None,
+                                           opacity_only=bool(opacity_only) and warp is None and self.long_step_extras)
             return (out["depth"].reshape(B, N), out.get("weights"), out["weights_sum"][:, None], out["image"].reshape(B, N, 3),
                     out["normal_map"], out["gradient_error"], 0.0, out.get("color"), out.get("alpha"), out.get("z_vals"))
         if needs_grad and full and self.fused_training == "core" and near_far is None:

@@ -176,6 +176,14 @@ def check_long_counts(num_steps, upsample_steps):
                            f"of 16, num_steps + upsample_steps <= {LONG_MAX_SAMPLES})")
 
 
+def check_save_stencil(who, num_steps, upsample_steps):
+    """the rule of the long renderer's stencil features (ac_render_out.feat7): one block per tile of 16 samples of a ray"""
+    T = int(num_steps) + int(upsample_steps)
+    if T % 16:
+        raise RuntimeError(f"{who}: save_stencil (feat7) needs num_steps + upsample_steps a multiple of 16, got {int(num_steps)} + {int(upsample_steps)} "
+                           f"= {T}; at such a count leave it off: render_core_backward gathers the stencil features again")
+
+
 def in_short_window(num_steps, upsample_steps):
     """the counts render_rays / sample_rays accept (multiples of 16, 16 <= num_steps <= 64, sum <= 128)"""
     ns, us = int(num_steps), int(upsample_steps)
@@ -184,25 +192,34 @@ def in_short_window(num_steps, upsample_steps):
 
 def render_rays_long(field, rays_o, rays_d, num_steps=64, upsample_steps=64, bound=1.6, inv_s=1.0, bg=None, noise=None,
                      cos_anneal_ratio=1.0, normal_epsilon_ratio=0.0, extras=False, debug_indices=False, out=None, events=None, warp=None,
-                     train_extras=False, near_far=None, precision="exact", skip_masked=False, opacity_only=False, table_dtype="float"):
+                     train_extras=False, near_far=None, precision="exact", skip_masked=False, opacity_only=False, table_dtype="float",
+                     save_stencil=False):
     """render_rays for any sample count the reference accepts (ac_render_rays_long): num_steps >= 2, upsample_steps >= 0 a multiple of 16, at most
     512 samples per ray.  Same arguments and result dict as render_rays; bit-identical to it where both accept the counts.  train_extras gives
-    sdf_out16 / pts but no stencil features; sort_index is [N, nup, T].  opacity_only is rejected.
+    sdf_out16 / pts; sort_index is [N, nup, T].
+    save_stencil (opt-in, with train_extras, canonical space): + feat7, the stencil features render_core_backward otherwise gathers again -- only where 16
+    divides num_steps + upsample_steps (RuntimeError naming the rule otherwise; such counts keep re-gathering).  Default: no feat7 in the result.
+    opacity_only as in render_rays (canonical space; with a warp it raises).
     warp = WarpMesh(...) renders in posed space (ac_render_rays_long_warped): + can_mid [N,T,3], mask [N,T] views of the scratch as from
     render_rays(warp=...), with skip_masked as there; without a warp skip_masked is rejected (a posed-space option).
     table_dtype: "float" only ("half" raises: the long renderer has no half-table form)."""
     check_table_dtype("render_rays_long", table_dtype, long=True)
     check_long_counts(num_steps, upsample_steps)
-    if opacity_only:
-        raise RuntimeError("render_rays_long: opacity_only is not supported")
+    if opacity_only and warp is not None:
+        raise RuntimeError("render_rays_long: opacity_only is not supported in posed space (warp=...): a canonical-space option of the long renderer")
     if skip_masked and warp is None:
         raise RuntimeError("render_rays_long: skip_masked is a posed-space option (pass warp=WarpMesh(...))")
+    if save_stencil:
+        check_save_stencil("render_rays_long", num_steps, upsample_steps)
+        if warp is not None or not train_extras:
+            raise RuntimeError("render_rays_long: save_stencil keeps the stencil features of a canonical training render (train_extras=True, no warp)")
     return _render(field, rays_o, rays_d, num_steps, upsample_steps, bound, inv_s, bg, noise, cos_anneal_ratio, normal_epsilon_ratio, extras,
-                   debug_indices, out, events, warp, train_extras, near_far, precision, skip_masked, False, long=True)
+                   debug_indices, out, events, warp, train_extras, near_far, precision, skip_masked, opacity_only, long=True,
+                   save_stencil=bool(save_stencil))
 
 
 def _render(field, rays_o, rays_d, num_steps, upsample_steps, bound, inv_s, bg, noise, cos_anneal_ratio, normal_epsilon_ratio, extras,
-            debug_indices, out, events, warp, train_extras, near_far, precision, skip_masked, opacity_only, long, half=False):
+            debug_indices, out, events, warp, train_extras, near_far, precision, skip_masked, opacity_only, long, half=False, save_stencil=False):
     rays_o = _chk(rays_o.reshape(-1, 3), "rays_o")
     rays_d = _chk(rays_d.reshape(-1, 3), "rays_d")
     N = rays_o.shape[0]
@@ -238,9 +255,9 @@ def _render(field, rays_o, rays_d, num_steps, upsample_steps, bound, inv_s, bg, 
     if train_extras:
         o.sdf_out16 = buf("sdf_out16", (N, T, 16)).data_ptr()
         o.pts = buf("pts", (N, T, 3)).data_ptr()
-        if not long:        # the hash features of every sample's 7-point stencil (0.9 KB per sample): the backward streams them back instead of gathering them again
+        if not long or save_stencil:      # the hash features of every sample's 7-point stencil (0.9 KB per sample): the backward streams them back instead of gathering them again
             o.feat7 = buf("feat7", (N * T // 16, 14, 64, 4)).data_ptr()
-        else:               # (none from the long renderer: render_core_backward gathers again; a reused result dict must not hand on another launch's)
+        else:               # (the long renderer's default: render_core_backward gathers again; a reused result dict must not hand on another launch's)
             res.pop("feat7", None)
     if debug_indices:
         o.ss_inds = buf("ss_inds", (N, max(nup, 1), 16), torch.int32).data_ptr()
@@ -314,6 +331,12 @@ def render_rays_pair(field, rays_o, rays_d, noise2, num_steps=64, upsample_steps
     render_rays(..., noise=noise2[0]) and render_rays(..., noise=noise2[1], extras=True, train_extras=True).
     table_dtype: "float" only ("half" raises: the pair launch is a training launch)."""
     check_table_dtype("render_rays_pair", table_dtype, pair=True)
+    return _render_pair(field, rays_o, rays_d, noise2, num_steps, upsample_steps, bound, inv_s, bg2, cos_anneal_ratio, normal_epsilon_ratio, precision,
+                        out, events, keep_weights, long=False, save_stencil=True)
+
+
+def _render_pair(field, rays_o, rays_d, noise2, num_steps, upsample_steps, bound, inv_s, bg2, cos_anneal_ratio, normal_epsilon_ratio, precision,
+                 out, events, keep_weights, long, save_stencil):
     rays_o = _chk(rays_o.reshape(-1, 3), "rays_o")
     rays_d = _chk(rays_d.reshape(-1, 3), "rays_d")
     N, dev, T = rays_o.shape[0], rays_o.device, num_steps + upsample_steps
@@ -337,7 +360,10 @@ def render_rays_pair(field, rays_o, rays_d, noise2, num_steps=64, upsample_steps
     per_sample = {"z_vals": (N, T), "color": (N, T, 3), "sdf": (N, T), "gradient": (N, T, 3), "sdf_out16": (N, T, 16), "pts": (N, T, 3)}      # what the backward reads
     if keep_weights:
         per_sample.update({"weights": (N, T), "alpha": (N, T)})
-    per_sample["feat7"] = (N * T // 16, 14, 64, 4)
+    if save_stencil:
+        per_sample["feat7"] = (N * T // 16, 14, 64, 4)
+    else:                   # (a reused result dict must not hand on another launch's)
+        res.pop("feat7", None)
     for k, shp in per_sample.items():
         setattr(o, k, buf(k, shp).data_ptr())
     noise2 = _chk(noise2.reshape(2 * N, num_steps), "noise2")
@@ -350,8 +376,9 @@ def render_rays_pair(field, rays_o, rays_d, noise2, num_steps=64, upsample_steps
     st = L.current_stream(dev)
     if events is not None:
         events[0].record()
-    L.check(L.lib().ac_render_rays_pair(C.byref(field.c), C.byref(op), rays_o.data_ptr(), rays_d.data_ptr(), L.ptr(bg2), noise2.data_ptr(),
-                                        lin_z.data_ptr(), lin_u.data_ptr(), C.byref(o), st), "render_rays_pair")
+    entry, who = (L.lib().ac_render_rays_long_pair, "render_rays_long_pair") if long else (L.lib().ac_render_rays_pair, "render_rays_pair")
+    L.check(entry(C.byref(field.c), C.byref(op), rays_o.data_ptr(), rays_d.data_ptr(), L.ptr(bg2), noise2.data_ptr(),
+                  lin_z.data_ptr(), lin_u.data_ptr(), C.byref(o), st), who)
     if events is not None:
         events[1].record()
     ra, rb = RenderResult(), RenderResult()
@@ -365,6 +392,20 @@ def render_rays_pair(field, rays_o, rays_d, noise2, num_steps=64, upsample_steps
     rb.opts = ra.opts = (op, inv_s_t, None, None)
     rb._keep = ra._keep = (noise2, bg2, res)
     return ra, rb
+
+
+def render_rays_long_pair(field, rays_o, rays_d, noise2, num_steps=64, upsample_steps=64, bound=1.6, inv_s=1.0, bg2=None, cos_anneal_ratio=1.0,
+                          normal_epsilon_ratio=0.0, precision="exact", out=None, events=None, keep_weights=False, table_dtype="float", save_stencil=False):
+    """render_rays_pair at the long renderer's counts (ac_render_rays_long_pair): same arguments, same (a, b) result; bit-identical to
+    render_rays_long(..., noise=noise2[0]) and render_rays_long(..., noise=noise2[1], extras=True, train_extras=True, save_stencil=...).
+    save_stencil as in render_rays_long: True keeps copy b's feat7 and raises where 16 does not divide num_steps + upsample_steps; default: no feat7.
+    table_dtype: "float" only."""
+    check_table_dtype("render_rays_long_pair", table_dtype, long=True, pair=True)
+    check_long_counts(num_steps, upsample_steps)
+    if save_stencil:
+        check_save_stencil("render_rays_long_pair", num_steps, upsample_steps)
+    return _render_pair(field, rays_o, rays_d, noise2, num_steps, upsample_steps, bound, inv_s, bg2, cos_anneal_ratio, normal_epsilon_ratio, precision,
+                        out, events, keep_weights, long=True, save_stencil=bool(save_stencil))
 
 
 def sample_rays(field, rays_o, rays_d, num_steps=64, upsample_steps=64, bound=1.6, noise=None, near_far=None):

@@ -261,12 +261,23 @@ int ac_render_rays_pair(const ac_field *field, const ac_render_opts *opts, const
 
 /* ac_render_rays for any sample count the reference accepts: num_steps >= 2 (any value, not only multiples of 16), upsample_steps >= 0 and a
  * multiple of 16, num_steps + upsample_steps <= 512 (anything else: AC_ERR_BAD_ARG naming the rule).  Canonical space (posed: ac_render_rays_long_warped); same arguments and
- * outputs as ac_render_rays (lin_z [num_steps]), except: sort_index is [N, upsample_steps/16, T] (T = num_steps + upsample_steps, -1 pad),
- * feat7 must be NULL and opts->opacity_only / skip_masked must be 0.  Where both accept the counts, every output is bit-identical to
- * ac_render_rays'.  Needs no scratch; gradient_error (eik_reduced) is formed by ac_eikonal_reduce2 on the same stream. */
+ * outputs as ac_render_rays (lin_z [num_steps]), except: sort_index is [N, upsample_steps/16, T] (T = num_steps + upsample_steps, -1 pad);
+ * feat7 (optional, the layout documented at ac_render_out) needs T a multiple of 16 -- any other count with feat7 set is AC_ERR_BAD_ARG naming the
+ * rule, and ac_render_core_backward gathers again there --; opts->skip_masked must be 0 (a posed-space option); opts->opacity_only is taken as by
+ * ac_render_rays (no colour network, image = the background over a black body, every other output unchanged bit for bit).  Where both accept the
+ * counts, every output (feat7 included) is bit-identical to ac_render_rays'.  Needs no scratch; gradient_error (eik_reduced) is formed by
+ * ac_eikonal_reduce2 on the same stream. */
 int ac_render_rays_long(const ac_field *field, const ac_render_opts *opts, const float *rays_o, const float *rays_d,
                         const float *bg, const float *noise, const float *lin_z, const float *lin_u,
                         const ac_render_out *out, ac_stream_t stream);
+/* ac_render_rays_pair for the sample counts of ac_render_rays_long, same contract: the N = opts->n_rays rays rendered twice in ONE launch; bg2 [2,N,3]
+ * or NULL, noise2 [2,N,num_steps]; image, weights_sum, depth, normal_map, eik hold 2N rows (rows [0,N) = the copy of noise2[0] / bg2[0]); the optional
+ * per-sample arrays and feat7 (16 | T, as above) are written for the SECOND copy only, N rows; eik_reduced [2][2], one pair per copy.  The 2N work items
+ * keep the long renderer's static hand-out (chunks of 512 items, chunk c to XCD c % 8) with the two copies of a ray as consecutive items of one chunk,
+ * so they meet in one XCD's L2.  Every value is bit-identical to two ac_render_rays_long calls.  No scratch. */
+int ac_render_rays_long_pair(const ac_field *field, const ac_render_opts *opts, const float *rays_o, const float *rays_d,
+                             const float *bg2, const float *noise2, const float *lin_z, const float *lin_u,
+                             const ac_render_out *out, ac_stream_t stream);
 /* the sampling stage of ac_render_rays_long alone -> z_vals [N, num_steps + upsample_steps]: the long counterpart of ac_sample_rays */
 int ac_sample_rays_long(const ac_field *field, const ac_render_opts *opts, const float *rays_o, const float *rays_d, const float *noise,
                         const float *lin_z, const float *lin_u, float *z_vals, ac_stream_t stream);
@@ -552,8 +563,8 @@ int ac_composite_backward(const float *rays_o, const float *rays_d, const float 
  * The forward is ac_render_rays itself with the per-sample outputs kept (z_vals, pts, sdf, sdf_out16, gradient, color and the
  * eikonal denominator of ac_eikonal_reduce2): the training render and the inference render are the same launch, bit for bit.
  * At the long renderer's counts (T = num_steps + upsample_steps > 128 or not a multiple of 16; the envelope of ac_composite_forward) the forward is
- * ac_render_rays_long with the same outputs; saved->feat7 must then be NULL when 16 does not divide T (that renderer does not write it: the stencil
- * features are gathered again), and a field with view directions needs T a multiple of 16 (AC_ERR_BAD_ARG naming the rule otherwise).
+ * ac_render_rays_long (or ac_render_rays_long_pair) with the same outputs; saved->feat7 must then be NULL when 16 does not divide T (that renderer
+ * writes it for whole tiles only: at other counts the stencil features are gathered again), and a field with view directions needs T a multiple of 16 (AC_ERR_BAD_ARG naming the rule otherwise).
  * The backward chains, on `stream`: normals from the finite-difference gradients -> NeuS alpha / compositing backward ->
  * colour MLP backward -> normalisation + eikonal backward -> fused SDF-query backward -> table-gradient scatter.
  *   upstream: d image [N,3], d weights_sum [N], d depth [N], d normal_map [N,3] (any may be NULL = 0), d gradient_error (1 float, device, or NULL)
