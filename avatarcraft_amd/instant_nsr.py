@@ -14,8 +14,10 @@ Where the work happens:
   * render_can=False (SMPL inverse warp, :166-172,198-203): no-grad only (render_warp.py), ac_render_rays_warped; at sample counts
     outside the fused renderer's window ac_render_rays_long_warped (opt-in: posed_long_rays).
 """
-import numpy as np
+import collections
 import math
+
+import numpy as np
 
 import torch
 import torch.nn as nn
@@ -46,6 +48,107 @@ class SingleVarianceNetwork(nn.Module):
 
     def forward(self, x):
         return torch.ones([len(x), 1], device=self.variance.device) * torch.exp(self.variance * 10.0)
+
+
+# What render_route() decides: the nsr_ops entry to launch (looked up by name at call time), the keyword options that depend on the route, and what follows
+# the launch -- None (an inference render), "last_train" (a training render without autograd: its outputs are kept for backward_last()), "guard" (the fused
+# training operator: its gradient_error feeds the NaN guard) or "autograd" (the entry only samples: _render_core_autograd runs on its z_vals).
+Route = collections.namedtuple("Route", "entry options then")
+_TRAINS = dict(extras=True, train_extras=True)
+
+
+def _keeps_stencil(long_step_extras, num_steps, upsample_steps):
+    """a training render at a long count keeps the stencil features (feat7): the switch, and a count 16 divides"""
+    return bool(long_step_extras) and (int(num_steps) + int(upsample_steps)) % 16 == 0
+
+
+def render_route(caller, num_steps, upsample_steps, *, posed, needs_grad, full, training, near_far, per_sample, opacity_only, fused_training,
+                 manual_backward, render_table_dtype, skip_masked_samples, posed_long_rays, long_step_extras, use_viewdirs):
+    """THE routing decision of every render of NeRFRenderer: given the sample counts, the space, whether a gradient is wanted, the model's switches and
+    the mode -> the Route to launch, or the error that names the rule.  Pure: no tensor, no device (DESIGN.md section 5.10 lists the outcomes).
+    caller: "run" (run()), "step_pair" (render_step_pair), "view_nograd" (render_view_nograd), "view_train" (render_view_train).
+    full: _fused_supported() for run(); for the three step renders "the default model, on the GPU".  near_far: a mesh-guided range is present.
+    The step renders are canonical and know no gradient: they ignore posed / needs_grad / near_far / per_sample."""
+    long_counts = not nsr_ops.in_short_window(num_steps, upsample_steps)
+    render = "render_rays_long" if long_counts else "render_rays"
+    if caller != "run":
+        if caller == "view_nograd":
+            if not full:
+                raise RuntimeError("render_view_nograd: needs the default model on the GPU")
+            # (at the long renderer's counts opacity_only renders the colour too unless long_step_extras is on: weight_sum is the same bits either way)
+            return Route(render, dict(extras=False, opacity_only=opacity_only) if long_step_extras or not long_counts else dict(extras=False), None)
+        # the two training renders of the stylisation step without autograd; with view directions the fused backward needs a count 16 divides
+        if not (training and fused_training == "core" and full and not (use_viewdirs and (int(num_steps) + int(upsample_steps)) % 16)):
+            raise RuntimeError(f"render_{caller}: needs the default model in train mode on the GPU")
+        if caller == "view_train":          # (never the stencil features at a long count: 0.9 KB per sample of a whole view)
+            return Route(render, _TRAINS, "last_train")
+        if not long_counts:
+            return Route("render_rays_pair", {}, "last_train")
+        if long_step_extras:                # the long pair launch; the stencil features where 16 divides the count
+            return Route("render_rays_long_pair", dict(save_stencil=_keeps_stencil(True, num_steps, upsample_steps)), "last_train")
+        return Route(render, _TRAINS, "last_train")            # (long_step_extras off): two launches of the long renderer
+    # counts outside the fused renderer's window go to the long renderer: canonical space, and posed space without gradients when posed_long_rays is on
+    if long_counts:
+        if posed and not posed_long_rays:
+            raise NotImplementedError(f"posed-space rendering supports num_steps and upsample_steps that are multiples of 16 with "
+                                      f"16 <= num_steps <= 64 and num_steps + upsample_steps <= 128 only (got {num_steps} + {upsample_steps}); "
+                                      f"longer rays render in canonical space (render_can=True), or in posed space without gradients with "
+                                      f"posed_long_rays = True")
+        nsr_ops.check_long_counts(num_steps, upsample_steps)
+    if render_table_dtype not in nsr_ops.TABLE_DTYPES:
+        raise RuntimeError(f"render_table_dtype must be one of {nsr_ops.TABLE_DTYPES}, got {render_table_dtype!r}")
+    # the half table: eval mode, no gradient wanted, the default model
+    half = render_table_dtype == "half" and not needs_grad and not training and full
+    if half and long_counts:
+        raise NotImplementedError(f"render_table_dtype = 'half' renders inside the fused renderer's window only (multiples of 16, 16 <= num_steps <= 64, "
+                                  f"at most 128 samples; got {num_steps} + {upsample_steps}): the long renderer reads the fp32 table, and an inference "
+                                  f"render does not switch tables silently")
+    if posed:
+        if long_counts and needs_grad:
+            raise NotImplementedError(f"posed-space training is built for the short window only (multiples of 16, 16 <= num_steps <= 64, at most 128 "
+                                      f"samples; got {num_steps} + {upsample_steps}): the long posed renderer (posed_long_rays) runs under no_grad")
+        if long_counts and opacity_only:
+            raise NotImplementedError("opacity_only is not supported by the long renderer")
+        if needs_grad and fused_training != "core":
+            raise NotImplementedError("posed-space rendering under autograd runs through the fused operator only (fused_training = 'core')")
+        if not full:
+            raise NotImplementedError("posed-space rendering is built for the default NeRFNetwork (with or without view directions; no curvature term)")
+    fused_op = needs_grad and full and fused_training == "core" and not near_far
+    # only the sample positions come from the fused (no-grad) stage; the render core runs under autograd
+    autograd = not posed and (needs_grad or not full)
+    if fused_op and manual_backward and not posed:
+        # (at the long counts the long renderer's launch: ac_render_core_backward takes its outputs as well)
+        keep = long_counts and _keeps_stencil(long_step_extras, num_steps, upsample_steps)
+        return Route(render, dict(_TRAINS, save_stencil=True) if keep else _TRAINS, "last_train")
+    if long_counts:
+        # (the fused training operator takes at most 128 samples: the long counts take the autograd render core, which handles any T)
+        if autograd:
+            return Route("sample_rays_long", {}, "autograd")
+        return Route(render, dict(extras=per_sample, skip_masked=bool(skip_masked_samples) and posed,
+                                  opacity_only=opacity_only and not posed and bool(long_step_extras)), None)
+    if fused_op:
+        return Route("render_core", {}, "guard")
+    if autograd:
+        return Route("sample_rays", {}, "autograd")
+    return Route(render, dict(extras=per_sample, skip_masked=skip_masked_samples, opacity_only=opacity_only,
+                              table_dtype="half" if half else "float"), None)
+
+
+def _background(bg, n, device, ones=False):
+    """a background colour as [n,3]: tensor [n,3] / [3] / scalar, broadcast without a copy; None stays None (the renderer's white), or with `ones` becomes
+    the white it stands for (the training renders, whose backward reads it)"""
+    if bg is None:
+        return torch.ones((n, 3), dtype=torch.float32, device=device) if ones else None
+    bg = torch.as_tensor(bg, dtype=torch.float32, device=device)
+    bg = bg.reshape(-1, 3) if bg.numel() >= 3 else bg.reshape(1, 1).expand(1, 3)
+    return bg.expand(n, 3) if bg.shape[0] == 1 else bg
+
+
+def _draw_noise(dst):
+    """jitter noise drawn straight into dst, a slice of a launch's noise buffer (torch.rand(out=...): no concatenation kernel)"""
+    r = torch.rand(tuple(dst.shape), device=dst.device, out=dst)
+    if r.data_ptr() != dst.data_ptr():                       # (a replaced torch.rand that ignores `out`: tests replaying recorded draws)
+        dst.copy_(r)
 
 
 class NeRFRenderer(nn.Module):
@@ -193,7 +296,17 @@ class NeRFRenderer(nn.Module):
 
     def _long_save_stencil(self, num_steps, upsample_steps):
         """a training render at a long count keeps the stencil features: long_step_extras, and a count 16 divides"""
-        return bool(self.long_step_extras) and (int(num_steps) + int(upsample_steps)) % 16 == 0
+        return _keeps_stencil(self.long_step_extras, num_steps, upsample_steps)
+
+    def _route(self, caller, num_steps, upsample_steps, full=None, posed=False, needs_grad=False, near_far=False, per_sample=True, opacity_only=False):
+        """render_route() with this model's switches; full = None (the step renders): the default model on the GPU, for a training step not a cuda_ray net"""
+        if full is None:
+            full = self._fused_supported() and self.encoder.embeddings.is_cuda and not (caller != "view_nograd" and getattr(self, "cuda_ray", False))
+        return render_route(caller, num_steps, upsample_steps, posed=posed, needs_grad=needs_grad, full=full, training=self.training, near_far=near_far,
+                            per_sample=per_sample, opacity_only=opacity_only, fused_training=self.fused_training,
+                            manual_backward=self._manual_backward, render_table_dtype=self.render_table_dtype,
+                            skip_masked_samples=self.skip_masked_samples, posed_long_rays=self.posed_long_rays,
+                            long_step_extras=self.long_step_extras, use_viewdirs=self.use_viewdirs)
 
     def render_step_pair(self, rays_o, rays_d, num_steps, upsample_steps, bound, bkg_fn, cos_anneal_ratio=1.0, normal_epsilon_ratio=0.0):
         """The two renders of net_style in one stylisation step (stylize.py:98-116 render_val, :143-152 the differentiable render of the same rays) as
@@ -203,28 +316,14 @@ class NeRFRenderer(nn.Module):
         stylize.sds_step pairs the renders only for a guidance with `private_rng = True`.
         Returns (rgb_val [N,3], rgb [N,3], gradient_error, weight_sum [N,1]) of which the last three belong to the training render, whose
         per-sample outputs are kept for backward_last().  Every value equals what the two separate renders give, bit for bit."""
-        if not (self.training and self.manual_backward_supported(num_steps, upsample_steps)):
-            raise RuntimeError("render_step_pair: needs the default model in train mode on the GPU")
+        route = self._route("step_pair", num_steps, upsample_steps)
         ro = rays_o.reshape(-1, 3).float().contiguous()
         rd = rays_d.reshape(-1, 3).float().contiguous()
         N, device = ro.shape[0], ro.device
-
-        def as_bg(b):
-            if b is None:
-                return torch.ones((N, 3), dtype=torch.float32, device=device)
-            b = torch.as_tensor(b, dtype=torch.float32, device=device)
-            b = b.reshape(-1, 3) if b.numel() >= 3 else b.reshape(1, 1).expand(1, 3)
-            return b.expand(N, 3) if b.shape[0] == 1 else b
         # the two noise draws land in the two halves of one buffer (torch.rand(out=...): the same two calls, no concatenation kernel)
         noise2 = torch.empty((2 * N, num_steps), dtype=torch.float32, device=device)
-
-        def draw(half):
-            dst = noise2[half * N:(half + 1) * N]
-            r = torch.rand((N, num_steps), device=device, out=dst)
-            if r.data_ptr() != dst.data_ptr():                   # (a replaced torch.rand that ignores `out`: tests replaying recorded draws)
-                dst.copy_(r)
-        bg_a = as_bg(bkg_fn()); draw(0)
-        bg_b = as_bg(bkg_fn()); draw(1)
+        bg_a = _background(bkg_fn(), N, device, ones=True); _draw_noise(noise2[:N])
+        bg_b = _background(bkg_fn(), N, device, ones=True); _draw_noise(noise2[N:])
         ck = (bg_a.data_ptr(), bg_b.data_ptr(), N)
         if bg_a is bg_b or (bg_a.data_ptr() == bg_b.data_ptr()):   # a constant background (cached on the device): its doubled copy is cached as well
             cache = self.__dict__.setdefault("_pair_bg_cache", {})
@@ -233,23 +332,47 @@ class NeRFRenderer(nn.Module):
             bg2 = cache[ck][0]
         else:
             bg2 = torch.cat([bg_a, bg_b]).contiguous()
+        render = getattr(nsr_ops, route.entry)
+        kw = dict(cos_anneal_ratio=cos_anneal_ratio, normal_epsilon_ratio=normal_epsilon_ratio, precision=self.render_precision)
         with torch.no_grad():
             field, inv_s = self._field(), self.forward_variance()
-            if nsr_ops.in_short_window(num_steps, upsample_steps):
-                ra, rb = nsr_ops.render_rays_pair(field, ro, rd, noise2, num_steps, upsample_steps, bound, inv_s, bg2=bg2,
-                                                  cos_anneal_ratio=cos_anneal_ratio, normal_epsilon_ratio=normal_epsilon_ratio, precision=self.render_precision)
-            elif self.long_step_extras:     # the long pair launch; the stencil features where 16 divides the count
-                ra, rb = nsr_ops.render_rays_long_pair(field, ro, rd, noise2, num_steps, upsample_steps, bound, inv_s, bg2=bg2,
-                                                       cos_anneal_ratio=cos_anneal_ratio, normal_epsilon_ratio=normal_epsilon_ratio,
-                                                       precision=self.render_precision, save_stencil=self._long_save_stencil(num_steps, upsample_steps))
-            else:           # (long_step_extras off): two launches of the long renderer, the same draws
-                kw = dict(cos_anneal_ratio=cos_anneal_ratio, normal_epsilon_ratio=normal_epsilon_ratio, precision=self.render_precision)
-                ra = nsr_ops.render_rays_long(field, ro, rd, num_steps, upsample_steps, bound, inv_s, bg=bg2[:N], noise=noise2[:N], **kw)
-                rb = nsr_ops.render_rays_long(field, ro, rd, num_steps, upsample_steps, bound, inv_s, bg=bg2[N:], noise=noise2[N:], extras=True,
-                                              train_extras=True, **kw)
+            if route.entry.endswith("_pair"):
+                ra, rb = render(field, ro, rd, noise2, num_steps, upsample_steps, bound, inv_s, bg2=bg2, **kw, **route.options)
+            else:           # two launches, the same draws: the route's options are the training copy's
+                ra = render(field, ro, rd, num_steps, upsample_steps, bound, inv_s, bg=bg2[:N], noise=noise2[:N], **kw)
+                rb = render(field, ro, rd, num_steps, upsample_steps, bound, inv_s, bg=bg2[N:], noise=noise2[N:], **route.options, **kw)
         self._last_train = (rb, ro, rd, bg2[N:], field)
         self._guard_finite(rb["eik_res"][0])
         return ra["image"], rb["image"], rb["eik_res"][0], rb["weights_sum"][:, None]
+
+    def _render_view(self, caller, rays_o, rays_d, num_steps, upsample_steps, bound, draw, batch_size, cos_anneal_ratio, normal_epsilon_ratio, **how):
+        """a whole view in ONE launch, its random draws exactly as the batch-by-batch loop makes them: per batch k of n rays draw(k, n) -> its background,
+        then (a training render, or train mode) its jitter noise, into slices of one buffer.  -> (out, ro, rd, bg, field)"""
+        train = caller == "view_train"
+        route = self._route(caller, num_steps, upsample_steps, **how)
+        ro = rays_o.reshape(-1, 3).float().contiguous()
+        rd = rays_d.reshape(-1, 3).float().contiguous()
+        N, device = ro.shape[0], ro.device
+        noise = torch.empty((N, num_steps), dtype=torch.float32, device=device) if train or self.training else None
+        bgs = []
+        for k, i in enumerate(range(0, N, batch_size)):
+            n = min(batch_size, N - i)
+            bgs.append(_background(draw(k, n), n, device, ones=train))
+            if noise is not None:
+                _draw_noise(noise[i:i + n])
+        if all(b is None for b in bgs):
+            bg = None
+        elif len(bgs) == 1:
+            bg = bgs[0].contiguous()
+        else:
+            bg = torch.cat([b if b is not None else _background(None, min(batch_size, N - k * batch_size), device, ones=True)
+                            for k, b in enumerate(bgs)]).contiguous()
+        with torch.no_grad():
+            field = self._field()
+            out = getattr(nsr_ops, route.entry)(field, ro, rd, num_steps, upsample_steps, bound, self.forward_variance(), bg=bg, noise=noise,
+                                                cos_anneal_ratio=cos_anneal_ratio, normal_epsilon_ratio=normal_epsilon_ratio,
+                                                precision=self.render_precision, **route.options)
+        return out, ro, rd, bg, field
 
     def render_view_nograd(self, rays_o, rays_d, num_steps, upsample_steps, bound, bkg_fn, batch_size, opacity_only=False, cos_anneal_ratio=1.0,
                            normal_epsilon_ratio=0.0):
@@ -258,40 +381,8 @@ class NeRFRenderer(nn.Module):
         Rays are independent, so every pixel equals the batch-by-batch render bit for bit -- provided the random draws are the same: they are made here
         exactly as the harness makes them, batch by batch and in its order (bkg_fn(n) -> background of the next n rays; then, in train mode, the jitter
         noise of those rays), into slices of one buffer.  -> (rgb [N,3], weight_sum [N,1]); 11.5 ms per 65 536 rays against 16 x 0.92."""
-        if not (self._fused_supported() and self.encoder.embeddings.is_cuda):
-            raise RuntimeError("render_view_nograd: needs the default model on the GPU")
-        ro = rays_o.reshape(-1, 3).float().contiguous()
-        rd = rays_d.reshape(-1, 3).float().contiguous()
-        N, device = ro.shape[0], ro.device
-        noise = torch.empty((N, num_steps), dtype=torch.float32, device=device) if self.training else None
-        bgs = []
-        for i in range(0, N, batch_size):
-            n = min(batch_size, N - i)
-            b = bkg_fn(n)
-            if b is not None:
-                b = torch.as_tensor(b, dtype=torch.float32, device=device)
-                b = b.reshape(-1, 3) if b.numel() >= 3 else b.reshape(1, 1).expand(1, 3)
-                b = b.expand(n, 3) if b.shape[0] == 1 else b
-            bgs.append(b)
-            if noise is not None:
-                dst = noise[i:i + n]
-                r = torch.rand((n, num_steps), device=device, out=dst)
-                if r.data_ptr() != dst.data_ptr():               # (a replaced torch.rand that ignores `out`: tests replaying recorded draws)
-                    dst.copy_(r)
-        if all(b is None for b in bgs):
-            bg = None
-        else:
-            bg = torch.cat([b if b is not None else torch.ones((min(batch_size, N - k * batch_size), 3), dtype=torch.float32, device=device)
-                            for k, b in enumerate(bgs)]).contiguous()
-        # (at the long renderer's counts opacity_only renders the colour too unless long_step_extras is on: weight_sum is the same bits either way)
-        short = nsr_ops.in_short_window(num_steps, upsample_steps)
-        if short:
-            render, kw = nsr_ops.render_rays, dict(opacity_only=bool(opacity_only))
-        else:
-            render, kw = nsr_ops.render_rays_long, (dict(opacity_only=bool(opacity_only)) if self.long_step_extras else {})
-        with torch.no_grad():
-            out = render(self._field(), ro, rd, num_steps, upsample_steps, bound, self.forward_variance(), bg=bg, noise=noise,
-                         cos_anneal_ratio=cos_anneal_ratio, normal_epsilon_ratio=normal_epsilon_ratio, extras=False, precision=self.render_precision, **kw)
+        out = self._render_view("view_nograd", rays_o, rays_d, num_steps, upsample_steps, bound, lambda k, n: bkg_fn(n), batch_size, cos_anneal_ratio,
+                                normal_epsilon_ratio, opacity_only=bool(opacity_only))[0]
         return out["image"], out["weights_sum"][:, None]
 
     def render_view_train(self, rays_o, rays_d, num_steps, upsample_steps, bound, draw_fn, batch_size, cos_anneal_ratio=1.0, normal_epsilon_ratio=0.0):
@@ -301,29 +392,9 @@ class NeRFRenderer(nn.Module):
         further draws of its own there, e.g. the frozen avatar's background), then the jitter noise of those rays.  The eikonal term stays a ratio PER PATCH
         (instant_nsr.py:266-272): eik [P] are the patches' gradient_errors (the bits a launch of the patch alone reports), and backward_last takes one g_eik
         per patch.  -> (rgb [N,3], eik [P], weight_sum [N,1]); pixels equal the patch-by-patch renders bit for bit."""
-        if not (self.training and self.manual_backward_supported(num_steps, upsample_steps)):
-            raise RuntimeError("render_view_train: needs the default model in train mode on the GPU")
-        ro = rays_o.reshape(-1, 3).float().contiguous()
-        rd = rays_d.reshape(-1, 3).float().contiguous()
-        N, device = ro.shape[0], ro.device
-        noise = torch.empty((N, num_steps), dtype=torch.float32, device=device)
-        bgs = []
-        for k, i in enumerate(range(0, N, batch_size)):
-            n = min(batch_size, N - i)
-            b = draw_fn(k, n)
-            b = torch.ones((n, 3), dtype=torch.float32, device=device) if b is None else torch.as_tensor(b, dtype=torch.float32, device=device)
-            b = b.reshape(-1, 3) if b.numel() >= 3 else b.reshape(1, 1).expand(1, 3)
-            bgs.append(b.expand(n, 3) if b.shape[0] == 1 else b)
-            dst = noise[i:i + n]
-            r = torch.rand((n, num_steps), device=device, out=dst)
-            if r.data_ptr() != dst.data_ptr():                   # (a replaced torch.rand that ignores `out`: tests replaying recorded draws)
-                dst.copy_(r)
-        bg = torch.cat(bgs).contiguous() if len(bgs) > 1 else bgs[0].contiguous()
-        render = nsr_ops.render_rays if nsr_ops.in_short_window(num_steps, upsample_steps) else nsr_ops.render_rays_long
+        out, ro, rd, bg, field = self._render_view("view_train", rays_o, rays_d, num_steps, upsample_steps, bound, draw_fn, batch_size, cos_anneal_ratio,
+                                                   normal_epsilon_ratio)
         with torch.no_grad():
-            field, inv_s = self._field(), self.forward_variance()
-            out = render(field, ro, rd, num_steps, upsample_steps, bound, inv_s, bg=bg, noise=noise, cos_anneal_ratio=cos_anneal_ratio,
-                         normal_epsilon_ratio=normal_epsilon_ratio, extras=True, train_extras=True, precision=self.render_precision)
             groups = nsr_ops.eikonal_groups(out["eik"], int(batch_size))
         self._last_train = (out, ro, rd, bg, field)
         self._last_train_groups = (int(batch_size), groups)
@@ -464,104 +535,51 @@ class NeRFRenderer(nn.Module):
         if not self._sdf_supported():
             raise NotImplementedError("the MI355X renderer needs the default SDF side of NeRFNetwork (16-level hash grid, include_input, "
                                       "SDF network 35-64-16); other widths / depths have no sampling kernel")
-        full = self._fused_supported()
-        # counts outside the window of the fused renderer (multiples of 16, num_steps <= 64, at most 128 samples) go to the long renderer:
-        # canonical space, and posed space without gradients when posed_long_rays is on
-        long_counts = not nsr_ops.in_short_window(num_steps, upsample_steps)
-        if long_counts:
-            if not render_can and not self.posed_long_rays:
-                raise NotImplementedError(f"posed-space rendering supports num_steps and upsample_steps that are multiples of 16 with "
-                                          f"16 <= num_steps <= 64 and num_steps + upsample_steps <= 128 only (got {num_steps} + {upsample_steps}); "
-                                          f"longer rays render in canonical space (render_can=True), or in posed space without gradients with "
-                                          f"posed_long_rays = True")
-            nsr_ops.check_long_counts(num_steps, upsample_steps)
         B, N = rays_o.shape[:2]
         device = rays_o.device
         ro = rays_o.reshape(-1, 3).float().contiguous()
         rd = rays_d.reshape(-1, 3).float().contiguous()
         inv_s_t = self.forward_variance()
-        noise = None
-        if self.training and perturb_overwrite:                  # :161-162
-            noise = torch.rand((N, num_steps), device=device)
-        bg = None
-        if bg_color is not None:                                 # tensor [N,3] / [3] / scalar; None -> 1 (white), :291-294
-            bg = torch.as_tensor(bg_color, dtype=torch.float32, device=device)
-            bg = bg.reshape(-1, 3) if bg.numel() >= 3 else bg.reshape(1, 1).expand(1, 3)
-            bg = bg.expand(N, 3).contiguous() if bg.shape[0] == 1 else bg.contiguous()
+        noise = torch.rand((N, num_steps), device=device) if self.training and perturb_overwrite else None      # :161-162
+        bg = None if bg_color is None else _background(bg_color, N, device).contiguous()      # None -> 1 (white), :291-294
+        full = self._fused_supported()
+        guided = render_can and verts is not None and use_mesh_guide
         needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
-        half = self.render_table_dtype == "half" and not needs_grad and not self.training and full
-        if self.render_table_dtype not in nsr_ops.TABLE_DTYPES:
-            raise RuntimeError(f"render_table_dtype must be one of {nsr_ops.TABLE_DTYPES}, got {self.render_table_dtype!r}")
-        if half and long_counts:
-            raise NotImplementedError(f"render_table_dtype = 'half' renders inside the fused renderer's window only (multiples of 16, 16 <= num_steps <= 64, "
-                                      f"at most 128 samples; got {num_steps} + {upsample_steps}): the long renderer reads the fp32 table, and an inference "
-                                      f"render does not switch tables silently")
-        warp = None
-        near_far = None
+        route = self._route("run", num_steps, upsample_steps, full, not render_can, needs_grad, guided, bool(per_sample), bool(opacity_only))
+        warp = near_far = None
         if not render_can:                                       # SMPL inverse warp :166-172,198-203 (inference path of render_warp.py)
-            if long_counts and needs_grad:
-                raise NotImplementedError(f"posed-space training is built for the short window only (multiples of 16, 16 <= num_steps <= 64, at most 128 "
-                                          f"samples; got {num_steps} + {upsample_steps}): the long posed renderer (posed_long_rays) runs under no_grad")
-            if long_counts and opacity_only:
-                raise NotImplementedError("opacity_only is not supported by the long renderer")
-            if needs_grad and self.fused_training != "core":
-                raise NotImplementedError("posed-space rendering under autograd runs through the fused operator only (fused_training = 'core')")
-            if not full:
-                raise NotImplementedError("posed-space rendering is built for the default NeRFNetwork (with or without view directions; no curvature term)")
             if verts is None or (not isinstance(verts, nsr_ops.WarpMesh) and (faces is None or Ts is None)):     # (a WarpMesh carries its faces and transforms)
                 raise RuntimeError("render_can=False needs verts, faces and Ts")
             warp = verts if isinstance(verts, nsr_ops.WarpMesh) else nsr_ops.WarpMesh(verts, faces, Ts, device, DEFAULT_GEO_THRESH,
                                                                                       DEFAULT_GEO_THRESH, use_mesh_guide)
-        elif verts is not None and use_mesh_guide:               # canonical render inside the mesh-guided range :147-153
+        elif guided:                                             # canonical render inside the mesh-guided range :147-153
             from .ray_utils import geometry_guided_near_far
             v = verts.verts if isinstance(verts, nsr_ops.WarpMesh) else verts
             near_far = geometry_guided_near_far(ro, rd, v, DEFAULT_GEO_THRESH)
-        if needs_grad and full and self.fused_training == "core" and near_far is None and self._manual_backward and warp is None:
-            # (at the long counts the long renderer's launch: ac_render_core_backward takes its outputs as well)
-            render = nsr_ops.render_rays_long if long_counts else nsr_ops.render_rays
-            kw = dict(save_stencil=True) if long_counts and self._long_save_stencil(num_steps, upsample_steps) else {}
-            with torch.no_grad():
-                field, inv_s_ng = self._field(), self.forward_variance()
-                out = render(field, ro, rd, num_steps, upsample_steps, bound, inv_s_ng, bg=bg, noise=noise, cos_anneal_ratio=cos_anneal_ratio,
-                             normal_epsilon_ratio=normal_epsilon_ratio, extras=True, train_extras=True, precision=self.render_precision, **kw)
-            self._last_train = (out, ro, rd, bg, field)
-            self._guard_finite(out["eik_res"][0])
-            return (out["depth"].reshape(B, N), out["weights"], out["weights_sum"][:, None], out["image"].reshape(B, N, 3), out["normal_map"],
-                    out["eik_res"][0], 0.0, out["color"], out["alpha"], out["z_vals"])
-        if long_counts:
-            if warp is None and (needs_grad or not full):
-                # (the fused training operator -- fused_training = "core" under autograd -- takes at most 128 samples: the long counts take the autograd
-                # render core, which handles any T)
-                z_vals = nsr_ops.sample_rays_long(self._field() if full else self._field_sdf_only(), ro, rd, num_steps, upsample_steps, bound,
-                                                  noise=noise, near_far=near_far)
-                return self._render_core_autograd(ro, rd, z_vals, num_steps, upsample_steps, bound, bg, cos_anneal_ratio, normal_epsilon_ratio, B, N,
-                                                  near_far=near_far)
-            out = nsr_ops.render_rays_long(self._field(), ro, rd, num_steps, upsample_steps, bound, inv_s_t, bg=bg, noise=noise,
-                                           cos_anneal_ratio=cos_anneal_ratio, normal_epsilon_ratio=normal_epsilon_ratio, extras=bool(per_sample),
-                                           warp=warp, near_far=near_far, precision=self.render_precision,
-                                           skip_masked=self.skip_masked_samples and warp is not None,
-                                           opacity_only=bool(opacity_only) and warp is None and self.long_step_extras)
-            return (out["depth"].reshape(B, N), out.get("weights"), out["weights_sum"][:, None], out["image"].reshape(B, N, 3),
-                    out["normal_map"], out["gradient_error"], 0.0, out.get("color"), out.get("alpha"), out.get("z_vals"))
-        if needs_grad and full and self.fused_training == "core" and near_far is None:
+        launch = getattr(nsr_ops, route.entry)
+        if route.then == "autograd":
+            # only the sample positions come from the fused (no-grad) stage (:176-184); the render core runs under autograd: through the fused
+            # operators for the default model, through torch MLPs over the HIP hash encoder for any colour-net variant (use_viewdirs, curvature)
+            z_vals = launch(self._field() if full else self._field_sdf_only(), ro, rd, num_steps, upsample_steps, bound, noise=noise, near_far=near_far)
+            return self._render_core_autograd(ro, rd, z_vals, num_steps, upsample_steps, bound, bg, cos_anneal_ratio, normal_epsilon_ratio, B, N,
+                                              near_far=near_far)
+        if route.then == "guard":                                # the fused training operator
             W = nsr_ops.weight_norm_all(list(self.sdf_net) + list(self.color_net))
             enc = self.encoder
-            (image, wsum, depth, nmap, gerr, weights, alpha, color, z_vals) = nsr_ops.render_core(
+            (image, wsum, depth, nmap, gerr, weights, alpha, color, z_vals) = launch(
                 enc.embeddings, W[0], self.sdf_net[0].bias, W[1], self.sdf_net[1].bias, W[2], W[3], W[4], inv_s_t, ro, rd, bg, noise, self._offsets_host(), enc.per_level_scale, enc.base_resolution,
                 num_steps, upsample_steps, bound, cos_anneal_ratio, normal_epsilon_ratio, precision=self.render_precision, warp=warp)
             self._guard_finite(gerr)
             return depth.reshape(B, N), weights, wsum[:, None], image.reshape(B, N, 3), nmap, gerr, 0.0, color, alpha, z_vals
-        if needs_grad or not full:
-            # only the sample positions come from the fused (no-grad) stage (:176-184); the render core runs under autograd: through the fused
-            # operators for the default model, through torch MLPs over the HIP hash encoder for any colour-net variant (use_viewdirs, curvature)
-            z_vals = nsr_ops.sample_rays(self._field() if full else self._field_sdf_only(), ro, rd, num_steps, upsample_steps, bound, noise=noise,
-                                         near_far=near_far)
-            return self._render_core_autograd(ro, rd, z_vals, num_steps, upsample_steps, bound, bg, cos_anneal_ratio, normal_epsilon_ratio, B, N,
-                                              near_far=near_far)
-        out = nsr_ops.render_rays(self._field(), ro, rd, num_steps, upsample_steps, bound, inv_s_t, bg=bg, noise=noise, cos_anneal_ratio=cos_anneal_ratio,
-                                  normal_epsilon_ratio=normal_epsilon_ratio, extras=bool(per_sample), warp=warp, near_far=near_far,
-                                  precision=self.render_precision, skip_masked=self.skip_masked_samples, opacity_only=bool(opacity_only),
-                                  table_dtype="half" if half else "float")
+        kw = dict(bg=bg, noise=noise, cos_anneal_ratio=cos_anneal_ratio, normal_epsilon_ratio=normal_epsilon_ratio, precision=self.render_precision, **route.options)
+        if route.then == "last_train":                           # a training render without autograd: its per-sample outputs wait for backward_last()
+            with torch.no_grad():
+                field = self._field()
+                out = launch(field, ro, rd, num_steps, upsample_steps, bound, self.forward_variance(), **kw)
+            self._last_train = (out, ro, rd, bg, field)
+            self._guard_finite(out["eik_res"][0])
+        else:
+            out = launch(self._field(), ro, rd, num_steps, upsample_steps, bound, inv_s_t, warp=warp, near_far=near_far, **kw)
         return (out["depth"].reshape(B, N), out.get("weights"), out["weights_sum"][:, None], out["image"].reshape(B, N, 3),
                 out["normal_map"], out["gradient_error"], 0.0, out.get("color"), out.get("alpha"), out.get("z_vals"))
 
@@ -584,7 +602,7 @@ class NeRFRenderer(nn.Module):
         pts = (rays_o.unsqueeze(-2) + rays_d.unsqueeze(-2) * z_mid.unsqueeze(-1)).clamp(-bound, bound).float()
         dirs = rays_d.unsqueeze(-2).expand_as(pts)
         flat = pts.reshape(-1, 3)
-        fd_eps = 0.005 * (1.0 - normal_epsilon_ratio)
+        fd_eps = nsr_ops.FD_STEP * (1.0 - normal_epsilon_ratio)
         if fd_eps > 0.0 and hasattr(self.encoder, "forward_stencil"):
             sdf_out, gradient = self.forward_sdf_stencil(flat, bound, fd_eps)      # 1 encoder launch + 1 MLP pass for the 7 points
         else:
@@ -618,11 +636,7 @@ class NeRFRenderer(nn.Module):
             curvature_error = (relax * cerr.reshape(N, T)).sum() / (relax.sum() + 1e-5)
         if fused_ops and flat.is_cuda and T % 16 == 0 and T <= 128:
             # NeuS alpha + compositing as one fused op each way (same arithmetic as the inference renderer)
-            bg = None
-            if bg_color is not None:
-                bg = torch.as_tensor(bg_color, dtype=torch.float32, device=flat.device)
-                bg = bg.reshape(-1, 3) if bg.numel() >= 3 else bg.reshape(1, 1).expand(1, 3)
-                bg = (bg.expand(N, 3) if bg.shape[0] == 1 else bg).contiguous()
+            bg = None if bg_color is None else _background(bg_color, N, flat.device).contiguous()
             image, wsum, depth, normal_map, weights, alpha = nsr_ops.composite(
                 z_vals, sdf.reshape(N, T), normal.reshape(N, T, 3), color.reshape(N, T, 3), self.forward_variance(), rays_o, rays_d, bg, num_steps0,
                 bound, cos_anneal_ratio)
@@ -675,7 +689,7 @@ class NeRFRenderer(nn.Module):
             raise NotImplementedError("the occupancy grid lives in canonical space: cuda_ray renders render_can=True only")
         if not self._fused_supported():
             raise NotImplementedError("run_cuda is built for the default NeRFNetwork (with or without view directions; no curvature term)")
-        fd_eps = 0.005 * (1.0 - normal_epsilon_ratio)
+        fd_eps = nsr_ops.FD_STEP * (1.0 - normal_epsilon_ratio)
         if not fd_eps > 0.0:
             raise RuntimeError("run_cuda: normal_epsilon_ratio must be < 1 (finite-difference step 0.005 * (1 - ratio) > 0)")
         B, N = rays_o.shape[:2]

@@ -7,8 +7,9 @@ libavatarcraft_hip.so; there is no eager fallback.
 """
 import ctypes as C
 import math
-
 import os
+
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -42,7 +43,6 @@ class Field:
         self.t = dict(table=_chk(table, "table", (offsets[-1], 2)), W1=_chk(W1, "W1", (64, 35)), b1=_chk(b1, "b1", (64,)),
                       W2=_chk(W2, "W2", (16, 64)), b2=_chk(b2, "b2", (16,)), Wc1=_chk(Wc1, "Wc1", (64, 21)),
                       Wc2=_chk(Wc2, "Wc2", (64, 64)), Wc3=_chk(Wc3, "Wc3", (3, 64)))
-        import numpy as np
         self.S = float(np.float32(np.log2(per_level_scale)))
         self.H = int(base_resolution)
         f = L.ac_field()
@@ -218,15 +218,15 @@ def render_rays_long(field, rays_o, rays_d, num_steps=64, upsample_steps=64, bou
                    save_stencil=bool(save_stencil))
 
 
-def _render(field, rays_o, rays_d, num_steps, upsample_steps, bound, inv_s, bg, noise, cos_anneal_ratio, normal_epsilon_ratio, extras,
-            debug_indices, out, events, warp, train_extras, near_far, precision, skip_masked, opacity_only, long, half=False, save_stencil=False):
-    rays_o = _chk(rays_o.reshape(-1, 3), "rays_o")
-    rays_d = _chk(rays_d.reshape(-1, 3), "rays_d")
-    N = rays_o.shape[0]
-    dev = rays_o.device
-    T = num_steps + upsample_steps
-    nup = upsample_steps // 16
-    lin_z, lin_u = linspace_tables(num_steps, dev)
+FD_STEP = 0.005                        # finite-difference step of the normals at normal_epsilon_ratio = 0 (instant_nsr.py:687-704)
+
+
+def _ray_args(rays_o, rays_d):
+    return _chk(rays_o.reshape(-1, 3), "rays_o"), _chk(rays_d.reshape(-1, 3), "rays_d")
+
+
+def _result_bufs(out, dev):
+    """-> (res, buf): a launch's result dict (`out` again, or a new one) and buf(name, shape[, dtype]) -> res[name], kept where it fits, else allocated"""
     res = out if out is not None else RenderResult()
 
     def buf(name, shape, dtype=_F32):
@@ -235,6 +235,31 @@ def _render(field, rays_o, rays_d, num_steps, upsample_steps, bound, inv_s, bg, 
             t = torch.empty(shape, dtype=dtype, device=dev)
             res[name] = t
         return t
+    return res, buf
+
+
+def _render_opts(N, num_steps, upsample_steps, bound, has_noise, inv_s=1.0, cos_anneal_ratio=1.0, normal_epsilon_ratio=0.0, near_far=None,
+                 precision="exact", skip_masked=False, opacity_only=False):
+    """-> (ac_render_opts, inv_s on the device or None, near [N] or None, far [N] or None): the struct and the tensors its pointers refer to"""
+    inv_s_f, inv_s_t = _inv_s_arg(inv_s)
+    nm = fm = None
+    if near_far is not None:
+        nm, fm = _chk(near_far[0].reshape(-1), "near", (N,)), _chk(near_far[1].reshape(-1), "far", (N,))
+    op = L.ac_render_opts(N, int(num_steps), int(upsample_steps), float(bound), inv_s_f, float(cos_anneal_ratio),
+                          float(np.float32(FD_STEP * (1.0 - normal_epsilon_ratio))), int(has_noise), L.ptr(inv_s_t), L.ptr(nm), L.ptr(fm),
+                          PRECISIONS[precision], int(bool(skip_masked)), int(bool(opacity_only)))
+    return op, inv_s_t, nm, fm
+
+
+def _render(field, rays_o, rays_d, num_steps, upsample_steps, bound, inv_s, bg, noise, cos_anneal_ratio, normal_epsilon_ratio, extras,
+            debug_indices, out, events, warp, train_extras, near_far, precision, skip_masked, opacity_only, long, half=False, save_stencil=False):
+    rays_o, rays_d = _ray_args(rays_o, rays_d)
+    N = rays_o.shape[0]
+    dev = rays_o.device
+    T = num_steps + upsample_steps
+    nup = upsample_steps // 16
+    lin_z, lin_u = linspace_tables(num_steps, dev)
+    res, buf = _result_bufs(out, dev)
     o = L.ac_render_out()
     o.image = buf("image", (N, 3)).data_ptr()
     o.weights_sum = buf("weights_sum", (N,)).data_ptr()
@@ -266,40 +291,25 @@ def _render(field, rays_o, rays_d, num_steps, upsample_steps, bound, inv_s, bg, 
         bg = _chk(bg.reshape(-1, 3), "bg_color", (N, 3))
     if noise is not None:
         noise = _chk(noise.reshape(N, num_steps), "noise")
-    import numpy as np
-    inv_s_f, inv_s_t = _inv_s_arg(inv_s)
-    nm = fm = None
-    if near_far is not None:
-        nm, fm = _chk(near_far[0].reshape(-1), "near", (N,)), _chk(near_far[1].reshape(-1), "far", (N,))
-    op = L.ac_render_opts(N, int(num_steps), int(upsample_steps), float(bound), inv_s_f, float(cos_anneal_ratio),
-                          float(np.float32(0.005 * (1.0 - normal_epsilon_ratio))), int(noise is not None), L.ptr(inv_s_t), L.ptr(nm), L.ptr(fm),
-                          PRECISIONS[precision], int(bool(skip_masked) and warp is not None), int(bool(opacity_only)))
+    opts = _render_opts(N, num_steps, upsample_steps, bound, noise is not None, inv_s, cos_anneal_ratio, normal_epsilon_ratio, near_far, precision,
+                        skip_masked and warp is not None, opacity_only)
+    op = opts[0]
     if isinstance(res, RenderResult):
-        res.opts = (op, inv_s_t, nm, fm)
+        res.opts = opts
     st = L.current_stream(dev)
     h16 = field.half_table().data_ptr() if half else None          # (converted once per Field; before the events: not part of the render's time)
     if events is not None:          # (start, end) torch.cuda.Event pair around the render kernel only (bench.py roofline)
         events[0].record()
-    if half and warp is None:
-        L.check(L.lib().ac_render_rays_h16(C.byref(field.c), h16, C.byref(op), rays_o.data_ptr(), rays_d.data_ptr(), L.ptr(bg), L.ptr(noise),
-                                           lin_z.data_ptr(), lin_u.data_ptr(), C.byref(o), st), "render_rays_h16")
-    elif long and warp is None:
-        L.check(L.lib().ac_render_rays_long(C.byref(field.c), C.byref(op), rays_o.data_ptr(), rays_d.data_ptr(), L.ptr(bg), L.ptr(noise),
-                                            lin_z.data_ptr(), lin_u.data_ptr(), C.byref(o), st), "render_rays_long")
-    elif warp is None:
-        L.check(L.lib().ac_render_rays(C.byref(field.c), C.byref(op), rays_o.data_ptr(), rays_d.data_ptr(), L.ptr(bg), L.ptr(noise),
-                                       lin_z.data_ptr(), lin_u.data_ptr(), C.byref(o), st), "render_rays")
+    who = ("render_rays_long" if long else "render_rays") + ("_warped" if warp is not None else "") + ("_h16" if half else "")
+    args = (C.byref(field.c),) + ((h16,) if half else ()) + (C.byref(op), rays_o.data_ptr(), rays_d.data_ptr(), L.ptr(bg), L.ptr(noise),
+                                                              lin_z.data_ptr(), lin_u.data_ptr())
+    if warp is None:
+        L.check(getattr(L.lib(), "ac_" + who)(*args, C.byref(o), st), who)
     else:
         offs = (C.c_size_t * 6)()
         nbytes = L.lib().ac_render_rays_warped_scratch(N, T, offs)
         scratch = buf("_warp_scratch", (max(int(nbytes), 1),), torch.uint8)
-        entry, who = (L.lib().ac_render_rays_long_warped, "render_rays_long_warped") if long else (L.lib().ac_render_rays_warped, "render_rays_warped")
-        rest = (C.byref(op), rays_o.data_ptr(), rays_d.data_ptr(), L.ptr(bg), L.ptr(noise), lin_z.data_ptr(), lin_u.data_ptr(), C.byref(warp.c),
-                scratch.data_ptr(), int(nbytes), C.byref(o), st)
-        if half:
-            L.check(L.lib().ac_render_rays_warped_h16(C.byref(field.c), h16, *rest), "render_rays_warped_h16")
-        else:
-            L.check(entry(C.byref(field.c), *rest), who)
+        L.check(getattr(L.lib(), "ac_" + who)(*args, C.byref(warp.c), scratch.data_ptr(), int(nbytes), C.byref(o), st), who)
         res["can_mid"] = scratch[offs[3]:offs[3] + N * T * 12].view(_F32).view(N, T, 3)
         res["mask"] = scratch[offs[4]:offs[4] + N * T].view(N, T)
         if skip_masked and warp.accel is not None and upsample_steps > 0:      # rays the cell grids proved masked out (never sampled): the scratch's last segment
@@ -337,18 +347,10 @@ def render_rays_pair(field, rays_o, rays_d, noise2, num_steps=64, upsample_steps
 
 def _render_pair(field, rays_o, rays_d, noise2, num_steps, upsample_steps, bound, inv_s, bg2, cos_anneal_ratio, normal_epsilon_ratio, precision,
                  out, events, keep_weights, long, save_stencil):
-    rays_o = _chk(rays_o.reshape(-1, 3), "rays_o")
-    rays_d = _chk(rays_d.reshape(-1, 3), "rays_d")
+    rays_o, rays_d = _ray_args(rays_o, rays_d)
     N, dev, T = rays_o.shape[0], rays_o.device, num_steps + upsample_steps
     lin_z, lin_u = linspace_tables(num_steps, dev)
-    res = out if out is not None else RenderResult()
-
-    def buf(name, shape, dtype=_F32):
-        t = res.get(name)
-        if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
-            t = torch.empty(shape, dtype=dtype, device=dev)
-            res[name] = t
-        return t
+    res, buf = _result_bufs(out, dev)
     o = L.ac_render_out()
     per_ray = {"image": (2 * N, 3), "weights_sum": (2 * N,), "depth": (2 * N,), "normal_map": (2 * N, 3), "eik": (2 * N, 2)}
     for k, shp in per_ray.items():
@@ -369,10 +371,8 @@ def _render_pair(field, rays_o, rays_d, noise2, num_steps, upsample_steps, bound
     noise2 = _chk(noise2.reshape(2 * N, num_steps), "noise2")
     if bg2 is not None:
         bg2 = _chk(bg2.reshape(-1, 3), "bg2", (2 * N, 3))
-    import numpy as np
-    inv_s_f, inv_s_t = _inv_s_arg(inv_s)
-    op = L.ac_render_opts(N, int(num_steps), int(upsample_steps), float(bound), inv_s_f, float(cos_anneal_ratio),
-                          float(np.float32(0.005 * (1.0 - normal_epsilon_ratio))), 1, L.ptr(inv_s_t), None, None, PRECISIONS[precision], 0)
+    opts = _render_opts(N, num_steps, upsample_steps, bound, True, inv_s, cos_anneal_ratio, normal_epsilon_ratio, precision=precision)
+    op = opts[0]
     st = L.current_stream(dev)
     if events is not None:
         events[0].record()
@@ -389,7 +389,7 @@ def _render_pair(field, rays_o, rays_d, noise2, num_steps, upsample_steps, bound
         rb[k] = res[k]
     ra["eik_res"], rb["eik_res"] = er2[0], er2[1]
     ra["gradient_error"], rb["gradient_error"] = er2[0, 0], er2[1, 0]
-    rb.opts = ra.opts = (op, inv_s_t, None, None)
+    rb.opts = ra.opts = opts
     rb._keep = ra._keep = (noise2, bg2, res)
     return ra, rb
 
@@ -421,17 +421,13 @@ def sample_rays_long(field, rays_o, rays_d, num_steps=64, upsample_steps=64, bou
 
 
 def _sample(field, rays_o, rays_d, num_steps, upsample_steps, bound, noise, near_far, long):
-    rays_o = _chk(rays_o.reshape(-1, 3), "rays_o")
-    rays_d = _chk(rays_d.reshape(-1, 3), "rays_d")
+    rays_o, rays_d = _ray_args(rays_o, rays_d)
     N, dev = rays_o.shape[0], rays_o.device
     lin_z, lin_u = linspace_tables(num_steps, dev)
     if noise is not None:
         noise = _chk(noise.reshape(N, num_steps), "noise")
     z = torch.empty((N, num_steps + upsample_steps), dtype=_F32, device=dev)
-    nm = fm = None
-    if near_far is not None:
-        nm, fm = _chk(near_far[0].reshape(-1), "near", (N,)), _chk(near_far[1].reshape(-1), "far", (N,))
-    op = L.ac_render_opts(N, int(num_steps), int(upsample_steps), float(bound), 1.0, 1.0, 0.005, int(noise is not None), None, L.ptr(nm), L.ptr(fm), 0, 0)
+    op, _, nm, fm = _render_opts(N, num_steps, upsample_steps, bound, noise is not None, near_far=near_far)
     name = "sample_rays_long" if long else "sample_rays"
     L.check(getattr(L.lib(), "ac_" + name)(C.byref(field.c), C.byref(op), rays_o.data_ptr(), rays_d.data_ptr(), L.ptr(noise), lin_z.data_ptr(),
                                            lin_u.data_ptr(), z.data_ptr(), L.current_stream(dev)), name)
@@ -442,7 +438,6 @@ class WarpMesh:
     """the posed SMPL mesh of one frame + its per-vertex rest->scene transforms, on the device (ac_warp_mesh)"""
 
     def __init__(self, verts, faces, Ts, device, threshold=0.05, geo_threshold=0.05, use_mesh_guide=True, accel=True):
-        import numpy as np
 
         def dev(a, dtype):
             if not isinstance(a, torch.Tensor):
@@ -504,7 +499,6 @@ def warp_mesh_sequence(frames, faces, device, threshold=0.05, geo_threshold=0.05
     faces [F,3] are uploaded and checked ONCE.  With overlap (the default on a GPU) the NEXT frame's upload and structure build (ac_warp_accel_build: five small
     launches, one of them a single-workgroup sort) are queued on a side stream before the current frame is handed out, so they run beside the current frame's
     render instead of in front of the next one's; the consumer's stream waits for a frame's mesh through an event.  Same meshes, same pixels."""
-    import numpy as np
     dev = torch.device(device)
     fh = np.asarray(faces.cpu() if isinstance(faces, torch.Tensor) else faces)[:, :3]
     faces_d = torch.from_numpy(np.ascontiguousarray(fh)).to(device=dev, dtype=torch.int32).contiguous()
@@ -620,32 +614,18 @@ class _RenderCore(torch.autograd.Function):
         z_vals, pts, sdf, sdf16, gradient, color, eik_res, rays_o, rays_d, bg, feat7 = ctx.saved_tensors
         if not ctx.has_bg:
             bg = None
-        N, T = z_vals.shape
-        dev = rays_o.device
-        c = lambda g: None if g is None else g.contiguous().to(_F32)
-        g_image, g_wsum, g_depth, g_nmap, g_eik = c(g_image), c(g_wsum), c(g_depth), c(g_nmap), c(g_eik)
         table = ctx.table
         # The table gradient is RETURNED to autograd like every other gradient (torch.autograd.grad, backward(inputs=...), hooks and DDP-style
         # reducers see it).  ACCUMULATE_TABLE_GRAD_IN_PLACE (opt-in, off by default) adds it straight into an existing contiguous fp32 table.grad
         # and returns None for that input instead: it saves one 49 MB zero-fill + add per backward pass for callers that only ever read .grad.
         in_place = ACCUMULATE_TABLE_GRAD_IN_PLACE and table.grad is not None and table.grad.is_contiguous() and table.grad.dtype == _F32
         g_table = table.grad if in_place else torch.zeros_like(table)       # accumulated into, like hash_encode_backward (hashgrid.py:61-68)
-        g_sdf_p = torch.empty(64 * 36 + 16 * 64 + 16, dtype=_F32, device=dev)
-        g_col_p = torch.empty(64 * 32 + 64 * 64 + 16 * 64, dtype=_F32, device=dev)
-        g_invs = torch.empty(N, dtype=_F32, device=dev)
-        sv = L.ac_core_saved(z_vals.data_ptr(), pts.data_ptr(), sdf.data_ptr(), sdf16.data_ptr(), gradient.data_ptr(), color.data_ptr(),
-                             eik_res[1:].data_ptr(), feat7.data_ptr() if ctx.has_feat else None, ctx.posed[0].data_ptr() if ctx.posed else None)
-        upg = L.ac_core_upstream(L.ptr(g_image), L.ptr(g_wsum), L.ptr(g_depth), L.ptr(g_nmap), L.ptr(g_eik), 0, 0)
-        gr = L.ac_core_grads(g_table.data_ptr(), g_sdf_p.data_ptr(), g_col_p.data_ptr(), g_invs.data_ptr())
-        scratch, need = core_scratch(field, N, T, dev)
-        op = ctx.opts[0]
-        vd = _viewdir_args(field, rays_d, N, T, sv, gr)
-        L.check(L.lib().ac_render_core_backward(C.byref(field.c), C.byref(op), rays_o.data_ptr(), rays_d.data_ptr(), L.ptr(bg), C.byref(sv), C.byref(upg),
-                                                C.byref(gr), scratch.data_ptr(), need, L.current_stream(dev)), "render_core_backward")
+        saved = (z_vals, pts, sdf, sdf16, gradient, color, eik_res[1:], feat7 if ctx.has_feat else None, ctx.posed[0] if ctx.posed else None)
+        g_sdf_p, g_col_p, g_invs, g_sh = _core_backward(field, ctx.opts[0], saved, rays_o, rays_d, bg, (g_image, g_wsum, g_depth, g_nmap, g_eik), g_table)
         gW1b = g_sdf_p[:64 * 36].view(64, 36)
         g_Wc1 = g_col_p[:2048].view(64, 32)[:, :21]
-        if vd is not None:
-            g_Wc1 = join_viewdir_grad(g_Wc1, _viewdir_weight_grad(vd, N, T))
+        if g_sh is not None:
+            g_Wc1 = join_viewdir_grad(g_Wc1, g_sh)
         return (None if in_place else g_table, gW1b[:, :35], gW1b[:, 35], g_sdf_p[64 * 36:64 * 36 + 1024].view(16, 64), g_sdf_p[64 * 36 + 1024:],
                 g_Wc1, g_col_p[2048:6144].view(64, 64), g_col_p[6144:].view(16, 64)[:3],
                 g_invs.sum().reshape(ctx.inv_s_shape), None, None, None, None, None)
@@ -804,33 +784,38 @@ def render_core_backward(field, opts, out, rays_o, rays_d, bg, g_image, g_wsum, 
     EFFECTIVE matrices.
     split = (level, torch.cuda.Stream): the scatter completes the table gradient of levels >= level first and orders that stream behind exactly that
     (ac_core_grads.side_stream / split_level): work enqueued there afterwards (the all-reduce of that slice) overlaps the rest of the backward."""
-    z_vals = out["z_vals"]
-    N, T = z_vals.shape
+    # eik_groups = (group_rays, res [G,2] from eikonal_groups): the launch holds G patches whose eikonal terms are separate ratios; g_eik is then [G]
+    if eik_groups is not None and g_eik is not None and g_eik.numel() != eik_groups[1].shape[0]:
+        raise RuntimeError("render_core_backward: one g_eik per group of rays")
+    saved = (out["z_vals"], out["pts"], out["sdf"], out["sdf_out16"], out["gradient"], out["color"],
+             out["eik_res"][1:] if eik_groups is None else eik_groups[1][:, 1:], out.get("feat7") if hasattr(out, "get") else None, None)
+    g = _core_backward(field, opts[0], saved, rays_o, rays_d, bg, (g_image, g_wsum, g_depth, g_nmap, g_eik), g_table, split=split,
+                       eik_group_rays=None if eik_groups is None else eik_groups[0])
+    return g if g[3] is not None else g[:3]                                            # (+ d Wc1_sh [64,16] for a field with view directions)
+
+
+def _core_backward(field, op, saved, rays_o, rays_d, bg, upstream, g_table, split=None, eik_group_rays=None):
+    """THE ac_render_core_backward call.  saved = the forward's (z_vals, pts, sdf, sdf_out16, gradient, color, eikonal denominator(s), feat7 | None, posed
+    mask | None); upstream = (g_image, g_wsum, g_depth, g_nmap, g_eik), tensors or None; eik_group_rays: patches of that many rays with one eikonal ratio
+    each.  The table gradient is accumulated into g_table.  -> (g_sdf_params, g_color_params, g_inv_s_per_ray, g_Wc1_sh | None), as render_core_backward."""
+    N, T = saved[0].shape
     dev = rays_o.device
-    c = lambda g: None if g is None else g.contiguous().to(_F32)
-    g_image, g_wsum, g_depth, g_nmap, g_eik = c(g_image), c(g_wsum), c(g_depth), c(g_nmap), c(g_eik)
     g_sdf_p = torch.empty(64 * 36 + 16 * 64 + 16, dtype=_F32, device=dev)
     g_col_p = torch.empty(64 * 32 + 64 * 64 + 16 * 64, dtype=_F32, device=dev)
     g_invs = torch.empty(N, dtype=_F32, device=dev)
-    # eik_groups = (group_rays, res [G,2] from eikonal_groups): the launch holds G patches whose eikonal terms are separate ratios; g_eik is then [G]
-    den_ptr = out["eik_res"][1:].data_ptr() if eik_groups is None else eik_groups[1][:, 1:].data_ptr()
-    sv = L.ac_core_saved(z_vals.data_ptr(), out["pts"].data_ptr(), out["sdf"].data_ptr(), out["sdf_out16"].data_ptr(), out["gradient"].data_ptr(),
-                         out["color"].data_ptr(), den_ptr, L.ptr(out.get("feat7") if hasattr(out, "get") else None))
-    upg = L.ac_core_upstream(L.ptr(g_image), L.ptr(g_wsum), L.ptr(g_depth), L.ptr(g_nmap), L.ptr(g_eik), 0, 0)
-    if eik_groups is not None:
-        if g_eik is not None and g_eik.numel() != eik_groups[1].shape[0]:
-            raise RuntimeError("render_core_backward: one g_eik per group of rays")
-        upg.eik_group_rays, upg.eik_den_stride = int(eik_groups[0]), 2
+    sv = L.ac_core_saved(*[L.ptr(t) for t in saved])
+    upstream = [None if g is None else g.contiguous().to(_F32) for g in upstream]        # (held until the launch is enqueued)
+    upg = L.ac_core_upstream(*[L.ptr(g) for g in upstream], 0, 0)
+    if eik_group_rays is not None:
+        upg.eik_group_rays, upg.eik_den_stride = int(eik_group_rays), 2
     gr = L.ac_core_grads(g_table.data_ptr(), g_sdf_p.data_ptr(), g_col_p.data_ptr(), g_invs.data_ptr())
     if split is not None:
         gr.split_level, gr.side_stream = int(split[0]), int(split[1].cuda_stream)
     scratch, need = core_scratch(field, N, T, dev)
     vd = _viewdir_args(field, rays_d, N, T, sv, gr)
-    L.check(L.lib().ac_render_core_backward(C.byref(field.c), C.byref(opts[0]), rays_o.data_ptr(), rays_d.data_ptr(), L.ptr(bg), C.byref(sv), C.byref(upg),
+    L.check(L.lib().ac_render_core_backward(C.byref(field.c), C.byref(op), rays_o.data_ptr(), rays_d.data_ptr(), L.ptr(bg), C.byref(sv), C.byref(upg),
                                             C.byref(gr), scratch.data_ptr(), need, L.current_stream(dev)), "render_core_backward")
-    if vd is not None:
-        return g_sdf_p, g_col_p, g_invs, _viewdir_weight_grad(vd, N, T)            # (+ d Wc1_sh [64,16] for a field with view directions)
-    return g_sdf_p, g_col_p, g_invs
+    return g_sdf_p, g_col_p, g_invs, _viewdir_weight_grad(vd, N, T)
 
 
 class _PackedShading(torch.autograd.Function):
@@ -902,7 +887,6 @@ class _SdfStencil(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_out, g_grad):
-        import numpy as np
         x, table, W1, b1, W2, b2 = ctx.saved_tensors
         offsets, pls, H, bound, eps = ctx.cfg
         dev = x.device
