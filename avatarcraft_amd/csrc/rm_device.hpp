@@ -181,7 +181,11 @@ __device__ __forceinline__ float pcg_first_float(uint64_t initstate, uint64_t in
 // the words in use, so that neither pass touches the empty ones) = position k
 // of t' = t + clamp(t dt_gamma, dt_min, dt_max) is a sample; far - near <= the cube's diagonal = 1024 dt_min bounds k -- and the writing pass replays the
 // recurrence (four instructions per position, no voxel, no look-up) and emits at the set bits: the same positions by construction, the same bits.
-// A sample at k >= 1024 (never seen: it needs a ray along the exact diagonal) raises the ray's overflow flag and the writer walks that ray again.
+// A sample at k >= 1024 raises the ray's overflow flag and the writer walks that ray again.  It takes a ray along the cube's exact diagonal whose last
+// positions are occupied: from (-2, -2, -2) bound along (1, 1, 1) / sqrt 3 the walk spans exactly 1024 dt_min (bound <= 1: every step is dt_min), and with
+// only the far corner's voxels occupied its last sample is position 1024 -- the grids corner33 (bound 1), corner64 and corner100 (bound 0.5) of tests/marcher_cases.py.
+// tests/test_gpu_marcher_edges.py::test_recorder_overflow_walks_the_ray_again runs that branch against the oracle (the condition k >= 1024 is asserted on
+// the oracle's samples); no camera ray of the other tests reaches it.
 constexpr int RM_REC_WORDS = 32;
 constexpr int RM_EDGE_MAX = 1026;            // the face table serves grids up to H = 1024
 struct RayRecorder {                       // one lane = one ray.  Only the words that hold a sample are written (and later read): wmask names them

@@ -22,7 +22,12 @@ def _round_up(n, align):
 @torch.no_grad()
 def march_rays_train(rays_o, rays_d, bound, density_grid, mean_density, iter_density, step_counter=None, mean_count=-1, perturb=False,
                      align=-1, force_all_rays=False):
-    """-> xyzs [M,3], dirs [M,3], deltas [M], rays [N,3] (index, offset, count)"""
+    """-> xyzs [M,3], dirs [M,3], deltas [M], rays [N,3] (index, offset, count)
+
+    Precondition: step_counter, if given, is ZERO on entry (every caller in instant_nsr.py zeroes its row first).  The native operator accumulates -- it
+    writes `rays` from row counter[1] and samples from counter[0] -- while this wrapper, like the reference's, allocates `rays` as [N,3] and sizes the sample
+    buffers for one call: a non-zero counter would make it write out of bounds.  A caller that accumulates over several calls sizes the buffers itself and
+    goes through `_backend.march_rays_train`."""
     o, d = _rays(rays_o), _rays(rays_d)
     n_rays, grid_res, dev = o.shape[0], density_grid.shape[0], o.device
     budgeted = (not force_all_rays) and mean_count > 0

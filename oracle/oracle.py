@@ -249,12 +249,22 @@ def sh_encode_backward_typed(grad, inputs, degree, dy_dx):
 
 # ------------------------------------------------------------------ raymarching
 def march_rays_train(rays_o, rays_d, grid, mean_density, bound, M=None, perturb=0, counter=None):
+    """counter: None, or the (samples, rays) counter earlier calls left; returned advanced (an int32 array of two is advanced in place, anything else is copied).
+    The operator accumulates: this call's rows of `rays` are counter[1] .. counter[1] + N - 1 (the rows before them stay zero) and its samples start at
+    counter[0], so `rays` has counter[1] + N rows and, without M, the sample buffers counter[0] + 1024 N."""
     rays_o = _f(rays_o).reshape(-1, 3); rays_d = _f(rays_d).reshape(-1, 3); grid = _f(grid)
     N, H = rays_o.shape[0], grid.shape[0]
-    M = N * 1024 if M is None else M
+    if counter is None:
+        counter = np.zeros(2, np.int32)
+    elif not (isinstance(counter, np.ndarray) and counter.dtype == np.int32 and counter.flags.c_contiguous and counter.flags.writeable):
+        counter = np.array(counter, np.int32)
+    if counter.shape != (2,):
+        raise ValueError("march_rays_train: counter must hold two integers")
+    if counter[0] < 0 or counter[1] < 0:
+        raise ValueError("march_rays_train: negative counter")
+    M = int(counter[0]) + N * 1024 if M is None else M
     xyzs = np.zeros((M, 3), np.float32); dirs = np.zeros((M, 3), np.float32); deltas = np.zeros(M, np.float32)
-    rays = np.zeros((N, 3), np.int32)
-    counter = np.zeros(2, np.int32) if counter is None else counter
+    rays = np.zeros((int(counter[1]) + N, 3), np.int32)
     lib().orc_march_rays_train(_p(rays_o), _p(rays_d), _p(grid), C.c_float(mean_density), C.c_int(0), C.c_float(bound),
                                C.c_uint32(N), C.c_uint32(H), C.c_uint32(M), _p(xyzs), _p(dirs), _p(deltas),
                                _p(rays, i32p), _p(counter, i32p), C.c_uint32(int(perturb)))
