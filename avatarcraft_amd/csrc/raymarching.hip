@@ -126,15 +126,13 @@ __global__ __launch_bounds__(256) void composite_train_fwd_kernel(const float *_
         return;
     }
     const float *s = sigmas + offset, *c = rgbs + (size_t)offset * 3;
-    float T = 1.0f, r = 0, g = 0, b = 0;
-    for (uint32_t step = 0; step < num_steps; ++step) {
-        if (T < 1e-4f) break;
-        const float alpha = s[step], w = alpha * T;
-        r += w * c[3 * step]; g += w * c[3 * step + 1]; b += w * c[3 * step + 2];
-        T *= 1.0f - alpha;
-    }
+    float rgb[3] = { 0, 0, 0 };
+    const float T = rm_composite_train(num_steps, rgb, [&](uint32_t step, float (&v)[3]) {
+        v[0] = c[3 * step]; v[1] = c[3 * step + 1]; v[2] = c[3 * step + 2];
+        return s[step];
+    });
     weights_sum[index] = 1.0f - T;
-    image[index * 3] = r; image[index * 3 + 1] = g; image[index * 3 + 2] = b;
+    image[index * 3] = rgb[0]; image[index * 3 + 1] = rgb[1]; image[index * 3 + 2] = rgb[2];
 }
 
 __global__ __launch_bounds__(256) void composite_train_bwd_kernel(const float *__restrict__ grad_weights_sum, const float *__restrict__ grad,
@@ -201,28 +199,20 @@ __global__ __launch_bounds__(256) void composite_rays_kernel(uint32_t n_alive, u
     const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= n_alive) return;
     const int index = rays_alive[n];
-    float t = rays_t[n];
     const float *s = sigmas + (size_t)n * n_step, *c = rgbs + (size_t)n * n_step * 3;
     const float *dl = deltas + (size_t)n * n_step * 2, *nr = normals + (size_t)n * n_step * 3;
-    float ws = weights_sum[index], d = depth[index];
-    float r = image[index * 3], g = image[index * 3 + 1], b = image[index * 3 + 2];
-    float nx = normal_map[index * 3], ny = normal_map[index * 3 + 1], nz = normal_map[index * 3 + 2];
+    RayAcc acc{ weights_sum[index], depth[index], image[index * 3], image[index * 3 + 1], image[index * 3 + 2],
+                normal_map[index * 3], normal_map[index * 3 + 1], normal_map[index * 3 + 2], rays_t[n] };
     uint32_t step = 0;
     while (step < n_step) {
         if (dl[0] == 0) break;
-        const float alpha = s[0], T = 1 - ws, w = alpha * T;
-        ws += w;
-        t += dl[1];
-        d += w * t;
-        r += w * c[0]; g += w * c[1]; b += w * c[2];
-        nx += w * nr[0]; ny += w * nr[1]; nz += w * nr[2];
-        if ((double)T < 1e-2) break;
+        if (rm_composite_step(acc, s[0], dl[1], c[0], c[1], c[2], nr[0], nr[1], nr[2])) break;
         s++; c += 3; dl += 2; nr += 3; step++;
     }
-    rays_t[n] = (step < n_step) ? -1.0f : t;
-    weights_sum[index] = ws; depth[index] = d;
-    image[index * 3] = r; image[index * 3 + 1] = g; image[index * 3 + 2] = b;
-    normal_map[index * 3] = nx; normal_map[index * 3 + 1] = ny; normal_map[index * 3 + 2] = nz;
+    rays_t[n] = (step < n_step) ? -1.0f : acc.t;
+    weights_sum[index] = acc.ws; depth[index] = acc.dep;
+    image[index * 3] = acc.r; image[index * 3 + 1] = acc.g; image[index * 3 + 2] = acc.b;
+    normal_map[index * 3] = acc.nx; normal_map[index * 3 + 1] = acc.ny; normal_map[index * 3 + 2] = acc.nz;
 }
 
 __global__ __launch_bounds__(256) void alive_flags_kernel(uint32_t n_alive, const float *__restrict__ rays_t_old, int32_t *__restrict__ flags)

@@ -1,6 +1,6 @@
 // avatarcraft_amd/csrc/rm_device.hpp -- device-side pieces of the occupancy-grid ray marcher (raymarching/src/raymarching.cu:56-222, 497-599), shared by
-// the stand-alone marching operators (raymarching.hip) and the fused occupancy renderer (sdf_train.hip): step sizes, the voxel lookup, the skip to the next
-// voxel, the slab test, pcg32.  Anonymous namespace: each translation unit gets its own copy.
+// the stand-alone marching operators (raymarching.hip) and the fused occupancy renderers (render_occupancy.hip): step sizes, the voxel lookup, the skip to the
+// next voxel, the slab test, pcg32, the compositors' per-sample arithmetic.  Anonymous namespace: each translation unit gets its own copy.
 #pragma once
 #include "ac_common.hpp"
 #include "ac_devmath.hpp"
@@ -70,6 +70,12 @@ __device__ __forceinline__ float rm_edge(const RayCtx &c, uint32_t m)
 {
     const float hm1 = (float)(c.H - 1);
     return (((float)m) / hm1 * 2 - 1) * c.bound;
+}
+// the table, filled by the whole workgroup; the caller synchronises before the walk reads it
+__device__ __forceinline__ void rm_edge_table(float *dst, uint32_t H, float bound)
+{
+    RayCtx c0{}; c0.H = H; c0.bound = bound;
+    for (uint32_t m = threadIdx.x; m <= H; m += blockDim.x) dst[m] = rm_edge(c0, m);
 }
 __device__ __forceinline__ float rm_skip_target_tab(const RayCtx &c, const float *edge, float t, float x, float y, float z, int nx, int ny, int nz)
 {
@@ -229,6 +235,37 @@ __device__ __forceinline__ float ray_t0(const RayCtx &c, float near, uint32_t n,
     float t0 = near;
     if (perturb) t0 += c.dt_min * pcg_first_float((uint64_t)n, 1);
     return t0;
+}
+
+// ---- the compositors' arithmetic, one copy each for the stand-alone operators and the fused launches ------------------------------------------------
+// kernel_composite_rays (raymarching.cu:611-707), one sample: the accumulators as the operator keeps them between rounds (t = rays_t), the sample's alpha,
+// its step dl1 = deltas[1], colour and normal.  Returns true when the ray stops behind this sample (T < 1e-2, compared in double like the reference's literal).
+struct RayAcc { float ws, dep, r, g, b, nx, ny, nz, t; };
+__device__ __forceinline__ bool rm_composite_step(RayAcc &s, float alpha, float dl1, float cr, float cg, float cb, float n0, float n1, float n2)
+{
+    const float T = 1 - s.ws, w = alpha * T;
+    s.ws += w;
+    s.t += dl1;
+    s.dep += w * s.t;
+    s.r += w * cr; s.g += w * cg; s.b += w * cb;
+    s.nx += w * n0; s.ny += w * n1; s.nz += w * n2;
+    return (double)T < 1e-2;
+}
+// kernel_composite_rays_train_forward (raymarching.cu:232-301), the loop over one ray's n packed samples: acc[c] += alpha T v[c] for NC channels on the same
+// weights, alpha = sample(k, v).  Returns the transmittance left (weights_sum = 1 - T).
+template <int NC, class Sample>
+__device__ __forceinline__ float rm_composite_train(uint32_t n, float (&acc)[NC], Sample &&sample)
+{
+    float T = 1.0f;
+    for (uint32_t k = 0; k < n; ++k) {
+        if (T < 1e-4f) break;
+        float v[NC];
+        const float alpha = sample(k, v), w = alpha * T;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) acc[c] += w * v[c];
+        T *= 1.0f - alpha;
+    }
+    return T;
 }
 
 }  // namespace

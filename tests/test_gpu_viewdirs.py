@@ -206,3 +206,42 @@ def test_sds_step_posed_render_and_occupancy_render_take_the_model():
     o = occ.render(ro_t[None], rd_t[None], num_steps=64, bound=1.6, upsample_steps=64, bg_color=None, cos_anneal_ratio=1.0, normal_epsilon_ratio=0.0, perturb=True)
     o["rgb"].sum().backward()
     assert float(occ.color_net[0].weight_v.grad[:, 3:19].abs().max()) > 0
+
+
+@pytest.mark.parametrize("side,n_rays", [(7, 37), (32, 1000)])
+def test_occupancy_inference_forms_agree_with_view_directions(side, n_rays):
+    """the view-direction branch of the shared field body (csrc/field_tile.hpp) in every inference form of the occupancy-grid render: the phased launch -- which
+    run_cuda only picks from 2048 rays on, so the 1024-ray render above never reaches it -- the one-wave-per-group launch, and ac_field_samples between
+    march_rays and composite_rays run as one round of 1024 steps give the same bits.  37 rays leave the last wave's group ragged; 1000 rays leave the last
+    16-sample tile and the last 64-ray wave ragged."""
+    from avatarcraft_amd import nsr_ops, raymarching
+    from avatarcraft_amd.instant_nsr import near_far_from_bound
+    occ = viewdirs_net(load_golden("viewdirs.npz"), cuda_ray=True)
+    with torch.no_grad():
+        occ.deviation_net.variance.fill_(float(np.log(512.0) / 10.0))          # the sharpness the density grid is built for
+    occ.update_extra_state(1.6)
+    ro, rd = make_rays(side, side, dist=1.8, f=0.75 * side)
+    o, d = torch.from_numpy(ro[:n_rays]).to(DEV), torch.from_numpy(rd[:n_rays]).to(DEV)
+    field, inv_s = occ._field(), occ.forward_variance()
+    assert field.has_viewdirs
+    args = (field, o, d, occ.density_grid, occ.mean_density, 1.6, 0.005, inv_s, 0.7)
+    keys = ("weights_sum", "depth", "image", "normal_map")
+    f0 = nsr_ops.occupancy_launch_failures()                                   # (counted over the life of the process: other tests time barriers out on purpose)
+    a = nsr_ops.render_rays_occupancy(*args, phased=False)
+    for rep in range(2):                                                       # (twice: the second call runs on the scratch the first one re-armed)
+        b = nsr_ops.render_rays_occupancy(*args, phased=True)
+        for k in keys:
+            assert torch.equal(a[k], b[k]), (k, rep)
+    # the stand-alone operators, one round
+    near, far = near_far_from_bound(o, d, 1.6, type='cube')
+    near, far = near.reshape(-1).contiguous(), far.reshape(-1).contiguous()
+    alive = torch.arange(n_rays, dtype=torch.int32, device=DEV); rt = near.clone()
+    xyzs, dirs, deltas = raymarching.march_rays(n_rays, 1024, alive, rt, o, d, 1.6, occ.density_grid, occ.mean_density, near, far, -1, False)
+    fs = nsr_ops.field_samples(field, xyzs, dirs, deltas, 1.6, 0.005, inv_s, 0.7)
+    c = dict(weights_sum=torch.zeros(n_rays, device=DEV), depth=torch.zeros(n_rays, device=DEV), image=torch.zeros(n_rays, 3, device=DEV),
+             normal_map=torch.zeros(n_rays, 3, device=DEV))
+    raymarching.composite_rays(n_rays, 1024, alive, rt, fs["alpha"], fs["rgb"], fs["normal"], deltas, *(c[k] for k in keys))
+    for k in keys:
+        assert torch.equal(a[k], c[k]), k
+    assert float(a["weights_sum"].max()) > 0.5                                 # (the view shows the body)
+    assert nsr_ops.occupancy_launch_failures() == f0                           # no barrier of these launches timed out
