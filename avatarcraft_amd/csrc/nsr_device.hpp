@@ -76,9 +76,15 @@ static_assert(OFF_WAVE % 4 == 0 && OFF_RWAVE % 4 == 0 && WAVE_SLAB % 4 == 0, "16
 #ifdef AC_PROFILE
 #define AC_T0() unsigned long long t_prof_ = __builtin_amdgcn_s_memtime(); const unsigned long long ray_r0_ = __builtin_amdgcn_s_memrealtime()
 #define AC_TICK(SLOT) { const unsigned long long t2_ = __builtin_amdgcn_s_memtime(); prof_acc[SLOT] += t2_ - t_prof_; t_prof_ = t2_; }
+// item boundaries of the fused renderer: slot 0 = end of an item's last tile -> first instruction of the wave's next item (publish or pixel write, ticket,
+// item decode), slot 1 = a continuing item's wait for its predecessor's flag + the load of the ray's state
+#define AC_BND_MARK() prof_bm = __builtin_amdgcn_s_memtime()
+#define AC_BND_TICK(SLOT) { const unsigned long long t3_ = __builtin_amdgcn_s_memtime(); prof_bnd[SLOT] += t3_ - prof_bm; prof_bm = t3_; }
 #else
 #define AC_T0()
 #define AC_TICK(SLOT)
+#define AC_BND_MARK()
+#define AC_BND_TICK(SLOT)
 #endif
 
 struct LevelRec { float scale; uint32_t my, mz, offset, mask, hashed, wsize, pad; };
@@ -102,16 +108,15 @@ struct RenderArgs {
     int skip_masked;            // ac_render_opts.skip_masked (MODE_FINAL only)
     int opacity_only;           // ac_render_opts.opacity_only: no colour network (rgb = 0)
     int perturb;
-    unsigned long long *prof;   // AC_PROFILE builds only: [n_waves][10]: 8 per-phase s_memtime counters, whole-wave s_memtime and s_memrealtime (100 MHz)
+    unsigned long long *prof;   // AC_PROFILE builds only: [n_waves][10]: 8 per-phase s_memtime counters, whole-wave s_memtime and s_memrealtime (100 MHz); [n_rays * 10 + ray] per-ray wall time; [n_rays * 11 + 2 wave + k] the boundary slots (AC_BND_TICK)
     // posed-space rendering (render_can=False) only: see ac_render_rays_warped
     const float *near_m, *far_m;   // [N] mesh-guided range (+-inf where the ray misses the body) or NULL
     const float *ext_pts;          // MODE_UPSAMPLE: warped coarse points [N,T0,3]; MODE_FINAL: warped mid points [N,T,3]
     const uint8_t *mask;           // MODE_FINAL: [N,T] alpha mask
-    uint32_t *ray_counter;         // [8 XCDs][8 segments] work counters (zeroed before the launch): waves fetch their next (ray, segment) instead of owning fixed rays
-    uint32_t *seg_flags;           // [N] number of finished segments of each ray (zeroed before the launch), or NULL when seg_n == 1
-    float *seg_state;              // [N][SEG_STATE] what a ray's next segment continues from: z values + running sums (library scratch)
-    uint64_t seg_cb;               // first tile of segment s in bits 4s .. 4s+3, s = 0 .. seg_n
-    int seg_n;                     // segments per ray (1 .. 8)
+    uint32_t *ray_counter;         // [8 XCDs] ticket counters, 8 words apart (zero before the launch): ticket t of an XCD takes item t of its work list
+    uint32_t *seg_flags;           // [N] number of finished items of each ray, tagged with the launch generation, or NULL (one item per ray)
+    float *seg_state;              // [N][SEG_STATE] what a ray's next item continues from: z values + running sums (library scratch)
+    const uint32_t *work_list;     // MODE_FULL: the work lists of the launch (render_worklist.hpp: 16 header words, then two words per item); NULL: one item per ray, in closed form
     // pair launches (ac_render_rays_pair): the same pair_n rays twice, n_rays = 2 * pair_n work items handed out as a0 b0 a1 b1 ...; copy a = rows
     // [0, pair_n), copy b = rows [pair_n, 2 pair_n) of noise, bg and the per-ray outputs; rays_o / rays_d / near_m / far_m have pair_n rows.  0 = off.
     int pair_n;

@@ -26,16 +26,16 @@
 //
 // Numerics contract: see ac_devmath.hpp and DESIGN.md; every value produced here is bit-identical
 // to oracle/ac_oracle.c:orc_render_rays on the same inputs.
+#include <algorithm>
 #include <atomic>
 #include <map>
 #include <mutex>
+#include <vector>
 #include "nsr_device.hpp"
+#include "render_worklist.hpp"      // (AC_XCD_CHUNK, AC_WORKLIST_POLICY and the XCD chunking live there, with the builder of the work lists)
 
 namespace {
 
-#ifndef AC_XCD_CHUNK
-#define AC_XCD_CHUNK 512
-#endif
 // a workgroup's waves on blocks of 8 consecutive rays (dynamic or static): 16 - 21 % slower than one ticket per wave -- profiles/r06_experiments.txt section 4c
 // EX = false: a launch that wants the per-ray results only (image, weights_sum, depth, normal_map, eik): none of the optional per-sample outputs is
 // compiled in, which takes their sixteen pointers (and the address arithmetic on them) out of the register budget of the tile loop
@@ -195,17 +195,58 @@ static int fill_render_args(RenderArgs &a, const ac_field *field, const ac_rende
     return AC_OK;
 }
 
-// Per-launch scratch of the dynamic hand-out: [8 XCDs][8 segments] work counters (256 B) | finished-workgroup counter | flags [N] u32 | state [N][SEG_STATE] f32.
+// Per-launch scratch of the dynamic hand-out: [8 XCDs] ticket counters, 32 bytes apart (256 B) | finished-workgroup counter | timed-out hand-offs |
+// flags [N] u32 | state [N][SEG_STATE] f32.
 // One slot per (device, stream), grown to the largest batch it has served and kept for the life of the process: launches of one stream run in order, so a
 // slot is never in use by two launches at once, however many streams render concurrently.
-#ifndef AC_RAY_SEGMENTS
-#define AC_RAY_SEGMENTS 4           // segments a ray is cut into (1 = whole rays as work items, rounds 1 - 2; at most 8)
-#endif
-struct SegSlot { char *p; size_t bytes; uint32_t gen; uint64_t last_use; };
+// The slot also keeps the device copies of the work lists (render_worklist.hpp) of the last few launch shapes it has served -- a view rendered in batches
+// alternates between two (the last batch differs) --: a list is built and uploaded once, on the launch's stream, from a pinned buffer that belongs to the
+// entry and is never written again; both buffers are freed only after the upload's event has completed.
+struct WorkList { int n_rays, tiles, pair_n, waves; uint32_t *dev, *host; hipEvent_t uploaded; uint64_t last_use; };
+constexpr size_t WORKLISTS_PER_SLOT = 4;
+struct SegSlot { char *p; size_t bytes; uint32_t gen; uint64_t last_use; std::vector<WorkList> lists; };
 constexpr size_t SEG_POOL_MAX = 32;        // (device, stream) slots kept; beyond that the least recently used one is freed (stream churn must not grow device memory without bound)
 static std::mutex g_seg_mu;
 static std::map<std::pair<int, hipStream_t>, SegSlot> g_seg_pool;
 static uint64_t g_seg_clock = 0;
+static void free_worklist(WorkList &w)
+{
+    if (w.uploaded) { (void)hipEventSynchronize(w.uploaded); (void)hipEventDestroy(w.uploaded); }       // no copy can still be reading the host buffer
+    if (w.dev) (void)hipFree(w.dev);
+    if (w.host) (void)hipHostFree(w.host);
+    w.dev = w.host = nullptr; w.uploaded = nullptr;
+}
+// the device copy of the work lists of this launch shape on the slot of (current device, stream); NULL: out of memory.  Call after seg_scratch (which makes the slot).
+static const uint32_t *seg_worklist(int n_rays, int tiles, int pair_n, int waves, hipStream_t stream)
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0) dev = 0;
+    std::lock_guard<std::mutex> lock(g_seg_mu);
+    auto it = g_seg_pool.find(std::make_pair(dev, stream));
+    if (it == g_seg_pool.end()) return nullptr;
+    std::vector<WorkList> &ls = it->second.lists;
+    for (WorkList &w : ls)
+        if (w.n_rays == n_rays && w.tiles == tiles && w.pair_n == pair_n && w.waves == waves) { w.last_use = ++g_seg_clock; return w.dev; }
+    if (ls.size() >= WORKLISTS_PER_SLOT) {
+        size_t v = 0;
+        for (size_t i = 1; i < ls.size(); ++i) if (ls[i].last_use < ls[v].last_use) v = i;
+        free_worklist(ls[v]);                                            // (hipFree waits for the device: no launch can still be reading the list)
+        ls.erase(ls.begin() + (long)v);
+    }
+    std::vector<uint32_t> words;
+    ac_worklist::build(n_rays, tiles, pair_n, waves, AC_WORKLIST_POLICY, words);
+    WorkList w{ n_rays, tiles, pair_n, waves, nullptr, nullptr, nullptr, ++g_seg_clock };
+    const size_t bytes = words.size() * sizeof(uint32_t);
+    if (hipMalloc(reinterpret_cast<void **>(&w.dev), bytes) != hipSuccess) { w.dev = nullptr; (void)hipGetLastError(); return nullptr; }
+    if (hipHostMalloc(reinterpret_cast<void **>(&w.host), bytes, hipHostMallocDefault) != hipSuccess) { w.host = nullptr; (void)hipGetLastError(); free_worklist(w); return nullptr; }
+    std::copy(words.begin(), words.end(), w.host);
+    if (hipEventCreateWithFlags(&w.uploaded, hipEventDisableTiming) != hipSuccess) { w.uploaded = nullptr; free_worklist(w); return nullptr; }
+    if (hipMemcpyAsync(w.dev, w.host, bytes, hipMemcpyHostToDevice, stream) != hipSuccess || hipEventRecord(w.uploaded, stream) != hipSuccess) {
+        (void)hipStreamSynchronize(stream); free_worklist(w); return nullptr;
+    }
+    ls.push_back(w);
+    return w.dev;
+}
 // -> the slot's memory and the generation of this launch (1 .. 2^28 - 1): a slot is zeroed when it is allocated; after that every launch leaves its
 // counters at zero (the kernel's last workgroup re-arms them) and tags its per-ray flags with its generation, so nothing is cleared between launches
 static char *seg_scratch(size_t need, uint32_t &gen, hipStream_t stream)
@@ -220,6 +261,7 @@ static char *seg_scratch(size_t need, uint32_t &gen, hipStream_t stream)
         auto victim = pool.begin();
         for (auto it = pool.begin(); it != pool.end(); ++it) if (it->second.last_use < victim->second.last_use) victim = it;
         if (victim->second.p) (void)hipFree(victim->second.p);
+        for (WorkList &w : victim->second.lists) free_worklist(w);
         pool.erase(victim);
     }
     SegSlot &sl = pool[key];
@@ -272,27 +314,27 @@ static void launch_render_p(const RenderArgs &a, hipStream_t stream)
     ac::allow_dynamic_lds(seen, reinterpret_cast<const void *>(kernel), lds_bytes);
     RenderArgs b = a;
     {
-        // segments: the tiles of a ray in seg_n nearly equal runs; the sampling stage (about 1.6 tiles' worth of time) rides with the first
+        // MODE_FULL: a ray's tiles are cut into items by the work lists of render_worklist.hpp (policy AC_WORKLIST_POLICY), whatever the tile count
+        // (posed space: the two halves stay with whole rays and decode their tickets in closed form, no list -- their ray count changes from frame to
+        //  frame; with skip_masked most tiles of the final pass are skipped anyway, and segments measured 8 % slower there)
         const int nt = (a.T0 + 16 * a.nup) / 16;
-        // (posed space: the final pass stays with whole rays -- with skip_masked most of its tiles are skipped anyway, and segments measured 8 % slower there)
-        int sn = (MODE != MODE_FULL) ? 1 : (nt < AC_RAY_SEGMENTS ? nt : AC_RAY_SEGMENTS);
-        if (sn < 1) sn = 1;
-        b.seg_n = sn; b.seg_cb = 0;
-        for (int q = 0; q <= sn; ++q) b.seg_cb |= (uint64_t)((nt * q) / sn) << (4 * q);
-        const size_t N = (size_t)a.n_rays, head = 512, flags = (N * 4 + 255) & ~(size_t)255;      // head: [0, 256) work counters | [256] finished workgroups
-        const size_t need = head + (sn > 1 ? flags + N * SEG_STATE * sizeof(float) : 0);
+        const bool listed = MODE == MODE_FULL;
+        const size_t N = (size_t)a.n_rays, head = 512, flags = (N * 4 + 255) & ~(size_t)255;      // head: [0, 256) ticket counters | [256] finished workgroups | [260] timeouts
+        const size_t need = head + (listed ? flags + N * SEG_STATE * sizeof(float) : 0);
         uint32_t gen = 0;
         char *sc = seg_scratch(need, gen, stream);
+        const int cus = (int)ac::cu_count();
+        if (blocks > cus) blocks = cus;
+        blocks = (blocks + 7) & ~7;                                      // every XCD gets the same number of workgroups
+        b.work_list = (listed && sc) ? seg_worklist(a.n_rays, nt, a.pair_n, (blocks / 8) * WAVES_PER_BLOCK, stream) : nullptr;
+        if (listed && !b.work_list) sc = nullptr;
         b.ray_counter = reinterpret_cast<uint32_t *>(sc);
         b.done_counter = sc ? reinterpret_cast<uint32_t *>(sc + 256) : nullptr;
         b.handoff_timeouts = sc ? reinterpret_cast<uint32_t *>(sc + 260) : nullptr;      // (never re-armed: counts over the life of the slot)
         b.gen = gen;
         b.eik_red = (MODE == MODE_UPSAMPLE) ? nullptr : a.out.eik_reduced;
-        b.seg_flags = sn > 1 ? reinterpret_cast<uint32_t *>(sc + head) : nullptr;
-        b.seg_state = sn > 1 ? reinterpret_cast<float *>(sc + head + flags) : nullptr;
-        const int cus = (int)ac::cu_count();
-        if (blocks > cus) blocks = cus;
-        blocks = (blocks + 7) & ~7;                                      // every XCD gets the same number of workgroups
+        b.seg_flags = (listed && sc) ? reinterpret_cast<uint32_t *>(sc + head) : nullptr;
+        b.seg_state = (listed && sc) ? reinterpret_cast<float *>(sc + head + flags) : nullptr;
         if (!sc) blocks = 0;                                             // (the scratch could not be allocated: an empty grid is a launch error the caller reports)
     }
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(BLOCK), lds_bytes, stream, b);

@@ -47,6 +47,7 @@ __global__ __launch_bounds__(BLOCK) void AC_RENDER_KERNEL(const RenderArgs a)
 #ifdef AC_PROFILE
     unsigned long long prof_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const unsigned long long prof_t0 = __builtin_amdgcn_s_memtime(), prof_r0 = __builtin_amdgcn_s_memrealtime();
+    unsigned long long prof_bnd[2] = {0, 0}, prof_bm = prof_t0;
 #endif
     // XCD-aware order: workgroup b runs on XCD b % 8 (observed dispatch rule; speed only): give every XCD a contiguous
     // slab of rays so that neighbouring pixels share one L2 instead of eight
@@ -66,36 +67,51 @@ __global__ __launch_bounds__(BLOCK) void AC_RENDER_KERNEL(const RenderArgs a)
     // (only launches that fill the device: a small batch -- a posed frame's tail, a unit test -- has no lock-step to break and would only pay the delay)
     if (a.n_rays >= 2048)
         for (int k_ = 0; k_ < AC_START_STAGGER * wave; ++k_) __builtin_amdgcn_s_sleep(64);
-    // Work items are (ray, segment) pairs fetched one at a time from per-XCD counters.  A ray is cut into seg_n segments of the tile loop (segment 0 =
-    // the sampling stage + the first tiles); a wave that finishes a segment leaves the ray's z values and running sums in seg_state and raises the ray's
-    // flag, whichever wave of the XCD fetches the next segment of that ray continues the SAME sequential arithmetic from there (bit-identical results).
-    // Every wave works through all segment-0 items of its XCD first, then the segment-1 items, ...: a 4096-ray launch is only two rays per wave slot,
-    // and with whole rays as work items it ended with the slowest pair (per-wave busy time: mean 664 us, max 802 us); now the last items are a
-    // quarter-ray long.  A wave never waits for an item nobody has started: segment s + 1 of a ray is handed out only after every segment-s item
-    // of the XCD has been fetched by a running wave.
+    // Work items are runs of tiles of one ray, fetched one at a time: every XCD has ONE ticket counter, and ticket t takes item t of the XCD's work list
+    // (render_worklist.hpp: built on the host, read here from its device copy; which ray, tiles [c_begin, c_end), the item's number within its ray,
+    // whether the sampling stage rides on it, whether it writes the pixel).  A wave that finishes an item which is not the ray's last leaves the ray's z
+    // values and running sums in seg_state and raises the ray's flag; whichever wave of the XCD takes the ray's next item continues the SAME sequential
+    // arithmetic from there (bit-identical results for every list).  A 4096-ray launch is only two rays per wave slot, and with whole rays as work items
+    // it ended with the slowest pair (per-wave busy time: mean 664 us, max 802 us); how the rays are cut decides how the launch ends.
+    // A wave never waits for an item nobody holds: a list is a linear extension of "item k of a ray before item k + 1", so the predecessor of an item has a
+    // smaller ticket, and tickets are only ever taken by resident waves (one workgroup per compute unit: the whole grid is resident).
     // The batch is dealt to the XCDs in chunks of AC_XCD_CHUNK consecutive rays (two image rows of a 256-wide view: neighbouring rays share grid
     // cells in the XCD's L2), chunk c to XCD c % 8; a batch of up to 8 chunks is cut into eight contiguous parts.  Large batches stay balanced
-    // that way when the body covers only some rows of the image (posed frames, skip_masked).
-    const int xper = ((a.n_rays + 7) / 8 + 7) & ~7, xchunk = xper < AC_XCD_CHUNK ? xper : AC_XCD_CHUNK, xcd = blockIdx.x & 7;
-    const int seg_n = (MODE == MODE_UPSAMPLE) ? 1 : a.seg_n;
-    for (int seg = 0; seg < seg_n; ++seg) {
-    const int c_begin = (MODE == MODE_UPSAMPLE) ? 0 : (int)((a.seg_cb >> (4 * seg)) & 15u), c_end = (MODE == MODE_UPSAMPLE) ? 0 : (int)((a.seg_cb >> (4 * seg + 4)) & 15u);
-    const bool seg_first = seg == 0, seg_last = seg + 1 == seg_n;
+    // that way when the body covers only some rows of the image (posed frames, skip_masked).  (The lists are built with the same chunking.)
+    // The two posed-space halves (MODE_UPSAMPLE, MODE_FINAL) keep one item per ray and no list: their tickets are decoded in closed form.
+    constexpr bool LISTED = MODE == MODE_FULL;
+    const int xchunk = ac_worklist::xcd_chunk(a.n_rays), xcd = blockIdx.x & 7;
+    uint32_t *const tk_counter = a.ray_counter + xcd * 8;
+    // (the list is read-only for the whole launch and its words are fetched at wave-uniform indices: scalar loads through the constant address space)
+    const __attribute__((address_space(4))) uint32_t *const wl = (const __attribute__((address_space(4))) uint32_t *)a.work_list;
+    uint32_t wl_cnt = 0;
+    const __attribute__((address_space(4))) uint32_t *wl_items = wl;
+    if constexpr (LISTED) { wl_cnt = wl[ac_worklist::XCDS + xcd]; wl_items = wl + ac_worklist::HEADER_WORDS + 2 * (size_t)wl[xcd]; }
+#define AC_TAKE_TICKET(TK) { uint32_t v_ = 0; if (lane == 0) v_ = atomicAdd(tk_counter, 1u); TK = (uint32_t)__builtin_amdgcn_readfirstlane((int)v_); }
+#define AC_FETCH_ITEM(TK, W0, W1) { W0 = 0u; W1 = 0u; if (TK < wl_cnt) { W0 = wl_items[2 * (size_t)TK]; W1 = wl_items[2 * (size_t)TK + 1]; } }
+    uint32_t tk = 0, it_ray = 0, it_meta = 0;              // the wave's next ticket and (LISTED) its item, all wave-uniform
+    if constexpr (LISTED) { AC_TAKE_TICKET(tk) AC_FETCH_ITEM(tk, it_ray, it_meta) }
     for (;;) {
-        int ray = 0;
-        if (lane == 0) ray = (int)atomicAdd(a.ray_counter + xcd * 8 + seg, 1u);
-        ray = __builtin_amdgcn_readfirstlane(ray);
-        {
-            const int k = ray / xchunk, base = (k * 8 + xcd) * xchunk;
-            if (base >= a.n_rays) break;
-            ray = base + (ray - k * xchunk);
-            if (ray >= a.n_rays) continue;
+        int ray = 0, c_begin = 0, c_end = MAXT / 16, seq = 0;
+        bool seg_first = true, seg_last = true;
+        bool tk_ahead = false;                                       // LISTED: this item has already taken the wave's next ticket (see the tile loop)
+        if constexpr (LISTED) {
+            if (tk >= wl_cnt) break;
+            ray = (int)it_ray;
+            c_begin = ac_worklist::meta_begin(it_meta); c_end = ac_worklist::meta_end(it_meta); seq = ac_worklist::meta_seq(it_meta);
+            seg_first = (it_meta & ac_worklist::META_SAMPLING) != 0u; seg_last = (it_meta & ac_worklist::META_LAST) != 0u;
+        } else {
+            AC_TAKE_TICKET(tk)
+            ray = ac_worklist::ticket_to_work(a.n_rays, xchunk, xcd, (int)tk);
+            if (ray == ac_worklist::TICKET_END) break;
+            if (ray == ac_worklist::TICKET_GAP) continue;
         }
         int rin = ray;                                               // row of this ray in rays_o / rays_d / near_m / far_m
-        if (a.pair_n) { rin = ray >> 1; ray = rin + ((ray & 1) ? a.pair_n : 0); }      // a0 b0 a1 b1 ...: the two copies of a ray meet in their XCD's L2
+        if (LISTED && a.pair_n && ray >= a.pair_n) rin = ray - a.pair_n;      // (pair launches: the list hands the copies out as a0 b0 a1 b1 ...: the two copies of a ray meet in their XCD's L2)
         (void)bid;                                                   // (used by the static hand-out, removed; dropping the remap changes the kernel's register setup)
         const int exr = ray - a.ex_from;                             // row in the per-sample outputs (pair launches keep them for copy b only)
         const bool ex_on = exr >= 0;
+        AC_BND_TICK(0)
         AC_T0();
         const float ox = a.rays_o[3 * rin], oy = a.rays_o[3 * rin + 1], oz = a.rays_o[3 * rin + 2];
         const float dx = a.rays_d[3 * rin], dy = a.rays_d[3 * rin + 1], dz = a.rays_d[3 * rin + 2];
@@ -312,11 +328,12 @@ __global__ __launch_bounds__(BLOCK) void AC_RENDER_KERNEL(const RenderArgs a)
         // registers: they are touched once per tile by one lane (lane 15, which holds the tile totals of the row scans), and ten registers less at the
         // peak of the stencil / MLP code is the difference between ~30 and ~10 spilled registers.  Slots: 1 s_w 2..4 rgb 5..7 normal 8 depth 9 10 eikonal
         float *const accs = zs0 + SLAB_ACC;
-        // use_viewdirs: layer-1 bias of the colour network for THIS ray's direction, in the wave's slab: formed by the ray's first segment (16 sh values + 64
-        // dot products of 16 terms), handed to the later ones with the segment state (64 floats: one store / one load per lane instead of the prologue again)
+        // use_viewdirs: layer-1 bias of the colour network for THIS ray's direction, in the wave's slab: formed by the ray's first item (16 sh values + 64
+        // dot products of 16 terms), handed to the later ones with the ray's state (64 floats: one store / one load per lane instead of the prologue again)
         if constexpr (SH && MODE != MODE_UPSAMPLE) { if (seg_first && !a.opacity_only) ray_sh_bias(zs0 + SLAB_SHB, a.Wsh, dx, dy, dz, lane); }
         if (!seg_first) {
-            // continue a ray another wave (of this XCD) started: wait until its previous segment is published, then take over z and the running sums.
+            AC_BND_MARK();
+            // continue a ray another wave (of this XCD) started: wait until its previous item is published, then take over z and the running sums.
             // All accesses to seg_flags / seg_state are agent-scope atomics = served by the XCD's L2, past the (incoherent) vector L1 caches.
             int timed_out = 0;
             if (lane == 0) {
@@ -324,8 +341,8 @@ __global__ __launch_bounds__(BLOCK) void AC_RENDER_KERNEL(const RenderArgs a)
                 // the flag of THIS launch: generation in the upper bits (a value left by an earlier launch in the same slot never matches)
                 for (;;) {
                     const uint32_t f = __hip_atomic_load(a.seg_flags + ray, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (((f >> 4) == a.gen && (f & 15u) >= (uint32_t)seg) || spins >= (1 << 21)) break;
-                    __builtin_amdgcn_s_sleep(8); ++spins;       // (bounded: ~1 s; a ray's previous segment takes ~100 us)
+                    if (((f >> 4) == a.gen && (f & 15u) >= (uint32_t)seq) || spins >= (1 << 21)) break;
+                    __builtin_amdgcn_s_sleep(8); ++spins;       // (bounded: ~1 s; a ray's previous item takes ~100 us)
                 }
                 timed_out = spins >= (1 << 21);
                 if (timed_out && a.handoff_timeouts) atomicAdd(a.handoff_timeouts, 1u);     // the host can ask (ac_render_handoff_timeouts): a lost hand-off is an ERROR, not only a NaN pixel
@@ -349,11 +366,12 @@ __global__ __launch_bounds__(BLOCK) void AC_RENDER_KERNEL(const RenderArgs a)
             cT = lane_bcast(cv, 0);
             if (lane < 16) accs[lane] = cv;
             if constexpr (SH) zs0[SLAB_SHB + lane] = __uint_as_float(__hip_atomic_load(st + MAXT + 16 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-            if (timed_out) {                                     // never observed; if the previous segment was not published in ~1 s the ray's pixel must not
+            if (timed_out) {                                     // never observed; if the previous item was not published in ~1 s the ray's pixel must not
                 cT = __builtin_nanf("");                         // look like a result: NaN, which the callers' finite checks and every parity test catch
                 if (lane < 16) accs[lane] = cT;
             }
             wave_sync();
+            AC_BND_TICK(1)
         }
         const float bxe = a.eps;
         const int c_hi = c_end < T / 16 ? c_end : T / 16;
@@ -380,6 +398,7 @@ __global__ __launch_bounds__(BLOCK) void AC_RENDER_KERNEL(const RenderArgs a)
             }
             f32x4 oc = { 0.0f, 0.0f, 0.0f, 0.0f };
             float gr[3] = { 0.0f, 0.0f, 0.0f };
+            uint32_t tk_v = 0;                                   // (LISTED, last tile of the item: the wave's next ticket on its way)
             if (!skip) {
             float fe0[4][2];
             encode_stencil<AC_RENDER_H16>(lds, fsl, fc, lane, px, py, pz, bxe, fe0);
@@ -456,6 +475,23 @@ __global__ __launch_bounds__(BLOCK) void AC_RENDER_KERNEL(const RenderArgs a)
             }
             }
             AC_TICK(4)
+            // The wave's NEXT ticket is taken here, in the item's last tile behind its SDF evaluations, and consumed a few microseconds later, behind the
+            // colour network and the compositing of the same tile -- so neither the ticket's round trip to the counter nor the fetch of the next item
+            // stands between two items.  Not earlier: a wave that takes a ticket commits the hand-out, and at the head of the tile (~35 us before it can
+            // start the item) that cost the launch 1.5 % -- near its end another wave is free first (profiles/worklist_experiments.txt).
+            // A wave holds at most ONE ticket ahead, and only while it is working on an item it needs nobody for any more (whatever this item waited for
+            // was consumed before its first tile).  So every wait in the launch still points from a ticket to a SMALLER one, and the holder of the
+            // smallest unfinished ticket is always running it: no cycle, the same no-deadlock argument as with tickets taken at the boundary.  (A
+            // ticket past the end of the list obliges to nothing.)
+            if constexpr (LISTED) {
+                if (c + 1 == c_hi && lane == 0) {
+                    // (the counter's address enters through an opaque vector-register copy: on a wave-uniform address LLVM's atomic optimizer rewrites the add
+                    //  into its one-lane-per-wave form, which waits for the returned value right behind the instruction -- the wait this is here to move)
+                    __attribute__((address_space(1))) uint32_t *tk_p = (__attribute__((address_space(1))) uint32_t *)tk_counter;
+                    asm volatile("" : "+v"(tk_p));
+                    tk_v = __hip_atomic_fetch_add(tk_p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
             const float gx = gr[0], gy = gr[1], gz = gr[2];        // every lane of a sample holds the same finite-difference gradient
             const FdNormal nrm = fd_normal(gx, gy, gz);
             const float gn = nrm.gn, nx = nrm.nx, ny = nrm.ny, nz = nrm.nz;
@@ -496,6 +532,9 @@ __global__ __launch_bounds__(BLOCK) void AC_RENDER_KERNEL(const RenderArgs a)
                 }
             }
             AC_TICK(6)
+            if constexpr (LISTED) {
+                if (c + 1 == c_hi) { tk = (uint32_t)__builtin_amdgcn_readfirstlane((int)tk_v); AC_FETCH_ITEM(tk, it_ray, it_meta) tk_ahead = true; }
+            }
             if (g == 0) {
                 const size_t si = (size_t)exr * T + i;
                 if (EX && ex_on && a.out.z_vals) a.out.z_vals[si] = zi;
@@ -512,8 +551,9 @@ __global__ __launch_bounds__(BLOCK) void AC_RENDER_KERNEL(const RenderArgs a)
                 *reinterpret_cast<f32x4 *>(a.out.sdf_out16 + ((size_t)exr * T + i) * 16 + 4 * g_x) = oc;
             }
         }
+        AC_BND_MARK();
         if (!seg_last) {
-            // hand the ray to its next segment: z values (once), the running sums, then the flag -- in that order (the stores are complete in L2
+            // hand the ray to its next item: z values (once), the running sums, then the flag -- in that order (the stores are complete in L2
             // before the flag leaves: s_waitcnt vmcnt(0); the reader's loads are issued after it has seen the flag)
             uint32_t *st = reinterpret_cast<uint32_t *>(a.seg_state + (size_t)ray * SEG_STATE);
             if (MODE != MODE_FINAL && seg_first)
@@ -527,8 +567,9 @@ __global__ __launch_bounds__(BLOCK) void AC_RENDER_KERNEL(const RenderArgs a)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every lane's state stores have left the wave ...
             wave_sync();
             // ... before the flag store is issued (relaxed, agent scope: see the taker's side for why no release / acquire pair is used)
-            if (lane == 0) __hip_atomic_store(a.seg_flags + ray, (a.gen << 4) | (uint32_t)(seg + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (lane == 0) __hip_atomic_store(a.seg_flags + ray, (a.gen << 4) | (uint32_t)(seq + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             wave_sync();
+            if constexpr (LISTED) { if (!tk_ahead) { AC_TAKE_TICKET(tk) AC_FETCH_ITEM(tk, it_ray, it_meta) } }       // (an item without tiles: the builder makes none)
             continue;
         }
         wave_sync();
@@ -547,8 +588,10 @@ __global__ __launch_bounds__(BLOCK) void AC_RENDER_KERNEL(const RenderArgs a)
 #ifdef AC_PROFILE               // per-ray wall time (100 MHz ticks) behind the per-wave records: [n_rays * 10 + ray]
         if (a.prof && lane == 0) a.prof[(size_t)a.n_rays * 10 + ray] = __builtin_amdgcn_s_memrealtime() - ray_r0_;
 #endif
+        if constexpr (LISTED) { if (!tk_ahead) { AC_TAKE_TICKET(tk) AC_FETCH_ITEM(tk, it_ray, it_meta) } }
     }
-    }
+#undef AC_TAKE_TICKET
+#undef AC_FETCH_ITEM
     // ---- epilogue: the last workgroup to finish reduces gradient_error and re-arms the slot's work counters (RenderArgs::done_counter) --------------------
     // (the arguments used here are read from the kernel-argument segment again, behind an opaque barrier: kept in scalar registers from the start of the kernel
     //  they cost the work loops two spilled vector registers)
@@ -598,6 +641,7 @@ __global__ __launch_bounds__(BLOCK) void AC_RENDER_KERNEL(const RenderArgs a)
     }
 #ifdef AC_PROFILE
     if (a.prof && lane == 0) { const int w_ = blockIdx.x * WAVES_PER_BLOCK + wave; for (int i = 0; i < 8; ++i) a.prof[w_ * 10 + i] = prof_acc[i];
+        a.prof[(size_t)a.n_rays * 11 + 2 * w_] = prof_bnd[0]; a.prof[(size_t)a.n_rays * 11 + 2 * w_ + 1] = prof_bnd[1];
         a.prof[w_ * 10 + 8] = __builtin_amdgcn_s_memtime() - prof_t0; a.prof[w_ * 10 + 9] = __builtin_amdgcn_s_memrealtime() - prof_r0; }   // shader clock vs 100 MHz
 #endif
 }
