@@ -5,6 +5,9 @@
 //                 on the HOST) -> u = -sdf -> PyMCubes marching_cubes(u, threshold) -> vertices scaled to world units.
 //                 Here: ac_field_sdf_grid (grid coordinates formed in the kernel from the three axis tables, the volume stays on the device) and
 //                 ac_marching_cubes_count / _emit (classify -> scan -> emit, shared-edge vertex indexing, no atomics: a deterministic mesh).
+//   mesh attributes  nothing in the reference: utils.save_mesh(vert, face, ...) (stylize.py:263-269) writes geometry only.  Here: ac_mesh_vertex_attrs -- every
+//                 vertex of the marching-cubes buffer through a few Newton steps along the finite-difference gradient onto the level set, then the normal and
+//                 the colour network at the final position (mesh_attrs_kernel: the seven-point stencil of field_tile.hpp on tiles of 16 vertices).
 //   density grid  NeRFRenderer.update_extra_state (:303-356): forward_sdf on the 129^3 grid -> logistic density -> zero pad + 2^3 max pool ->
 //                 maximum(grid * decay, new) -> mean.  Here two launches (ac_density_grid_update): the density of every grid point on the x-tiles of
 //                 ac_field_sdf_grid into a scratch volume, then one streaming pass that pools, merges into the running grid in place and forms the mean.
@@ -18,7 +21,7 @@
 // with the normal towards u <= iso = out of the body for u = -sdf.  PyMCubes is not in this image: "unpinned vs PyMCubes, pinned vs the definition".
 // Order of the output (what makes the mesh reproducible bit for bit, and equal to the CPU oracle's serial loop): vertices by owning grid point (linear
 // index, z fastest) then by axis x, y, z; triangles by cell (linear index) then by table position.
-#include "nsr_device.hpp"
+#include "field_tile.hpp"
 
 #define AC_MC_CONST static __constant__ const
 #include "ac_mc_table.hpp"
@@ -280,6 +283,90 @@ __global__ __launch_bounds__(256) void mc_triangles_kernel(const uint32_t *__res
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- attributes of a mesh's vertices
+// What a coloured export needs per vertex and marching cubes does not give: a position ON the level set (the linear zero crossing of a grid edge is off it by
+// up to 8.6e-3 on the golden field at 24^3), the field's normal and the colour network there.  Shaped like field_samples_kernel (render_occupancy.hip): a wave owns
+// tiles of 16 vertices, lane (n, g) works on vertex n of the tile, the four lanes of a vertex hold the same position.  Per vertex, all in fp32:
+//   p = clamp((float)vertex); at most `steps` times: stencil at p -> s, g; r = s - target; |r| <= tol: stop; gg = (gx gx + gy gy) + gz gz; not gg > 1e-12:
+//   stop (status 2); q = clamp(p - (r / gg) g); max_k |q_k - p0_k| > max_move: stop (status 3); p = q.  Then normal and colour at the final p.
+// The status is the reason the steps ended: 0 the tolerance test of a step was met, 1 all `steps` steps were taken (the value at the final p is in `sdf`).
+// One copy of the stencil code serves the steps AND the final evaluation: iteration `it` evaluates at p, then the lanes still moving step; when no lane of the
+// wave moved (or it == steps: no step is allowed) that evaluation was at every lane's final position and the loop ends -- at most steps + 1 trips, the count
+// wave-uniform, stopped lanes ride along at their p.  No atomics, no waits on other waves.
+struct MeshAttrArgs {
+    const double *verts;        // [V,3] as mc_vertices_kernel writes them
+    const float *dirs;          // [V,3] or NULL: -normal
+    uint32_t V;
+    int steps;
+    float target, tol, max_move;
+    float *pos, *nrm, *rgb, *sdf;      // [V,3] [V,3] [V,3] | NULL, [V] | NULL
+    uint8_t *status;                   // [V] | NULL
+};
+
+__global__ __launch_bounds__(FBLOCK) void mesh_attrs_kernel(const RenderArgs a, const MeshAttrArgs m)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    fill_lds_sdf(lds, a);
+    if (m.rgb) fill_lds_color(lds, a);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
+    float *fsl = lds + OFF_WAVE + wave * FE_SLAB;
+    const FieldCtx fc = make_ctx(a);
+    const float bound = a.bound, eps = a.eps;
+    const uint32_t ntiles = (m.V + 15) / 16;
+    for (uint32_t tile = blockIdx.x * FW + wave; tile < ntiles; tile += gridDim.x * FW) {
+        const uint32_t b = tile * 16 + n, bb = b < m.V ? b : m.V - 1;
+        const double *vx = m.verts + 3 * (size_t)bb;
+        float px = clampf((float)vx[0], -bound, bound), py = clampf((float)vx[1], -bound, bound), pz = clampf((float)vx[2], -bound, bound);
+        const float p0x = px, p0y = py, p0z = pz;
+        bool moving = true;
+        uint32_t st = 1u;
+        f32x4 o16;
+        float gr[3], s;
+#pragma unroll 1
+        for (int it = 0;; ++it) {
+            float fe0[4][2];
+            encode_stencil(lds, fsl, fc, lane, px, py, pz, eps, fe0);
+            fd_forward(lds, fsl, lane, px, py, pz, eps, bound, fe0, o16, gr);
+            s = __shfl(o16[0], n);                                               // output 0 lives in the lanes g == 0
+            wave_sync();                                                         // (every lane is done with the feature slab)
+            bool moved = false;
+            if (moving && it < m.steps) {
+                const float r = s - m.target;
+                const float gg = (gr[0] * gr[0] + gr[1] * gr[1]) + gr[2] * gr[2];
+                if (__builtin_fabsf(r) <= m.tol) { moving = false; st = 0u; }
+                else if (!(gg > 1e-12f)) { moving = false; st = 2u; }
+                else {
+                    const float t = r / gg;
+                    const float qx = clampf(px - t * gr[0], -bound, bound), qy = clampf(py - t * gr[1], -bound, bound), qz = clampf(pz - t * gr[2], -bound, bound);
+                    const float dm = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(qx - p0x), __builtin_fabsf(qy - p0y)), __builtin_fabsf(qz - p0z));
+                    if (dm > m.max_move) { moving = false; st = 3u; }
+                    else { px = qx; py = qy; pz = qz; moved = true; }
+                }
+            }
+            if (it >= m.steps || __ballot(moved) == 0ull) break;               // (wave-uniform)
+        }
+        const FdNormal fn = fd_normal(gr[0], gr[1], gr[2]);
+        float rgb[3] = { 0.0f, 0.0f, 0.0f };
+        if (m.rgb) {                                                             // (uniform over the launch)
+            if (a.Wsh) {
+                float dx = -fn.nx, dy = -fn.ny, dz = -fn.nz;
+                if (m.dirs) { const float *d = m.dirs + 3 * (size_t)bb; dx = d[0]; dy = d[1]; dz = d[2]; }
+                sample_sh_bias(fsl, a.Wsh, dx, dy, dz, lane);
+                color_tile(lds, lane, px, py, pz, fn.nx, fn.ny, fn.nz, o16, rgb, fsl + 4 * lane, 256);
+            } else color_tile(lds, lane, px, py, pz, fn.nx, fn.ny, fn.nz, o16, rgb);
+        }
+        if (b < m.V && g == 0) {
+            m.pos[3 * (size_t)b] = px; m.pos[3 * (size_t)b + 1] = py; m.pos[3 * (size_t)b + 2] = pz;
+            m.nrm[3 * (size_t)b] = fn.nx; m.nrm[3 * (size_t)b + 1] = fn.ny; m.nrm[3 * (size_t)b + 2] = fn.nz;
+            if (m.rgb) { m.rgb[3 * (size_t)b] = rgb[0]; m.rgb[3 * (size_t)b + 1] = rgb[1]; m.rgb[3 * (size_t)b + 2] = rgb[2]; }
+            if (m.sdf) m.sdf[b] = s;
+            if (m.status) m.status[b] = (uint8_t)st;
+        }
+        wave_sync();
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------- density grid of the ray marcher
 // Round 6: two launches instead of one.  Round 5 gave every workgroup a brick of 16 x 8 x 8 outputs PLUS the one-point halo the 2^3 max pool reads
 // (17 x 9 x 9 = 1377 evaluations for 1024 outputs, 3.58 M for the 2.15 M points of the 129^3 grid) and cut them into tiles of 16 consecutive evaluations of
@@ -467,6 +554,29 @@ AC_API int ac_marching_cubes_emit(const float *volume, uint32_t nx, uint32_t ny,
         hipLaunchKernelGGL(mc_triangles_kernel, dim3(l.nblk), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t *>(sc + l.bits), d, cnt4, bsum, boff, voff,
                            triangles, n_triangles);
     return ac::check_launch("marching_cubes_emit");
+}
+
+AC_API int ac_mesh_vertex_attrs(const ac_field *field, const double *vertices, uint32_t V, const float *dirs, const ac_mesh_attr_opts *opts,
+                                float *positions, float *normals, float *rgb, float *sdf, uint8_t *status, ac_stream_t stream)
+{
+    if (!opts) { ac::set_error("mesh_vertex_attrs: NULL opts"); return AC_ERR_BAD_ARG; }
+    if (opts->refine_steps < 0 || opts->refine_steps > 16 || !(opts->max_move > 0.0f) || !(opts->fd_eps > 0.0f) || !(opts->bound > 0.0f)) {
+        ac::set_error("mesh_vertex_attrs: refine_steps outside 0..16, or max_move, fd_eps or bound not > 0"); return AC_ERR_BAD_ARG;
+    }
+    if (V == 0) return AC_OK;
+    if (!vertices || !positions || !normals) { ac::set_error("mesh_vertex_attrs: NULL buffer"); return AC_ERR_BAD_ARG; }
+    if (V > 0xffffffe0u) { ac::set_error("mesh_vertex_attrs: more than 2^32 - 32 vertices"); return AC_ERR_BAD_ARG; }
+    RenderArgs a{};
+    if (int rc = prep_args(a, field, opts->bound, opts->fd_eps)) return rc;
+    MeshAttrArgs m{ vertices, dirs, V, opts->refine_steps, opts->target_sdf, opts->tol, opts->max_move, positions, normals, rgb, sdf, status };
+    const size_t lds_bytes = FWD_LDS_FLOATS * sizeof(float);
+    static uint64_t seen = 0;
+    ac::allow_dynamic_lds(seen, reinterpret_cast<const void *>(mesh_attrs_kernel), lds_bytes);
+    uint32_t blocks = ((V + 15) / 16 + FW - 1) / FW;              // persistent, one workgroup per CU (140 KB of LDS), like ac_field_samples
+    const uint32_t cus = ac::cu_count();
+    if (blocks > cus) blocks = cus;
+    hipLaunchKernelGGL(mesh_attrs_kernel, dim3(blocks), dim3(FBLOCK), lds_bytes, (hipStream_t)stream, a, m);
+    return ac::check_launch("mesh_vertex_attrs");
 }
 
 static uint32_t dp_blocks(uint32_t H)

@@ -1,6 +1,7 @@
 """The two inference drivers of the reference as functions (no file I/O, no option parsing): the main loops of render_canonical.py:38-99
 (360-degree views of the canonical avatar, body and head rings) and render_warp.py:40-125 (SMPL-driven animation / shape
-interpolation through the posed-space renderer), plus the camera of the latter, SMPLDataset.gen_rays_pose (utils/SMPLDataset.py:86-103)."""
+interpolation through the posed-space renderer), plus the camera of the latter, SMPLDataset.gen_rays_pose (utils/SMPLDataset.py:86-103); and the one
+driver that does write a file: export_mesh, the coloured form of the trainer's extract_geometry + save_mesh (stylize.py:263-269)."""
 import numpy as np
 import torch
 
@@ -132,3 +133,12 @@ def render_animation(net, body_model, cam_pose, poses=None, render_type="animate
             if table_dtype is not None and prev_table is not None:
                 net.render_table_dtype = prev_table
         yield i, rgb.reshape(resolution, resolution, 3)
+
+
+def export_mesh(net, path, bound=NSR_BOUND, resolution=512, **kw):
+    """the canonical avatar as a binary PLY with per-vertex normals and colours: net.extract_colored_mesh(bound, resolution, **kw) -> geometry.save_ply;
+    the reference's counterpart (extract_geometry(NSR_BOUND, 512) + save_mesh, stylize.py:263-269) writes vertices and faces only.  Returns the mesh dict."""
+    from .geometry import save_ply
+    mesh = net.extract_colored_mesh(bound, resolution, **kw)
+    save_ply(path, mesh["vertices"], mesh["triangles"], normals=mesh["normals"], colors=mesh.get("colors"))
+    return mesh

@@ -81,3 +81,29 @@ def marching_tetrahedra(u, level=0.0):
         return torch.stack([pid // (Y * Z), (pid // Z) % Y, pid % Z], 1).float()
     verts = coords(pa) + t[:, None] * (coords(pb) - coords(pa))
     return verts, faces
+
+
+def save_ply(path, vertices, triangles, normals=None, colors=None):
+    """binary little-endian PLY: float32 x y z [nx ny nz], uchar red green blue (round(clip(c, 0, 1) * 255)), faces as `list uchar int vertex_indices`.
+    vertices [V,3], triangles [F,3], normals [V,3], colors [V,3] in [0, 1]: numpy arrays or tensors on any device."""
+    import numpy as np
+    arr = lambda a, dt: np.ascontiguousarray((a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)), dtype=dt)
+    v, t = arr(vertices, "<f4").reshape(-1, 3), arr(triangles, "<i4").reshape(-1, 3)
+    cols, props = [("xyz", "<f4", (3,))], ["float x", "float y", "float z"]
+    if normals is not None:
+        cols.append(("n", "<f4", (3,))); props += ["float nx", "float ny", "float nz"]
+    if colors is not None:
+        cols.append(("rgb", "u1", (3,))); props += ["uchar red", "uchar green", "uchar blue"]
+    vert = np.empty(len(v), dtype=cols)
+    vert["xyz"] = v
+    if normals is not None:
+        vert["n"] = arr(normals, "<f4").reshape(-1, 3)
+    if colors is not None:
+        vert["rgb"] = np.round(np.clip(arr(colors, "<f8").reshape(-1, 3), 0.0, 1.0) * 255.0).astype(np.uint8)
+    face = np.empty(len(t), dtype=[("n", "u1"), ("idx", "<i4", (3,))])
+    face["n"] = 3; face["idx"] = t
+    head = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}"] + ["property " + p for p in props]
+    head += [f"element face {len(t)}", "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(head) + "\n").encode("ascii"))
+        fh.write(vert.tobytes()); fh.write(face.tobytes())

@@ -1070,6 +1070,30 @@ class NeRFNetwork(NeRFRenderer):
         vertices = vertices / (resolution - 1.0) * (2 * bound) - bound
         return vertices, triangles
 
+    def extract_colored_mesh(self, bound: float, resolution: int, threshold: float = 0.0, refine_steps: int = 3, tol: float = 1e-5, colors: bool = True,
+                             return_torch=False):
+        """the mesh of extract_geometry(mesher="native") with what a viewer wants on it (the reference's save_mesh, stylize.py:263-269, writes bare geometry):
+        every vertex projected from the grid edge's linear zero crossing onto the level set sdf = -threshold (at most refine_steps Newton steps along the
+        finite-difference gradient, never further than one grid cell), the field's normal and the colour network there -- one launch over the marching-cubes
+        buffer (ac_mesh_vertex_attrs).  -> dict(vertices [V,3] float64, triangles [F,3] int32 (extract_geometry's), normals [V,3] float32, colors [V,3]
+        float32 in [0, 1] (colors=True), sdf [V] at the final positions, status [V] uint8: 0 converged to tol, 1 all steps taken (sdf tells how close), 2 degenerate gradient,
+        3 stopped by the one-cell limit); numpy arrays, or device tensors with return_torch=True.  With view directions the colour is the one seen along -normal.
+        colors=True needs the default colour side (RuntimeError otherwise); colors=False works wherever extract_geometry(mesher="native") does."""
+        if not (self.encoder.embeddings.is_cuda and self._sdf_supported()):
+            raise RuntimeError("extract_colored_mesh needs the default SDF side of NeRFNetwork on the GPU")
+        if colors and not self._fused_supported(ignore_curvature=True):
+            raise RuntimeError("extract_colored_mesh(colors=True): the colour side of this model is not the default one (colour net 21-64-64-3, or 37-64-64-3 "
+                               "with the degree-4 view-direction encoder); colors=False exports positions and normals")
+        v, t = self.extract_geometry(bound, resolution, threshold=threshold, mesher="native", return_torch=True)
+        with torch.no_grad():
+            f = self._field() if self._fused_supported(ignore_curvature=True) else self._field_sdf_only()
+            a = nsr_ops.mesh_vertex_attrs(f, v, bound, nsr_ops.FD_STEP, refine_steps=refine_steps, tol=tol, max_move=2.0 * bound / (resolution - 1.0),
+                                          target_sdf=-float(threshold), want_rgb=colors)
+        out = dict(vertices=a["positions"].double(), triangles=t, normals=a["normals"], sdf=a["sdf"], status=a["status"])
+        if colors:
+            out["colors"] = a["rgb"]
+        return out if return_torch else {k: x.cpu().numpy() for k, x in out.items()}
+
     # ------------------------------------------------------------------ occupancy grid of the ray marcher, reference :303-356
     def update_extra_state(self, bound, decay=0.95):
         """density grid for raymarching.march_rays_train / march_rays (only with cuda_ray=True, like the reference): the SDF on the 129^3

@@ -1264,6 +1264,31 @@ def marching_cubes(volume, iso=0.0, den=1.0, span=(1.0, 1.0, 1.0), lo=(0.0, 0.0,
     return verts, tris
 
 
+def mesh_vertex_attrs(field, vertices, bound, eps=FD_STEP, refine_steps=3, tol=1e-5, max_move=None, target_sdf=0.0, dirs=None, want_rgb=True):
+    """ac_mesh_vertex_attrs: what a coloured export needs per vertex, in one launch.  vertices [V,3] float64 on the device (marching_cubes' buffer as it is);
+    every vertex takes at most refine_steps Newton steps along the finite-difference gradient onto sdf = target_sdf (never further than max_move per
+    coordinate from where it started; None: one cell of a 512^3 grid over the bound), then the normal and the colour network are evaluated at the final position.
+    dirs [V,3] float32: view directions for a field with Wc1_sh (None: -normal).  want_rgb=False: no colour network (an SDF-only field is enough).
+    -> dict(positions [V,3], normals [V,3], rgb [V,3] | None, sdf [V], status [V] uint8, why the steps ended: 0 a step found |sdf - target| <= tol, 1 all steps taken (the last is
+    not tested: read sdf), 2 degenerate gradient, 3 max_move)"""
+    if not isinstance(vertices, torch.Tensor) or not vertices.is_cuda:
+        raise RuntimeError("vertices must be a CUDA tensor")
+    if vertices.dtype != torch.float64 or vertices.dim() != 2 or vertices.shape[1] != 3 or not vertices.is_contiguous():
+        raise RuntimeError("mesh_vertex_attrs: vertices must be a contiguous float64 [V,3] tensor")
+    V, dev = vertices.shape[0], vertices.device
+    if dirs is not None:
+        dirs = _chk(dirs, "dirs", (V, 3))
+    if max_move is None:
+        max_move = 2.0 * float(bound) / 511.0
+    opts = L.ac_mesh_attr_opts(float(bound), float(eps), float(target_sdf), int(refine_steps), float(tol), float(max_move))
+    f = lambda *sh: torch.empty(sh, dtype=_F32, device=dev)
+    out = dict(positions=f(V, 3), normals=f(V, 3), rgb=f(V, 3) if want_rgb else None, sdf=f(V), status=torch.empty(V, dtype=torch.uint8, device=dev))
+    L.check(L.lib().ac_mesh_vertex_attrs(C.byref(field.c), vertices.data_ptr(), V, L.ptr(dirs), C.byref(opts), out["positions"].data_ptr(),
+                                         out["normals"].data_ptr(), L.ptr(out["rgb"]), out["sdf"].data_ptr(), out["status"].data_ptr(),
+                                         L.current_stream(dev)), "mesh_vertex_attrs")
+    return out
+
+
 _DG_SCRATCH = {}
 
 

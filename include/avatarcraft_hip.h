@@ -500,6 +500,28 @@ int ac_marching_cubes_count(const float *volume, uint32_t nx, uint32_t ny, uint3
 int ac_marching_cubes_emit(const float *volume, uint32_t nx, uint32_t ny, uint32_t nz, float iso, void *scratch, size_t scratch_bytes,
                            double den, const double span[3], const double lo[3], double *vertices, uint32_t n_vertices, int32_t *triangles,
                            uint32_t n_triangles, ac_stream_t stream);
+/* ac_mesh_vertex_attrs stands in for nothing: the reference's export is utils.save_mesh(vert, face, ...) (stylize.py:263-269), geometry only -- the avatar's
+ * colours never reach the file.  One launch over the vertices ac_marching_cubes_emit wrote (DEVICE doubles, read as they are): per vertex, all in fp32,
+ *   p = clamp((float)vertex, +-bound); p0 = p; at most refine_steps times: the seven-point stencil at p exactly as ac_field_samples evaluates it (fd_eps) ->
+ *   s = sdf, g = raw finite-difference gradient; r = s - target_sdf; |r| <= tol: stop; gg = (gx gx + gy gy) + gz gz; not gg > 1e-12: stop (status 2);
+ *   t = r / gg; q = clamp(p - t g, +-bound); max_k |q_k - p0_k| > max_move: stop and keep p (status 3); p = q.
+ * At the final p: positions = p, normals = g / (1e-5 + |g|), rgb = the colour network on (p, normal, geometry features) with the view direction dirs[v], or
+ * -normal where dirs is NULL (it matters for a field with Wc1_sh only), sdf = s there, status = why the steps ended: 0 a step's test |r| <= tol was met (the
+ * vertex is at a position with |sdf - target_sdf| <= tol) | 1 refine_steps steps taken (the last one is not tested: read sdf) | 2 degenerate gradient |
+ * 3 stopped by max_move.  The Newton steps of a wave run while any of its 64 lanes still moves, at most refine_steps: bounded, no atomics, no waits.
+ * rgb == NULL skips the colour network (a field whose colour matrices are placeholders is then enough); sdf, status and dirs are optional too.
+ * Every value is bit-identical to the CPU oracle's orc_field_samples chained by the same fp32 arithmetic (tests/test_gpu_mesh_attrs.py). */
+typedef struct ac_mesh_attr_opts {
+    float bound, fd_eps;        /* as ac_field_samples: clamp, finite-difference step            */
+    float target_sdf;           /* level the vertices are projected onto (0; -threshold of extract_geometry) */
+    int32_t refine_steps;       /* 0 = leave the vertices where they are; at most 16             */
+    float tol;                  /* |sdf - target| <= tol: converged                              */
+    float max_move;             /* largest |coordinate change| from the input vertex, > 0        */
+} ac_mesh_attr_opts;
+int ac_mesh_vertex_attrs(const ac_field *field, const double *vertices /*[V,3], as ac_marching_cubes_emit writes them*/, uint32_t V,
+                         const float *dirs /*optional [V,3]; NULL: -normal*/, const ac_mesh_attr_opts *opts,
+                         float *positions /*[V,3]*/, float *normals /*[V,3]*/, float *rgb /*optional [V,3]*/,
+                         float *sdf /*optional [V]: value at the final position*/, uint8_t *status /*optional [V]*/, ac_stream_t stream);
 /* ac_density_grid_update replaces the grid update of NeRFRenderer.update_extra_state (models/instant_nsr.py:303-346) in two launches (round 6: the densities on
  * ac_field_sdf_grid's x-tiles into the scratch, then one pooling / merging pass; round 5's single launch evaluated a halo per brick and was 3 x slower): forward_sdf on
  * the H^3 grid axis x axis x axis (axis [H], device: torch.linspace(-bound, bound, H)) -> density = inv_s e^(-inv_s |sdf|) / (1 + e^(-inv_s |sdf|)) in the
