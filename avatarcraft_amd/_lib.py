@@ -72,6 +72,10 @@ class ac_mesh_attr_opts(C.Structure):
     _fields_ = [("bound", f32), ("fd_eps", f32), ("target_sdf", f32), ("refine_steps", i32), ("tol", f32), ("max_move", f32)]
 
 
+class ac_atlas_opts(C.Structure):
+    _fields_ = [("size", u32), ("cell", u32)]
+
+
 _SIGS = {
     "ac_version": ([], C.c_int),
     "ac_last_error": ([], C.c_char_p),
@@ -159,6 +163,7 @@ _SIGS = {
     "ac_marching_cubes_count": ([vp, u32, u32, u32, f32, vp, C.c_size_t, vp, vp], C.c_int),
     "ac_marching_cubes_emit": ([vp, u32, u32, u32, f32, vp, C.c_size_t, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, u32, vp, u32, vp], C.c_int),
     "ac_mesh_vertex_attrs": ([C.POINTER(ac_field), vp, u32, vp, C.POINTER(ac_mesh_attr_opts), vp, vp, vp, vp, vp, vp], C.c_int),
+    "ac_mesh_bake_texture": ([C.POINTER(ac_field), vp, u32, vp, u32, C.POINTER(ac_atlas_opts), C.POINTER(ac_mesh_attr_opts), vp, vp, vp, vp, vp, vp], C.c_int),
     "ac_density_grid_update_scratch": ([u32], C.c_size_t),
     "ac_density_grid_update": ([C.POINTER(ac_field), vp, u32, f32, f32, f32, vp, vp, vp, C.c_size_t, vp], C.c_int),
     "ac_table_to_half": ([vp, u32, vp, vp, vp], C.c_int),

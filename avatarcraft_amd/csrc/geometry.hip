@@ -303,6 +303,56 @@ struct MeshAttrArgs {
     uint8_t *status;                   // [V] | NULL
 };
 
+// "refine and shade one tile of 16 points": the loop above and the evaluation at the final p, shared by the vertex kernel and the texel kernel below.  In: lane
+// (n, g)'s point p (clamped; the four lanes of a point agree) and whether it may move.  Out: the final p, sdf, status, normal and colour there (rgb in the lanes
+// g == 0).  dirs / di: the launch's view directions and this lane's row in them, or NULL: -normal.  Every lane of the wave calls it.
+struct RefineOpts { int steps; float target, tol, max_move; bool want_rgb; };
+struct TileShade { float s; uint32_t st; FdNormal fn; float rgb[3]; };
+
+__device__ __forceinline__ TileShade refine_shade_tile(float *lds, float *fsl, const FieldCtx &fc, const RenderArgs &a, const RefineOpts &m, int lane,
+                                                       const float *dirs, size_t di, bool moving, float &px, float &py, float &pz)
+{
+    const int n = lane & 15;
+    const float bound = a.bound, eps = a.eps;
+    const float p0x = px, p0y = py, p0z = pz;
+    uint32_t st = 1u;
+    f32x4 o16;
+    float gr[3], s;
+#pragma unroll 1
+    for (int it = 0;; ++it) {
+        float fe0[4][2];
+        encode_stencil(lds, fsl, fc, lane, px, py, pz, eps, fe0);
+        fd_forward(lds, fsl, lane, px, py, pz, eps, bound, fe0, o16, gr);
+        s = __shfl(o16[0], n);                                               // output 0 lives in the lanes g == 0
+        wave_sync();                                                         // (every lane is done with the feature slab)
+        bool moved = false;
+        if (moving && it < m.steps) {
+            const float r = s - m.target;
+            const float gg = (gr[0] * gr[0] + gr[1] * gr[1]) + gr[2] * gr[2];
+            if (__builtin_fabsf(r) <= m.tol) { moving = false; st = 0u; }
+            else if (!(gg > 1e-12f)) { moving = false; st = 2u; }
+            else {
+                const float t = r / gg;
+                const float qx = clampf(px - t * gr[0], -bound, bound), qy = clampf(py - t * gr[1], -bound, bound), qz = clampf(pz - t * gr[2], -bound, bound);
+                const float dm = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(qx - p0x), __builtin_fabsf(qy - p0y)), __builtin_fabsf(qz - p0z));
+                if (dm > m.max_move) { moving = false; st = 3u; }
+                else { px = qx; py = qy; pz = qz; moved = true; }
+            }
+        }
+        if (it >= m.steps || __ballot(moved) == 0ull) break;               // (wave-uniform)
+    }
+    TileShade r{ s, st, fd_normal(gr[0], gr[1], gr[2]), { 0.0f, 0.0f, 0.0f } };
+    if (m.want_rgb) {                                                        // (uniform over the launch)
+        if (a.Wsh) {
+            float dx = -r.fn.nx, dy = -r.fn.ny, dz = -r.fn.nz;
+            if (dirs) { const float *d = dirs + 3 * di; dx = d[0]; dy = d[1]; dz = d[2]; }
+            sample_sh_bias(fsl, a.Wsh, dx, dy, dz, lane);
+            color_tile(lds, lane, px, py, pz, r.fn.nx, r.fn.ny, r.fn.nz, o16, r.rgb, fsl + 4 * lane, 256);
+        } else color_tile(lds, lane, px, py, pz, r.fn.nx, r.fn.ny, r.fn.nz, o16, r.rgb);
+    }
+    return r;
+}
+
 __global__ __launch_bounds__(FBLOCK) void mesh_attrs_kernel(const RenderArgs a, const MeshAttrArgs m)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -312,56 +362,87 @@ __global__ __launch_bounds__(FBLOCK) void mesh_attrs_kernel(const RenderArgs a, 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
     float *fsl = lds + OFF_WAVE + wave * FE_SLAB;
     const FieldCtx fc = make_ctx(a);
-    const float bound = a.bound, eps = a.eps;
+    const float bound = a.bound;
+    const RefineOpts ro{ m.steps, m.target, m.tol, m.max_move, m.rgb != nullptr };
     const uint32_t ntiles = (m.V + 15) / 16;
     for (uint32_t tile = blockIdx.x * FW + wave; tile < ntiles; tile += gridDim.x * FW) {
         const uint32_t b = tile * 16 + n, bb = b < m.V ? b : m.V - 1;
         const double *vx = m.verts + 3 * (size_t)bb;
         float px = clampf((float)vx[0], -bound, bound), py = clampf((float)vx[1], -bound, bound), pz = clampf((float)vx[2], -bound, bound);
-        const float p0x = px, p0y = py, p0z = pz;
-        bool moving = true;
-        uint32_t st = 1u;
-        f32x4 o16;
-        float gr[3], s;
-#pragma unroll 1
-        for (int it = 0;; ++it) {
-            float fe0[4][2];
-            encode_stencil(lds, fsl, fc, lane, px, py, pz, eps, fe0);
-            fd_forward(lds, fsl, lane, px, py, pz, eps, bound, fe0, o16, gr);
-            s = __shfl(o16[0], n);                                               // output 0 lives in the lanes g == 0
-            wave_sync();                                                         // (every lane is done with the feature slab)
-            bool moved = false;
-            if (moving && it < m.steps) {
-                const float r = s - m.target;
-                const float gg = (gr[0] * gr[0] + gr[1] * gr[1]) + gr[2] * gr[2];
-                if (__builtin_fabsf(r) <= m.tol) { moving = false; st = 0u; }
-                else if (!(gg > 1e-12f)) { moving = false; st = 2u; }
-                else {
-                    const float t = r / gg;
-                    const float qx = clampf(px - t * gr[0], -bound, bound), qy = clampf(py - t * gr[1], -bound, bound), qz = clampf(pz - t * gr[2], -bound, bound);
-                    const float dm = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(qx - p0x), __builtin_fabsf(qy - p0y)), __builtin_fabsf(qz - p0z));
-                    if (dm > m.max_move) { moving = false; st = 3u; }
-                    else { px = qx; py = qy; pz = qz; moved = true; }
-                }
-            }
-            if (it >= m.steps || __ballot(moved) == 0ull) break;               // (wave-uniform)
-        }
-        const FdNormal fn = fd_normal(gr[0], gr[1], gr[2]);
-        float rgb[3] = { 0.0f, 0.0f, 0.0f };
-        if (m.rgb) {                                                             // (uniform over the launch)
-            if (a.Wsh) {
-                float dx = -fn.nx, dy = -fn.ny, dz = -fn.nz;
-                if (m.dirs) { const float *d = m.dirs + 3 * (size_t)bb; dx = d[0]; dy = d[1]; dz = d[2]; }
-                sample_sh_bias(fsl, a.Wsh, dx, dy, dz, lane);
-                color_tile(lds, lane, px, py, pz, fn.nx, fn.ny, fn.nz, o16, rgb, fsl + 4 * lane, 256);
-            } else color_tile(lds, lane, px, py, pz, fn.nx, fn.ny, fn.nz, o16, rgb);
-        }
+        const TileShade r = refine_shade_tile(lds, fsl, fc, a, ro, lane, m.dirs, (size_t)bb, true, px, py, pz);
         if (b < m.V && g == 0) {
             m.pos[3 * (size_t)b] = px; m.pos[3 * (size_t)b + 1] = py; m.pos[3 * (size_t)b + 2] = pz;
-            m.nrm[3 * (size_t)b] = fn.nx; m.nrm[3 * (size_t)b + 1] = fn.ny; m.nrm[3 * (size_t)b + 2] = fn.nz;
-            if (m.rgb) { m.rgb[3 * (size_t)b] = rgb[0]; m.rgb[3 * (size_t)b + 1] = rgb[1]; m.rgb[3 * (size_t)b + 2] = rgb[2]; }
-            if (m.sdf) m.sdf[b] = s;
-            if (m.status) m.status[b] = (uint8_t)st;
+            m.nrm[3 * (size_t)b] = r.fn.nx; m.nrm[3 * (size_t)b + 1] = r.fn.ny; m.nrm[3 * (size_t)b + 2] = r.fn.nz;
+            if (m.rgb) { m.rgb[3 * (size_t)b] = r.rgb[0]; m.rgb[3 * (size_t)b + 1] = r.rgb[1]; m.rgb[3 * (size_t)b + 2] = r.rgb[2]; }
+            if (m.sdf) m.sdf[b] = r.s;
+            if (m.status) m.status[b] = (uint8_t)r.st;
+        }
+        wave_sync();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- texture bake: the same body over texels
+// The atlas is closed form (avatarcraft_amd/geometry.py: atlas_layout): the S x S image is cut into R x R cells of c x c texels, R = S / c; triangle t
+// lives in cell t >> 1 (column k % R, row k / R), half t & 1.  Texel (i, j) of a cell belongs to half 0 iff i + j <= c - 2.  Its barycentric weights, in fp32, every
+// operation rounded once, L = c - 5:  half 0: w1 = (i - 1) / L, w2 = (j - 1) / L;  half 1: w1 = (c - 2 - i) / L, w2 = (c - 2 - j) / L;  w1 = max(w1, 0),
+// w2 = max(w2, 0), s = w1 + w2;  s > 1: w1 /= s, w2 /= s, w0 = 0;  else w0 = 1 - s -- a texel outside the UV triangle takes a point ON the triangle (the gutter).
+// Its point, per coordinate: p = (w0 P0 + w1 P1) + w2 P2, clamped to +-bound; then refine_shade_tile, view direction -normal.
+// A wave takes tiles of 16 consecutive texels of an image row (ceil(S / 16) tiles per row).  A tile without an owned texel issues no field evaluation (the test is
+// wave-uniform); in a tile with some, the lanes of the others ride along at the first owned texel's point without moving, and store owner = -1 and zeros.
+struct BakeArgs {
+    const float *pos;           // [V,3]
+    const int32_t *tris;        // [T,3], every index in [0, V)
+    uint32_t T, S, c, R;
+    RefineOpts ro;
+    float *rgb, *nrm, *sdf;     // [S,S,3], [S,S,3] | NULL, [S,S] | NULL
+    int32_t *owner;             // [S,S]
+    uint8_t *status;            // [S,S] | NULL
+};
+
+__global__ __launch_bounds__(FBLOCK) void texture_bake_kernel(const RenderArgs a, const BakeArgs m)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    fill_lds_sdf(lds, a);
+    fill_lds_color(lds, a);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
+    float *fsl = lds + OFF_WAVE + wave * FE_SLAB;
+    const FieldCtx fc = make_ctx(a);
+    const float bound = a.bound;
+    const uint32_t S = m.S, c = m.c, per_row = (S + 15) / 16, ntiles = per_row * S;
+    const float L = (float)(c - 5u);
+    for (uint32_t tile = blockIdx.x * FW + wave; tile < ntiles; tile += gridDim.x * FW) {
+        const uint32_t y = tile / per_row, x = (tile - y * per_row) * 16 + n;
+        const uint32_t cx = x / c, cy = y / c, i = x - cx * c, j = y - cy * c;
+        const uint32_t h = i + j + 2 <= c ? 0u : 1u, t = 2 * (cy * m.R + cx) + h;
+        const bool owned = x < S && cx < m.R && cy < m.R && t < m.T;
+        const unsigned long long own_mask = __ballot(owned);
+        float px = 0.0f, py = 0.0f, pz = 0.0f;
+        TileShade r{ 0.0f, 0u, FdNormal{ 0.0f, 0.0f, 0.0f, 0.0f }, { 0.0f, 0.0f, 0.0f } };
+        if (own_mask) {                                                          // (wave-uniform)
+            if (owned) {
+                const int di = h ? (int)(c - 2u - i) : (int)i - 1, dj = h ? (int)(c - 2u - j) : (int)j - 1;
+                float w1 = __builtin_fmaxf((float)di / L, 0.0f), w2 = __builtin_fmaxf((float)dj / L, 0.0f), w0 = 0.0f;
+                const float s = w1 + w2;
+                if (s > 1.0f) { w1 = w1 / s; w2 = w2 / s; } else w0 = 1.0f - s;
+                const int32_t *tv = m.tris + 3 * (size_t)t;
+                const float *P0 = m.pos + 3 * (size_t)tv[0], *P1 = m.pos + 3 * (size_t)tv[1], *P2 = m.pos + 3 * (size_t)tv[2];
+                px = clampf((w0 * P0[0] + w1 * P1[0]) + w2 * P2[0], -bound, bound);
+                py = clampf((w0 * P0[1] + w1 * P1[1]) + w2 * P2[1], -bound, bound);
+                pz = clampf((w0 * P0[2] + w1 * P1[2]) + w2 * P2[2], -bound, bound);
+            }
+            const int first = __builtin_ctzll(own_mask) & 15;                   // (the four lanes of a texel agree, so its lane g == 0 is the lowest set bit)
+            const float fx = __shfl(px, first), fy = __shfl(py, first), fz = __shfl(pz, first);
+            if (!owned) { px = fx; py = fy; pz = fz; }
+            r = refine_shade_tile(lds, fsl, fc, a, m.ro, lane, nullptr, 0, owned, px, py, pz);
+        }
+        if (x < S && g == 0) {
+            const size_t b = (size_t)y * S + x;
+            m.owner[b] = owned ? (int32_t)t : -1;
+            m.rgb[3 * b] = owned ? r.rgb[0] : 0.0f; m.rgb[3 * b + 1] = owned ? r.rgb[1] : 0.0f; m.rgb[3 * b + 2] = owned ? r.rgb[2] : 0.0f;
+            if (m.nrm) { m.nrm[3 * b] = owned ? r.fn.nx : 0.0f; m.nrm[3 * b + 1] = owned ? r.fn.ny : 0.0f; m.nrm[3 * b + 2] = owned ? r.fn.nz : 0.0f; }
+            if (m.sdf) m.sdf[b] = owned ? r.s : 0.0f;
+            if (m.status) m.status[b] = owned ? (uint8_t)r.st : (uint8_t)0;
         }
         wave_sync();
     }
@@ -577,6 +658,32 @@ AC_API int ac_mesh_vertex_attrs(const ac_field *field, const double *vertices, u
     if (blocks > cus) blocks = cus;
     hipLaunchKernelGGL(mesh_attrs_kernel, dim3(blocks), dim3(FBLOCK), lds_bytes, (hipStream_t)stream, a, m);
     return ac::check_launch("mesh_vertex_attrs");
+}
+
+AC_API int ac_mesh_bake_texture(const ac_field *field, const float *positions, uint32_t V, const int32_t *triangles, uint32_t T, const ac_atlas_opts *atlas,
+                                const ac_mesh_attr_opts *opts, float *rgb, int32_t *owner, float *normals, float *sdf, uint8_t *status, ac_stream_t stream)
+{
+    if (!atlas || !opts) { ac::set_error("mesh_bake_texture: NULL atlas or opts"); return AC_ERR_BAD_ARG; }
+    if (opts->refine_steps < 0 || opts->refine_steps > 16 || !(opts->max_move > 0.0f) || !(opts->fd_eps > 0.0f) || !(opts->bound > 0.0f)) {
+        ac::set_error("mesh_bake_texture: refine_steps outside 0..16, or max_move, fd_eps or bound not > 0"); return AC_ERR_BAD_ARG;
+    }
+    const uint32_t S = atlas->size, c = atlas->cell;
+    if (c < 8) { ac::set_error("mesh_bake_texture: cell %u < 8", c); return AC_ERR_BAD_ARG; }
+    if (S < c || S > 32768u) { ac::set_error("mesh_bake_texture: size %u outside cell .. 32768", S); return AC_ERR_BAD_ARG; }
+    const uint32_t R = S / c;
+    if ((uint64_t)T > 2ull * R * R) { ac::set_error("mesh_bake_texture: %u triangles, but a %u x %u atlas of %u-texel cells holds 2 (size / cell)^2 = %llu", T, S, S, c, 2ull * R * R); return AC_ERR_BAD_ARG; }
+    if (!rgb || !owner || (T && (!positions || !triangles || !V))) { ac::set_error("mesh_bake_texture: NULL buffer"); return AC_ERR_BAD_ARG; }
+    RenderArgs a{};
+    if (int rc = prep_args(a, field, opts->bound, opts->fd_eps)) return rc;
+    BakeArgs m{ positions, triangles, T, S, c, R, { opts->refine_steps, opts->target_sdf, opts->tol, opts->max_move, true }, rgb, normals, sdf, owner, status };
+    const size_t lds_bytes = FWD_LDS_FLOATS * sizeof(float);
+    static uint64_t seen = 0;
+    ac::allow_dynamic_lds(seen, reinterpret_cast<const void *>(texture_bake_kernel), lds_bytes);
+    uint32_t blocks = (((S + 15) / 16) * S + FW - 1) / FW;         // persistent, one workgroup per CU, like ac_mesh_vertex_attrs
+    const uint32_t cus = ac::cu_count();
+    if (blocks > cus) blocks = cus;
+    hipLaunchKernelGGL(texture_bake_kernel, dim3(blocks), dim3(FBLOCK), lds_bytes, (hipStream_t)stream, a, m);
+    return ac::check_launch("mesh_bake_texture");
 }
 
 static uint32_t dp_blocks(uint32_t H)

@@ -137,8 +137,17 @@ def render_animation(net, body_model, cam_pose, poses=None, render_type="animate
 
 def export_mesh(net, path, bound=NSR_BOUND, resolution=512, **kw):
     """the canonical avatar as a binary PLY with per-vertex normals and colours: net.extract_colored_mesh(bound, resolution, **kw) -> geometry.save_ply;
-    the reference's counterpart (extract_geometry(NSR_BOUND, 512) + save_mesh, stylize.py:263-269) writes vertices and faces only.  Returns the mesh dict."""
-    from .geometry import save_ply
+    the reference's counterpart (extract_geometry(NSR_BOUND, 512) + save_mesh, stylize.py:263-269) writes vertices and faces only.  Returns the mesh dict.
+    A path ending in .obj writes a TEXTURED mesh instead: net.extract_textured_mesh(bound, resolution, **kw) -> name.obj, name.mtl (geometry.save_obj) and
+    name.png (geometry.save_png)."""
+    import os
+    from .geometry import save_obj, save_ply, save_png
+    if str(path).lower().endswith(".obj"):
+        mesh = net.extract_textured_mesh(bound, resolution, **kw)
+        png = os.path.splitext(str(path))[0] + ".png"
+        save_png(png, mesh["texture"])
+        save_obj(str(path), mesh["vertices"], mesh["triangles"], mesh["uv"], normals=mesh["normals"], texture=os.path.basename(png))
+        return mesh
     mesh = net.extract_colored_mesh(bound, resolution, **kw)
     save_ply(path, mesh["vertices"], mesh["triangles"], normals=mesh["normals"], colors=mesh.get("colors"))
     return mesh

@@ -107,3 +107,127 @@ def save_ply(path, vertices, triangles, normals=None, colors=None):
     with open(path, "wb") as fh:
         fh.write(("\n".join(head) + "\n").encode("ascii"))
         fh.write(vert.tobytes()); fh.write(face.tobytes())
+
+
+# ---------------------------------------------------------------------------------------------------- texture atlas (closed form; the kernel restates it in integers)
+# The S x S texture is cut into R x R square cells of c x c texels (R = S // c; texels beyond R c belong to nobody).  Triangle t lives in cell k = t >> 1, at
+# column k % R and row k // R, in half h = t & 1: texel (i, j) of a cell -- i along x, centre at (i + 0.5, j + 0.5) -- belongs to half 0 iff i + j <= c - 2.
+# The UV corners sit ON texel centres, in the triangle's vertex order: half 0 at (1, 1), (c - 4, 1), (1, c - 4), half 1 at (c - 2, c - 2), (3, c - 2), (c - 2, 3);
+# legs of L = c - 5 texels, three texel diagonals between the two hypotenuses -- a bilinear lookup inside a UV triangle reads texels of its own half only
+# (tests/test_texture_atlas_host.py, exact arithmetic).  Nothing wider (mip levels, anisotropic filters) is guaranteed.
+ATLAS_MIN_CELL = 8
+
+
+def _atlas_cell(n_triangles, size, cell):
+    n_triangles, size = int(n_triangles), int(size)
+    if n_triangles < 0 or size < 1:
+        raise ValueError("atlas: n_triangles >= 0 and size >= 1")
+    if cell is None:                                                     # the largest cell whose grid still holds every triangle
+        cell = next((c for c in range(size, ATLAS_MIN_CELL - 1, -1) if 2 * (size // c) ** 2 >= n_triangles), None)
+        if cell is None:
+            raise ValueError(f"atlas: {n_triangles} triangles do not fit a {size} x {size} texture with cells of {ATLAS_MIN_CELL} texels or more")
+        return cell
+    cell = int(cell)
+    if cell < ATLAS_MIN_CELL:
+        raise ValueError(f"atlas: cell {cell} < {ATLAS_MIN_CELL}")
+    if size < cell or 2 * (size // cell) ** 2 < n_triangles:
+        raise ValueError(f"atlas: {n_triangles} triangles, but a {size} x {size} texture of {cell}-texel cells holds 2 (size // cell)^2 = {2 * (size // cell) ** 2}")
+    return cell
+
+
+def atlas_weights(cell):
+    """per texel of one cell: (half [c,c] int32, weights [c,c,3] float32), both indexed [j, i] -- the barycentric weights (w0, w1, w2) of the texel in the triangle
+    of ITS half, every operation in fp32 and rounded once (ac_mesh_bake_texture's arithmetic); texels outside the UV triangle get a point on it"""
+    import numpy as np
+    F = np.float32
+    c = int(cell)
+    j, i = np.meshgrid(np.arange(c), np.arange(c), indexing="ij")
+    half = (i + j > c - 2).astype(np.int32)
+    L = F(c - 5)
+    w1 = np.maximum(np.where(half == 0, i - 1, c - 2 - i).astype(F) / L, F(0))
+    w2 = np.maximum(np.where(half == 0, j - 1, c - 2 - j).astype(F) / L, F(0))
+    s = w1 + w2
+    over = s > F(1)
+    sd = np.where(over, s, F(1))
+    w1, w2 = np.where(over, w1 / sd, w1), np.where(over, w2 / sd, w2)
+    w0 = np.where(over, F(0), F(1) - s)
+    w = np.stack([w0, w1, w2], -1)
+    assert w.dtype == F
+    return half, w
+
+
+def atlas_layout(n_triangles, size, cell=None):
+    """-> dict(cell, per_row, uv [T,3,2] float64).  cell=None: the largest cell >= 8 with 2 (size // cell)^2 >= n_triangles; ValueError when nothing fits.
+    uv in the OBJ convention (u = (x + 0.5) / size, v = 1 - (y + 0.5) / size for the texel centre (x, y), image row 0 on top), one row per triangle corner in the
+    triangle's vertex order.  Both halves wind the same way: counter-clockwise in texel coordinates (x, y)."""
+    import numpy as np
+    c = _atlas_cell(n_triangles, size, cell)
+    R = int(size) // c
+    t = np.arange(int(n_triangles))
+    k, h = t >> 1, t & 1
+    corners = np.array([[[1, 1], [c - 4, 1], [1, c - 4]], [[c - 2, c - 2], [3, c - 2], [c - 2, 3]]], np.int64)[h]          # [T,3,2] texel (i, j)
+    x = (k % R * c)[:, None] + corners[..., 0]
+    y = (k // R * c)[:, None] + corners[..., 1]
+    uv = np.stack([(x + 0.5) / float(size), 1.0 - (y + 0.5) / float(size)], -1)
+    return dict(cell=c, per_row=R, uv=uv.reshape(-1, 3, 2))
+
+
+def atlas_owner(n_triangles, size, cell):
+    """-> int32 [S,S], indexed [y, x]: the triangle that owns each texel, -1 for nobody (the margin beyond R cell, cells past the last triangle, the second half
+    of the last cell of an odd count)"""
+    import numpy as np
+    c = _atlas_cell(n_triangles, size, cell)
+    S = int(size)
+    R = S // c
+    y, x = np.meshgrid(np.arange(S), np.arange(S), indexing="ij")
+    cx, cy = x // c, y // c
+    i, j = x - cx * c, y - cy * c
+    t = 2 * (cy * R + cx) + (i + j > c - 2)
+    return np.where((cx < R) & (cy < R) & (t < int(n_triangles)), t, -1).astype(np.int32)
+
+
+def save_png(path, rgb8):
+    """8-bit RGB PNG from a uint8 [H,W,3] array, row 0 on top: one IDAT chunk, filter 0 on every row (zlib and struct only)"""
+    import struct
+    import zlib
+    import numpy as np
+    a = np.asarray(rgb8.detach().cpu().numpy() if isinstance(rgb8, torch.Tensor) else rgb8)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("save_png: a uint8 [H,W,3] array")
+    H, W = a.shape[:2]
+    rows = np.zeros((H, 1 + 3 * W), np.uint8)
+    rows[:, 1:] = a.reshape(H, 3 * W)
+    chunk = lambda tag, data: struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xffffffff)
+    with open(path, "wb") as fh:
+        fh.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2, 0, 0, 0)) + chunk(b"IDAT", zlib.compress(rows.tobytes(), 6))
+                 + chunk(b"IEND", b""))
+
+
+def save_obj(path, vertices, triangles, uv, normals=None, texture=None):
+    """Wavefront OBJ: `v` per vertex, `vt` three per triangle (uv [T,3,2], atlas_layout's), `vn` per vertex, `f a/ta/na b/tb/nb c/tc/nc` (`a/ta` without normals),
+    1-based; triangle t uses vt 3t+1 .. 3t+3.  texture: the image's file name -- then a sibling .mtl (same stem) with map_Kd is written and referenced.
+    Numbers are written with repr, so they read back to the same doubles."""
+    import os
+    import numpy as np
+    arr = lambda a, dt: np.ascontiguousarray((a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)), dtype=dt)
+    v, t, w = arr(vertices, np.float64).reshape(-1, 3), arr(triangles, np.int64).reshape(-1, 3), arr(uv, np.float64).reshape(-1, 2)
+    if len(w) != 3 * len(t):
+        raise ValueError("save_obj: uv must be [T,3,2]")
+    out = []
+    stem = os.path.splitext(path)[0]
+    if texture is not None:
+        with open(stem + ".mtl", "w") as fh:
+            fh.write(f"newmtl baked\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {texture}\n")
+        out += [f"mtllib {os.path.basename(stem)}.mtl", "usemtl baked"]
+    out += ["v %r %r %r" % tuple(r) for r in v.tolist()]
+    out += ["vt %r %r" % tuple(r) for r in w.tolist()]
+    if normals is not None:
+        n = arr(normals, np.float64).reshape(-1, 3)
+        if len(n) != len(v):
+            raise ValueError("save_obj: one normal per vertex")
+        out += ["vn %r %r %r" % tuple(r) for r in n.tolist()]
+        out += ["f %d/%d/%d %d/%d/%d %d/%d/%d" % (a + 1, 3 * k + 1, a + 1, b + 1, 3 * k + 2, b + 1, c + 1, 3 * k + 3, c + 1) for k, (a, b, c) in enumerate(t.tolist())]
+    else:
+        out += ["f %d/%d %d/%d %d/%d" % (a + 1, 3 * k + 1, b + 1, 3 * k + 2, c + 1, 3 * k + 3) for k, (a, b, c) in enumerate(t.tolist())]
+    with open(path, "w") as fh:
+        fh.write("\n".join(out) + "\n")

@@ -1094,6 +1094,31 @@ class NeRFNetwork(NeRFRenderer):
             out["colors"] = a["rgb"]
         return out if return_torch else {k: x.cpu().numpy() for k, x in out.items()}
 
+    def extract_textured_mesh(self, bound: float, resolution: int, texture_size: int = 2048, cell=None, threshold: float = 0.0, refine_steps: int = 3,
+                              tol: float = 1e-5, return_torch=False):
+        """extract_colored_mesh's mesh with the colour network baked into a texture instead of sampled at the vertices, so that colour detail no longer depends on
+        the vertex density: every triangle gets half a cell of a closed-form texture_size^2 atlas (geometry.atlas_layout; cell=None: the largest that fits), every
+        owned texel's point on its triangle is projected onto the level set like a vertex (never further than one grid cell) and shaded there, one launch
+        (ac_mesh_bake_texture).  -> the dict of extract_colored_mesh plus uv [T,3,2] float64 (three corners per triangle, OBJ convention), texture [S,S,3] uint8
+        (q = floor(clamp(x, 0, 1) 255 + 0.5), row 0 on top), owner [S,S] int32 (-1: nobody, texture 0), texel_sdf [S,S], texel_status [S,S] uint8.
+        The atlas guarantees bilinear lookups only (no mip chain).  Same model requirements as extract_colored_mesh(colors=True)."""
+        from .geometry import atlas_layout
+        m = self.extract_colored_mesh(bound, resolution, threshold=threshold, refine_steps=refine_steps, tol=tol, colors=True, return_torch=True)
+        T = m["triangles"].shape[0]
+        try:
+            lay = atlas_layout(T, texture_size, cell)
+        except ValueError as e:
+            raise RuntimeError(f"extract_textured_mesh: {e}") from e
+        with torch.no_grad():
+            b = nsr_ops.mesh_bake_texture(self._field(), m["vertices"].float(), m["triangles"], texture_size, lay["cell"], bound, nsr_ops.FD_STEP,
+                                          refine_steps=refine_steps, tol=tol, max_move=2.0 * bound / (resolution - 1.0), target_sdf=-float(threshold))
+            tex = torch.floor(b["rgb"].clamp(0.0, 1.0) * 255.0 + 0.5).to(torch.uint8)
+        m.update(texture=tex, owner=b["owner"], texel_sdf=b["sdf"], texel_status=b["status"])
+        if not return_torch:
+            m = {k: x.cpu().numpy() for k, x in m.items()}
+        m["uv"] = torch.from_numpy(lay["uv"]).to(tex.device) if return_torch else lay["uv"]
+        return m
+
     # ------------------------------------------------------------------ occupancy grid of the ray marcher, reference :303-356
     def update_extra_state(self, bound, decay=0.95):
         """density grid for raymarching.march_rays_train / march_rays (only with cuda_ray=True, like the reference): the SDF on the 129^3

@@ -1289,6 +1289,43 @@ def mesh_vertex_attrs(field, vertices, bound, eps=FD_STEP, refine_steps=3, tol=1
     return out
 
 
+def mesh_bake_texture(field, positions, triangles, size, cell, bound, eps=FD_STEP, refine_steps=3, tol=1e-5, max_move=None, target_sdf=0.0, want_normals=False):
+    """ac_mesh_bake_texture: mesh_vertex_attrs' work per TEXEL of the closed-form atlas (geometry.atlas_layout), in one launch.  positions [V,3] float32 on the
+    device (mesh_vertex_attrs' `positions`: vertices on the level set), triangles [T,3] int32, size x size texels in cells of `cell` (None: the largest that fits).
+    Every owned texel's point on its triangle takes at most refine_steps Newton steps (max_move from that point; None: one cell of a 512^3 grid), then normal, sdf and
+    the colour seen along -normal are evaluated there.  -> dict(rgb [S,S,3], owner [S,S] int32 (-1: nobody; everything else is 0 there), normals [S,S,3] | None,
+    sdf [S,S], status [S,S] uint8 as mesh_vertex_attrs').  The triangle indices are checked on the device BEFORE the launch (the kernel reads through them unchecked):
+    RuntimeError for one outside [0, V)."""
+    if not isinstance(positions, torch.Tensor) or not isinstance(triangles, torch.Tensor) or not positions.is_cuda or not triangles.is_cuda:
+        raise RuntimeError("mesh_bake_texture: positions and triangles must be CUDA tensors")
+    if positions.dtype != _F32 or positions.dim() != 2 or positions.shape[1] != 3 or not positions.is_contiguous():
+        raise RuntimeError("mesh_bake_texture: positions must be a contiguous float32 [V,3] tensor")
+    if triangles.dtype != torch.int32 or triangles.dim() != 2 or triangles.shape[1] != 3 or not triangles.is_contiguous() or triangles.device != positions.device:
+        raise RuntimeError("mesh_bake_texture: triangles must be a contiguous int32 [T,3] tensor on the device of positions")
+    V, T, S, dev = positions.shape[0], triangles.shape[0], int(size), positions.device
+    if cell is None:
+        from .geometry import atlas_layout
+        try:
+            cell = atlas_layout(T, S)["cell"]
+        except ValueError as e:
+            raise RuntimeError(f"mesh_bake_texture: {e}") from e
+    if T and (int(triangles.min()) < 0 or int(triangles.max()) >= V):
+        raise RuntimeError(f"mesh_bake_texture: a triangle index outside [0, {V}); nothing was launched")
+    if max_move is None:
+        max_move = 2.0 * float(bound) / 511.0
+    if not 0 < S <= 32768:
+        raise RuntimeError(f"mesh_bake_texture: size {S} outside 1 .. 32768")
+    atlas = L.ac_atlas_opts(S, max(int(cell), 0))
+    opts = L.ac_mesh_attr_opts(float(bound), float(eps), float(target_sdf), int(refine_steps), float(tol), float(max_move))
+    f = lambda *sh: torch.empty(sh, dtype=_F32, device=dev)
+    out = dict(rgb=f(S, S, 3), owner=torch.empty((S, S), dtype=torch.int32, device=dev), normals=f(S, S, 3) if want_normals else None, sdf=f(S, S),
+               status=torch.empty((S, S), dtype=torch.uint8, device=dev))
+    L.check(L.lib().ac_mesh_bake_texture(C.byref(field.c), positions.data_ptr(), V, triangles.data_ptr(), T, C.byref(atlas), C.byref(opts), out["rgb"].data_ptr(),
+                                         out["owner"].data_ptr(), L.ptr(out["normals"]), out["sdf"].data_ptr(), out["status"].data_ptr(),
+                                         L.current_stream(dev)), "mesh_bake_texture")
+    return out
+
+
 _DG_SCRATCH = {}
 
 

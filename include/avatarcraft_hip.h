@@ -522,6 +522,25 @@ int ac_mesh_vertex_attrs(const ac_field *field, const double *vertices /*[V,3], 
                          const float *dirs /*optional [V,3]; NULL: -normal*/, const ac_mesh_attr_opts *opts,
                          float *positions /*[V,3]*/, float *normals /*[V,3]*/, float *rgb /*optional [V,3]*/,
                          float *sdf /*optional [V]: value at the final position*/, uint8_t *status /*optional [V]*/, ac_stream_t stream);
+/* ac_mesh_bake_texture: the same per-point work over the TEXELS of a closed-form atlas instead of the vertices -- colour detail no longer tied to vertex density
+ * (an added entry, no struct of an existing call changes: ac_version() stays 10).  The size x size image (row 0 on top, [y][x]) is cut into R x R cells of
+ * cell x cell texels, R = size / cell (texels beyond R cell belong to nobody); triangle t lives in cell k = t >> 1 at column k % R, row k / R, half t & 1.
+ * Texel (i, j) of a cell (i along x) belongs to half 0 iff i + j <= cell - 2.  With L = cell - 5, in fp32, every operation rounded once:
+ *   half 0: w1 = (i - 1) / L, w2 = (j - 1) / L;   half 1: w1 = (cell - 2 - i) / L, w2 = (cell - 2 - j) / L;   w1 = max(w1, 0); w2 = max(w2, 0); s = w1 + w2;
+ *   s > 1: w1 /= s, w2 /= s, w0 = 0; else w0 = 1 - s        (a texel outside its UV triangle takes a point ON the triangle: the gutter needs no dilation pass)
+ *   p = clamp((w0 P0 + w1 P1) + w2 P2, +-bound) per coordinate, P* = positions[triangles[t][*]]
+ * then ac_mesh_vertex_attrs's loop from p, unchanged (refine_steps, tol, max_move from the texel's starting point, the same status 0..3), and normal, sdf and colour at the
+ * final point with the view direction -normal.  The UV corners sit on the texel centres (1, 1), (cell - 4, 1), (1, cell - 4) of half 0 and (cell - 2, cell - 2),
+ * (3, cell - 2), (cell - 2, 3) of half 1: their weights are exactly (1,0,0), (0,1,0), (0,0,1), and a bilinear lookup inside a UV triangle reads its own texels only.
+ * Per owned texel: rgb, owner = t, normals, sdf, status.  Per unowned texel: owner = -1, every other output 0, no field evaluation.
+ * PRECONDITION: every triangle index lies in [0, V) -- the kernel reads positions through them unchecked (nsr_ops.mesh_bake_texture checks on the device first).
+ * AC_ERR_BAD_ARG: a NULL required buffer, cell < 8, size < cell (or > 32768), T > 2 (size / cell)^2, opts outside what ac_mesh_vertex_attrs accepts.
+ * The field needs its colour side.  Bit-identical to the CPU oracle's orc_field_samples chained by the same fp32 arithmetic (tests/test_gpu_texture_bake.py). */
+typedef struct ac_atlas_opts { uint32_t size, cell; } ac_atlas_opts;
+int ac_mesh_bake_texture(const ac_field *field, const float *positions /*[V,3]*/, uint32_t V, const int32_t *triangles /*[T,3]*/, uint32_t T,
+                         const ac_atlas_opts *atlas, const ac_mesh_attr_opts *opts,
+                         float *rgb /*[S,S,3]*/, int32_t *owner /*[S,S]*/, float *normals /*optional [S,S,3]*/, float *sdf /*optional [S,S]*/,
+                         uint8_t *status /*optional [S,S]*/, ac_stream_t stream);
 /* ac_density_grid_update replaces the grid update of NeRFRenderer.update_extra_state (models/instant_nsr.py:303-346) in two launches (round 6: the densities on
  * ac_field_sdf_grid's x-tiles into the scratch, then one pooling / merging pass; round 5's single launch evaluated a halo per brick and was 3 x slower): forward_sdf on
  * the H^3 grid axis x axis x axis (axis [H], device: torch.linspace(-bound, bound, H)) -> density = inv_s e^(-inv_s |sdf|) / (1 + e^(-inv_s |sdf|)) in the

@@ -1,0 +1,243 @@
+"""-m gpu: ac_mesh_bake_texture (csrc/geometry.hip) and the textured export around it -- nsr_ops.mesh_bake_texture, NeRFNetwork.extract_textured_mesh,
+drivers.export_mesh(".obj").  The kernel runs ac_mesh_vertex_attrs' per-point body over the texels of the closed-form atlas (avatarcraft_amd/geometry.py); every
+output is compared BIT FOR BIT with `bake_reference`: the atlas' weights and point in numpy fp32, then tests/test_gpu_mesh_attrs.py's `restate` around the CPU
+oracle's orc_field_samples.  Measured on the oracle (golden field, bound 1.6, eps 0.005, the 24^3 mesh of 364 triangles projected by 3 steps, S = 128, c = 8,
+11 648 owned texels): max |sdf| over the owned texels 1.62e-2 at 0 steps (flat triangles under a curved surface), 1.36e-4 after 3 steps; status histogram after 3
+steps [9 210, 2 438, 0, 0]."""
+import numpy as np
+import pytest
+import torch
+
+from tests.common import load_golden
+from tests.gpu_common import assert_bitwise
+from tests.test_gpu_mesh_attrs import BOUND, EPS, TOL, F, cell, env, oracle_twin, restate      # noqa: F401  (env: the module-scoped fixture, built once for both files)
+from tests.test_gpu_model import DEV
+
+pytestmark = pytest.mark.gpu
+_REF = {}
+
+
+def bake_reference(O, of, pos, tris, S, c, steps, max_move):
+    """ac_mesh_bake_texture in numpy fp32 (every operation rounds once, in the kernel's order) around the oracle's stencil -> images like the kernel's"""
+    from avatarcraft_amd.geometry import atlas_owner, atlas_weights
+    pos, tris = np.asarray(pos, F), np.asarray(tris)
+    own = atlas_owner(len(tris), S, c)
+    _, w = atlas_weights(c)
+    ys, xs = np.nonzero(own >= 0)
+    t = own[ys, xs]
+    wt = w[ys % c, xs % c]                                                            # [N,3] (owned texels lie inside the R c square)
+    P = pos[tris[t]]                                                                  # [N,3 corners,3]
+    p = (wt[:, 0:1] * P[:, 0] + wt[:, 1:2] * P[:, 1]) + wt[:, 2:3] * P[:, 2]
+    assert p.dtype == F
+    r = restate(O, of, p, steps, max_move)
+    out = dict(rgb=np.zeros((S, S, 3), F), normals=np.zeros((S, S, 3), F), sdf=np.zeros((S, S), F), status=np.zeros((S, S), np.uint8), owner=own,
+               start=np.clip(p, F(-BOUND), F(BOUND)), texels=(ys, xs))
+    for k in ("rgb", "normals", "sdf", "status"):
+        out[k][ys, xs] = r[k]
+    return out
+
+
+def same(got, want, what):
+    for k in ("rgb", "normals", "sdf"):
+        assert_bitwise(got[k], want[k], f"{what}: {k}")
+    assert np.array_equal(got["status"].cpu().numpy(), want["status"]), what
+    own = got["owner"].cpu().numpy()
+    assert own.dtype == np.int32 and np.array_equal(own, want["owner"]), what
+    un = own < 0                                                                      # unowned texels: all-zero
+    for k in ("rgb", "normals", "sdf", "status"):
+        assert not got[k].cpu().numpy()[un].any(), (what, k)
+
+
+@pytest.fixture(scope="module")
+def meshes(env):
+    """positions ON the level set (ac_mesh_vertex_attrs, 3 steps: what extract_colored_mesh hands to the bake) and triangles of the 24^3 and 48^3 meshes"""
+    if "bake_meshes" not in env:
+        from avatarcraft_amd import nsr_ops
+        env["bake_meshes"] = {res: (nsr_ops.mesh_vertex_attrs(env["gf"], env["meshes"][res][0], BOUND, EPS, refine_steps=3, tol=TOL, max_move=cell(res))["positions"],
+                                    env["meshes"][res][1]) for res in (24, 48)}
+        assert env["bake_meshes"][24][1].shape == (2 * 184 - 4, 3) and env["bake_meshes"][48][1].shape == (2 * 812 - 4, 3)      # closed, genus 0
+    return env["bake_meshes"]
+
+
+def bake(env, pos, tris, S, c, steps, res=24, **kw):
+    from avatarcraft_amd import nsr_ops
+    return nsr_ops.mesh_bake_texture(env["gf"], pos, tris, S, c, BOUND, EPS, refine_steps=steps, tol=TOL, max_move=cell(res), want_normals=True, **kw)
+
+
+def reference(oracle, env, meshes, res, S, c, steps, T=None):
+    key = (res, S, c, steps, T)
+    if key not in _REF:
+        pos, tris = meshes[res]
+        _REF[key] = bake_reference(oracle, env["of"], pos.cpu().numpy(), tris.cpu().numpy()[:T], S, c, steps, cell(res))
+    return _REF[key]
+
+
+@pytest.mark.parametrize("steps", [0, 1, 3])
+def test_bit_for_bit_against_the_oracle(oracle, env, meshes, steps):
+    from avatarcraft_amd.geometry import atlas_owner
+    pos, tris = meshes[24]
+    T = tris.shape[0]
+    got = bake(env, pos, tris, 128, 8, steps)
+    want = reference(oracle, env, meshes, 24, 128, 8, steps)
+    same(got, want, f"24^3, S 128, c 8, {steps} steps")
+    own = got["owner"].cpu().numpy()
+    assert np.array_equal(own, atlas_owner(T, 128, 8)) and (own >= 0).sum() == (T // 2) * 64 and got["rgb"].shape == (128, 128, 3)
+    assert got["status"].dtype == torch.uint8 and got["owner"].dtype == torch.int32
+    plain = bake(env, pos, tris, 128, 8, steps)                                        # again: the same bits
+    assert all(torch.equal(plain[k], got[k]) for k in got)
+    from avatarcraft_amd import nsr_ops
+    lean = nsr_ops.mesh_bake_texture(env["gf"], pos, tris, 128, 8, BOUND, EPS, refine_steps=steps, tol=TOL, max_move=cell(24))
+    assert lean["normals"] is None and all(torch.equal(lean[k], got[k]) for k in ("rgb", "owner", "sdf", "status"))
+
+
+def test_corner_texels_equal_the_vertices(env, meshes):
+    """at refine_steps=0 a UV corner's weights are exactly (1,0,0), (0,1,0), (0,0,1): its texel is ac_mesh_vertex_attrs at that vertex, without the oracle"""
+    from avatarcraft_amd import nsr_ops
+    from avatarcraft_amd.geometry import atlas_layout
+    pos, tris = meshes[24]
+    S = 128
+    got = bake(env, pos, tris, S, 8, 0)
+    va = nsr_ops.mesh_vertex_attrs(env["gf"], pos.double(), BOUND, EPS, refine_steps=0, tol=TOL, max_move=cell(24))
+    assert torch.equal(va["positions"], pos)
+    uv = atlas_layout(tris.shape[0], S, 8)["uv"]
+    x = torch.from_numpy(np.rint(uv[..., 0] * S - 0.5).astype(np.int64)).to(DEV)
+    y = torch.from_numpy(np.rint((1.0 - uv[..., 1]) * S - 0.5).astype(np.int64)).to(DEV)
+    vid = tris.long()                                                                  # [T,3]: the vertex at each corner
+    assert torch.equal(got["owner"][y, x], torch.arange(tris.shape[0], device=DEV, dtype=torch.int32)[:, None].expand(-1, 3))
+    for k, vk in (("rgb", "rgb"), ("normals", "normals"), ("sdf", "sdf")):
+        assert torch.equal(got[k][y, x], va[vk][vid]), k
+
+
+def test_edges_of_the_launch(oracle, env, meshes):
+    pos, tris = meshes[24]
+    T = tris.shape[0]
+    full = bake(env, pos, tris, 128, 8, 3)
+    own = full["owner"]
+    # T odd: the last triangle dropped -- its half cell is nobody's now, every other texel keeps its bits
+    odd = bake(env, pos, tris[:T - 1].contiguous(), 128, 8, 3)
+    keep = own < T - 1
+    assert bool((odd["owner"][~keep] == -1).all()) and int((~keep & (own >= 0)).sum()) == 64 - 28
+    for k in full:
+        assert torch.equal(odd[k][keep], full[k][keep]), k
+        assert not bool(odd[k][~keep & (own >= 0)].ne(0).any()) or k == "owner", k
+    # T = 1: half a cell in the image's corner
+    one = bake(env, pos, tris[:1].contiguous(), 128, 8, 3)
+    assert int((one["owner"] == 0).sum()) == 28 and int((one["owner"] >= 0).sum()) == 28 and bool((one["owner"][8:] == -1).all())
+    first = own == 0
+    for k in full:
+        assert torch.equal(one[k][first], full[k][first]), k
+    assert not bool(one["rgb"][~first].ne(0).any()) and not bool(one["sdf"][~first].ne(0).any()) and not bool(one["status"][~first].ne(0).any())
+    # T = 0: nobody owns anything
+    none = bake(env, pos, tris[:0].contiguous(), 128, 8, 3)
+    assert bool((none["owner"] == -1).all()) and all(not bool(none[k].ne(0).any()) for k in ("rgb", "normals", "sdf", "status"))
+    # S = 100, c = 12: rows that are no multiple of 16 texels, a margin of 4 texels, cells that straddle the 16-texel tiles; 127 of the 128 triangles it holds
+    got = bake(env, pos, tris[:127].contiguous(), 100, 12, 3)
+    same(got, reference(oracle, env, meshes, 24, 100, 12, 3, T=127), "S 100, c 12")
+    assert bool((got["owner"][96:] == -1).all()) and bool((got["owner"][:, 96:] == -1).all())
+    # positions that start at a non-zero storage offset (4-byte aligned only)
+    shifted = torch.cat([torch.full((7, 3), 9.0, device=DEV), pos])[7:]
+    assert shifted.storage_offset() == 21 and shifted.is_contiguous()
+    off = bake(env, shifted, tris, 128, 8, 3)
+    assert all(torch.equal(off[k], full[k]) for k in full)
+
+
+def test_tiles_of_wholly_unowned_texels(oracle, env, meshes):
+    """the 48^3 mesh in S = 256, c = 8: 810 of the 1024 cells, so the last rows hold tiles without an owned texel (no field evaluation), and more than one
+    workgroup's worth of tiles"""
+    pos, tris = meshes[48]
+    assert tris.shape[0] == 1620
+    got = bake(env, pos, tris, 256, 8, 3, res=48)
+    same(got, reference(oracle, env, meshes, 48, 256, 8, 3), "48^3, S 256, c 8")
+    assert bool((got["owner"][208:] == -1).all()) and int((got["owner"] >= 0).sum()) == 810 * 64
+
+
+def test_projection_does_its_work(oracle, env, meshes):
+    """thresholds from the oracle restatement (module docstring: 1.62e-2 at 0 steps, 1.36e-4 after 3), with the vertex test's factor of two"""
+    r0, r3 = reference(oracle, env, meshes, 24, 128, 8, 0), reference(oracle, env, meshes, 24, 128, 8, 3)
+    owned = r0["owner"] >= 0
+    m0, m3 = float(np.abs(r0["sdf"][owned]).max()), float(np.abs(r3["sdf"][owned]).max())
+    hist = np.bincount(r3["status"][owned], minlength=4).tolist()
+    print("oracle: max |sdf| over owned texels", m0, "at 0 steps,", m3, "after 3; status histogram", hist)
+    assert m0 > 8.1e-3 and m3 < 2.72e-4 and hist[2] == 0 and hist[3] == 0
+    pos, tris = meshes[24]
+    g0, g3 = bake(env, pos, tris, 128, 8, 0), bake(env, pos, tris, 128, 8, 3)
+    o = g3["owner"] >= 0
+    k0, k3 = float(g0["sdf"][o].abs().max()), float(g3["sdf"][o].abs().max())
+    assert k3 < k0 and k0 > 8.1e-3 and k3 < 2.72e-4
+    assert not bool(((g3["status"] == 2) | (g3["status"] == 3))[o].any())
+    assert torch.bincount(g3["status"][o].long(), minlength=4).tolist() == hist
+
+
+def test_view_directions(oracle):
+    """a field with view directions: the colour seen along -normal, bit for bit at refine_steps=1"""
+    from avatarcraft_amd import nsr_ops
+    from tests.test_gpu_viewdirs import viewdirs_net
+    g = load_golden("viewdirs.npz")
+    net = viewdirs_net(g)
+    of = oracle_twin(oracle, net, g["offsets"], g["per_level_scale"])
+    assert of.has_viewdirs and net._field().has_viewdirs
+    m = net.extract_colored_mesh(BOUND, 24, return_torch=True)
+    pos, tris = m["vertices"].float(), m["triangles"]
+    T = tris.shape[0]
+    assert 16 < T <= 512
+    got = nsr_ops.mesh_bake_texture(net._field(), pos, tris, 128, 8, BOUND, EPS, refine_steps=1, tol=TOL, max_move=cell(24), want_normals=True)
+    same(got, bake_reference(oracle, of, pos.cpu().numpy(), tris.cpu().numpy(), 128, 8, 1, cell(24)), "dirs = -normal")
+
+
+def test_end_to_end(env, tmp_path):
+    from avatarcraft_amd import drivers, nsr_ops
+    from avatarcraft_amd.geometry import atlas_layout, save_ply
+    from tests.test_texture_atlas_host import read_obj, read_png
+    net = env["net"]
+    m = net.extract_textured_mesh(BOUND, 48, texture_size=256, return_torch=True)
+    c = net.extract_colored_mesh(BOUND, 48, return_torch=True)
+    assert set(m) == set(c) | {"uv", "texture", "owner", "texel_sdf", "texel_status"} and all(torch.equal(m[k], c[k]) for k in c)
+    T = m["triangles"].shape[0]
+    lay = atlas_layout(T, 256)
+    assert lay["cell"] == 8 and np.array_equal(m["uv"].cpu().numpy(), lay["uv"]) and m["texture"].dtype == torch.uint8 and m["texture"].shape == (256, 256, 3)
+    b = nsr_ops.mesh_bake_texture(net._field(), c["vertices"].float(), c["triangles"], 256, 8, BOUND, EPS, refine_steps=3, tol=TOL, max_move=cell(48))
+    assert torch.equal(m["texture"], torch.floor(b["rgb"].clamp(0.0, 1.0) * 255.0 + 0.5).to(torch.uint8))
+    assert torch.equal(m["owner"], b["owner"]) and torch.equal(m["texel_sdf"], b["sdf"]) and torch.equal(m["texel_status"], b["status"])
+    assert bool((m["texture"][m["owner"] < 0] == 0).all()) and int(m["texture"][m["owner"] >= 0].max()) > 0
+    d = drivers.export_mesh(net, str(tmp_path / "a.obj"), bound=BOUND, resolution=48, texture_size=256)
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["a.mtl", "a.obj", "a.png"]
+    assert all(isinstance(x, np.ndarray) for x in d.values()) and np.array_equal(d["texture"], m["texture"].cpu().numpy())
+    assert np.array_equal(read_png(str(tmp_path / "a.png")), d["texture"])
+    o = read_obj(str(tmp_path / "a.obj"))
+    assert np.array_equal(o["v"], d["vertices"]) and np.array_equal(o["f"][..., 0], d["triangles"] + 1) and np.array_equal(o["vt"], lay["uv"].reshape(-1, 2))
+    assert "map_Kd a.png" in (tmp_path / "a.mtl").read_text()
+    # every other suffix: the coloured PLY, byte for byte what save_ply writes from extract_colored_mesh
+    drivers.export_mesh(net, str(tmp_path / "a.ply"), bound=BOUND, resolution=48)
+    cn = net.extract_colored_mesh(BOUND, 48)
+    save_ply(str(tmp_path / "b.ply"), cn["vertices"], cn["triangles"], normals=cn["normals"], colors=cn["colors"])
+    assert (tmp_path / "a.ply").read_bytes() == (tmp_path / "b.ply").read_bytes()
+
+
+def test_errors_before_any_launch(env, meshes):
+    from avatarcraft_amd import nsr_ops
+    pos, tris = meshes[24]
+    run = lambda p, t, S, c, **kw: nsr_ops.mesh_bake_texture(env["gf"], p, t, S, c, BOUND, EPS, **kw)
+    with pytest.raises(RuntimeError, match="cell 7 < 8"):
+        run(pos, tris, 128, 7)
+    with pytest.raises(RuntimeError, match=r"364 triangles.*holds 2 \(size / cell\)\^2 = 288"):
+        run(pos, tris, 128, 10)
+    with pytest.raises(RuntimeError, match="do not fit"):
+        run(pos, tris, 64, None)
+    with pytest.raises(RuntimeError, match="size 4 outside cell"):
+        run(pos, tris[:0].contiguous(), 4, 8)
+    with pytest.raises(RuntimeError, match="refine_steps outside 0..16"):
+        run(pos, tris, 128, 8, refine_steps=17)
+    with pytest.raises(RuntimeError, match="CUDA tensor"):
+        run(pos.cpu(), tris, 128, 8)
+    with pytest.raises(RuntimeError, match="CUDA tensor"):
+        run(pos, tris.cpu(), 128, 8)
+    with pytest.raises(RuntimeError, match="float32"):
+        run(pos.double(), tris, 128, 8)
+    bad = tris.clone(); bad[5, 1] = pos.shape[0]                                       # an index equal to V: the wrapper's check, nothing is launched
+    with pytest.raises(RuntimeError, match=r"outside \[0, 184\); nothing was launched"):
+        run(pos, bad, 128, 8)
+    bad[5, 1] = -1
+    with pytest.raises(RuntimeError, match="nothing was launched"):
+        run(pos, bad, 128, 8)
+    with pytest.raises(RuntimeError, match="too|fit|holds"):
+        env["net"].extract_textured_mesh(BOUND, 48, texture_size=64)
