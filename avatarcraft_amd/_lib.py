@@ -76,6 +76,10 @@ class ac_atlas_opts(C.Structure):
     _fields_ = [("size", u32), ("cell", u32)]
 
 
+class ac_mesh_pose_opts(C.Structure):
+    _fields_ = [("iters", i32), ("tol", f32)]
+
+
 _SIGS = {
     "ac_version": ([], C.c_int),
     "ac_last_error": ([], C.c_char_p),
@@ -164,6 +168,10 @@ _SIGS = {
     "ac_marching_cubes_emit": ([vp, u32, u32, u32, f32, vp, C.c_size_t, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, u32, vp, u32, vp], C.c_int),
     "ac_mesh_vertex_attrs": ([C.POINTER(ac_field), vp, u32, vp, C.POINTER(ac_mesh_attr_opts), vp, vp, vp, vp, vp, vp], C.c_int),
     "ac_mesh_bake_texture": ([C.POINTER(ac_field), vp, u32, vp, u32, C.POINTER(ac_atlas_opts), C.POINTER(ac_mesh_attr_opts), vp, vp, vp, vp, vp, vp], C.c_int),
+    "ac_mesh_bind_scratch": ([u32, u32], C.c_size_t),
+    "ac_mesh_bind": ([vp, u32, vp, u32, vp, u32, vp, vp, vp, vp, vp, C.c_size_t, vp], C.c_int),
+    "ac_mesh_pose_scratch": ([u32], C.c_size_t),
+    "ac_mesh_pose": ([vp, vp, u32, vp, vp, C.POINTER(ac_warp_mesh), C.POINTER(ac_mesh_pose_opts), vp, C.c_size_t, vp, vp, vp, vp, vp, vp], C.c_int),
     "ac_density_grid_update_scratch": ([u32], C.c_size_t),
     "ac_density_grid_update": ([C.POINTER(ac_field), vp, u32, f32, f32, f32, vp, vp, vp, C.c_size_t, vp], C.c_int),
     "ac_table_to_half": ([vp, u32, vp, vp, vp], C.c_int),

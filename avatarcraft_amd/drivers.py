@@ -1,7 +1,8 @@
 """The two inference drivers of the reference as functions (no file I/O, no option parsing): the main loops of render_canonical.py:38-99
 (360-degree views of the canonical avatar, body and head rings) and render_warp.py:40-125 (SMPL-driven animation / shape
 interpolation through the posed-space renderer), plus the camera of the latter, SMPLDataset.gen_rays_pose (utils/SMPLDataset.py:86-103); and the one
-driver that does write a file: export_mesh, the coloured form of the trainer's extract_geometry + save_mesh (stylize.py:263-269)."""
+drivers that do write files: export_mesh, the coloured form of the trainer's extract_geometry + save_mesh (stylize.py:263-269), and export_animation, the
+same mesh posed frame by frame (render_warp.py's sequence as geometry instead of pixels)."""
 import numpy as np
 import torch
 
@@ -151,3 +152,66 @@ def export_mesh(net, path, bound=NSR_BOUND, resolution=512, **kw):
     mesh = net.extract_colored_mesh(bound, resolution, **kw)
     save_ply(path, mesh["vertices"], mesh["triangles"], normals=mesh["normals"], colors=mesh.get("colors"))
     return mesh
+
+
+def animation_paths(out_pattern):
+    """the files of export_animation for a pattern like "out/frame_%04d.obj": (kind "obj" | "ply", frame path function, shared .mtl path, shared .png path).
+    The shared material / texture take the pattern's stem without its frame directive and the separators around it ("out/frame.mtl", "out/frame.png";
+    "texture" if nothing is left); a .ply sequence has neither (None)."""
+    import os
+    import re
+    pat = str(out_pattern)
+    try:
+        differ = pat % 0 != pat % 1
+    except (TypeError, ValueError):
+        differ = False
+    if not differ:
+        raise ValueError(f"export_animation: out_pattern {pat!r} needs one integer directive such as %04d")
+    ext = os.path.splitext(pat)[1].lower()
+    if ext not in (".obj", ".ply"):
+        raise ValueError(f"export_animation: out_pattern {pat!r} must end in .obj (textured) or .ply (vertex colours)")
+    frame = lambda i: pat % int(i)
+    if ext == ".ply":
+        return "ply", frame, None, None
+    d, base = os.path.split(os.path.splitext(pat)[0])
+    stem = re.sub(r"%[0-9]*d", "", base).strip("_-. ") or "texture"
+    return "obj", frame, os.path.join(d, stem + ".mtl"), os.path.join(d, stem + ".png")
+
+
+def export_animation(net, body_model, poses=None, shape_from=None, shape_to=None, out_pattern="frame_%04d.obj", render_type=None, bound=NSR_BOUND,
+                     resolution=512, iters=3, tol=1e-5, max_frames=100, device="cuda", rank=None, world=None, **kw):
+    """the animated avatar as GEOMETRY: the canonical mesh extracted (and, for .obj, its texture baked) ONCE, bound to the SMPL guide once, then only its
+    vertices and normals moved per frame of calc_local_trans (net.pose_mesh: ac_mesh_pose) -- every frame has the same triangles, UVs and texture.
+    poses [F,72] (render_type "animate") or shape_from / shape_to [1,10] ("interp_shape"; render_type None picks by which is given).
+    out_pattern ending in .obj: frame files (geometry.save_obj) that all reference ONE material and ONE texture image, written before the first frame
+    (animation_paths names them); ending in .ply: binary PLYs with vertex normals and colours.  **kw goes to extract_textured_mesh / extract_colored_mesh
+    (texture_size, threshold, refine_steps ...); iters / tol to pose_mesh.
+    yields (frame index, posed mesh dict of pose_mesh); rank / world: this process writes the frames shard_indices(n_frames, rank, world) like
+    render_animation (the shared files are written by every rank with the same content)."""
+    import os
+    from .geometry import canonical_guide, save_mtl, save_obj, save_ply, save_png
+    kind, frame_path, mtl, png = animation_paths(out_pattern)
+    if render_type is None:
+        render_type = "animate" if poses is not None else "interp_shape"
+    world_verts, Ts, n_frames = calc_local_trans(body_model, render_type=render_type, poses=poses, shape_from=shape_from, shape_to=shape_to,
+                                                 max_frames=max_frames)
+    faces = np.asarray(body_model.faces)[:, :3]
+    mine = list(shard_indices(n_frames, rank, world))
+    mesh = net.extract_textured_mesh(bound, resolution, **kw) if kind == "obj" else net.extract_colored_mesh(bound, resolution, **kw)
+    if kind == "obj":
+        save_png(png, mesh["texture"])
+        save_mtl(mtl, os.path.basename(png))
+    guide = dict(faces=faces, canonical=canonical_guide(world_verts[0], Ts[0])) if n_frames else None
+    # one WarpMesh per frame, the next frame's upload + culling structure prepared beside the current frame's searches (nsr_ops.warp_mesh_sequence)
+    if torch.device(device).type == "cuda":
+        from . import nsr_ops
+        meshes = nsr_ops.warp_mesh_sequence(((world_verts[i], Ts[i]) for i in mine), faces, device)
+    else:
+        meshes = (None for _ in mine)
+    for i, wm in zip(mine, meshes):
+        posed = net.pose_mesh(mesh, guide, wm if wm is not None else world_verts[i], Ts[i], iters=iters, tol=tol)
+        if kind == "obj":
+            save_obj(frame_path(i), posed["vertices"], posed["triangles"], posed["uv"], normals=posed.get("normals"), mtllib=os.path.basename(mtl))
+        else:
+            save_ply(frame_path(i), posed["vertices"], posed["triangles"], normals=posed.get("normals"), colors=posed.get("colors"))
+        yield i, posed

@@ -109,6 +109,32 @@ def save_ply(path, vertices, triangles, normals=None, colors=None):
         fh.write(vert.tobytes()); fh.write(face.tobytes())
 
 
+def canonical_guide(world_verts, Ts):
+    """the SMPL guide in the canonical space of the field: (inv(Ts[i]) @ (v_i, 1))[:3] per vertex in fp64, cast to fp32 -- the point the inverse warp sends a
+    posed guide vertex to (no homogeneous division, like ray_utils.warp_samples_to_canonical).  world_verts [Vg,3], Ts [>= Vg,4,4] of ANY one frame
+    (smpl.calc_local_trans): the result does not depend on the frame.  numpy."""
+    import numpy as np
+    v = np.asarray(world_verts.detach().cpu().numpy() if isinstance(world_verts, torch.Tensor) else world_verts, dtype=np.float64).reshape(-1, 3)
+    T = np.asarray(Ts.detach().cpu().numpy() if isinstance(Ts, torch.Tensor) else Ts, dtype=np.float64).reshape(-1, 4, 4)
+    if len(T) < len(v):
+        raise ValueError("canonical_guide: Ts must hold one 4x4 per vertex")
+    h = np.concatenate([v, np.ones((len(v), 1))], axis=1)
+    return np.einsum("vij,vj->vi", np.linalg.inv(T[:len(v)]), h)[:, :3].astype(np.float32)
+
+
+def skin_weights(bind, faces, lbs_weights):
+    """a rig for users who pose the exported mesh elsewhere: per mesh vertex sum_k bary_k * lbs_weights[faces[face_id][k]] -> [V,J] float64.  bind: the dict of
+    nsr_ops.mesh_bind (face_id [V], bary [V,3]; tensors or arrays), faces [F,3] of the guide, lbs_weights [Vg,J] (SMPL's `weights`).  Rows sum to what
+    the guide's rows sum to (1) up to the rounding of the barycentrics.  numpy."""
+    import numpy as np
+    arr = lambda a, dt: np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=dt)
+    fid, bc = arr(bind["face_id"], np.int64).reshape(-1), arr(bind["bary"], np.float64).reshape(-1, 3)
+    f, w = arr(faces, np.int64)[:, :3], arr(lbs_weights, np.float64)
+    if len(fid) and (fid.min() < 0 or fid.max() >= len(f)):
+        raise ValueError("skin_weights: a binding face outside the guide's faces")
+    return np.einsum("vk,vkj->vj", bc, w[f[fid]])
+
+
 # ---------------------------------------------------------------------------------------------------- texture atlas (closed form; the kernel restates it in integers)
 # The S x S texture is cut into R x R square cells of c x c texels (R = S // c; texels beyond R c belong to nobody).  Triangle t lives in cell k = t >> 1, at
 # column k % R and row k // R, in half h = t & 1: texel (i, j) of a cell -- i along x, centre at (i + 0.5, j + 0.5) -- belongs to half 0 iff i + j <= c - 2.
@@ -203,9 +229,16 @@ def save_png(path, rgb8):
                  + chunk(b"IEND", b""))
 
 
-def save_obj(path, vertices, triangles, uv, normals=None, texture=None):
+def save_mtl(path, texture):
+    """the material file save_obj references: one material `baked` whose diffuse map is the image `texture` (a file name next to the .mtl)"""
+    with open(path, "w") as fh:
+        fh.write(f"newmtl baked\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {texture}\n")
+
+
+def save_obj(path, vertices, triangles, uv, normals=None, texture=None, mtllib=None):
     """Wavefront OBJ: `v` per vertex, `vt` three per triangle (uv [T,3,2], atlas_layout's), `vn` per vertex, `f a/ta/na b/tb/nb c/tc/nc` (`a/ta` without normals),
     1-based; triangle t uses vt 3t+1 .. 3t+3.  texture: the image's file name -- then a sibling .mtl (same stem) with map_Kd is written and referenced.
+    mtllib: instead, the file name of a material file that exists already (save_mtl) and is only referenced -- the frames of an animation share one.
     Numbers are written with repr, so they read back to the same doubles."""
     import os
     import numpy as np
@@ -215,10 +248,13 @@ def save_obj(path, vertices, triangles, uv, normals=None, texture=None):
         raise ValueError("save_obj: uv must be [T,3,2]")
     out = []
     stem = os.path.splitext(path)[0]
+    if texture is not None and mtllib is not None:
+        raise ValueError("save_obj: texture (write a sibling .mtl) or mtllib (reference an existing one), not both")
     if texture is not None:
-        with open(stem + ".mtl", "w") as fh:
-            fh.write(f"newmtl baked\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {texture}\n")
+        save_mtl(stem + ".mtl", texture)
         out += [f"mtllib {os.path.basename(stem)}.mtl", "usemtl baked"]
+    if mtllib is not None:
+        out += [f"mtllib {mtllib}", "usemtl baked"]
     out += ["v %r %r %r" % tuple(r) for r in v.tolist()]
     out += ["vt %r %r" % tuple(r) for r in w.tolist()]
     if normals is not None:

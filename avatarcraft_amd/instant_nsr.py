@@ -1119,6 +1119,46 @@ class NeRFNetwork(NeRFRenderer):
         m["uv"] = torch.from_numpy(lay["uv"]).to(tex.device) if return_torch else lay["uv"]
         return m
 
+    def pose_mesh(self, mesh, body_guide, verts, Ts=None, iters: int = 3, tol: float = 1e-5):
+        """the exported mesh in the pose of one frame: the dict of extract_colored_mesh / extract_textured_mesh with its `vertices` moved to where the posed
+        renderer draws them -- the p with W^-1(p) = vertex, W^-1 the SMPL-guided inverse warp of the frame (ac_mesh_pose: at most iters fixed-point steps from a
+        start bound to the canonical guide, iters + 1 closest-face searches) -- and its `normals` carried along by the blended transform's cofactor matrix.
+        body_guide: dict(faces [F,3] of the SMPL guide, and `canonical` [Vg,3], the guide in canonical space; absent: geometry.canonical_guide(verts, Ts), which
+        is frame independent, is stored there).  The binding of the mesh to the guide (ac_mesh_bind: once per mesh, pose independent) is stored as
+        body_guide["bind"] on the first call and reused: keep one body_guide per exported mesh.
+        verts [Vg,3], Ts [>= Vg,4,4]: the frame's posed guide and transforms (calc_local_trans), or verts = an nsr_ops.WarpMesh of the frame (Ts unused).
+        -> a shallow copy of `mesh` with vertices (float64, the input's convention), normals, and per vertex residual (float32: max-norm of W^-1(p) - vertex at
+        the returned p), status (uint8: 0 within tol, 1 iters used up, 2 not finite) and mask (uint8: 0 = farther from the guide than the renderer's mask
+        threshold, where it would draw nothing; kept and flagged); the export's own `status` (of the level-set projection) is replaced: read it from `mesh`.  triangles, uv, texture, colors and every other entry are the input's own objects.
+        numpy in, numpy out; device tensors in, device tensors out."""
+        from .geometry import canonical_guide
+        dev = self.encoder.embeddings.device
+        if dev.type != "cuda":
+            raise RuntimeError("pose_mesh needs the model on the GPU (there is no CPU path)")
+        as_torch = isinstance(mesh["vertices"], torch.Tensor)
+        to_dev = lambda a, dt: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))).to(device=dev, dtype=dt).contiguous()
+        wm = verts if isinstance(verts, nsr_ops.WarpMesh) else None
+        if "bind" not in body_guide:
+            if "canonical" not in body_guide:
+                if wm is not None:
+                    raise RuntimeError("pose_mesh: body_guide needs `canonical` when the frame arrives as a WarpMesh")
+                body_guide["canonical"] = canonical_guide(verts, Ts)
+            body_guide["bind"] = nsr_ops.mesh_bind(to_dev(mesh["vertices"], torch.float32), to_dev(body_guide["canonical"], torch.float32),
+                                                   to_dev(np.asarray(body_guide["faces"])[:, :3] if not isinstance(body_guide["faces"], torch.Tensor)
+                                                          else body_guide["faces"][:, :3], torch.int32))
+        if wm is None:
+            wm = nsr_ops.WarpMesh(verts, body_guide["faces"], Ts, dev)
+        n = mesh.get("normals")
+        with torch.no_grad():
+            a = nsr_ops.mesh_pose(to_dev(mesh["vertices"], torch.float32), None if n is None else to_dev(n, torch.float32), body_guide["bind"], wm,
+                                  iters=iters, tol=tol)
+        out = dict(mesh)
+        new = dict(vertices=a["positions"].double(), residual=a["residual"], status=a["status"], mask=a["mask"])
+        if n is not None:
+            new["normals"] = a["normals"]
+        out.update(new if as_torch else {k: x.cpu().numpy() for k, x in new.items()})
+        return out
+
     # ------------------------------------------------------------------ occupancy grid of the ray marcher, reference :303-356
     def update_extra_state(self, bound, decay=0.95):
         """density grid for raymarching.march_rays_train / march_rays (only with cuda_ray=True, like the reference): the SDF on the 129^3

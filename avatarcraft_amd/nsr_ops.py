@@ -1326,6 +1326,80 @@ def mesh_bake_texture(field, positions, triangles, size, cell, bound, eps=FD_STE
     return out
 
 
+def mesh_bind(points, guide_verts, faces, accel=True):
+    """ac_mesh_bind: once per exported mesh, pose independent.  points [V,3] float32 (the mesh's canonical vertices), guide_verts [Vg,3] float32 (the SMPL guide
+    in canonical space: geometry.canonical_guide), faces [F,3] int32, all on one device.  -> dict(face_id [V] int32 the closest guide face, bary [V,3] float64 of
+    the closest point on it, dist2 [V] float64).  accel: search through the culling structure (built here) where it covers the guide; the same bits either way."""
+    for t in (points, guide_verts, faces):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError("mesh_bind: points, guide_verts and faces must be CUDA tensors")
+    points, guide_verts = _chk(points, "points"), _chk(guide_verts, "guide_verts")
+    if points.dim() != 2 or points.shape[1] != 3 or guide_verts.dim() != 2 or guide_verts.shape[1] != 3:
+        raise RuntimeError("mesh_bind: points and guide_verts must be [N,3]")
+    if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3 or not faces.is_contiguous() or faces.device != points.device:
+        raise RuntimeError("mesh_bind: faces must be a contiguous int32 [F,3] tensor on the device of points")
+    V, Vg, F, dev = points.shape[0], guide_verts.shape[0], faces.shape[0], points.device
+    if F == 0 or Vg == 0 or int(faces.min()) < 0 or int(faces.max()) >= Vg:
+        raise RuntimeError(f"mesh_bind: an empty guide or a face index outside [0, {Vg}); nothing was launched")
+    st = L.current_stream(dev)
+    acc = None
+    nbytes = int(L.lib().ac_warp_accel_bytes(F)) if accel else 0
+    if nbytes and V:
+        acc = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        L.check(L.lib().ac_warp_accel_build(guide_verts.data_ptr(), faces.data_ptr(), Vg, F, acc.data_ptr(), nbytes, st), "warp_accel_build")
+    out = dict(face_id=torch.empty(V, dtype=torch.int32, device=dev), bary=torch.empty((V, 3), dtype=torch.float64, device=dev),
+               dist2=torch.empty(V, dtype=torch.float64, device=dev))
+    need = int(L.lib().ac_mesh_bind_scratch(V, Vg))
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    L.check(L.lib().ac_mesh_bind(points.data_ptr(), V, guide_verts.data_ptr(), Vg, faces.data_ptr(), F, L.ptr(acc), out["face_id"].data_ptr(),
+                                 out["bary"].data_ptr(), out["dist2"].data_ptr(), scratch.data_ptr(), need, st), "mesh_bind")
+    return out
+
+
+def mesh_pose(points, normals, bind, mesh, iters=3, tol=1e-5, want=("residual", "status", "mask")):
+    """ac_mesh_pose: once per frame.  points [V,3] float32 canonical vertices, normals [V,3] float32 canonical normals or None, bind = mesh_bind's dict (face_id,
+    bary), mesh = the frame's WarpMesh (posed guide, faces, Ts, culling structure or none).  Every vertex iterates p <- A(p) c + t(p) / kappa(p) from the bound
+    start until W^-1(p) is within tol of c (max norm), at most iters times (iters + 1 closest-face searches).
+    -> dict(positions [V,3], normals [V,3] | None, residual [V], status [V] uint8: 0 within tol, 1 iters used up (read residual), 2 not finite, mask [V] uint8:
+    0 = farther from the guide than the renderer's mask threshold -- kept and flagged); `want` names the optional ones to return (the others are None).
+    The binding's faces are checked on the device BEFORE the launch: RuntimeError for one outside [0, F)."""
+    if not isinstance(mesh, WarpMesh):
+        raise RuntimeError("mesh_pose: mesh must be an nsr_ops.WarpMesh")
+    face_id, bary = bind["face_id"], bind["bary"]
+    for t in (points, normals, face_id, bary):
+        if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda):
+            raise RuntimeError("mesh_pose: points, normals and the binding must be CUDA tensors")
+    points = _chk(points, "points")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise RuntimeError("mesh_pose: points must be [V,3]")
+    V, dev = points.shape[0], points.device
+    if normals is not None:
+        normals = _chk(normals, "normals", (V, 3))
+    if face_id.dtype != torch.int32 or tuple(face_id.shape) != (V,) or not face_id.is_contiguous():
+        raise RuntimeError("mesh_pose: bind['face_id'] must be a contiguous int32 [V] tensor")
+    if bary.dtype != torch.float64 or tuple(bary.shape) != (V, 3) or not bary.is_contiguous():
+        raise RuntimeError("mesh_pose: bind['bary'] must be a contiguous float64 [V,3] tensor")
+    if any(t is not None and t.device != mesh.verts.device for t in (points, normals, face_id, bary)):
+        raise RuntimeError("mesh_pose: every tensor must live on the mesh's device")
+    F = mesh.faces.shape[0]
+    if V and (int(face_id.min()) < 0 or int(face_id.max()) >= F):
+        raise RuntimeError(f"mesh_pose: a binding face outside [0, {F}); nothing was launched")
+    unknown = set(want) - {"residual", "status", "mask"}
+    if unknown:
+        raise ValueError(f"mesh_pose: unknown outputs {sorted(unknown)}")
+    opts = L.ac_mesh_pose_opts(int(iters), float(tol))
+    out = dict(positions=torch.empty((V, 3), dtype=_F32, device=dev), normals=torch.empty((V, 3), dtype=_F32, device=dev) if normals is not None else None,
+               residual=torch.empty(V, dtype=_F32, device=dev) if "residual" in want else None,
+               status=torch.empty(V, dtype=torch.uint8, device=dev) if "status" in want else None,
+               mask=torch.empty(V, dtype=torch.uint8, device=dev) if "mask" in want else None)
+    need = int(L.lib().ac_mesh_pose_scratch(V))
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    L.check(L.lib().ac_mesh_pose(points.data_ptr(), L.ptr(normals), V, face_id.data_ptr(), bary.data_ptr(), C.byref(mesh.c), C.byref(opts), scratch.data_ptr(),
+                                 need, out["positions"].data_ptr(), L.ptr(out["normals"]), L.ptr(out["residual"]), L.ptr(out["status"]), L.ptr(out["mask"]),
+                                 L.current_stream(dev)), "mesh_pose")
+    return out
+
+
 _DG_SCRATCH = {}
 
 

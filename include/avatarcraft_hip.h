@@ -729,6 +729,44 @@ int ac_render_rays_long_warped(const ac_field *field, const ac_render_opts *opts
                                const ac_warp_mesh *mesh, void *scratch, size_t scratch_bytes, const ac_render_out *out,
                                ac_stream_t stream);
 
+/* ---- posing the exported mesh: forward SMPL warp of its vertices (csrc/mesh_pose.hip; added entries, no struct of an existing call changes: ABI stays 10)
+ * The posed renderer draws { p : sdf(W^-1(p)) = 0 } with W^-1 the inverse warp of ac_warp_samples, so the posed position of a canonical vertex c is the p
+ * with W^-1(p) = c -- a fixed point of p <- fwd(M(p), c).  The mesh keeps its triangles, UVs and texture; only its vertices move.  fp64 unless stated:
+ *   Blended transform: a face with corners i0, i1, i2 and a point q on it; barycentrics bu, bv, bw by the formula of ac_warp_samples (d00 .. d21, den, bv, bw,
+ *     bu = 1 - bv - bw); M = T[i0] bu + T[i1] bv + T[i2] bw element by element in that order; M = [[A, t], [., kappa]], kappa = M[3][3].
+ *   Forward application: fwd(M, c) = A c + t / kappa, each coordinate (A[r][0] c0 + A[r][1] c1) + A[r][2] c2 + t[r] / kappa left to right, rounded to fp32:
+ *     the p that solves (M^-1 (p, 1))[:3] = c (it includes the reference's quirk that the Ts carry eye(4) / SMPL_SCALE).
+ *   Normal: n' = C n with C the cofactor matrix of A (the transposed adjugate), then n' / (1e-30 + |n'|), rounded to fp32.
+ *
+ * ac_mesh_bind, once per exported mesh (pose independent): for points [V,3] the closest face of the guide IN CANONICAL SPACE (guide_verts [Vg,3], faces [F,3];
+ *   the search of ac_warp_samples unchanged -- the culled form when accel, an ac_warp_accel_build of (guide_verts, faces), is given and F <= 16384, else the
+ *   exhaustive one; both give the same bits) -> face_id [V], bary [V,3] fp64 of the closest point (bu, bv, bw), optional dist2 [V] fp64.
+ *   scratch: ac_mesh_bind_scratch(V, Vg) bytes.
+ * ac_mesh_pose, once per frame: points [V,3] (c), optional canonical normals [V,3], the binding, the frame's mesh (posed verts, faces, T, accel, threshold as
+ *   ac_render_rays_warped takes them; near/far guide and seeds are not used), on one stream:
+ *     p_0 = fwd(M_bind, c), M_bind blended from the frame's T with the binding's face and barycentrics;
+ *     for k = 0 .. iters: search at p_k -> can_k = W^-1(p_k), closest point, face, dist^2;  r_k = max_j |can_k[j] - c[j]|;
+ *       a difference that is not finite: status 2, stop, keep p_k  |  r_k <= tol: status 0, stop  |  k == iters: status 1, stop  |  else p_{k+1} = fwd(M(p_k), c),
+ *       M(p_k) blended at the search's closest point and face.
+ *   A stopped vertex keeps its outputs and rides along: every launch covers all V vertices (lane = vertex), no atomics, no waits, iters + 1 searches.
+ *   Outputs: positions [V,3] (also the iteration's working buffer); optional normals_out [V,3] = Normal with the A of M(p) at the returned p (needs normals;
+ *   0 with status 2); optional residual [V] fp32 = the r of the returned position (+inf with status 2); optional status [V] u8; optional mask [V] u8 =
+ *   dist^2 < mesh.threshold at the returned position -- a vertex with mask 0 lies where the renderer draws nothing; it is kept and flagged.
+ *   scratch: ac_mesh_pose_scratch(V) bytes.  AC_ERR_BAD_ARG: iters outside 0 .. 16, tol not >= 0, a NULL required buffer, normals_out without normals.
+ *   PRECONDITION: every binding face lies in [0, F) and every face index in [0, V') -- nsr_ops.mesh_pose checks the binding on the device first (a binding
+ *   face outside the range is not read through: its vertex stays at c with status 2).
+ * Every value is bit-identical to the same arithmetic in numpy fp64 around the CPU oracle's orc_warp_samples (tests/test_gpu_mesh_pose.py). */
+typedef struct ac_mesh_pose_opts { int32_t iters; float tol; } ac_mesh_pose_opts;
+size_t ac_mesh_bind_scratch(uint32_t V, uint32_t Vg);
+int ac_mesh_bind(const float *points /*[V,3]*/, uint32_t V, const float *guide_verts /*[Vg,3]*/, uint32_t Vg, const int32_t *faces /*[F,3]*/, uint32_t F,
+                 const void *accel /*or NULL*/, int32_t *face_id /*[V]*/, double *bary /*[V,3]*/, double *dist2 /*optional [V]*/,
+                 void *scratch, size_t scratch_bytes, ac_stream_t stream);
+size_t ac_mesh_pose_scratch(uint32_t V);
+int ac_mesh_pose(const float *points /*[V,3]*/, const float *normals /*optional [V,3]*/, uint32_t V, const int32_t *face_id /*[V]*/, const double *bary /*[V,3]*/,
+                 const ac_warp_mesh *mesh, const ac_mesh_pose_opts *opts, void *scratch, size_t scratch_bytes,
+                 float *positions /*[V,3]*/, float *normals_out /*optional [V,3]*/, float *residual /*optional [V]*/, uint8_t *status /*optional [V]*/,
+                 uint8_t *mask /*optional [V]*/, ac_stream_t stream);
+
 /* ---- rendering from a half-precision hash table (opt-in, inference only) ----------------------------------------------------------------------------
  * The half table holds ONE dword per entry of the fp32 table [n_entries][2] (n_entries = field->offsets[16]): channel 0 as an IEEE binary16 in the low
  * half, channel 1 in the high half -- 4 bytes per entry instead of 8, the same level offsets.  ac_table_to_half makes it: every value is rounded to
