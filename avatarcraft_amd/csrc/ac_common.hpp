@@ -21,7 +21,8 @@ int warp_samples_accel_impl(const float *pts, const float *verts, const int32_t 
 // skip_masked rendering: ray_dead[r] = 1 if no sample of ray r (coarse samples coarse_pts [N, T0, 3] and everything between them) can be unmasked
 int warp_ray_cull(const float *coarse_pts, uint32_t N, uint32_t T0, double threshold, const void *accel, uint8_t *ray_dead, ac_stream_t stream);
 
-// the steps of a posed-space render that ac_render_rays_warped and ac_render_rays_long_warped share (render_fused.hip):
+// the steps of a posed-space render: the posed entries of both renderers run them through the one sequence render_posed (render_entry.hpp, which also
+// owns the mesh and scratch checks, the scratch view and the order of the phase marks); the steps themselves are defined once, in render_fused.hip:
 //   warped_coarse_pts: pts[n, i] = o + d * z_i of the coarse samples (unclamped), the input of the first closest-face search; `who` names the launch in an error;
 //   warp_any: one closest-face search + inverse warp of P points through the mesh's culling structure (or the exhaustive search without one);
 //             spr / seed_off: this search's columns [seed_off, seed_off + spr) of ac_warp_mesh.seed_faces;

@@ -32,6 +32,7 @@
 #include <mutex>
 #include <vector>
 #include "nsr_device.hpp"
+#include "render_entry.hpp"
 #include "render_worklist.hpp"      // (AC_XCD_CHUNK, AC_WORKLIST_POLICY and the XCD chunking live there, with the builder of the work lists)
 
 namespace {
@@ -157,42 +158,6 @@ __global__ __launch_bounds__(256) void coarse_pts_kernel(const float *__restrict
     float zi = near + span * lin_z[i];
     if (perturb) zi = zi + (noise[idx] - 0.5f) * sample_dist;
     pts[3 * (size_t)idx] = ox + dx * zi; pts[3 * (size_t)idx + 1] = oy + dy * zi; pts[3 * (size_t)idx + 2] = oz + dz * zi;
-}
-
-static int check_render_args(const char *who, const ac_render_opts *op, const float *rays_o, const float *rays_d, const float *noise,
-                             const float *lin_z, const float *lin_u, const ac_render_out *out)
-{
-    if (op->num_steps % 16 || op->upsample_steps % 16 || op->num_steps < 16 || op->num_steps > 64 ||
-        op->upsample_steps < 0 || op->num_steps + op->upsample_steps > MAXT) {
-        ac::set_error("%s: num_steps=%d upsample_steps=%d unsupported (multiples of 16, num_steps<=64, sum<=128)", who,
-                      op->num_steps, op->upsample_steps);
-        return AC_ERR_BAD_ARG;
-    }
-    if (!(op->fd_eps > 0.0f)) {      // the reference stops here too: `assert (gradient == gradient).all()` after dividing by eps = 0 (instant_nsr.py:274)
-        ac::set_error("%s: fd_eps = %g (normal_epsilon_ratio >= 1): the finite-difference normals divide by it, it must be positive", who, (double)op->fd_eps);
-        return AC_ERR_BAD_ARG;
-    }
-    if (op->n_rays <= 0) return AC_OK;
-    if (!rays_o || !rays_d || !lin_z || (op->upsample_steps && !lin_u) || (op->perturb && !noise) || !out->image ||
-        !out->weights_sum || !out->depth || !out->normal_map || !out->eik) {
-        ac::set_error("%s: NULL buffer", who); return AC_ERR_BAD_ARG;
-    }
-    return AC_OK;
-}
-
-static int fill_render_args(RenderArgs &a, const ac_field *field, const ac_render_opts *op, const float *rays_o, const float *rays_d,
-                            const float *bg, const float *noise, const float *lin_z, const float *lin_u, const ac_render_out *out)
-{
-    if (int rc = fill_render_common(a, field, op, rays_o, rays_d, bg, noise, lin_z, lin_u)) return rc;
-    a.out = *out;
-    a.pair_n = 0; a.ex_from = 0; a.ex_rows = op->n_rays;
-    if (op->precision != 0 && op->precision != 1) { ac::set_error("ac_render_opts: precision %d unknown (0 = exact, 1 = fast)", op->precision); return AC_ERR_BAD_ARG; }
-    if (op->skip_masked != 0 && op->skip_masked != 1) { ac::set_error("ac_render_opts: skip_masked must be 0 or 1"); return AC_ERR_BAD_ARG; }
-    a.skip_masked = op->skip_masked;
-    if (op->opacity_only != 0 && op->opacity_only != 1) { ac::set_error("ac_render_opts: opacity_only must be 0 or 1"); return AC_ERR_BAD_ARG; }
-    a.opacity_only = op->opacity_only;
-    if ((op->near_m != nullptr) != (op->far_m != nullptr)) { ac::set_error("ac_render_opts: near_m and far_m go together"); return AC_ERR_BAD_ARG; }
-    return AC_OK;
 }
 
 // Per-launch scratch of the dynamic hand-out: [8 XCDs] ticket counters, 32 bytes apart (256 B) | finished-workgroup counter | timed-out hand-offs |
@@ -339,10 +304,6 @@ static void launch_render_p(const RenderArgs &a, hipStream_t stream)
     }
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(BLOCK), lds_bytes, stream, b);
 }
-static bool wants_samples(const ac_render_out &o)
-{
-    return o.z_vals || o.weights || o.alpha || o.color || o.sdf || o.gradient || o.ss_inds || o.sort_index || o.sdf_out16 || o.pts || o.feat7;
-}
 // h16: a.table is the half table (the ac_*_h16 entries): the same instantiations of the kernel's second inclusion
 template <int MODE>
 static void launch_render(const RenderArgs &a, hipStream_t stream, bool h16 = false)
@@ -390,43 +351,23 @@ AC_API int ac_table_to_half(const float *table, uint32_t n_entries, void *table_
     return ac::check_launch("table_to_half");
 }
 
-// what the ac_*_h16 entries refuse on top of check_render_args (which holds them to the short window): the half table is an inference path
-static int check_h16_args(const char *who, const ac_field *field, const void *table_h16, const ac_render_opts *op, const ac_render_out *out)
-{
-    if (!field) { ac::set_error("%s: NULL field", who); return AC_ERR_BAD_ARG; }
-    if (!table_h16) { ac::set_error("%s: NULL half table (ac_table_to_half makes it: one dword per entry)", who); return AC_ERR_BAD_ARG; }
-    if (op->opacity_only) { ac::set_error("%s: opacity_only is not built for the half table (it serves the frozen avatar of a training step: fp32 entries)", who); return AC_ERR_BAD_ARG; }
-    if (out->feat7 || out->sdf_out16 || out->pts) {
-        ac::set_error("%s: feat7 / sdf_out16 / pts are the training extras: the half table is an inference path (nothing trains from it)", who);
-        return AC_ERR_BAD_ARG;
-    }
-    return AC_OK;
-}
-// fill_render_args with the half table in the table's place: field->table is not read
-static int fill_render_args_h16(RenderArgs &a, const ac_field *field, const void *table_h16, const ac_render_opts *op, const float *rays_o, const float *rays_d,
-                                const float *bg, const float *noise, const float *lin_z, const float *lin_u, const ac_render_out *out)
-{
-    ac_field f = *field;
-    f.table = static_cast<const float *>(table_h16);
-    if (int rc = fill_render_args(a, &f, op, rays_o, rays_d, bg, noise, lin_z, lin_u, out)) return rc;
-    a.table_bytes = (uint32_t)f.offsets[16] * 4u;               // the descriptor covers n_entries dwords: the hardware bounds check in the half table's unit
-    return AC_OK;
-}
+static_assert(SHORT_MAX_T == MAXT, "the short window is this kernel's slab");
 
 AC_API int ac_render_rays(const ac_field *field, const ac_render_opts *op, const float *rays_o, const float *rays_d,
                           const float *bg, const float *noise, const float *lin_z, const float *lin_u,
                           const ac_render_out *out, ac_stream_t stream)
 {
-    if (!op || !out) { ac::set_error("render_rays: NULL opts/out"); return AC_ERR_BAD_ARG; }
-    if (int rc = check_render_args("render_rays", op, rays_o, rays_d, noise, lin_z, lin_u, out)) return rc;
+    static const RenderEntry d("render_rays", 0);
+    const RayInputs in = { rays_o, rays_d, bg, noise, lin_z, lin_u };
+    if (int rc = check_render_entry(d, field, nullptr, op, in, nullptr, out)) return rc;
     if (op->n_rays <= 0) return AC_OK;
     RenderArgs a{};
-    if (int rc = fill_render_args(a, field, op, rays_o, rays_d, bg, noise, lin_z, lin_u, out)) return rc;
+    if (int rc = fill_entry_args(a, field, nullptr, op, in, out)) return rc;
 #ifdef AC_PROFILE
     a.prof = g_prof;
 #endif
     launch_render<MODE_FULL>(a, (hipStream_t)stream);
-    return ac::check_launch("render_rays");
+    return ac::check_launch(d.name);
 }
 
 // ac_render_rays from the half table: the same launch on the kernel's half-table inclusion
@@ -434,14 +375,14 @@ AC_API int ac_render_rays_h16(const ac_field *field, const void *table_h16, cons
                               const float *bg, const float *noise, const float *lin_z, const float *lin_u,
                               const ac_render_out *out, ac_stream_t stream)
 {
-    if (!op || !out) { ac::set_error("render_rays_h16: NULL opts/out"); return AC_ERR_BAD_ARG; }
-    if (int rc = check_render_args("render_rays_h16", op, rays_o, rays_d, noise, lin_z, lin_u, out)) return rc;
-    if (int rc = check_h16_args("render_rays_h16", field, table_h16, op, out)) return rc;
+    static const RenderEntry d("render_rays_h16", K_H16);
+    const RayInputs in = { rays_o, rays_d, bg, noise, lin_z, lin_u };
+    if (int rc = check_render_entry(d, field, table_h16, op, in, nullptr, out)) return rc;
     if (op->n_rays <= 0) return AC_OK;
     RenderArgs a{};
-    if (int rc = fill_render_args_h16(a, field, table_h16, op, rays_o, rays_d, bg, noise, lin_z, lin_u, out)) return rc;
+    if (int rc = fill_entry_args(a, field, table_h16, op, in, out)) return rc;
     launch_render<MODE_FULL>(a, (hipStream_t)stream, true);
-    return ac::check_launch("render_rays_h16");
+    return ac::check_launch(d.name);
 }
 
 // The same N rays rendered twice in one launch, with two draws of the jitter noise and two backgrounds: what one stylisation step does with net_style
@@ -455,18 +396,15 @@ AC_API int ac_render_rays_pair(const ac_field *field, const ac_render_opts *op, 
                                const float *bg2, const float *noise2, const float *lin_z, const float *lin_u,
                                const ac_render_out *out, ac_stream_t stream)
 {
-    if (!op || !out) { ac::set_error("render_rays_pair: NULL opts/out"); return AC_ERR_BAD_ARG; }
-    if (int rc = check_render_args("render_rays_pair", op, rays_o, rays_d, noise2, lin_z, lin_u, out)) return rc;
+    static const RenderEntry d("render_rays_pair", K_PAIR);
+    const RayInputs in = { rays_o, rays_d, bg2, noise2, lin_z, lin_u };
+    if (int rc = check_render_entry(d, field, nullptr, op, in, nullptr, out)) return rc;
     if (op->n_rays <= 0) return AC_OK;
-    if (op->n_rays > (1 << 29)) { ac::set_error("render_rays_pair: too many rays"); return AC_ERR_BAD_ARG; }
     RenderArgs a{};
-    if (int rc = fill_render_args(a, field, op, rays_o, rays_d, bg2, noise2, lin_z, lin_u, out)) return rc;
-    a.pair_n = op->n_rays; a.n_rays = 2 * op->n_rays; a.ex_from = op->n_rays; a.ex_rows = op->n_rays;
-#ifdef AC_PROFILE
-    a.prof = nullptr;
-#endif
+    if (int rc = fill_entry_args(a, field, nullptr, op, in, out)) return rc;
+    make_pair_args(a);
     launch_render<MODE_FULL>(a, (hipStream_t)stream);
-    return ac::check_launch("render_rays_pair");
+    return ac::check_launch(d.name);
 }
 
 // the sampling stage alone (coarse z, coarse sdf, NeuS up-sampling): what the reference computes under no_grad before the
@@ -474,32 +412,28 @@ AC_API int ac_render_rays_pair(const ac_field *field, const ac_render_opts *op, 
 AC_API int ac_sample_rays(const ac_field *field, const ac_render_opts *op, const float *rays_o, const float *rays_d, const float *noise,
                           const float *lin_z, const float *lin_u, float *z_vals, ac_stream_t stream)
 {
-    if (!op || !z_vals) { ac::set_error("sample_rays: NULL opts/z_vals"); return AC_ERR_BAD_ARG; }
-    ac_render_out dummy{};
-    float sink = 0.0f;                       // check_render_args wants the mandatory outputs non-NULL; this mode never writes them
-    dummy.image = dummy.weights_sum = dummy.depth = dummy.normal_map = dummy.eik = &sink;
-    if (int rc = check_render_args("sample_rays", op, rays_o, rays_d, noise, lin_z, lin_u, &dummy)) return rc;
+    static const RenderEntry d("sample_rays", K_SAMPLING);
+    const RayInputs in = { rays_o, rays_d, nullptr, noise, lin_z, lin_u };
+    if (int rc = check_render_entry(d, field, nullptr, op, in, nullptr, nullptr, z_vals)) return rc;
     if (op->n_rays <= 0) return AC_OK;
     RenderArgs a{};
-    if (int rc = fill_render_args(a, field, op, rays_o, rays_d, nullptr, noise, lin_z, lin_u, &dummy)) return rc;
-    a.out = ac_render_out{};
+    if (int rc = fill_entry_args(a, field, nullptr, op, in, nullptr)) return rc;
     a.zbuf = z_vals;
     launch_render<MODE_UPSAMPLE>(a, (hipStream_t)stream);
-    return ac::check_launch("sample_rays");
+    return ac::check_launch(d.name);
 }
 
 // scratch layout of ac_render_rays_warped (byte offsets, 256-byte aligned): near_m, far_m [N] f32; pts, can [N,T,3] f32;
-// mask [N,T] u8; zbuf [N,T] f32
+// mask [N,T] u8; zbuf [N,T] f32; behind the six documented segments: ray_dead [N] u8 (skip_masked)
 AC_API size_t ac_render_rays_warped_scratch(int32_t n_rays, int32_t T, size_t offs[6])
 {
-    const size_t N = n_rays > 0 ? (size_t)n_rays : 0, NT = N * (size_t)(T > 0 ? T : 0);
-    const size_t sz[6] = { N * 4, N * 4, NT * 12, NT * 12, NT, NT * 4 };
-    size_t o = 0;
-    for (int i = 0; i < 6; ++i) { if (offs) offs[i] = o; o += (sz[i] + 255) & ~(size_t)255; }
-    return o + ((N + 255) & ~(size_t)255);                     // + ray_dead [N] u8 (skip_masked), behind the six documented segments
+    size_t o[7];
+    const size_t need = warped_scratch_offsets(n_rays, T, o);
+    if (offs) std::copy(o, o + 6, offs);
+    return need;
 }
 
-// the helpers of the posed sequence below; ac:: linkage (ac_common.hpp) because ac_render_rays_long_warped (render_long.hip) chains the same steps
+// the helpers of the posed sequence (render_entry.hpp: render_posed); ac:: linkage (ac_common.hpp) because ac_render_rays_long_warped (render_long.hip) runs it too
 int ac::warped_coarse_pts(const char *who, const float *rays_o, const float *rays_d, const float *near_m, const float *far_m, const float *lin_z, const float *noise,
                           int n_rays, int T0, float bound, int perturb, float *pts, hipStream_t st)
 {
@@ -519,10 +453,9 @@ int ac::warp_any(const ac_warp_mesh *m, const float *pts, uint32_t P, float *can
     return ac_warp_samples(pts, m->verts, m->faces, m->T, P, m->V, m->F, m->threshold, nullptr, can, nullptr, nullptr, nullptr, mask, stream);
 }
 
-// Measurement hook (bench.py's posed-frame roofline): with ac_debug_warped_phases(1) every ac_render_rays_warped call records HIP events on its stream
+// Measurement hook (bench.py's posed-frame roofline): with ac_debug_warped_phases(1) every posed render (render_posed) records HIP events on its stream
 // at the phase boundaries -- [0] start, [1] near / far + coarse points + ray cull, [2] first warp search, [3] up-sampling pass, [4] second warp search,
 // [5] final pass -- and ac_debug_warped_phase_ms() returns the five intervals of the LAST call in ms (it waits for that call).  Off by default.
-// (ac_render_rays_long_warped marks the same boundaries.)
 namespace {
 hipEvent_t g_phase_ev[6];
 int g_phase_on = 0, g_phase_have = 0;
@@ -542,69 +475,17 @@ AC_API int ac_debug_warped_phase_ms(float out[5])
     return AC_OK;
 }
 
-// the posed sequence of ac_render_rays_warped; table_h16 non-NULL (ac_render_rays_warped_h16): both render passes gather from the half table
-static int render_rays_warped_any(const ac_field *field, const void *table_h16, const ac_render_opts *op, const float *rays_o, const float *rays_d,
-                                  const float *bg, const float *noise, const float *lin_z, const float *lin_u,
-                                  const ac_warp_mesh *mesh, void *scratch, size_t scratch_bytes, const ac_render_out *out,
-                                  ac_stream_t stream)
+// the posed entries of the short window: render_posed on this kernel's two halves; h16: both passes gather from the half table
+static int render_rays_warped_any(const RenderEntry &d, const ac_field *field, const void *table_h16, const ac_render_opts *op, const RayInputs &in,
+                                  const ac_warp_mesh *mesh, void *scratch, size_t scratch_bytes, const ac_render_out *out, ac_stream_t stream)
 {
-    const bool h16 = table_h16 != nullptr;
-    if (!mesh->verts || !mesh->faces || !mesh->T || mesh->V == 0 || mesh->F == 0) {
-        ac::set_error("render_rays_warped: NULL mesh buffer or empty mesh"); return AC_ERR_BAD_ARG;
-    }
-    const int N = op->n_rays, T0 = op->num_steps, T = T0 + op->upsample_steps;
-    size_t offs[6];
-    const size_t need = ac_render_rays_warped_scratch(N, T, offs);
-    if (!scratch || scratch_bytes < need) {
-        ac::set_error("render_rays_warped: scratch of %zu bytes needed, %zu given", need, scratch_bytes); return AC_ERR_BAD_ARG;
-    }
-    char *sc = static_cast<char *>(scratch);
-    float *near_m = reinterpret_cast<float *>(sc + offs[0]), *far_m = reinterpret_cast<float *>(sc + offs[1]);
-    float *pts = reinterpret_cast<float *>(sc + offs[2]), *can = reinterpret_cast<float *>(sc + offs[3]);
-    uint8_t *mask = reinterpret_cast<uint8_t *>(sc + offs[4]);
-    float *zbuf = reinterpret_cast<float *>(sc + offs[5]);
-    const uint8_t *ray_dead = nullptr;
-    hipStream_t st = (hipStream_t)stream;
+    if (int rc = check_render_entry(d, field, table_h16, op, in, mesh, out)) return rc;
+    if (op->n_rays <= 0) return AC_OK;
     RenderArgs a{};
-    if (int rc = h16 ? fill_render_args_h16(a, field, table_h16, op, rays_o, rays_d, bg, noise, lin_z, lin_u, out)
-                     : fill_render_args(a, field, op, rays_o, rays_d, bg, noise, lin_z, lin_u, out)) return rc;
-    ac::warped_phase_mark(0, st);
-    if (mesh->use_mesh_guide) {
-        if (int rc = ac_mesh_near_far(rays_o, rays_d, mesh->verts, (uint32_t)N, mesh->V, mesh->geo_threshold, near_m, far_m, stream)) return rc;
-        a.near_m = near_m; a.far_m = far_m;
-    }
-    a.zbuf = zbuf; a.mid_pts = pts;
-    if (op->upsample_steps > 0) {                                 // coarse samples -> canonical space (:166-172)
-        if (int rc = ac::warped_coarse_pts("render_rays_warped (coarse points)", rays_o, rays_d, a.near_m, a.far_m, lin_z, noise, N, T0, op->bound, op->perturb, pts, st))
-            return rc;
-        if (op->skip_masked && mesh->accel) {                     // rays that cannot hold an unmasked sample: no search, no field evaluation
-            uint8_t *rdead = reinterpret_cast<uint8_t *>(sc + ac_render_rays_warped_scratch(N, T, nullptr) - (((size_t)N + 255) & ~(size_t)255));
-            if (int rc = ac::warp_ray_cull(pts, (uint32_t)N, (uint32_t)T0, mesh->threshold, mesh->accel, rdead, stream)) return rc;
-            ray_dead = rdead;
-        }
-        ac::warped_phase_mark(1, st);
-        if (int rc = ac::warp_any(mesh, pts, (uint32_t)(N * T0), can, mask, stream, 0, ray_dead, (uint32_t)T0, 0u)) return rc;
-    } else ac::warped_phase_mark(1, st);
-    ac::warped_phase_mark(2, st);
-    a.ext_pts = can;
-    a.ray_dead = ray_dead;
-    launch_render<MODE_UPSAMPLE>(a, st, h16);                     // coarse sdf, up-sampling, mid points (posed space)
-    if (int rc = ac::check_launch("render_rays_warped (up-sampling)")) return rc;
-    ac::warped_phase_mark(3, st);
-    // (skip_masked: the final pass does not evaluate masked-out samples, so the search may leave out those the cell grids prove masked)
-    if (int rc = ac::warp_any(mesh, pts, (uint32_t)(N * T), can, mask, stream, op->skip_masked, ray_dead, (uint32_t)T, (uint32_t)T0)) return rc;     // :198-203
-    ac::warped_phase_mark(4, st);
-    a.mask = mask;
-    launch_render<MODE_FINAL>(a, st, h16);
-    ac::warped_phase_mark(5, st);
-    return ac::check_launch("render_rays_warped");
-}
-
-static int check_warped_args(const char *who, const ac_render_opts *op, const float *rays_o, const float *rays_d, const float *noise, const float *lin_z,
-                             const float *lin_u, const ac_warp_mesh *mesh, const ac_render_out *out)
-{
-    if (!op || !out || !mesh) { ac::set_error("%s: NULL opts/out/mesh", who); return AC_ERR_BAD_ARG; }
-    return check_render_args(who, op, rays_o, rays_d, noise, lin_z, lin_u, out);
+    if (int rc = fill_entry_args(a, field, table_h16, op, in, out)) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    return render_posed(d, a, mesh, scratch, scratch_bytes, stream, [&](const RenderArgs &b) { launch_render<MODE_UPSAMPLE>(b, st, d.h16); },
+                        [&](const RenderArgs &b) { launch_render<MODE_FINAL>(b, st, d.h16); });
 }
 
 AC_API int ac_render_rays_warped(const ac_field *field, const ac_render_opts *op, const float *rays_o, const float *rays_d,
@@ -612,9 +493,8 @@ AC_API int ac_render_rays_warped(const ac_field *field, const ac_render_opts *op
                                  const ac_warp_mesh *mesh, void *scratch, size_t scratch_bytes, const ac_render_out *out,
                                  ac_stream_t stream)
 {
-    if (int rc = check_warped_args("render_rays_warped", op, rays_o, rays_d, noise, lin_z, lin_u, mesh, out)) return rc;
-    if (op->n_rays <= 0) return AC_OK;
-    return render_rays_warped_any(field, nullptr, op, rays_o, rays_d, bg, noise, lin_z, lin_u, mesh, scratch, scratch_bytes, out, stream);
+    static const RenderEntry d("render_rays_warped", K_POSED);
+    return render_rays_warped_any(d, field, nullptr, op, { rays_o, rays_d, bg, noise, lin_z, lin_u }, mesh, scratch, scratch_bytes, out, stream);
 }
 
 // ac_render_rays_warped from the half table (same scratch: ac_render_rays_warped_scratch)
@@ -623,10 +503,8 @@ AC_API int ac_render_rays_warped_h16(const ac_field *field, const void *table_h1
                                      const ac_warp_mesh *mesh, void *scratch, size_t scratch_bytes, const ac_render_out *out,
                                      ac_stream_t stream)
 {
-    if (int rc = check_warped_args("render_rays_warped_h16", op, rays_o, rays_d, noise, lin_z, lin_u, mesh, out)) return rc;
-    if (int rc = check_h16_args("render_rays_warped_h16", field, table_h16, op, out)) return rc;
-    if (op->n_rays <= 0) return AC_OK;
-    return render_rays_warped_any(field, table_h16, op, rays_o, rays_d, bg, noise, lin_z, lin_u, mesh, scratch, scratch_bytes, out, stream);
+    static const RenderEntry d("render_rays_warped_h16", K_POSED | K_H16);
+    return render_rays_warped_any(d, field, table_h16, op, { rays_o, rays_d, bg, noise, lin_z, lin_u }, mesh, scratch, scratch_bytes, out, stream);
 }
 
 static_assert((OFF_RWAVE + CF_OVERLAY) * sizeof(float) <= AC_FIELD_PREPARED_BYTES && OFF_C1F % 4 == 0 && OFF_B1 % 4 == 0 && OFF_RWAVE % 4 == 0, "the prepared image fits its buffer");

@@ -19,10 +19,11 @@
 #define AC_WPB 7
 #endif
 #include "nsr_device.hpp"
+#include "render_entry.hpp"
 
 namespace {
 
-constexpr int LONG_MAX_T = MAXT;
+static_assert(LONG_MAX_T == MAXT, "the long window is this kernel's slab");
 constexpr int NCH = MAXT / 64;          // 64-lane chunks of the up-sampling scans
 
 template <int MODE, bool FAST, bool EX, bool SH>
@@ -461,35 +462,6 @@ __global__ __launch_bounds__(BLOCK) void render_rays_long_kernel(const RenderArg
     }
 }
 
-static int check_long_args(const char *who, const ac_render_opts *op, const float *rays_o, const float *rays_d, const float *noise,
-                           const float *lin_z, const float *lin_u, bool posed = false)
-{
-    if (op->num_steps < 2 || op->upsample_steps < 0 || op->upsample_steps % 16 || op->num_steps + op->upsample_steps > LONG_MAX_T) {
-        ac::set_error("%s: num_steps=%d upsample_steps=%d unsupported (num_steps >= 2, upsample_steps >= 0 and a multiple of 16, "
-                      "num_steps + upsample_steps <= %d)", who, op->num_steps, op->upsample_steps, LONG_MAX_T);
-        return AC_ERR_BAD_ARG;
-    }
-    if (!(op->fd_eps > 0.0f)) {
-        ac::set_error("%s: fd_eps = %g (normal_epsilon_ratio >= 1): the finite-difference normals divide by it, it must be positive", who, (double)op->fd_eps);
-        return AC_ERR_BAD_ARG;
-    }
-    if (op->precision != 0 && op->precision != 1) { ac::set_error("%s: precision %d unknown (0 = exact, 1 = fast)", who, op->precision); return AC_ERR_BAD_ARG; }
-    if (op->opacity_only != 0 && op->opacity_only != 1) { ac::set_error("%s: opacity_only must be 0 or 1", who); return AC_ERR_BAD_ARG; }
-    if (op->opacity_only && posed) {
-        ac::set_error("%s: opacity_only is a canonical-space option of the long renderer (ac_render_rays_long); the posed entry evaluates the colour network", who);
-        return AC_ERR_BAD_ARG;
-    }
-    if (op->skip_masked != 0 && op->skip_masked != 1) { ac::set_error("%s: skip_masked must be 0 or 1", who); return AC_ERR_BAD_ARG; }
-    if (op->skip_masked && !posed) {
-        ac::set_error("%s: skip_masked is a posed-space option; this entry is canonical (posed: ac_render_rays_long_warped)", who); return AC_ERR_BAD_ARG;
-    }
-    if ((op->near_m != nullptr) != (op->far_m != nullptr)) { ac::set_error("%s: near_m and far_m go together", who); return AC_ERR_BAD_ARG; }
-    if (op->n_rays > 0 && (!rays_o || !rays_d || !lin_z || (op->upsample_steps && !lin_u) || (op->perturb && !noise))) {
-        ac::set_error("%s: NULL buffer", who); return AC_ERR_BAD_ARG;
-    }
-    return AC_OK;
-}
-
 template <int MODE, bool FAST, bool EX, bool SH>
 static void launch_long_p(const RenderArgs &a, hipStream_t stream)
 {
@@ -503,32 +475,19 @@ static void launch_long_p(const RenderArgs &a, hipStream_t stream)
     hipLaunchKernelGGL((render_rays_long_kernel<MODE, FAST, EX, SH>), dim3(blocks), dim3(BLOCK), lds_bytes, stream, a);
 }
 
-static bool long_wants_samples(const ac_render_out &o)
+// the training options of the canonical launch (pair launch, opacity_only, feat7) are compiled into its EX instantiations only
+template <int MODE>
+static void launch_long(const RenderArgs &a, hipStream_t st)
 {
-    return o.z_vals || o.weights || o.alpha || o.color || o.sdf || o.gradient || o.ss_inds || o.sort_index || o.sdf_out16 || o.pts;
-}
-
-// the stencil features exist per tile of 16 samples of one ray: only a count 16 divides has them (other counts gather again in the backward)
-static int check_long_feat7(const char *who, const ac_render_opts *op, const ac_render_out *out)
-{
-    const int T = op->num_steps + op->upsample_steps;
-    if (out->feat7 && T % 16) {
-        ac::set_error("%s: feat7 needs T = num_steps + upsample_steps a multiple of 16 (T = %d); at other counts pass NULL: ac_render_core_backward gathers again", who, T);
-        return AC_ERR_BAD_ARG;
+    if constexpr (MODE == MODE_UPSAMPLE) {                                      // (the sampling launch can export the sample indices)
+        if (!a.out.ss_inds && !a.out.sort_index) launch_long_p<MODE, false, false, false>(a, st);
+        else launch_long_p<MODE, false, true, false>(a, st);
+    } else {
+        const bool ex = wants_samples(a.out) || (MODE == MODE_FULL && (a.pair_n || a.opacity_only));
+        dispatch_variants(a.fast, ex, a.Wsh != nullptr, [&](auto fast, auto ex_, auto sh) {
+            launch_long_p<MODE, decltype(fast)::value, decltype(ex_)::value, decltype(sh)::value>(a, st);
+        });
     }
-    return AC_OK;
-}
-
-// the canonical launch: the training options (pair launch, opacity_only, feat7) are compiled into the EX instantiations only
-static int launch_long_full(const char *who, RenderArgs &a, const ac_render_opts *op, const ac_render_out *out, hipStream_t st)
-{
-    a.out = *out;
-    a.opacity_only = op->opacity_only;
-    const bool ex = long_wants_samples(a.out) || a.out.feat7 || a.pair_n || a.opacity_only;
-    dispatch_variants(a.fast, ex, a.Wsh != nullptr, [&](auto fast, auto ex_, auto sh) {
-        launch_long_p<MODE_FULL, decltype(fast)::value, decltype(ex_)::value, decltype(sh)::value>(a, st);
-    });
-    return ac::check_launch(who);
 }
 
 }  // namespace
@@ -537,14 +496,14 @@ AC_API int ac_render_rays_long(const ac_field *field, const ac_render_opts *op, 
                                const float *bg, const float *noise, const float *lin_z, const float *lin_u,
                                const ac_render_out *out, ac_stream_t stream)
 {
-    if (!op || !out) { ac::set_error("render_rays_long: NULL opts/out"); return AC_ERR_BAD_ARG; }
-    if (int rc = check_long_args("render_rays_long", op, rays_o, rays_d, noise, lin_z, lin_u)) return rc;
-    if (int rc = check_long_feat7("render_rays_long", op, out)) return rc;
+    static const RenderEntry d("render_rays_long", K_LONG);
+    const RayInputs in = { rays_o, rays_d, bg, noise, lin_z, lin_u };
+    if (int rc = check_render_entry(d, field, nullptr, op, in, nullptr, out)) return rc;
     if (op->n_rays <= 0) return AC_OK;
-    if (!out->image || !out->weights_sum || !out->depth || !out->normal_map || !out->eik) { ac::set_error("render_rays_long: NULL buffer"); return AC_ERR_BAD_ARG; }
     RenderArgs a{};
-    if (int rc = fill_render_common(a, field, op, rays_o, rays_d, bg, noise, lin_z, lin_u)) return rc;
-    if (int rc = launch_long_full("render_rays_long", a, op, out, (hipStream_t)stream)) return rc;
+    if (int rc = fill_entry_args(a, field, nullptr, op, in, out)) return rc;
+    launch_long<MODE_FULL>(a, (hipStream_t)stream);
+    if (int rc = ac::check_launch(d.name)) return rc;
     // gradient_error in the fixed order the other renderer's last workgroup uses (eikonal_reduce_kernel's): bit-identical
     if (out->eik_reduced) return ac_eikonal_reduce2(out->eik, op->n_rays, out->eik_reduced, stream);
     return AC_OK;
@@ -557,17 +516,15 @@ AC_API int ac_render_rays_long_pair(const ac_field *field, const ac_render_opts 
                                     const float *bg2, const float *noise2, const float *lin_z, const float *lin_u,
                                     const ac_render_out *out, ac_stream_t stream)
 {
-    const char *who = "render_rays_long_pair";
-    if (!op || !out) { ac::set_error("%s: NULL opts/out", who); return AC_ERR_BAD_ARG; }
-    if (int rc = check_long_args(who, op, rays_o, rays_d, noise2, lin_z, lin_u)) return rc;
-    if (int rc = check_long_feat7(who, op, out)) return rc;
+    static const RenderEntry d("render_rays_long_pair", K_LONG | K_PAIR);
+    const RayInputs in = { rays_o, rays_d, bg2, noise2, lin_z, lin_u };
+    if (int rc = check_render_entry(d, field, nullptr, op, in, nullptr, out)) return rc;
     if (op->n_rays <= 0) return AC_OK;
-    if (op->n_rays > (1 << 29)) { ac::set_error("%s: too many rays", who); return AC_ERR_BAD_ARG; }
-    if (!out->image || !out->weights_sum || !out->depth || !out->normal_map || !out->eik) { ac::set_error("%s: NULL buffer", who); return AC_ERR_BAD_ARG; }
     RenderArgs a{};
-    if (int rc = fill_render_common(a, field, op, rays_o, rays_d, bg2, noise2, lin_z, lin_u)) return rc;
-    a.pair_n = op->n_rays; a.n_rays = 2 * op->n_rays; a.ex_from = op->n_rays; a.ex_rows = op->n_rays;
-    if (int rc = launch_long_full(who, a, op, out, (hipStream_t)stream)) return rc;
+    if (int rc = fill_entry_args(a, field, nullptr, op, in, out)) return rc;
+    make_pair_args(a);
+    launch_long<MODE_FULL>(a, (hipStream_t)stream);
+    if (int rc = ac::check_launch(d.name)) return rc;
     if (out->eik_reduced) {
         if (int rc = ac_eikonal_reduce2(out->eik, op->n_rays, out->eik_reduced, stream)) return rc;
         return ac_eikonal_reduce2(out->eik + 2 * (size_t)op->n_rays, op->n_rays, out->eik_reduced + 2, stream);
@@ -578,79 +535,33 @@ AC_API int ac_render_rays_long_pair(const ac_field *field, const ac_render_opts 
 AC_API int ac_sample_rays_long(const ac_field *field, const ac_render_opts *op, const float *rays_o, const float *rays_d, const float *noise,
                                const float *lin_z, const float *lin_u, float *z_vals, ac_stream_t stream)
 {
-    if (!op || !z_vals) { ac::set_error("sample_rays_long: NULL opts/z_vals"); return AC_ERR_BAD_ARG; }
-    if (int rc = check_long_args("sample_rays_long", op, rays_o, rays_d, noise, lin_z, lin_u)) return rc;
+    static const RenderEntry d("sample_rays_long", K_LONG | K_SAMPLING);
+    const RayInputs in = { rays_o, rays_d, nullptr, noise, lin_z, lin_u };
+    if (int rc = check_render_entry(d, field, nullptr, op, in, nullptr, nullptr, z_vals)) return rc;
     if (op->n_rays <= 0) return AC_OK;
     RenderArgs a{};
-    if (int rc = fill_render_common(a, field, op, rays_o, rays_d, nullptr, noise, lin_z, lin_u)) return rc;
+    if (int rc = fill_entry_args(a, field, nullptr, op, in, nullptr)) return rc;
     a.zbuf = z_vals;
-    launch_long_p<MODE_UPSAMPLE, false, false, false>(a, (hipStream_t)stream);
-    return ac::check_launch("sample_rays_long");
+    launch_long<MODE_UPSAMPLE>(a, (hipStream_t)stream);
+    return ac::check_launch(d.name);
 }
 
-// Posed space at the long counts: ac_render_rays_warped's sequence (render_fused.hip) on this kernel -- mesh near / far -> coarse posed points -> (ray cull)
-// -> first closest-face search -> MODE_UPSAMPLE (coarse sdf at the warped coarse points, up-sampling, z and the posed mid points) -> second search ->
-// MODE_FINAL (field at the warped mid points, alpha * mask, optional skipping of fully masked tiles).  Scratch: ac_render_rays_warped_scratch(n_rays, T, offs).
+// Posed space at the long counts: the posed sequence (render_entry.hpp: render_posed) on this kernel's MODE_UPSAMPLE and MODE_FINAL.
+// Scratch: ac_render_rays_warped_scratch(n_rays, T, offs).
 AC_API int ac_render_rays_long_warped(const ac_field *field, const ac_render_opts *op, const float *rays_o, const float *rays_d,
                                       const float *bg, const float *noise, const float *lin_z, const float *lin_u,
                                       const ac_warp_mesh *mesh, void *scratch, size_t scratch_bytes, const ac_render_out *out,
                                       ac_stream_t stream)
 {
-    const char *who = "render_rays_long_warped";
-    if (!op || !out || !mesh) { ac::set_error("%s: NULL opts/out/mesh", who); return AC_ERR_BAD_ARG; }
-    if (int rc = check_long_args(who, op, rays_o, rays_d, noise, lin_z, lin_u, true)) return rc;
-    if (out->feat7) { ac::set_error("%s: feat7 (the fused training backward's features) is not produced by the long renderer", who); return AC_ERR_BAD_ARG; }
+    static const RenderEntry d("render_rays_long_warped", K_LONG | K_POSED);
+    const RayInputs in = { rays_o, rays_d, bg, noise, lin_z, lin_u };
+    if (int rc = check_render_entry(d, field, nullptr, op, in, mesh, out)) return rc;
     if (op->n_rays <= 0) return AC_OK;
-    if (!out->image || !out->weights_sum || !out->depth || !out->normal_map || !out->eik) { ac::set_error("%s: NULL buffer", who); return AC_ERR_BAD_ARG; }
-    if (!mesh->verts || !mesh->faces || !mesh->T || mesh->V == 0 || mesh->F == 0) { ac::set_error("%s: NULL mesh buffer or empty mesh", who); return AC_ERR_BAD_ARG; }
-    const int N = op->n_rays, T0 = op->num_steps, T = T0 + op->upsample_steps;
-    if ((size_t)N * (size_t)T > 0x7fffffffu) { ac::set_error("%s: %d rays x %d samples: too many samples for one launch", who, N, T); return AC_ERR_BAD_ARG; }
-    size_t offs[6];
-    const size_t need = ac_render_rays_warped_scratch(N, T, offs);
-    if (!scratch || scratch_bytes < need) { ac::set_error("%s: scratch of %zu bytes needed, %zu given", who, need, scratch_bytes); return AC_ERR_BAD_ARG; }
-    char *sc = static_cast<char *>(scratch);
-    float *near_m = reinterpret_cast<float *>(sc + offs[0]), *far_m = reinterpret_cast<float *>(sc + offs[1]);
-    float *pts = reinterpret_cast<float *>(sc + offs[2]), *can = reinterpret_cast<float *>(sc + offs[3]);
-    uint8_t *mask = reinterpret_cast<uint8_t *>(sc + offs[4]);
-    float *zbuf = reinterpret_cast<float *>(sc + offs[5]);
-    const uint8_t *ray_dead = nullptr;
-    const hipStream_t st = (hipStream_t)stream;
     RenderArgs a{};
-    if (int rc = fill_render_common(a, field, op, rays_o, rays_d, bg, noise, lin_z, lin_u)) return rc;
-    a.out = *out;
-    a.skip_masked = op->skip_masked;
-    ac::warped_phase_mark(0, st);
-    if (mesh->use_mesh_guide) {
-        if (int rc = ac_mesh_near_far(rays_o, rays_d, mesh->verts, (uint32_t)N, mesh->V, mesh->geo_threshold, near_m, far_m, stream)) return rc;
-        a.near_m = near_m; a.far_m = far_m;
-    }
-    a.zbuf = zbuf; a.mid_pts = pts;
-    if (op->upsample_steps > 0) {
-        if (int rc = ac::warped_coarse_pts("render_rays_long_warped (coarse points)", rays_o, rays_d, a.near_m, a.far_m, lin_z, noise, N, T0, op->bound, op->perturb, pts, st))
-            return rc;
-        if (op->skip_masked && mesh->accel) {                     // rays that cannot hold an unmasked sample: no search, no field evaluation
-            uint8_t *rdead = reinterpret_cast<uint8_t *>(sc + need - (((size_t)N + 255) & ~(size_t)255));
-            if (int rc = ac::warp_ray_cull(pts, (uint32_t)N, (uint32_t)T0, mesh->threshold, mesh->accel, rdead, stream)) return rc;
-            ray_dead = rdead;
-        }
-        ac::warped_phase_mark(1, st);
-        if (int rc = ac::warp_any(mesh, pts, (uint32_t)(N * T0), can, mask, stream, 0, ray_dead, (uint32_t)T0, 0u)) return rc;
-    } else ac::warped_phase_mark(1, st);
-    ac::warped_phase_mark(2, st);
-    a.ext_pts = can;
-    a.ray_dead = ray_dead;
-    if (a.out.ss_inds || a.out.sort_index) launch_long_p<MODE_UPSAMPLE, false, true, false>(a, st);      // (the sampling launch can export the sample indices)
-    else launch_long_p<MODE_UPSAMPLE, false, false, false>(a, st);
-    if (int rc = ac::check_launch("render_rays_long_warped (up-sampling)")) return rc;
-    ac::warped_phase_mark(3, st);
-    if (int rc = ac::warp_any(mesh, pts, (uint32_t)(N * T), can, mask, stream, op->skip_masked, ray_dead, (uint32_t)T, (uint32_t)T0)) return rc;
-    ac::warped_phase_mark(4, st);
-    a.mask = mask;
-    dispatch_variants(a.fast, long_wants_samples(a.out), a.Wsh != nullptr, [&](auto fast, auto ex, auto sh) {
-        launch_long_p<MODE_FINAL, decltype(fast)::value, decltype(ex)::value, decltype(sh)::value>(a, st);
-    });
-    ac::warped_phase_mark(5, st);
-    if (int rc = ac::check_launch(who)) return rc;
+    if (int rc = fill_entry_args(a, field, nullptr, op, in, out)) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = render_posed(d, a, mesh, scratch, scratch_bytes, stream, [&](const RenderArgs &b) { launch_long<MODE_UPSAMPLE>(b, st); },
+                              [&](const RenderArgs &b) { launch_long<MODE_FINAL>(b, st); })) return rc;
     if (out->eik_reduced) return ac_eikonal_reduce2(out->eik, op->n_rays, out->eik_reduced, stream);
     return AC_OK;
 }

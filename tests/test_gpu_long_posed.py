@@ -291,6 +291,32 @@ def test_whole_frame_in_one_batch():
     nsr_ops.free_scratch()
 
 
+def test_phase_marks_of_both_posed_entries():
+    """ac_debug_warped_phases: both posed entries mark the six boundaries of the one posed sequence; the hook changes no value"""
+    from avatarcraft_amd import nsr_ops, _lib as L
+    e = _env()
+    ro, rd = t(e["ro"][200:216]), t(e["rd"][200:216])              # (16 rays of the middle row of the 20 x 20 view: they cross the body)
+    wm = nsr_ops.WarpMesh(*e["body"], DEV, use_mesh_guide=True)
+    calls = [lambda: nsr_ops.render_rays(e["f"], ro, rd, 32, 32, 1.6, e["inv_s"], extras=True, warp=wm),
+             lambda: nsr_ops.render_rays_long(e["f"], ro, rd, 20, 16, 1.6, e["inv_s"], extras=True, warp=wm)]     # (20: a count only the long kernel takes)
+    plain = [_clone(c()) for c in calls]
+    torch.cuda.synchronize()
+    L.lib().ac_debug_warped_phases(1)
+    try:
+        for c, ref in zip(calls, plain):
+            got = _clone(c())
+            ph = (C.c_float * 5)(*([-1.0] * 5))
+            assert L.lib().ac_debug_warped_phase_ms(C.addressof(ph)) == 0
+            assert all(np.isfinite(v) and v >= 0.0 for v in ph), list(ph)
+            torch.cuda.synchronize()
+            for k in RAY_KEYS + SAMPLE_KEYS + ["can_mid", "eik_res"]:
+                assert_bitwise(got[k], ref[k].cpu().numpy(), k)
+            assert torch.equal(got["mask"], ref["mask"])
+    finally:
+        L.lib().ac_debug_warped_phases(0)
+    assert float(plain[0]["weights_sum"].max()) > 0.5 and plain[1]["z_vals"].shape == (16, 36)
+
+
 def test_rules():
     from avatarcraft_amd import nsr_ops, _lib as L
     e = _env()
