@@ -76,6 +76,14 @@ class ac_atlas_opts(C.Structure):
     _fields_ = [("size", u32), ("cell", u32)]
 
 
+class ac_surface_opts(C.Structure):
+    _fields_ = [("bound", f32), ("fd_eps", f32), ("level", f32), ("tol", f32), ("max_iters", i32), ("step_scale", f32), ("min_step", f32), ("guard", f32)]
+
+
+class ac_surface_out(C.Structure):
+    _fields_ = [("image", vp), ("weights_sum", vp), ("depth", vp), ("position", vp), ("normal_map", vp), ("sdf", vp), ("status", vp), ("iters", vp)]
+
+
 class ac_mesh_pose_opts(C.Structure):
     _fields_ = [("iters", i32), ("tol", f32)]
 
@@ -168,6 +176,7 @@ _SIGS = {
     "ac_marching_cubes_emit": ([vp, u32, u32, u32, f32, vp, C.c_size_t, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, u32, vp, u32, vp], C.c_int),
     "ac_mesh_vertex_attrs": ([C.POINTER(ac_field), vp, u32, vp, C.POINTER(ac_mesh_attr_opts), vp, vp, vp, vp, vp, vp], C.c_int),
     "ac_mesh_bake_texture": ([C.POINTER(ac_field), vp, u32, vp, u32, C.POINTER(ac_atlas_opts), C.POINTER(ac_mesh_attr_opts), vp, vp, vp, vp, vp, vp], C.c_int),
+    "ac_render_rays_surface": ([C.POINTER(ac_field), C.POINTER(ac_surface_opts), vp, vp, u32, vp, C.POINTER(ac_surface_out), vp], C.c_int),
     "ac_mesh_bind_scratch": ([u32, u32], C.c_size_t),
     "ac_mesh_bind": ([vp, u32, vp, u32, vp, u32, vp, vp, vp, vp, vp, C.c_size_t, vp], C.c_int),
     "ac_mesh_pose_scratch": ([u32], C.c_size_t),

@@ -448,6 +448,110 @@ __global__ __launch_bounds__(FBLOCK) void texture_bake_kernel(const RenderArgs a
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- first-hit render of the level set
+// The image of the surface the export writes: per ray the first point with sdf = level, found by sphere-tracing steps until the sign changes and guarded false
+// position inside the bracket (the procedure, operation by operation: include/avatarcraft_hip.h, ac_render_rays_surface), then refine_shade_tile with steps = 0
+// at that point -- normal, sdf and colour as ac_field_samples gives them.  A wave owns tiles of 16 consecutive rays, lane (n, g) serves ray n of the tile (the
+// four lanes of a ray hold the same state).  Every trip of the root-finder loop is ONE sdf_tile call at every lane's current point, then the scalar update in the
+// lanes still active; stopped lanes ride along at their point.  The loop ends when no lane of the wave is active or after max_iters trips: wave-uniform, bounded.
+// A tile without a shaded ray (status 0, 1 or 3) skips the stencil and the colour network; in a tile with some, the other lanes ride along at the first shaded
+// lane's point.  No atomics, no waits on other waves, plain vector stores.
+struct SurfaceArgs {
+    const float *rays_o, *rays_d, *bg;     // [N,3] [N,3] [N,3] | NULL: white
+    uint32_t N;
+    int max_iters;
+    float level, tol, step_scale, min_step, guard;
+    float *image, *weights_sum, *depth, *position, *normal_map, *sdf;      // each [N] / [N,3] | NULL
+    uint8_t *status, *iters;               // [N], [N] | NULL
+};
+
+__global__ __launch_bounds__(FBLOCK) void surface_rays_kernel(const RenderArgs a, const SurfaceArgs m)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    fill_lds_sdf(lds, a);
+    if (m.image) fill_lds_color(lds, a);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
+    float *fsl = lds + OFF_WAVE + wave * FE_SLAB;
+    const FieldCtx fc = make_ctx(a);
+    const float bound = a.bound;
+    const RefineOpts ro{ 0, 0.0f, 0.0f, 0.0f, m.image != nullptr };
+    const uint32_t ntiles = (m.N + 15) / 16;
+    for (uint32_t tile = blockIdx.x * FW + wave; tile < ntiles; tile += gridDim.x * FW) {
+        const uint32_t b = tile * 16 + n, bb = b < m.N ? b : m.N - 1;
+        const float *po = m.rays_o + 3 * (size_t)bb, *pd = m.rays_d + 3 * (size_t)bb;
+        const float ox = po[0], oy = po[1], oz = po[2], dx = pd[0], dy = pd[1], dz = pd[2];
+        float near, far;
+        cube_near_far(ox, oy, oz, dx, dy, dz, bound, near, far);
+        float t = near, t_lo = 0.0f, s_lo = 0.0f, t_hi = 0.0f, s_hi = 0.0f;
+        uint32_t st = 2u, iters = 0u;
+        bool active = far > near, have_lo = false, bracketed = false;
+        float px = clampf(ox + t * dx, -bound, bound), py = clampf(oy + t * dy, -bound, bound), pz = clampf(oz + t * dz, -bound, bound);
+#pragma unroll 1
+        for (int it = 1; it <= m.max_iters; ++it) {
+            if (__ballot(active) == 0ull) break;                                 // (wave-uniform)
+            const f32x4 o = sdf_tile(lds, fc, lane, px, py, pz);
+            const float s = __shfl(o[0], n) - m.level;                           // output 0 lives in the lanes g == 0
+            if (active) {
+                iters = (uint32_t)it;
+                float t_next = t;
+                bool in_bracket = false;
+                if (!(__builtin_fabsf(s) < __builtin_inff())) { st = 5u; active = false; }
+                else if (__builtin_fabsf(s) <= m.tol) { st = 0u; active = false; }
+                else if (bracketed) {
+                    if (s > 0.0f) { t_lo = t; s_lo = s; } else { t_hi = t; s_hi = s; }
+                    in_bracket = true;
+                } else if (s > 0.0f) {                                           // still outside: a sphere-tracing step, never past far
+                    if (t >= far) { st = 2u; active = false; }
+                    else {
+                        t_lo = t; s_lo = s; have_lo = true;
+                        t_next = __builtin_fminf(t + __builtin_fmaxf(m.step_scale * s, m.min_step), far);
+                    }
+                } else if (!have_lo) { st = 3u; active = false; }                // the first evaluation is already inside
+                else { bracketed = true; t_hi = t; s_hi = s; in_bracket = true; }
+                if (in_bracket) {                                                // guarded false position
+                    const float w = t_hi - t_lo, q = s_lo / (s_lo - s_hi), f = t_lo + w * q, gd = m.guard * w;
+                    t_next = __builtin_fminf(__builtin_fmaxf(f, t_lo + gd), t_hi - gd);
+                }
+                if (active) {
+                    if (it == m.max_iters) { st = bracketed ? 1u : 4u; active = false; }       // (t stays the last evaluated t)
+                    else {
+                        t = t_next;
+                        px = clampf(ox + t * dx, -bound, bound); py = clampf(oy + t * dy, -bound, bound); pz = clampf(oz + t * dz, -bound, bound);
+                    }
+                }
+            }
+        }
+        const bool shaded = st == 0u || st == 1u || st == 3u;
+        const unsigned long long sh_mask = __ballot(shaded);
+        TileShade r{ 0.0f, 0u, FdNormal{ 0.0f, 0.0f, 0.0f, 0.0f }, { 0.0f, 0.0f, 0.0f } };
+        const float hx = px, hy = py, hz = pz;                                   // this ray's own point
+        if (sh_mask) {                                                           // (wave-uniform)
+            const int first = __builtin_ctzll(sh_mask) & 15;                     // (the four lanes of a ray agree, so its lane g == 0 is the lowest set bit)
+            const float fx = __shfl(px, first), fy = __shfl(py, first), fz = __shfl(pz, first);
+            if (!shaded) { px = fx; py = fy; pz = fz; }
+            r = refine_shade_tile(lds, fsl, fc, a, ro, lane, m.rays_d, (size_t)bb, false, px, py, pz);
+        }
+        if (b < m.N && g == 0) {
+            const size_t b3 = 3 * (size_t)b;
+            if (m.image) {
+                float c0 = 1.0f, c1 = 1.0f, c2 = 1.0f;
+                if (shaded) { c0 = r.rgb[0]; c1 = r.rgb[1]; c2 = r.rgb[2]; }
+                else if (m.bg) { c0 = m.bg[b3]; c1 = m.bg[b3 + 1]; c2 = m.bg[b3 + 2]; }
+                m.image[b3] = c0; m.image[b3 + 1] = c1; m.image[b3 + 2] = c2;
+            }
+            if (m.weights_sum) m.weights_sum[b] = shaded ? 1.0f : 0.0f;
+            if (m.depth) m.depth[b] = shaded ? t : 0.0f;
+            if (m.position) { m.position[b3] = shaded ? hx : 0.0f; m.position[b3 + 1] = shaded ? hy : 0.0f; m.position[b3 + 2] = shaded ? hz : 0.0f; }
+            if (m.normal_map) { m.normal_map[b3] = shaded ? r.fn.nx : 0.0f; m.normal_map[b3 + 1] = shaded ? r.fn.ny : 0.0f; m.normal_map[b3 + 2] = shaded ? r.fn.nz : 0.0f; }
+            if (m.sdf) m.sdf[b] = shaded ? r.s : 0.0f;
+            m.status[b] = (uint8_t)st;
+            if (m.iters) m.iters[b] = (uint8_t)iters;
+        }
+        wave_sync();
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------- density grid of the ray marcher
 // Round 6: two launches instead of one.  Round 5 gave every workgroup a brick of 16 x 8 x 8 outputs PLUS the one-point halo the 2^3 max pool reads
 // (17 x 9 x 9 = 1377 evaluations for 1024 outputs, 3.58 M for the 2.15 M points of the 129^3 grid) and cut them into tiles of 16 consecutive evaluations of
@@ -684,6 +788,32 @@ AC_API int ac_mesh_bake_texture(const ac_field *field, const float *positions, u
     if (blocks > cus) blocks = cus;
     hipLaunchKernelGGL(texture_bake_kernel, dim3(blocks), dim3(FBLOCK), lds_bytes, (hipStream_t)stream, a, m);
     return ac::check_launch("mesh_bake_texture");
+}
+
+AC_API int ac_render_rays_surface(const ac_field *field, const ac_surface_opts *opts, const float *rays_o, const float *rays_d, uint32_t N, const float *bg,
+                                  const ac_surface_out *out, ac_stream_t stream)
+{
+    if (!field || !opts || !out) { ac::set_error("render_rays_surface: NULL field, opts or out"); return AC_ERR_BAD_ARG; }
+    if (opts->max_iters < 1 || opts->max_iters > 255) { ac::set_error("render_rays_surface: max_iters %d outside 1..255", opts->max_iters); return AC_ERR_BAD_ARG; }
+    if (!(opts->tol >= 0.0f) || !(opts->fd_eps > 0.0f) || !(opts->step_scale > 0.0f) || !(opts->min_step > 0.0f) || !(opts->bound > 0.0f)) {
+        ac::set_error("render_rays_surface: tol not >= 0, or fd_eps, step_scale, min_step or bound not > 0"); return AC_ERR_BAD_ARG;
+    }
+    if (!(opts->guard >= 0.0f && opts->guard < 0.5f)) { ac::set_error("render_rays_surface: guard outside [0, 0.5)"); return AC_ERR_BAD_ARG; }
+    if (N == 0) return AC_OK;
+    if (!rays_o || !rays_d || !out->status) { ac::set_error("render_rays_surface: NULL rays or status"); return AC_ERR_BAD_ARG; }
+    if (N > 0xffffffe0u) { ac::set_error("render_rays_surface: more than 2^32 - 32 rays"); return AC_ERR_BAD_ARG; }
+    RenderArgs a{};
+    if (int rc = prep_args(a, field, opts->bound, opts->fd_eps)) return rc;
+    SurfaceArgs m{ rays_o, rays_d, bg, N, opts->max_iters, opts->level, opts->tol, opts->step_scale, opts->min_step, opts->guard,
+                   out->image, out->weights_sum, out->depth, out->position, out->normal_map, out->sdf, out->status, out->iters };
+    const size_t lds_bytes = FWD_LDS_FLOATS * sizeof(float);
+    static uint64_t seen = 0;
+    ac::allow_dynamic_lds(seen, reinterpret_cast<const void *>(surface_rays_kernel), lds_bytes);
+    uint32_t blocks = ((N + 15) / 16 + FW - 1) / FW;              // persistent, one workgroup per CU, like ac_mesh_vertex_attrs
+    const uint32_t cus = ac::cu_count();
+    if (blocks > cus) blocks = cus;
+    hipLaunchKernelGGL(surface_rays_kernel, dim3(blocks), dim3(FBLOCK), lds_bytes, (hipStream_t)stream, a, m);
+    return ac::check_launch("render_rays_surface");
 }
 
 static uint32_t dp_blocks(uint32_t H)

@@ -53,8 +53,11 @@ def shard_indices(n, rank=None, world=None):
 
 
 def render_canonical_360(net, n_views=100, render_hw=(256, 256), center=(0.0, 0.0, 0.0), up=(0.0, 1.0, 0.0), white_bkg=True, with_head=True,
-                         rays_per_batch=4096, device="cuda", rank=None, world=None, table_dtype=None):
+                         rays_per_batch=4096, device="cuda", rank=None, world=None, table_dtype=None, surface=False):
     """yields (ring name, view index, rgb [H,W,3] float32 in [0,1], depth [H,W]) for the body ring and, with_head, the head ring.
+    surface=True: the same tuple from net.render_surface -- the first-hit render of the level set (the surface export_mesh writes) instead of the volumetric one,
+    a view in one launch; its depth is the METRIC distance along the ray (0 where nothing is hit), not the near/far-normalised depth of the default.
+    table_dtype does not apply to it.
     table_dtype: None (default) leaves net.render_table_dtype as the caller set it; "float" / "half" sets it around each view's render and restores it
     (also when the consumer abandons the generator).  "half" takes effect for a net in eval() mode (NeRFNetwork.render_table_dtype).
     rank / world: this process renders the views shard_indices(n_views, rank, world) of every ring (default: its rank in the default process group;
@@ -70,6 +73,11 @@ def render_canonical_360(net, n_views=100, render_hw=(256, 256), center=(0.0, 0.
             if i not in mine:
                 continue
             ro, rd = cap2rays(pose2cap([h, w], pose), device=device)
+            if surface:
+                with torch.no_grad():
+                    r = net.render_surface(ro.reshape(1, -1, 3), rd.reshape(1, -1, 3), NSR_BOUND, bg_color=None if white_bkg else 0.0)
+                yield name, i, r["rgb"].reshape(h, w, 3), r["depth"].reshape(h, w)
+                continue
             prev_table = getattr(net, "render_table_dtype", None)
             if table_dtype is not None and prev_table is not None:
                 net.render_table_dtype = table_dtype

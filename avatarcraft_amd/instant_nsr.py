@@ -1094,6 +1094,41 @@ class NeRFNetwork(NeRFRenderer):
             out["colors"] = a["rgb"]
         return out if return_torch else {k: x.cpu().numpy() for k, x in out.items()}
 
+    def render_surface(self, rays_o, rays_d, bound, bg_color=None, normal_epsilon_ratio=0.0, max_ray_batch=None, **opts):
+        """the image of the level set itself (ac_render_rays_surface) -- exactly the surface extract_colored_mesh / export_mesh write: per ray the first point with
+        sdf = level, the field's normal and colour there, its METRIC distance and a hit mask, about 18 SDF evaluations per ray instead of the volumetric render's
+        1008.  Rays as render() takes them ([B,N,3]); opts: level, tol, max_iters, step_scale, min_step, guard of nsr_ops.render_rays_surface, and want_rgb
+        (False: no colour network, rgb = None; works wherever extract_colored_mesh(colors=False) does).
+        -> dict with render()'s keys that make sense here, in its shapes -- rgb [B,N,3] (background where nothing is hit), depth [B,N] (the distance t along the
+        ray, NOT normalised to near/far as run()'s; 0 where nothing is hit), weight_sum [B N,1] (1 or 0), normal [B N,3] -- plus position [B,N,3], sdf [B,N],
+        status [B,N] uint8 (as nsr_ops.render_rays_surface; shaded = 0, 1 or 3), iters [B,N] uint8.
+        No gradient flows through a root finder's iteration count: the call raises where autograd would record (grad mode on and a parameter that requires grad).
+        It does not go through render() / render_route.  Same model requirements as extract_colored_mesh."""
+        want_rgb = bool(opts.pop("want_rgb", True))
+        if not (self.encoder.embeddings.is_cuda and self._sdf_supported()):
+            raise RuntimeError("render_surface needs the default SDF side of NeRFNetwork on the GPU")
+        if want_rgb and not self._fused_supported(ignore_curvature=True):
+            raise RuntimeError("render_surface: the colour side of this model is not the default one (colour net 21-64-64-3, or 37-64-64-3 with the degree-4 "
+                               "view-direction encoder); want_rgb=False renders geometry only")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise RuntimeError("render_surface builds no autograd graph (the hit point is the result of a root finder): call it under torch.no_grad()")
+        B, N = rays_o.shape[:2]
+        n = B * N
+        fd_eps = nsr_ops.FD_STEP * (1.0 - normal_epsilon_ratio)
+        nsr_ops.surface_opts(bound, fd_eps, **opts)                                   # bad options raise before any device work
+        with torch.no_grad():
+            ro = rays_o.reshape(-1, 3).float().contiguous()
+            rd = rays_d.reshape(-1, 3).float().contiguous()
+            bg = None if bg_color is None else _background(bg_color, n, ro.device).contiguous()
+            f = self._field() if self._fused_supported(ignore_curvature=True) else self._field_sdf_only()
+            step = max(int(max_ray_batch or n), 1)                                    # (None: the whole view in one launch)
+            parts = [nsr_ops.render_rays_surface(f, ro[h:h + step], rd[h:h + step], bound, fd_eps, bg=None if bg is None else bg[h:h + step], want_rgb=want_rgb,
+                                                 **opts) for h in (range(0, n, step) or (0,))]
+            o = parts[0] if len(parts) == 1 else {k: (None if parts[0][k] is None else torch.cat([p[k] for p in parts])) for k in parts[0]}
+        return {"rgb": None if o["image"] is None else o["image"].reshape(B, N, 3), "depth": o["depth"].reshape(B, N), "weight_sum": o["weights_sum"][:, None],
+                "normal": o["normal_map"], "position": o["position"].reshape(B, N, 3), "sdf": o["sdf"].reshape(B, N), "status": o["status"].reshape(B, N),
+                "iters": o["iters"].reshape(B, N)}
+
     def extract_textured_mesh(self, bound: float, resolution: int, texture_size: int = 2048, cell=None, threshold: float = 0.0, refine_steps: int = 3,
                               tol: float = 1e-5, return_torch=False):
         """extract_colored_mesh's mesh with the colour network baked into a texture instead of sampled at the vertices, so that colour detail no longer depends on

@@ -1326,6 +1326,55 @@ def mesh_bake_texture(field, positions, triangles, size, cell, bound, eps=FD_STE
     return out
 
 
+def surface_opts(bound, fd_eps, level=0.0, tol=1e-4, max_iters=64, step_scale=1.0, min_step=1e-3, guard=0.125):
+    """ac_surface_opts from Python numbers; the checks of ac_render_rays_surface made here, before any device work (RuntimeError naming the option)"""
+    who = "render_rays_surface"
+    try:
+        mi = int(max_iters)
+        bound, fd_eps, level, tol, step_scale, min_step, guard = (float(v) for v in (bound, fd_eps, level, tol, step_scale, min_step, guard))
+    except (TypeError, ValueError) as e:
+        raise RuntimeError(f"{who}: options must be numbers ({e})") from e
+    if mi != max_iters or not 1 <= mi <= 255:
+        raise RuntimeError(f"{who}: max_iters {max_iters!r} outside 1..255")
+    if not tol >= 0.0:
+        raise RuntimeError(f"{who}: tol {tol!r} not >= 0")
+    for name, v in (("bound", bound), ("fd_eps", fd_eps), ("step_scale", step_scale), ("min_step", min_step)):
+        if not (v > 0.0 and np.float32(v) > 0.0):
+            raise RuntimeError(f"{who}: {name} {v!r} not > 0")
+    if not (0.0 <= guard and np.float32(guard) < np.float32(0.5)):
+        raise RuntimeError(f"{who}: guard {guard!r} outside [0, 0.5)")
+    return L.ac_surface_opts(bound, fd_eps, level, tol, mi, step_scale, min_step, guard)
+
+
+def render_rays_surface(field, rays_o, rays_d, bound, fd_eps, *, level=0.0, tol=1e-4, max_iters=64, step_scale=1.0, min_step=1e-3, guard=0.125, bg=None,
+                        want_rgb=True):
+    """ac_render_rays_surface: the first-hit render of the level set sdf = level, one launch.  rays_o, rays_d [N,3] float32 on the device.  Per ray: sphere-tracing
+    steps max(step_scale s, min_step) from the cube's near until the sign changes, then guarded false position inside the bracket until |sdf - level| <= tol, at
+    most max_iters evaluations (the procedure operation by operation: include/avatarcraft_hip.h); then normal, sdf and colour at the point found, as field_samples
+    gives them (view direction: the rays_d row as given, for a field with Wc1_sh).  bg [N,3] or None (white).  want_rgb=False: no colour network (an SDF-only
+    field is enough), image = None.
+    -> dict(image [N,3] | None, weights_sum [N] (1 or 0), depth [N] (metric t; 0 where not shaded), position [N,3], normal_map [N,3], sdf [N], status [N] uint8
+    (0 hit, 1 out of iterations inside a bracket, 2 miss, 3 starts inside, 4 out of iterations without a bracket, 5 value not finite; shaded =
+    0, 1 or 3), iters [N] uint8 = SDF evaluations of the root finder)"""
+    opts = surface_opts(bound, fd_eps, level, tol, max_iters, step_scale, min_step, guard)
+    rays_o = _chk(rays_o, "rays_o")
+    if rays_o.dim() != 2 or rays_o.shape[1] != 3:
+        raise RuntimeError(f"render_rays_surface: rays_o must be [N,3], got {tuple(rays_o.shape)}")
+    N, dev = rays_o.shape[0], rays_o.device
+    rays_d = _chk(rays_d, "rays_d", (N, 3))
+    if bg is not None:
+        bg = _chk(bg, "bg", (N, 3))
+    if rays_d.device != dev or (bg is not None and bg.device != dev) or field.device != dev:
+        raise RuntimeError("render_rays_surface: field, rays_o, rays_d and bg must live on one device")
+    f = lambda *sh: torch.empty(sh, dtype=_F32, device=dev)
+    u8 = lambda: torch.empty(N, dtype=torch.uint8, device=dev)
+    out = dict(image=f(N, 3) if want_rgb else None, weights_sum=f(N), depth=f(N), position=f(N, 3), normal_map=f(N, 3), sdf=f(N), status=u8(), iters=u8())
+    so = L.ac_surface_out(*[L.ptr(out[k]) for k in ("image", "weights_sum", "depth", "position", "normal_map", "sdf", "status", "iters")])
+    L.check(L.lib().ac_render_rays_surface(C.byref(field.c), C.byref(opts), rays_o.data_ptr(), rays_d.data_ptr(), N, L.ptr(bg), C.byref(so),
+                                           L.current_stream(dev)), "render_rays_surface")
+    return out
+
+
 def mesh_bind(points, guide_verts, faces, accel=True):
     """ac_mesh_bind: once per exported mesh, pose independent.  points [V,3] float32 (the mesh's canonical vertices), guide_verts [Vg,3] float32 (the SMPL guide
     in canonical space: geometry.canonical_guide), faces [F,3] int32, all on one device.  -> dict(face_id [V] int32 the closest guide face, bary [V,3] float64 of

@@ -541,6 +541,53 @@ int ac_mesh_bake_texture(const ac_field *field, const float *positions /*[V,3]*/
                          const ac_atlas_opts *atlas, const ac_mesh_attr_opts *opts,
                          float *rgb /*[S,S,3]*/, int32_t *owner /*[S,S]*/, float *normals /*optional [S,S,3]*/, float *sdf /*optional [S,S]*/,
                          uint8_t *status /*optional [S,S]*/, ac_stream_t stream);
+/* ac_render_rays_surface: the image of the level set itself -- per ray the FIRST point with sdf = level, the field's normal and colour there, its metric distance
+ * and a hit mask; one launch, about 18 SDF evaluations per ray where the volumetric render takes 1008 (an added entry, no struct of an existing call changes:
+ * ac_version stays 10).  It stands in for nothing in the reference.  All fp32, every operation rounded once (t*d then the add; correctly rounded division); per ray:
+ *   near, far = the cube's slab test exactly as ac_render_rays forms it (near >= 0.05)
+ *   if not (far > near): status 2, iters 0, t = near, no evaluation
+ *   t = near; have_lo = bracketed = false
+ *   for it = 1 .. max_iters:
+ *       p = clamp(o + t d, +-bound) per coordinate;  s = forward_sdf(p)[0] - level (the bits of ac_field_sdf);  iters = it
+ *       s not finite            -> status 5, stop
+ *       |s| <= tol              -> status 0, stop
+ *       if not bracketed:
+ *           if s > 0:
+ *               t >= far        -> status 2, stop
+ *               (t_lo, s_lo) = (t, s); have_lo = true
+ *               t_next = min(t + max(step_scale s, min_step), far);  goto advance
+ *           not have_lo         -> status 3, stop                         (the first evaluation is already inside)
+ *           bracketed = true; (t_hi, s_hi) = (t, s)
+ *       else: s > 0 ? (t_lo, s_lo) = (t, s) : (t_hi, s_hi) = (t, s)
+ *       w = t_hi - t_lo; q = s_lo / (s_lo - s_hi); f = t_lo + w q; g = guard w
+ *       t_next = min(max(f, t_lo + g), t_hi - g)                          (guarded false position)
+ *     advance:
+ *       it == max_iters -> status bracketed ? 1 : 4, stop                 (t stays the last EVALUATED t)
+ *       t = t_next
+ * status: 0 hit | 1 out of iterations inside a bracket | 2 miss (left or never entered the cube) | 3 starts inside | 4 out of iterations without a bracket |
+ * 5 value not finite.  SHADED rays are those with status 0, 1 or 3: one seven-point stencil at p = clamp(o + t d) with fd_eps, exactly what ac_mesh_vertex_attrs
+ * does with refine_steps = 0: sdf = the centre's raw output 0, normal = g / (1e-5 + |g|), rgb = the colour network on (p, normal, features) with the ray's
+ * rays_d row AS GIVEN as view direction (a field with Wc1_sh; none otherwise) -- the bits ac_field_samples returns for that point and direction.
+ * Outputs ([N] or [N,3]; each optional except status): image = rgb where shaded, else bg (bg == NULL: white, as in ac_render_rays; image == NULL: the colour
+ * network is skipped and a field whose colour matrices are placeholders is enough) | weights_sum = 1 or 0 | depth = t for shaded rays, 0 elsewhere -- METRIC, where
+ * the depth of NeRFNetwork.run is normalised to the near/far range | position = p, normal_map, sdf: 0 where not shaded | status, iters: uint8.
+ * A wave serves 16 rays and runs while any of them is active, at most max_iters trips: bounded, no atomics, no waits.  N == 0 launches nothing.
+ * AC_ERR_BAD_ARG before any launch: a NULL field, rays or status, max_iters outside 1..255, tol not >= 0, fd_eps, step_scale, min_step or bound not > 0, guard
+ * outside [0, 0.5).  Bit-identical to the CPU oracle's orc_field_sdf / orc_field_samples chained by the same fp32 arithmetic (tests/test_gpu_surface_render.py). */
+typedef struct ac_surface_opts {
+    float bound, fd_eps;        /* as ac_field_samples: clamp, finite-difference step of the shading stencil */
+    float level;                /* the level set that is rendered (0)                                         */
+    float tol;                  /* |sdf - level| <= tol: hit (1e-4)                                           */
+    int32_t max_iters;          /* evaluations per ray at most, 1..255 (64)                                   */
+    float step_scale, min_step; /* outside step = max(step_scale s, min_step) (1, 1e-3)                       */
+    float guard;                /* the false-position point keeps guard * width from both bracket ends (1/8)  */
+} ac_surface_opts;
+typedef struct ac_surface_out {
+    float *image, *weights_sum, *depth, *position, *normal_map, *sdf;
+    uint8_t *status, *iters;
+} ac_surface_out;
+int ac_render_rays_surface(const ac_field *field, const ac_surface_opts *opts, const float *rays_o /*[N,3]*/, const float *rays_d /*[N,3]*/, uint32_t N,
+                           const float *bg /*optional [N,3]*/, const ac_surface_out *out, ac_stream_t stream);
 /* ac_density_grid_update replaces the grid update of NeRFRenderer.update_extra_state (models/instant_nsr.py:303-346) in two launches (round 6: the densities on
  * ac_field_sdf_grid's x-tiles into the scratch, then one pooling / merging pass; round 5's single launch evaluated a halo per brick and was 3 x slower): forward_sdf on
  * the H^3 grid axis x axis x axis (axis [H], device: torch.linspace(-bound, bound, H)) -> density = inv_s e^(-inv_s |sdf|) / (1 + e^(-inv_s |sdf|)) in the
