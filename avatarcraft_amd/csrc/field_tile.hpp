@@ -1,4 +1,4 @@
-// avatarcraft_amd/csrc/field_tile.hpp -- the field on a tile of 16 packed samples, shared by the training operators (sdf_train.hip) and the occupancy-grid
+// avatarcraft_amd/csrc/field_tile.hpp -- the field on a tile of 16 packed samples, shared by the training operators (train_common.hpp) and the occupancy-grid
 // renderers (render_occupancy.hip): the workgroup shape and LDS image of the forward SDF query, the seven-evaluation stencil (fd_forward) and the whole
 // per-sample body (field_tile: stencil, normal, colour, NeuS alpha).  Anonymous namespace, like nsr_device.hpp: each translation unit gets its own copy.
 #pragma once

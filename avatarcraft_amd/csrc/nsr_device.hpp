@@ -1,5 +1,5 @@
 // avatarcraft_amd/csrc/nsr_device.hpp -- device-side building blocks of the Instant-NSR field on gfx950, shared by the fused
-// renderer (render_fused.hip) and the fused training operators (sdf_train.hip): LDS layout, MFMA-ordered weight fragments,
+// renderer (render_fused.hip) and the fused training operators (train_common.hpp): LDS layout, MFMA-ordered weight fragments,
 // hash-grid gathers (single point and 7-point finite-difference stencil), SDF / colour MLP tiles, DPP scans.
 // Everything lives in an anonymous namespace: each translation unit gets its own copy.
 #pragma once

@@ -420,7 +420,7 @@ __global__ __launch_bounds__(BLOCK) void AC_RENDER_KERNEL(const RenderArgs a)
                 }
             }
             AC_TICK(3)
-            // (the stencil stays inline here, in render_long.hip and in sdf_train.hip's fd_forward: as one shared helper it changes the generated code)
+            // (the stencil stays inline here, in render_long.hip and in field_tile.hpp's fd_forward: as one shared helper it changes the generated code)
             const float pc0 = sel4(g, px, py, pz, 0.0f);
             float spos = 0.0f;
             if constexpr (FAST) {

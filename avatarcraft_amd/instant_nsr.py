@@ -927,7 +927,7 @@ class NeRFNetwork(NeRFRenderer):
         """forward_sdf(x) (:627-642) and finite_difference_normals_approximator(x) (:687-704) together: the seven hash encodings
         come from one stencil launch (encoder.forward_stencil) and the SDF MLP runs once over the 7B points.
         Returns (sdf_out [B,16], gradient [B,3])."""
-        if self.fused_training and self._sdf_supported() and x.is_cuda:            # one kernel forward, two backward (csrc/sdf_train.hip)
+        if self.fused_training and self._sdf_supported() and x.is_cuda:            # one kernel forward, two backward (csrc/sdf_stencil_train.hip)
             l0, l1, enc = self.sdf_net[0], self.sdf_net[1], self.encoder
             W = nsr_ops.weight_norm_all([l0, l1])                                   # the same effective matrices as every other fused path, bit for bit
             return nsr_ops.sdf_stencil(x, enc.embeddings, W[0], l0.bias, W[1], l1.bias, self._offsets_host(), enc.per_level_scale,

@@ -863,7 +863,7 @@ def packed_shading(sdf16, gradient, inv_s, xyzs, dirs, deltas, n_valid, cos_anne
 
 class _SdfStencil(torch.autograd.Function):
     """forward_sdf(x) + finite_difference_normals_approximator(x) of the render core as one fused op with a fused backward
-    (csrc/sdf_train.hip).  Inputs: x [B,3], the hash table, the EFFECTIVE sdf_net matrices (weight norm stays in torch).
+    (csrc/sdf_stencil_train.hip).  Inputs: x [B,3], the hash table, the EFFECTIVE sdf_net matrices (weight norm stays in torch).
     x may require grad (the curvature term's perturbed points, models/instant_nsr.py:276-288: positions that are a function of the normal): the backward then
     also returns d loss / d x = the share through the MLP's own xyz inputs (ac_sdf_stencil_backward_inputs) + the share through the encodings (the
     reference's dy_dx path, hashencoder.cu:177-220,311-337: ac_hash_stencil_input_backward)."""
@@ -925,7 +925,7 @@ class _SdfStencil(torch.autograd.Function):
 
 
 class _ColorMlp(torch.autograd.Function):
-    """forward_color of the render core (use_viewdirs = False) as a fused op with a fused backward (csrc/sdf_train.hip).
+    """forward_color of the render core (use_viewdirs = False) as a fused op with a fused backward (csrc/color_train.hip).
     Inputs: x [B,3] (no grad), normal [B,3], sdf_out [B,16] (column 0 unused), the EFFECTIVE colour matrices."""
 
     @staticmethod
@@ -968,7 +968,7 @@ def color_mlp(x, normal, sdf_out, Wc1, Wc2, Wc3):
 
 
 class _Composite(torch.autograd.Function):
-    """NeuS alpha + compositing of the render core as one fused op each way (csrc/sdf_train.hip)"""
+    """NeuS alpha + compositing of the render core as one fused op each way (csrc/composite.hip)"""
 
     @staticmethod
     def forward(ctx, z_vals, sdf, normal, color, inv_s, rays_o, rays_d, bg, num_steps, bound, car):

@@ -655,6 +655,7 @@ int ac_composite_backward(const float *rays_o, const float *rays_d, const float 
  * writes it for whole tiles only: at other counts the stencil features are gathered again), and a field with view directions needs T a multiple of 16 (AC_ERR_BAD_ARG naming the rule otherwise).
  * The backward chains, on `stream`: normals from the finite-difference gradients -> NeuS alpha / compositing backward ->
  * colour MLP backward -> normalisation + eikonal backward -> fused SDF-query backward -> table-gradient scatter.
+ * Every argument rule is checked before the first of them: a call refused with AC_ERR_BAD_ARG has queued nothing and written nothing.
  *   upstream: d image [N,3], d weights_sum [N], d depth [N], d normal_map [N,3] (any may be NULL = 0), d gradient_error (1 float, device, or NULL)
  *   results : g_table [offsets[16],2] ACCUMULATED into (like hash_encode_backward); g_sdf_params [3344] and g_color_params [7168]
  *             (layouts of ac_sdf_stencil_backward / ac_color_backward, w.r.t. the EFFECTIVE matrices); g_inv_s_per_ray [N].

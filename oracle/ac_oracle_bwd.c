@@ -5,7 +5,7 @@
  *     loss = <g_image, image> + <g_wsum, weights_sum> + <g_depth, depth> + <g_nmap, normal_map> + g_eik * gradient_error
  * (reference models/instant_nsr.py:190-299 differentiated by torch; the callers are stylize.py:163-193 and reconstruct.py:101-112) --
  * restated as one analytic reverse pass in DOUBLE precision, including the scatter into the hash table.  It is an independent witness for the
- * HIP backward (sdf_train.hip / hash_stencil.hip), which runs in fp32 with recomputed activations and a binned scatter: the two share no
+ * HIP backward (render_core_backward.hip / hash_stencil.hip), which runs in fp32 with recomputed activations and a binned scatter: the two share no
  * code, no summation order and no number format.  Pinned against the reference's own autograd by tests/golden/train_grad.npz.
  *
  * What is differentiated, and what is a constant (exactly as in the reference):

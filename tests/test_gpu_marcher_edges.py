@@ -1,4 +1,4 @@
-"""-m gpu: the occupancy-grid marcher (csrc/rm_device.hpp, raymarching.hip, the fused occupancy renderers of sdf_train.hip) against the CPU oracle at
+"""-m gpu: the occupancy-grid marcher (csrc/rm_device.hpp, raymarching.hip, the fused occupancy renderers of render_occupancy.hip) against the CPU oracle at
 the cases of tests/marcher_cases.py -- grids of other sizes and bounds (bound <= 1: dt_gamma = 0; H = 17 .. 129, not powers of two), rays with +0.0 /
 -0.0 direction components, origins inside the volume and on its boundary, a ray that misses, the diagonal ray whose last sample overflows the
 recorder's 1024 positions, a non-zero counter on entry, both sides of the `>= M` cut, every exit of the inference compositor, and the single-workgroup

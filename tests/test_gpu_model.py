@@ -287,7 +287,7 @@ def test_posed_render_matches_reference_render():
 
 
 def test_fused_sdf_query_matches_autograd_formulation():
-    """sdf_stencil (csrc/sdf_train.hip) against the torch formulation (stencil encoder + nn.Linear/Softplus autograd): values and the
+    """sdf_stencil (csrc/sdf_stencil_train.hip) against the torch formulation (stencil encoder + nn.Linear/Softplus autograd): values and the
     gradients w.r.t. the hash table and every sdf_net parameter, for a loss that uses all 16 outputs and the finite-difference normals"""
     net, _ = golden_net(train=True)
     rs = np.random.RandomState(4)
@@ -352,7 +352,7 @@ def test_fused_sdf_query_ragged_sizes(B):
 
 @pytest.mark.parametrize("B", [0, 5, 4099])
 def test_fused_color_mlp_matches_autograd(B):
-    """color_mlp (csrc/sdf_train.hip) against forward_color with torch autograd: rgb, d normal, d feat and the three weight gradients"""
+    """color_mlp (csrc/color_train.hip) against forward_color with torch autograd: rgb, d normal, d feat and the three weight gradients"""
     from avatarcraft_amd import nsr_ops
     net, _ = golden_net(train=True)
     rs = np.random.RandomState(B + 1)
@@ -382,7 +382,7 @@ def test_fused_color_mlp_matches_autograd(B):
 
 
 def test_fused_composite_matches_autograd_formulation():
-    """composite (csrc/sdf_train.hip) against the torch formulation of alpha + compositing: all outputs, and the gradients of a loss
+    """composite (csrc/composite.hip) against the torch formulation of alpha + compositing: all outputs, and the gradients of a loss
     that uses image, weights_sum, depth and normal_map w.r.t. every parameter (incl. the variance); then the whole training render
     with everything fused against everything in torch"""
     net, _ = golden_net(train=True)

@@ -1,7 +1,7 @@
 """The fp64 backward of the render core in oracle/ac_oracle_bwd.c (test infrastructure):
   * CPU: pinned against the reference's own autograd -- tests/golden/train_grad.npz, recorded by running the reference's
     NeRFNetwork.render + the three backward passes of stylize.py:163-193 on 256 rays (tests/golden/make_golden.py);
-  * -m gpu: the HIP backward (ac_render_core_backward: sdf_train.hip + hash_stencil.hip) against it on the 4096-ray patch of BASELINE
+  * -m gpu: the HIP backward (ac_render_core_backward: render_core_backward.hip and the operators it chains + hash_stencil.hip) against it on the 4096-ray patch of BASELINE
     configuration 3 -- every MLP gradient and 65 536 sampled table entries within 3e-4 of each tensor's largest entry (fp32 accumulation of 524 288 terms against fp64)."""
 import numpy as np
 import pytest
