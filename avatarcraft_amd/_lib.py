@@ -84,6 +84,10 @@ class ac_surface_out(C.Structure):
     _fields_ = [("image", vp), ("weights_sum", vp), ("depth", vp), ("position", vp), ("normal_map", vp), ("sdf", vp), ("status", vp), ("iters", vp)]
 
 
+class ac_surface_warped_out(C.Structure):
+    _fields_ = [("canonical", vp), ("normal_can", vp), ("face_id", vp)]
+
+
 class ac_mesh_pose_opts(C.Structure):
     _fields_ = [("iters", i32), ("tol", f32)]
 
@@ -177,6 +181,9 @@ _SIGS = {
     "ac_mesh_vertex_attrs": ([C.POINTER(ac_field), vp, u32, vp, C.POINTER(ac_mesh_attr_opts), vp, vp, vp, vp, vp, vp], C.c_int),
     "ac_mesh_bake_texture": ([C.POINTER(ac_field), vp, u32, vp, u32, C.POINTER(ac_atlas_opts), C.POINTER(ac_mesh_attr_opts), vp, vp, vp, vp, vp, vp], C.c_int),
     "ac_render_rays_surface": ([C.POINTER(ac_field), C.POINTER(ac_surface_opts), vp, vp, u32, vp, C.POINTER(ac_surface_out), vp], C.c_int),
+    "ac_render_rays_surface_warped_scratch": ([u32], C.c_size_t),
+    "ac_render_rays_surface_warped": ([C.POINTER(ac_field), C.POINTER(ac_surface_opts), f32, vp, vp, u32, vp, C.POINTER(ac_warp_mesh), vp, C.c_size_t,
+                                       C.POINTER(ac_surface_out), C.POINTER(ac_surface_warped_out), vp], C.c_int),
     "ac_mesh_bind_scratch": ([u32, u32], C.c_size_t),
     "ac_mesh_bind": ([vp, u32, vp, u32, vp, u32, vp, vp, vp, vp, vp, C.c_size_t, vp], C.c_int),
     "ac_mesh_pose_scratch": ([u32], C.c_size_t),

@@ -22,6 +22,7 @@
 // Order of the output (what makes the mesh reproducible bit for bit, and equal to the CPU oracle's serial loop): vertices by owning grid point (linear
 // index, z fastest) then by axis x, y, z; triangles by cell (linear index) then by table position.
 #include "field_tile.hpp"
+#include "mesh_blend.hpp"
 
 #define AC_MC_CONST static __constant__ const
 #include "ac_mc_table.hpp"
@@ -552,6 +553,207 @@ __global__ __launch_bounds__(FBLOCK) void surface_rays_kernel(const RenderArgs a
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- first-hit render of the POSED level set
+// The image of { p : sdf(W^-1(p)) = level, p inside the mask }: the set the posed renderer draws and net.pose_mesh moves the exported mesh onto (the procedure,
+// operation by operation: include/avatarcraft_hip.h, ac_render_rays_surface_warped).  Every evaluation of the traced function needs the closest-face search of
+// warp.hip at the ray's posed point first.  That search is wave-cooperative and compiled for <= 128 VGPRs, the sdf_tile code needs about 226: they stay separate
+// kernels and the root finder's loop is unrolled on the HOST -- a sequence on one stream, the per-ray state kept in the scratch between the launches:
+//   posed_start_kernel: near / far, the ray state, the first posed point;
+//   max_iters times: the search (unchanged, through its internal launcher; the per-ray `stopped` byte is its ray_dead with one sample per ray), then
+//     posed_trip_kernel: ONE sdf_tile call per tile of 16 rays at the clamped canonical points -- only for a tile with an active unmasked ray (ballot) -- and the
+//     scalar update; it writes the state, the next posed point (the shaded point of a ray that stops) and the stopped byte;
+//   one search at the shaded points (ray_dead = the `noshade` byte), then posed_shade_kernel: refine_shade_tile with steps = 0 at the clamped canonical point behind
+//     surface_rays_kernel's ride-along rule, then the blended transform and the cofactor normal of mesh_blend.hpp in fp64, lane = ray.
+// The host cannot know when every ray has stopped: all max_iters trips are enqueued, a trip without an active ray reads 16 bytes per tile and evaluates nothing.
+// No atomics, no grid barrier, no waits on other waves, plain vector stores; a short last tile reads ray N - 1 and stores nothing for its padding lanes.
+enum : uint8_t { PF_HAVE_LO = 1, PF_BRACKETED = 2, PF_LO_MASKED = 4 };
+struct PosedState {                        // the scratch of ac_render_rays_surface_warped, one row per ray
+    float *pts, *can;                      // [N,3] the posed point the next search reads | its canonical point (the search's can_pts_f32)
+    double *closest, *dist2;               // [N,3], [N] of the search
+    int32_t *face;                         // [N]
+    uint8_t *smask;                        // [N] the search's mask
+    uint8_t *stopped, *noshade;            // [N] ray_dead of the trips' searches | of the shading search
+    uint8_t *st, *iters, *flags;           // [N] status, evaluations, PF_*
+    float *t, *t_lo, *s_lo, *t_hi, *s_hi, *far;      // [N] each; t = the shaded parameter once the ray has stopped
+};
+struct PosedArgs {
+    const float *rays_o, *rays_d, *bg;
+    uint32_t N;
+    int max_iters;
+    float level, tol, step_scale, min_step, guard, w_tol, rt;
+    PosedState s;
+};
+
+__global__ __launch_bounds__(256) void posed_start_kernel(const PosedArgs m, float bound)
+{
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= m.N) return;
+    const float *po = m.rays_o + 3 * (size_t)b, *pd = m.rays_d + 3 * (size_t)b;
+    float near, far;
+    cube_near_far(po[0], po[1], po[2], pd[0], pd[1], pd[2], bound, near, far);
+    const PosedState &s = m.s;
+    s.t[b] = near; s.far[b] = far;
+    s.t_lo[b] = 0.0f; s.s_lo[b] = 0.0f; s.t_hi[b] = 0.0f; s.s_hi[b] = 0.0f;
+    s.flags[b] = 0; s.st[b] = 2; s.iters[b] = 0;
+    s.stopped[b] = far > near ? 0 : 1;
+    s.noshade[b] = 1;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) s.pts[3 * (size_t)b + k] = clampf(po[k] + near * pd[k], -bound, bound);
+}
+
+__global__ __launch_bounds__(FBLOCK) void posed_trip_kernel(const RenderArgs a, const PosedArgs m, int it)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    fill_lds_sdf(lds, a);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
+    const FieldCtx fc = make_ctx(a);
+    const float bound = a.bound;
+    const PosedState &s = m.s;
+    const uint32_t ntiles = (m.N + 15) / 16;
+    for (uint32_t tile = blockIdx.x * FW + wave; tile < ntiles; tile += gridDim.x * FW) {
+        const uint32_t b = tile * 16 + n, bb = b < m.N ? b : m.N - 1;
+        const bool active = s.stopped[bb] == 0;                                  // a stopped ray was not searched: nothing of the search is read for it
+        const bool unmasked = active && s.smask[bb] != 0;
+        const unsigned long long um = __ballot(unmasked);
+        float sv = 0.0f;
+        if (um) {                                                                // (wave-uniform) one evaluation at the clamped canonical points
+            float cx = 0.0f, cy = 0.0f, cz = 0.0f;
+            if (unmasked) {
+                const float *c = s.can + 3 * (size_t)bb;
+                cx = clampf(c[0], -bound, bound); cy = clampf(c[1], -bound, bound); cz = clampf(c[2], -bound, bound);
+            }
+            const int first = __builtin_ctzll(um) & 15;                          // (the four lanes of a ray agree) the other lanes ride along at its point
+            const float fx = __shfl(cx, first), fy = __shfl(cy, first), fz = __shfl(cz, first);
+            if (!unmasked) { cx = fx; cy = fy; cz = fz; }
+            const f32x4 o = sdf_tile(lds, fc, lane, cx, cy, cz);
+            sv = __shfl(o[0], n) - m.level;                                      // output 0 lives in the lanes g == 0
+        }
+        if (active && b < m.N && g == 0) {
+            float t = s.t[b], t_lo = s.t_lo[b], s_lo = s.s_lo[b], t_hi = s.t_hi[b], s_hi = s.s_hi[b];
+            const float far = s.far[b];
+            uint32_t fl = s.flags[b], st = 2u;
+            bool stop = false, in_bracket = false;
+            float sc = sv, k = m.step_scale, t_next = t;
+            if (!unmasked) {                                                     // outside the mask: the gap to the drawable region, an exact safe step
+                const float e = __builtin_sqrtf((float)s.dist2[b]) - m.rt;
+                if (!(__builtin_fabsf(e) < __builtin_inff())) { st = 5u; stop = true; }
+                sc = __builtin_fmaxf(e, m.min_step); k = 1.0f;
+            }
+            if (stop) {}
+            else if (!(__builtin_fabsf(sc) < __builtin_inff())) { st = 5u; stop = true; }
+            else if (unmasked && __builtin_fabsf(sc) <= m.tol) { st = 0u; stop = true; }
+            else if (fl & PF_BRACKETED) {
+                if (sc > 0.0f) { t_lo = t; s_lo = sc; fl = unmasked ? (fl & ~(uint32_t)PF_LO_MASKED) : (fl | PF_LO_MASKED); } else { t_hi = t; s_hi = sc; }
+                in_bracket = true;
+            } else if (sc > 0.0f) {                                              // still outside: a sphere-tracing step, never past far
+                if (t >= far) { st = 2u; stop = true; }
+                else {
+                    t_lo = t; s_lo = sc; fl |= PF_HAVE_LO; fl = unmasked ? (fl & ~(uint32_t)PF_LO_MASKED) : (fl | PF_LO_MASKED);
+                    t_next = __builtin_fminf(t + __builtin_fmaxf(k * sc, m.min_step), far);
+                }
+            } else if (!(fl & PF_HAVE_LO)) { st = 3u; stop = true; }             // the first evaluation is already inside
+            else { fl |= PF_BRACKETED; t_hi = t; s_hi = sc; in_bracket = true; }
+            if (in_bracket) {
+                const float w = t_hi - t_lo;
+                if (w <= m.w_tol) { st = 6u; stop = true; }                      // the bracket closed on a jump: the mask boundary cuts the body here
+                else {                                                           // guarded false position; bisection while the positive end is a masked point
+                    const float q = (fl & PF_LO_MASKED) ? 0.5f : s_lo / (s_lo - s_hi), f = t_lo + w * q, gd = m.guard * w;
+                    t_next = __builtin_fminf(__builtin_fmaxf(f, t_lo + gd), t_hi - gd);
+                }
+            }
+            if (!stop && it == m.max_iters) { st = (fl & PF_BRACKETED) ? 1u : 4u; stop = true; }
+            bool shaded = false;
+            if (stop) {
+                shaded = st == 0u || st == 1u || st == 3u || st == 6u;
+                if (st == 1u || st == 6u) t = t_hi;                              // the shaded parameter: the bracket's inner end
+                s.stopped[b] = 1; s.noshade[b] = shaded ? 0 : 1; s.st[b] = (uint8_t)st;
+            } else t = t_next;
+            s.iters[b] = (uint8_t)it;
+            s.t[b] = t; s.t_lo[b] = t_lo; s.s_lo[b] = s_lo; s.t_hi[b] = t_hi; s.s_hi[b] = s_hi; s.flags[b] = (uint8_t)fl;
+            if (!stop || shaded) {                                               // the next search's point | the shading search's point
+                const float *po = m.rays_o + 3 * (size_t)b, *pd = m.rays_d + 3 * (size_t)b;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) s.pts[3 * (size_t)b + c] = clampf(po[c] + t * pd[c], -bound, bound);
+            }
+        }
+    }
+}
+
+struct PosedOut {
+    float *image, *weights_sum, *depth, *position, *normal_map, *sdf, *canonical, *normal_can;      // each [N] / [N,3] | NULL
+    int32_t *face_id;                      // [N] | NULL
+    uint8_t *status, *iters;               // [N], [N] | NULL
+    const float *verts; const int32_t *faces; const double *T;                                      // the frame's guide
+};
+
+__global__ __launch_bounds__(FBLOCK) void posed_shade_kernel(const RenderArgs a, const PosedArgs m, const PosedOut out)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    fill_lds_sdf(lds, a);
+    if (out.image) fill_lds_color(lds, a);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
+    float *fsl = lds + OFF_WAVE + wave * FE_SLAB;
+    const FieldCtx fc = make_ctx(a);
+    const float bound = a.bound;
+    const PosedState &s = m.s;
+    const RefineOpts ro{ 0, 0.0f, 0.0f, 0.0f, out.image != nullptr };
+    const uint32_t ntiles = (m.N + 15) / 16;
+    for (uint32_t tile = blockIdx.x * FW + wave; tile < ntiles; tile += gridDim.x * FW) {
+        const uint32_t b = tile * 16 + n, bb = b < m.N ? b : m.N - 1;
+        const bool shaded = s.noshade[bb] == 0;
+        const unsigned long long sh_mask = __ballot(shaded);
+        TileShade r{ 0.0f, 0u, FdNormal{ 0.0f, 0.0f, 0.0f, 0.0f }, { 0.0f, 0.0f, 0.0f } };
+        float cx = 0.0f, cy = 0.0f, cz = 0.0f;
+        if (sh_mask) {                                                           // (wave-uniform)
+            if (shaded) {
+                const float *c = s.can + 3 * (size_t)bb;
+                cx = clampf(c[0], -bound, bound); cy = clampf(c[1], -bound, bound); cz = clampf(c[2], -bound, bound);
+            }
+            const float hx = cx, hy = cy, hz = cz;                               // this ray's own point
+            const int first = __builtin_ctzll(sh_mask) & 15;
+            const float fx = __shfl(cx, first), fy = __shfl(cy, first), fz = __shfl(cz, first);
+            if (!shaded) { cx = fx; cy = fy; cz = fz; }
+            r = refine_shade_tile(lds, fsl, fc, a, ro, lane, m.rays_d, (size_t)bb, false, cx, cy, cz);
+            cx = hx; cy = hy; cz = hz;
+        }
+        if (b < m.N && g == 0) {
+            const size_t b3 = 3 * (size_t)b;
+            if (out.image) {
+                float c0 = 1.0f, c1 = 1.0f, c2 = 1.0f;
+                if (shaded) { c0 = r.rgb[0]; c1 = r.rgb[1]; c2 = r.rgb[2]; }
+                else if (m.bg) { c0 = m.bg[b3]; c1 = m.bg[b3 + 1]; c2 = m.bg[b3 + 2]; }
+                out.image[b3] = c0; out.image[b3 + 1] = c1; out.image[b3 + 2] = c2;
+            }
+            if (out.weights_sum) out.weights_sum[b] = shaded ? 1.0f : 0.0f;
+            if (out.depth) out.depth[b] = shaded ? s.t[b] : 0.0f;
+            if (out.position) { out.position[b3] = shaded ? s.pts[b3] : 0.0f; out.position[b3 + 1] = shaded ? s.pts[b3 + 1] : 0.0f; out.position[b3 + 2] = shaded ? s.pts[b3 + 2] : 0.0f; }
+            if (out.canonical) { out.canonical[b3] = shaded ? cx : 0.0f; out.canonical[b3 + 1] = shaded ? cy : 0.0f; out.canonical[b3 + 2] = shaded ? cz : 0.0f; }
+            if (out.normal_can) { out.normal_can[b3] = shaded ? r.fn.nx : 0.0f; out.normal_can[b3 + 1] = shaded ? r.fn.ny : 0.0f; out.normal_can[b3 + 2] = shaded ? r.fn.nz : 0.0f; }
+            if (out.sdf) out.sdf[b] = shaded ? r.s : 0.0f;
+            if (out.face_id) out.face_id[b] = shaded ? s.face[b] : -1;
+            if (out.normal_map) {
+                float nm[3] = { 0.0f, 0.0f, 0.0f };
+                if (shaded) {                                                    // ac_mesh_pose's rules: M blended at the search's closest point and face
+                    const size_t f = (size_t)s.face[b];                          // the search's own answer: always a face of the mesh
+                    const int32_t f0v = out.faces[3 * f], f1v = out.faces[3 * f + 1], f2v = out.faces[3 * f + 2];
+                    const double q[3] = { s.closest[b3], s.closest[b3 + 1], s.closest[b3 + 2] };
+                    double bc[3];
+                    face_bary(q, out.verts, f0v, f1v, f2v, bc);
+                    const Blend M = blend3(out.T, f0v, f1v, f2v, bc);
+                    const float nc[3] = { r.fn.nx, r.fn.ny, r.fn.nz };
+                    normal_store(M, nc, nm);
+                }
+                out.normal_map[b3] = nm[0]; out.normal_map[b3 + 1] = nm[1]; out.normal_map[b3 + 2] = nm[2];
+            }
+            out.status[b] = s.st[b];
+            if (out.iters) out.iters[b] = s.iters[b];
+        }
+        wave_sync();
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------- density grid of the ray marcher
 // Round 6: two launches instead of one.  Round 5 gave every workgroup a brick of 16 x 8 x 8 outputs PLUS the one-point halo the 2^3 max pool reads
 // (17 x 9 x 9 = 1377 evaluations for 1024 outputs, 3.58 M for the 2.15 M points of the 129^3 grid) and cut them into tiles of 16 consecutive evaluations of
@@ -814,6 +1016,79 @@ AC_API int ac_render_rays_surface(const ac_field *field, const ac_surface_opts *
     if (blocks > cus) blocks = cus;
     hipLaunchKernelGGL(surface_rays_kernel, dim3(blocks), dim3(FBLOCK), lds_bytes, (hipStream_t)stream, a, m);
     return ac::check_launch("render_rays_surface");
+}
+
+static size_t posed_state(PosedState *s, void *scratch, uint32_t N)
+{
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    char *b = static_cast<char *>(scratch);
+    size_t o = 0;
+    auto take = [&](size_t bytes) { char *p = b ? b + o : nullptr; o += up(bytes); return p; };
+    const size_t n = N;
+    double *closest = reinterpret_cast<double *>(take(n * 24)), *dist2 = reinterpret_cast<double *>(take(n * 8));
+    float *pts = reinterpret_cast<float *>(take(n * 12)), *can = reinterpret_cast<float *>(take(n * 12));
+    int32_t *face = reinterpret_cast<int32_t *>(take(n * 4));
+    float *f[6];
+    for (auto &p : f) p = reinterpret_cast<float *>(take(n * 4));
+    uint8_t *u[6];
+    for (auto &p : u) p = reinterpret_cast<uint8_t *>(take(n));
+    if (s) *s = PosedState{ pts, can, closest, dist2, face, u[0], u[1], u[2], u[3], u[4], u[5], f[0], f[1], f[2], f[3], f[4], f[5] };
+    return o;
+}
+
+AC_API size_t ac_render_rays_surface_warped_scratch(uint32_t N) { return posed_state(nullptr, nullptr, N); }
+
+AC_API int ac_render_rays_surface_warped(const ac_field *field, const ac_surface_opts *opts, float w_tol, const float *rays_o, const float *rays_d, uint32_t N,
+                                         const float *bg, const ac_warp_mesh *mesh, void *scratch, size_t scratch_bytes, const ac_surface_out *out,
+                                         const ac_surface_warped_out *out_w, ac_stream_t stream)
+{
+    const char *who = "render_rays_surface_warped";
+    if (!field || !opts || !out) { ac::set_error("%s: NULL field, opts or out", who); return AC_ERR_BAD_ARG; }
+    if (opts->max_iters < 1 || opts->max_iters > 255) { ac::set_error("%s: max_iters %d outside 1..255", who, opts->max_iters); return AC_ERR_BAD_ARG; }
+    if (!(opts->tol >= 0.0f) || !(opts->fd_eps > 0.0f) || !(opts->step_scale > 0.0f) || !(opts->min_step > 0.0f) || !(opts->bound > 0.0f)) {
+        ac::set_error("%s: tol not >= 0, or fd_eps, step_scale, min_step or bound not > 0", who); return AC_ERR_BAD_ARG;
+    }
+    if (!(opts->guard >= 0.0f && opts->guard < 0.5f)) { ac::set_error("%s: guard outside [0, 0.5)", who); return AC_ERR_BAD_ARG; }
+    if (!(w_tol >= 0.0f)) { ac::set_error("%s: w_tol not >= 0", who); return AC_ERR_BAD_ARG; }
+    if (!mesh || !mesh->verts || !mesh->faces || !mesh->T || mesh->F == 0) { ac::set_error("%s: NULL mesh, verts, faces or T, or a mesh without faces", who); return AC_ERR_BAD_ARG; }
+    if (N == 0) return AC_OK;
+    if (!rays_o || !rays_d || !out->status) { ac::set_error("%s: NULL rays or status", who); return AC_ERR_BAD_ARG; }
+    if (N > 0xffffffe0u) { ac::set_error("%s: more than 2^32 - 32 rays", who); return AC_ERR_BAD_ARG; }
+    const size_t need = ac_render_rays_surface_warped_scratch(N);
+    if (!scratch || scratch_bytes < need) { ac::set_error("%s: scratch smaller than %zu bytes", who, need); return AC_ERR_BAD_ARG; }
+    RenderArgs a{};
+    if (int rc = prep_args(a, field, opts->bound, opts->fd_eps)) return rc;
+    PosedArgs m{ rays_o, rays_d, bg, N, opts->max_iters, opts->level, opts->tol, opts->step_scale, opts->min_step, opts->guard, w_tol,
+                 sqrtf((float)mesh->threshold), {} };
+    posed_state(&m.s, scratch, N);
+    const PosedState &s = m.s;
+    const hipStream_t st = (hipStream_t)stream;
+    // the culled search where the structure covers the mesh (it skips the rays flagged in `dead`), else the exhaustive one: the same bits
+    const bool culled = mesh->accel && ac_warp_accel_bytes(mesh->F) != 0;
+    auto search = [&](const uint8_t *dead, double *closest, int32_t *face) {
+        if (culled)
+            return ac::warp_samples_accel_impl(s.pts, mesh->verts, mesh->faces, mesh->T, N, mesh->V, mesh->F, mesh->threshold, mesh->accel, nullptr, s.can, closest,
+                                               s.dist2, face, s.smask, stream, 0, dead, 1);
+        return ac_warp_samples(s.pts, mesh->verts, mesh->faces, mesh->T, N, mesh->V, mesh->F, mesh->threshold, nullptr, s.can, closest, s.dist2, face, s.smask, stream);
+    };
+    hipLaunchKernelGGL(posed_start_kernel, dim3((N + 255) / 256), dim3(256), 0, st, m, opts->bound);
+    if (int rc = ac::check_launch(who)) return rc;
+    uint32_t blocks = ((N + 15) / 16 + FW - 1) / FW;              // persistent, one workgroup per CU, like ac_render_rays_surface
+    const uint32_t cus = ac::cu_count();
+    if (blocks > cus) blocks = cus;
+    const size_t trip_lds = OFF_WAVE * sizeof(float), shade_lds = FWD_LDS_FLOATS * sizeof(float);
+    for (int it = 1; it <= opts->max_iters; ++it) {
+        if (int rc = search(s.stopped, nullptr, nullptr)) return rc;
+        hipLaunchKernelGGL(posed_trip_kernel, dim3(blocks), dim3(FBLOCK), trip_lds, st, a, m, it);
+        if (int rc = ac::check_launch(who)) return rc;
+    }
+    if (int rc = search(s.noshade, s.closest, s.face)) return rc;
+    const PosedOut po{ out->image, out->weights_sum, out->depth, out->position, out->normal_map, out->sdf, out_w ? out_w->canonical : nullptr,
+                       out_w ? out_w->normal_can : nullptr, out_w ? out_w->face_id : nullptr, out->status, out->iters, mesh->verts, mesh->faces, mesh->T };
+    static uint64_t seen = 0;
+    ac::allow_dynamic_lds(seen, reinterpret_cast<const void *>(posed_shade_kernel), shade_lds);
+    hipLaunchKernelGGL(posed_shade_kernel, dim3(blocks), dim3(FBLOCK), shade_lds, st, a, m, po);
+    return ac::check_launch(who);
 }
 
 static uint32_t dp_blocks(uint32_t H)

@@ -91,7 +91,7 @@ def render_canonical_360(net, n_views=100, render_hw=(256, 256), center=(0.0, 0.
 
 
 def render_animation(net, body_model, cam_pose, poses=None, render_type="animate", shape_from=None, shape_to=None, resolution=256, max_frames=100,
-                     white_bkg=True, rays_per_batch=None, device="cuda", rank=None, world=None, num_steps=32, upsample_steps=32, table_dtype=None):
+                     white_bkg=True, rays_per_batch=None, device="cuda", rank=None, world=None, num_steps=32, upsample_steps=32, table_dtype=None, surface=False):
     """yields (frame index, rgb [res,res,3]) for an SMPL pose sequence (render_type "animate", poses [F,72]) or a shape interpolation
     ("interp_shape", shape_from / shape_to [1,10]), seen from the dataset camera `cam_pose` [4,4]; 32 + 32 samples per ray like the reference.
     num_steps / upsample_steps: render_warp.py's two command-line counts; outside the fused renderer's window (multiples of 16, num_steps <= 64, at most 128
@@ -101,6 +101,9 @@ def render_animation(net, body_model, cam_pose, poses=None, render_type="animate
     switches above ("half": a net in eval() mode, counts inside the fused renderer's window -- NeRFNetwork.render_table_dtype).
     rays_per_batch: the reference cuts a frame into 64 * 128 = 8192-ray batches (render_warp.py) to bound its memory; the default here is the whole
     frame in one batch (0.13 GB of scratch at 256 x 256): same pixels, and the launches are full when the body covers a fraction of the image.
+    surface=True: every frame is the first-hit render of the posed level set instead (net.render_surface_posed, one call per frame at its default
+    options, on the GPU only) and the generator yields (frame index, rgb [res,res,3], depth [res,res]: the distance along the ray, 0 where nothing is hit);
+    the sample counts, rays_per_batch and table_dtype do not apply.
     rank / world: this process renders the frames shard_indices(n_frames, rank, world) (default: its rank in the default process group; without one,
     every frame); the frame index yielded is the global one.  The SMPL forward of the sequence (calc_local_trans: a few ms) runs on every rank."""
     if rays_per_batch is None:
@@ -118,6 +121,13 @@ def render_animation(net, body_model, cam_pose, poses=None, render_type="animate
     else:
         meshes = (None for _ in mine)
     for i, mesh in zip(mine, meshes):
+        if surface:
+            if mesh is None:
+                raise RuntimeError("render_animation(surface=True) needs the GPU (there is no CPU path)")
+            with torch.no_grad():
+                r = net.render_surface_posed(ro[None], rd[None], NSR_BOUND, mesh, faces, Ts[i], bg_color=None if white_bkg else 0.0)
+            yield i, r["rgb"].reshape(resolution, resolution, 3), r["depth"].reshape(resolution, resolution)
+            continue
         # the loop keeps rgb only: samples the warp masks out (alpha * 0) need no field evaluation (bit-identical pixels).  The switch is set around
         # each frame's render and restored (also when the consumer abandons the generator): the caller's net keeps its documented default
         prev = getattr(net, "skip_masked_samples", None)

@@ -1129,6 +1129,43 @@ class NeRFNetwork(NeRFRenderer):
                 "normal": o["normal_map"], "position": o["position"].reshape(B, N, 3), "sdf": o["sdf"].reshape(B, N), "status": o["status"].reshape(B, N),
                 "iters": o["iters"].reshape(B, N)}
 
+    def render_surface_posed(self, rays_o, rays_d, bound, verts, faces, Ts, bg_color=None, max_ray_batch=None, normal_epsilon_ratio=0.0, **opts):
+        """render_surface in the pose of one frame (ac_render_rays_surface_warped): per ray the first point of { p : sdf(W^-1(p)) = level } inside the warp's mask
+        -- the set the posed volumetric render draws and pose_mesh moves the exported mesh onto -- about a dozen closest-face searches per ray where a posed
+        volumetric frame takes 64.  verts [Vg,3], faces [F,3], Ts [>= Vg,4,4]: the frame's posed guide and transforms (calc_local_trans), or verts = an
+        nsr_ops.WarpMesh of the frame (faces, Ts unused).  opts: level, tol, max_iters, step_scale, min_step, guard, w_tol of nsr_ops.render_rays_surface_warped,
+        and want_rgb.
+        -> render_surface's keys and shapes -- rgb [B,N,3], depth [B,N] (the ray parameter of the shaded point; 0 where nothing is hit), weight_sum [B N,1],
+        normal [B N,3] (POSED), position [B,N,3] (posed), sdf, status (shaded = 0, 1, 3 or 6; 6 = the mask boundary cuts the body there), iters [B,N] -- plus
+        canonical [B,N,3] (the shaded point in canonical space), normal_can [B N,3] and face_id [B,N] int32 (closest guide face, -1 where not shaded).
+        Builds no autograd graph: the call raises where autograd would record.  It does not go through render() / render_route."""
+        want_rgb = bool(opts.pop("want_rgb", True))
+        if not (self.encoder.embeddings.is_cuda and self._sdf_supported()):
+            raise RuntimeError("render_surface_posed needs the default SDF side of NeRFNetwork on the GPU")
+        if want_rgb and not self._fused_supported(ignore_curvature=True):
+            raise RuntimeError("render_surface_posed: the colour side of this model is not the default one (colour net 21-64-64-3, or 37-64-64-3 with the "
+                               "degree-4 view-direction encoder); want_rgb=False renders geometry only")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise RuntimeError("render_surface_posed builds no autograd graph (the hit point is the result of a root finder): call it under torch.no_grad()")
+        B, N = rays_o.shape[:2]
+        n = B * N
+        fd_eps = nsr_ops.FD_STEP * (1.0 - normal_epsilon_ratio)
+        nsr_ops.surface_warped_opts(bound, fd_eps, **opts)                            # bad options raise before any device work
+        with torch.no_grad():
+            ro = rays_o.reshape(-1, 3).float().contiguous()
+            rd = rays_d.reshape(-1, 3).float().contiguous()
+            wm = verts if isinstance(verts, nsr_ops.WarpMesh) else nsr_ops.WarpMesh(verts, faces, Ts, ro.device)
+            bg = None if bg_color is None else _background(bg_color, n, ro.device).contiguous()
+            f = self._field() if self._fused_supported(ignore_curvature=True) else self._field_sdf_only()
+            step = max(int(max_ray_batch or n), 1)                                    # (None: the whole view in one call)
+            parts = [nsr_ops.render_rays_surface_warped(f, ro[h:h + step], rd[h:h + step], bound, wm, fd_eps, bg=None if bg is None else bg[h:h + step],
+                                                        want_rgb=want_rgb, **opts) for h in (range(0, n, step) or (0,))]
+            o = parts[0] if len(parts) == 1 else {k: (None if parts[0][k] is None else torch.cat([p[k] for p in parts])) for k in parts[0]}
+        return {"rgb": None if o["image"] is None else o["image"].reshape(B, N, 3), "depth": o["depth"].reshape(B, N), "weight_sum": o["weights_sum"][:, None],
+                "normal": o["normal_map"], "position": o["position"].reshape(B, N, 3), "sdf": o["sdf"].reshape(B, N), "status": o["status"].reshape(B, N),
+                "iters": o["iters"].reshape(B, N), "canonical": o["canonical"].reshape(B, N, 3), "normal_can": o["normal_can"],
+                "face_id": o["face_id"].reshape(B, N)}
+
     def extract_textured_mesh(self, bound: float, resolution: int, texture_size: int = 2048, cell=None, threshold: float = 0.0, refine_steps: int = 3,
                               tol: float = 1e-5, return_torch=False):
         """extract_colored_mesh's mesh with the colour network baked into a texture instead of sampled at the vertices, so that colour detail no longer depends on

@@ -1326,9 +1326,8 @@ def mesh_bake_texture(field, positions, triangles, size, cell, bound, eps=FD_STE
     return out
 
 
-def surface_opts(bound, fd_eps, level=0.0, tol=1e-4, max_iters=64, step_scale=1.0, min_step=1e-3, guard=0.125):
+def surface_opts(bound, fd_eps, level=0.0, tol=1e-4, max_iters=64, step_scale=1.0, min_step=1e-3, guard=0.125, who="render_rays_surface"):
     """ac_surface_opts from Python numbers; the checks of ac_render_rays_surface made here, before any device work (RuntimeError naming the option)"""
-    who = "render_rays_surface"
     try:
         mi = int(max_iters)
         bound, fd_eps, level, tol, step_scale, min_step, guard = (float(v) for v in (bound, fd_eps, level, tol, step_scale, min_step, guard))
@@ -1372,6 +1371,60 @@ def render_rays_surface(field, rays_o, rays_d, bound, fd_eps, *, level=0.0, tol=
     so = L.ac_surface_out(*[L.ptr(out[k]) for k in ("image", "weights_sum", "depth", "position", "normal_map", "sdf", "status", "iters")])
     L.check(L.lib().ac_render_rays_surface(C.byref(field.c), C.byref(opts), rays_o.data_ptr(), rays_d.data_ptr(), N, L.ptr(bg), C.byref(so),
                                            L.current_stream(dev)), "render_rays_surface")
+    return out
+
+
+SURFACE_WARPED_OUTPUTS = ("image", "weights_sum", "depth", "position", "normal_map", "sdf", "status", "iters", "canonical", "normal_can", "face_id")
+
+
+def surface_warped_opts(bound, fd_eps, level=0.0, tol=1e-4, max_iters=64, step_scale=1.0, min_step=1e-3, guard=0.125, w_tol=1e-4):
+    """(ac_surface_opts, w_tol) from Python numbers; the checks of ac_render_rays_surface_warped made here, before any device work (RuntimeError naming the option)"""
+    who = "render_rays_surface_warped"
+    opts = surface_opts(bound, fd_eps, level, tol, max_iters, step_scale, min_step, guard, who=who)
+    try:
+        w_tol = float(w_tol)
+    except (TypeError, ValueError) as e:
+        raise RuntimeError(f"{who}: w_tol must be a number ({e})") from e
+    if not (w_tol >= 0.0 and np.float32(w_tol) >= 0.0):
+        raise RuntimeError(f"{who}: w_tol {w_tol!r} not >= 0")
+    return opts, w_tol
+
+
+def render_rays_surface_warped(field, rays_o, rays_d, bound, warp, fd_eps=FD_STEP, *, level=0.0, tol=1e-4, max_iters=64, step_scale=1.0, min_step=1e-3, guard=0.125,
+                               w_tol=1e-4, bg=None, want_rgb=True):
+    """ac_render_rays_surface_warped: the first-hit render of the POSED level set { p : sdf(W^-1(p)) = level, p inside the mask }, W^-1 the inverse warp of the
+    frame `warp` (an nsr_ops.WarpMesh) -- what the posed renderer draws and mesh_pose moves a mesh onto.  rays_o, rays_d [N,3] float32 on the device.  Per ray and
+    trip one closest-face search at the posed point, then either the canonical SDF there (inside the mask) or the gap to the mask (outside: an exact safe step);
+    sphere tracing to the sign change, guarded false position inside the bracket (bisection while its outer end is a masked point), at most max_iters trips (the
+    procedure operation by operation: include/avatarcraft_hip.h).  One C call; the scratch is allocated here.
+    -> dict(image [N,3] | None, weights_sum [N], depth [N] (the ray parameter of the shaded point), position [N,3] (posed), normal_map [N,3] (posed), sdf [N],
+    status [N] uint8 (0 .. 5 as render_rays_surface, 6 = the bracket closed on the mask boundary to within w_tol; shaded = 0, 1, 3 or 6), iters [N] uint8 (searches
+    of the root finder), canonical [N,3] (the shaded point in canonical space), normal_can [N,3], face_id [N] int32 (closest guide face; -1 where not shaded))"""
+    who = "render_rays_surface_warped"
+    opts, w_tol = surface_warped_opts(bound, fd_eps, level, tol, max_iters, step_scale, min_step, guard, w_tol)
+    rays_o = _chk(rays_o, "rays_o")
+    if rays_o.dim() != 2 or rays_o.shape[1] != 3:
+        raise RuntimeError(f"{who}: rays_o must be [N,3], got {tuple(rays_o.shape)}")
+    if not isinstance(warp, WarpMesh):
+        raise RuntimeError(f"{who}: warp must be an nsr_ops.WarpMesh")
+    N, dev = rays_o.shape[0], rays_o.device
+    rays_d = _chk(rays_d, "rays_d", (N, 3))
+    if bg is not None:
+        bg = _chk(bg, "bg", (N, 3))
+    if rays_d.device != dev or (bg is not None and bg.device != dev) or field.device != dev or warp.verts.device != dev:
+        raise RuntimeError(f"{who}: field, rays_o, rays_d, bg and the mesh must live on one device")
+    if warp.faces.shape[0] == 0:
+        raise RuntimeError(f"{who}: a mesh without faces")
+    f = lambda *sh: torch.empty(sh, dtype=_F32, device=dev)
+    u8 = lambda: torch.empty(N, dtype=torch.uint8, device=dev)
+    out = dict(image=f(N, 3) if want_rgb else None, weights_sum=f(N), depth=f(N), position=f(N, 3), normal_map=f(N, 3), sdf=f(N), status=u8(), iters=u8(),
+               canonical=f(N, 3), normal_can=f(N, 3), face_id=torch.empty(N, dtype=torch.int32, device=dev))
+    so = L.ac_surface_out(*[L.ptr(out[k]) for k in ("image", "weights_sum", "depth", "position", "normal_map", "sdf", "status", "iters")])
+    sw = L.ac_surface_warped_out(*[L.ptr(out[k]) for k in ("canonical", "normal_can", "face_id")])
+    need = int(L.lib().ac_render_rays_surface_warped_scratch(N))
+    scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    L.check(L.lib().ac_render_rays_surface_warped(C.byref(field.c), C.byref(opts), w_tol, rays_o.data_ptr(), rays_d.data_ptr(), N, L.ptr(bg), C.byref(warp.c),
+                                                  scratch.data_ptr(), need, C.byref(so), C.byref(sw), L.current_stream(dev)), who)
     return out
 
 

@@ -815,6 +815,69 @@ int ac_mesh_pose(const float *points /*[V,3]*/, const float *normals /*optional 
                  float *positions /*[V,3]*/, float *normals_out /*optional [V,3]*/, float *residual /*optional [V]*/, uint8_t *status /*optional [V]*/,
                  uint8_t *mask /*optional [V]*/, ac_stream_t stream);
 
+/* ---- first-hit render of the POSED level set (csrc/geometry.hip; added entries and one new struct, no struct of an existing call changes: ABI stays 10)
+ * ac_render_rays_surface_warped: ac_render_rays_surface through the SMPL warp -- per ray the first point p of { p : sdf(W^-1(p)) = level, p inside the mask },
+ * W^-1 the inverse warp of ac_warp_samples for the frame's mesh: the set ac_render_rays_warped draws (alpha * mask) and ac_mesh_pose moves a mesh onto.  It
+ * stands in for nothing in the reference.  Inputs: those of ac_render_rays_surface, plus w_tol (1e-4) and an ac_warp_mesh of which verts, faces, T, V, F,
+ * threshold and accel are used (near/far guide and seeds are not).  rt = sqrtf((float)threshold).  All fp32, every operation rounded once (t*d then the add;
+ * correctly rounded division and square root), in this order, unless marked fp64; per ray:
+ *   near, far = the cube's slab test exactly as ac_render_rays_surface forms it
+ *   if not (far > near): status 2, iters 0, no search, no evaluation
+ *   t = near; have_lo = bracketed = lo_masked = false
+ *   for it = 1 .. max_iters:
+ *       p = clamp(o + t d, +-bound) per coordinate                                      (posed space)
+ *       search at p: the bits of ac_warp_samples -> can (its can_pts_f32), dist2 (fp64), m = mask (dist2 < threshold);  iters = it
+ *       if m:  c = clamp(can, +-bound);  s = forward_sdf(c)[0] - level (the bits of ac_field_sdf);  k = step_scale
+ *       else:  e = sqrtf((float)dist2) - rt;  e not finite -> status 5, stop;  s = max(e, min_step);  k = 1
+ *       s not finite            -> status 5, stop
+ *       m and |s| <= tol        -> status 0, stop                                       (a masked point is never a hit)
+ *       if not bracketed:
+ *           if s > 0:
+ *               t >= far        -> status 2, stop
+ *               (t_lo, s_lo, lo_masked) = (t, s, !m); have_lo = true
+ *               t_next = min(t + max(k s, min_step), far);  goto advance
+ *           not have_lo         -> status 3, stop                                       (the first evaluation is already inside; necessarily unmasked)
+ *           bracketed = true; (t_hi, s_hi) = (t, s)
+ *       else: s > 0 ? (t_lo, s_lo, lo_masked) = (t, s, !m) : (t_hi, s_hi) = (t, s)
+ *       w = t_hi - t_lo
+ *       w <= w_tol              -> status 6, stop                                       (the bracket closed on a jump: the mask boundary cuts the body here)
+ *       q = lo_masked ? 0.5 : s_lo / (s_lo - s_hi);  f = t_lo + w q;  g = guard w
+ *       t_next = min(max(f, t_lo + g), t_hi - g)
+ *     advance:
+ *       it == max_iters -> status bracketed ? 1 : 4, stop
+ *       t = t_next
+ * Outside the mask (dist2 >= threshold) the posed renderer draws nothing; the traced function there is the Euclidean gap to the drawable region, an exact safe
+ * step for a unit direction up to the fp32 rounding of the gap (about 1e-7): a gap step never jumps over the body, and a ray far from it reaches it, or far,
+ * in a few trips.  Inside the mask the traced function is the canonical SDF scaled by step_scale, as in ac_render_rays_surface.  t_hi is always an unmasked
+ * point (s <= 0 implies m: masked values are >= min_step > 0).  When the bracket's positive end is a masked point the function jumps at the mask boundary and
+ * false position would crawl: the rule bisects instead.  t is the ray PARAMETER: for |d| != 1 a gap step of e moves the point by e |d| (safe only for
+ * |d| <= 1); directions are used as given, never normalised.
+ * status 0 .. 5 as in ac_render_rays_surface; 6 = the bracket closed on the mask boundary.  SHADED rays are those with status 0, 1, 3 and 6; their parameter
+ * t_s is t for status 0 and 3, t_hi for status 1 and 6.  Shading: one more search at p_s = clamp(o + t_s d); c = clamp(can); one seven-point stencil at c with
+ * fd_eps exactly as ac_render_rays_surface shades (sdf, the canonical normal n_c, rgb with the ray's rays_d row AS GIVEN as view direction); the posed normal
+ * by ac_mesh_pose's rules: M blended from T at the search's closest point and face with the barycentrics of ac_warp_samples, n = cofactor(A) n_c / (1e-30 +
+ * length) in fp64, rounded to fp32.
+ * Outputs ([N] or [N,3]; each optional except out->status; each 0 where the ray is not shaded, except image): out->image = rgb, else bg (NULL: white; image ==
+ * NULL skips the colour network) | weights_sum = 1 or 0 | depth = t_s | position = p_s (posed) | normal_map = the posed normal | sdf = the centre's raw
+ * output 0 at c | status, iters (searches of the root finder) uint8 | out_w (optional) -> canonical = c | normal_can = n_c | face_id = the closest face at
+ * p_s (int32, -1 where not shaded).
+ * One C call enqueues, on one stream: a prologue, max_iters x (the closest-face search, unchanged: the culled form when accel is given and F <= 16384, else
+ * the exhaustive one, same bits; then a trip kernel that evaluates the field once per tile of 16 rays that has an active unmasked ray), one search at the
+ * shaded points and the shading kernel.  A ray that has stopped is flagged to the culled search and is not searched again.  No atomics, no waits.  N == 0
+ * launches nothing.  scratch: ac_render_rays_surface_warped_scratch(N) bytes (90 N + a few KB).
+ * AC_ERR_BAD_ARG before any launch: everything ac_render_rays_surface refuses; w_tol not >= 0; a NULL mesh or a mesh with NULL verts, faces or T; F == 0;
+ * a scratch smaller than ac_render_rays_surface_warped_scratch(N).  PRECONDITION, as for ac_mesh_pose: every face index lies in [0, V').
+ * Bit-identical to the same fp32 arithmetic in numpy around the CPU oracle's orc_warp_samples / orc_field_sdf / orc_field_samples
+ * (tests/test_gpu_surface_posed.py). */
+typedef struct ac_surface_warped_out {
+    float *canonical, *normal_can;      /* [N,3] each */
+    int32_t *face_id;                   /* [N] */
+} ac_surface_warped_out;
+size_t ac_render_rays_surface_warped_scratch(uint32_t N);
+int ac_render_rays_surface_warped(const ac_field *field, const ac_surface_opts *opts, float w_tol, const float *rays_o /*[N,3]*/, const float *rays_d /*[N,3]*/,
+                                  uint32_t N, const float *bg /*optional [N,3]*/, const ac_warp_mesh *mesh, void *scratch, size_t scratch_bytes,
+                                  const ac_surface_out *out, const ac_surface_warped_out *out_w /*optional*/, ac_stream_t stream);
+
 /* ---- rendering from a half-precision hash table (opt-in, inference only) ----------------------------------------------------------------------------
  * The half table holds ONE dword per entry of the fp32 table [n_entries][2] (n_entries = field->offsets[16]): channel 0 as an IEEE binary16 in the low
  * half, channel 1 in the high half -- 4 bytes per entry instead of 8, the same level offsets.  ac_table_to_half makes it: every value is rounded to
