@@ -474,8 +474,13 @@ __global__ __launch_bounds__(SAVED ? TW_S * 64 : TBLOCK) void sdf_stencil_bwd_ke
 #pragma unroll
             for (int s1 = 0; s1 < 8; ++s1) TI[(3 + 2 * (4 * (s1 >> 1) + g) + (s1 & 1)) * TLD + n] = fe[s1 >> 1][s1 & 1];
             }
+            // db2: the centre evaluation alone.  The two offset evaluations of an axis carry +s and -s on output 0 (exact negatives, s = g_k / (2 eps) ~ 100 x
+            // the centre's upstream): their shares cancel exactly, and adding them to the running sum left only the rounding of (sum + s) - s behind --
+            // db2[0] was 10 x further from float64 autograd than float32 autograd is (tests/test_gpu_field_ops.py)
+            if (!rank1) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) gb2[r] += d2[r];
+                for (int r = 0; r < 4; ++r) gb2[r] += d2[r];
+            }
             wave_sync();
             ++step;
             if constexpr (!PIPE) {
