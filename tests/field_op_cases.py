@@ -10,7 +10,8 @@ A second mode of the same restatements, "K", is a model of the ROUNDING the kern
   * softplus(beta = 100) and its derivative from the 128-piece cubic of tools/gen_softplus_table.fit(), the backward being the cubic's own derivative;
   * SDF backward: dinp = W1[:, 3:]^T d1 as a three-term bf16 split (weights rounded to nearest, d1 truncated: split8_bf16), layer 1 of the six offset
     evaluations recomputed as the centre's plus a three-term split of W1[:, 3:] (fe - fe0) (sdf_l1_delta, differences truncated); dW1 += d1 inp^T is
-    a float32 product in the stand-alone operator (the bf16 form belongs to the saved-feature variant, which only ac_render_core_backward reaches);
+    a float32 product in the stand-alone operator (the bf16 form belongs to the saved-feature variant, which only ac_render_core_backward reaches:
+    SdfLayer1's dw1, used by tests/core_backward_cases.py);
   * colour backward: layer 3 of the recomputation, dh1 = Wc2^T dh2 and dinp = Wc1^T dh1 as three-term splits, both factors rounded to nearest;
   * every (sample, point, corner) contribution to the table gradient rounded to 16 / 17 explicit mantissa bits (rec_round) and summed exactly (the
     64-bit fixed-point grid lies 2^-40 below the level's largest record at these sizes), one rounding to float32 at the end.
@@ -212,18 +213,27 @@ class DeclaredLinear(torch.autograd.Function):
 
 class SdfLayer1(torch.autograd.Function):
     """a = [p, feat] W1^T + b1 with the backward of sdf_stencil_bwd_kernel: d p through W1[:, :3] in float32, d feat as the truncated three-term split,
-    d W1 and d b1 float32.  value: the pre-activation the backward recomputes for an offset evaluation (sdf_l1_delta), in place of the plain product"""
+    d W1 and d b1 float32.  value: the pre-activation the backward recomputes for an offset evaluation (sdf_l1_delta), in place of the plain product.
+    dw1: None = d W1 += d1 inp^T as a float32 product (the stand-alone operator); "split" = the saved-feature variant's (sdf_stencil_bwd_kernel<SAVED =
+    true>, reached through ac_render_core_backward alone): d1 and inp = [p, feat, 1] split hi + lo, each part rounded to nearest, hi hi + lo hi + hi lo
+    with float32 sums, d b1 the column of ones of that product; "hi" = the hi x hi term alone (a mutant)"""
 
     @staticmethod
-    def forward(ctx, p, feat, W1, b1, value, drop_lo):
+    def forward(ctx, p, feat, W1, b1, value, drop_lo, dw1=None):
         ctx.save_for_backward(p, feat, W1)
-        ctx.drop_lo = drop_lo
+        ctx.drop_lo, ctx.dw1 = drop_lo, dw1
         return p @ W1[:, :3].T + feat @ W1[:, 3:].T + b1 if value is None else value.clone()
 
     @staticmethod
     def backward(ctx, g):
         p, feat, W1 = ctx.saved_tensors
-        return (g @ W1[:, :3], split_mm(g, W1[:, 3:].T.contiguous(), "trunc", ctx.drop_lo), g.T @ torch.cat([p, feat], -1), g.sum(0), None, None)
+        inp = torch.cat([p, feat], -1)
+        if ctx.dw1 is None:
+            gW, gb = g.T @ inp, g.sum(0)
+        else:
+            (dh, dl), (ih, il) = split_bf16(g, "rn"), split_bf16(inp, "rn")
+            gW, gb = (dh.T @ ih, dh.sum(0)) if ctx.dw1 == "hi" else (dh.T @ ih + dl.T @ ih + dh.T @ il, dh.sum(0) + dl.sum(0))
+        return (g @ W1[:, :3], split_mm(g, W1[:, 3:].T.contiguous(), "trunc", ctx.drop_lo), gW, gb, None, None, None)
 
 
 def round_record(v, drop):
@@ -259,9 +269,9 @@ def sdf_query_ref(pts, feat, W1, b1, W2, b2, act=None, mutant=None):
     return o[0], fd_gradient(o[1:, :, 0], pts, mutant == "div_clamped")
 
 
-def sdf_query_declared(pts, feat, W1, b1, W2, b2, drop_lo=False):
-    """the arithmetic of sdf_stencil_bwd_kernel: the centre's layer 1 in float32, the six offset evaluations' as corrections of it"""
-    a0 = SdfLayer1.apply(pts[0], feat[0], W1, b1, None, drop_lo)
+def sdf_query_declared(pts, feat, W1, b1, W2, b2, drop_lo=False, dw1=None):
+    """the arithmetic of sdf_stencil_bwd_kernel: the centre's layer 1 in float32, the six offset evaluations' as corrections of it (dw1: SdfLayer1)"""
+    a0 = SdfLayer1.apply(pts[0], feat[0], W1, b1, None, drop_lo, dw1)
     out16 = TableSoftplus.apply(a0) @ W2.T + b2
     sd = []
     with torch.no_grad():
@@ -270,7 +280,7 @@ def sdf_query_declared(pts, feat, W1, b1, W2, b2, drop_lo=False):
         k = (e - 1) >> 1
         with torch.no_grad():
             value = a0 + split_mm(feat[e] - feat[0], W1d[:, 3:], "trunc") + (pts[e, :, k] - pts[0, :, k])[:, None] * W1d[:, k]
-        a = SdfLayer1.apply(pts[e], feat[e], W1, b1, value, drop_lo)
+        a = SdfLayer1.apply(pts[e], feat[e], W1, b1, value, drop_lo, dw1)
         sd.append((TableSoftplus.apply(a) * W2[0]).sum(-1) + b2[0])
     return out16, fd_gradient(torch.stack(sd), pts)
 
@@ -498,14 +508,14 @@ def color_cases():
     return cases
 
 
-def color_rows_pass(x, n, o, Wt):
-    """float64 arrays: no hidden pre-activation of layer 1 or 2 within GATE_MARGIN of its terms' absolute sum"""
+def color_rows_pass(x, n, o, Wt, margin=GATE_MARGIN):
+    """float64 arrays: no hidden pre-activation of layer 1 or 2 within margin (GATE_MARGIN) of its terms' absolute sum"""
     h = np.concatenate([x, n, o[:, 1:]], -1)
     W1, W2 = Wt["Wc1"].double().numpy(), Wt["Wc2"].double().numpy()
     a1, s1 = h @ W1.T, np.abs(h) @ np.abs(W1).T
     h1 = np.maximum(a1, 0.0)
     a2, s2 = h1 @ W2.T, h1 @ np.abs(W2).T
-    return ~((np.abs(a1) < GATE_MARGIN * s1).any(-1) | (np.abs(a2) < GATE_MARGIN * s2).any(-1))
+    return ~((np.abs(a1) < margin * s1).any(-1) | (np.abs(a2) < margin * s2).any(-1))
 
 
 ZERO_NORMAL_FROM = 3                                       # candidate row from which the row with an all-zero normal is placed

@@ -45,9 +45,11 @@ def cube_near_far(ro, rd, bound):
 
 
 # ---- restatements --------------------------------------------------------------------------------------------------------------------------------
-def neus_alpha_ref(sdf, true_cos, deltas, inv_s, car):
-    """models/instant_nsr.py:222-243; sdf, true_cos, deltas of one shape, inv_s broadcastable, car a Python float"""
-    iter_cos = -(F.softplus(-true_cos * 0.5 + 0.5, beta=100) * (1.0 - car) + F.softplus(-true_cos, beta=100) * car)
+def neus_alpha_ref(sdf, true_cos, deltas, inv_s, car, softplus=None):
+    """models/instant_nsr.py:222-243; sdf, true_cos, deltas of one shape, inv_s broadcastable, car a Python float (softplus: another evaluation of
+    softplus(beta = 100) -- the kernels' table cubic, for a model of their declared arithmetic)"""
+    softplus = softplus or (lambda a: F.softplus(a, beta=100))
+    iter_cos = -(softplus(-true_cos * 0.5 + 0.5) * (1.0 - car) + softplus(-true_cos) * car)
     next_sdf = sdf + iter_cos * deltas * 0.5
     prev_sdf = sdf - iter_cos * deltas * 0.5
     prev_cdf, next_cdf = torch.sigmoid(prev_sdf * inv_s), torch.sigmoid(next_sdf * inv_s)
@@ -69,11 +71,11 @@ def composite_from_alpha(alpha, color, z, near, far, bg, normal=None):
     return out
 
 
-def composite_ref(z, sdf, normal, color, inv_s, rays_d, bg, near, far, num_steps, car):
+def composite_ref(z, sdf, normal, color, inv_s, rays_d, bg, near, far, num_steps, car, softplus=None):
     """models/instant_nsr.py:222-263, 290-294 -> image [N,3], weights_sum [N], depth [N], normal_map [N,3], weights [N,T], alpha [N,T]"""
     deltas = torch.cat([z[:, 1:] - z[:, :-1], ((far - near) / num_steps)[:, None]], dim=-1)
     true_cos = (rays_d[:, None, :] * normal).sum(-1)
-    alpha = neus_alpha_ref(sdf, true_cos, deltas, inv_s, car)
+    alpha = neus_alpha_ref(sdf, true_cos, deltas, inv_s, car, softplus)
     out = composite_from_alpha(alpha, color, z, near, far, bg, normal)
     out["alpha"] = alpha
     return out
