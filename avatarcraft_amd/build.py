@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libavatarcraft_hip.so")
 SOURCES = ["ac_capi.hip", "hashgrid.hip", "hash_stencil.hip", "shencoder.hip", "raymarching.hip", "render_fused.hip", "render_long.hip", "render_occupancy.hip", "sdf_stencil_train.hip", "color_train.hip",
-           "composite.hip", "render_core_backward.hip", "warp.hip", "step_glue.hip", "geometry.hip", "mesh_pose.hip"]
+           "composite.hip", "render_core_backward.hip", "warp.hip", "warp_accel_build.hip", "step_glue.hip", "geometry.hip", "mesh_pose.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fvisibility=hidden",
          "-Wno-unused-result",
          # no compiler-formed packed-fp32 (v_pk_*_f32) code: the one run-to-run non-determinism ever observed in the renderer (round 2: the "face-value"
@@ -32,11 +32,12 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 #   hash_stencil.hip (table-gradient scatter): max-memory-clause -- the queue fill is a long sequence of LDS record traffic between short arithmetic sections:
 #       1.246 -> 1.188 ms per 4096-ray patch (the same strategy costs the render kernel 7 %, so it is not a global flag);
 #   render_fused.hip: iterative-maxocc -- 0.763 -> 0.752 ms per 4096-ray launch of the instantiation without per-sample outputs (+0.6 % on the training one);
-#   warp.hip: iterative-maxocc -- posed frame 8.21 -> 8.08 ms.
+#   warp.hip: iterative-maxocc -- posed frame 8.21 -> 8.08 ms (warp_accel_build.hip: the structure's builder kernels, compiled as they were inside warp.hip).
 PER_FILE_FLAGS = {"hash_stencil.hip": ["-mllvm", "-amdgpu-sched-strategy=max-memory-clause"],
                   "render_fused.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-maxocc"],
                   "render_long.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-maxocc"],
-                  "warp.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-maxocc"]}
+                  "warp.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-maxocc"],
+                  "warp_accel_build.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-maxocc"]}
 
 
 # Library variants built next to the product (in-tree, so that they travel to the GPU box; git-ignored like every .so): the same objects except the listed

@@ -556,7 +556,7 @@ __global__ __launch_bounds__(FBLOCK) void surface_rays_kernel(const RenderArgs a
 // ---------------------------------------------------------------------------------------------------------------- first-hit render of the POSED level set
 // The image of { p : sdf(W^-1(p)) = level, p inside the mask }: the set the posed renderer draws and net.pose_mesh moves the exported mesh onto (the procedure,
 // operation by operation: include/avatarcraft_hip.h, ac_render_rays_surface_warped).  Every evaluation of the traced function needs the closest-face search of
-// warp.hip at the ray's posed point first.  That search is wave-cooperative and compiled for <= 128 VGPRs, the sdf_tile code needs about 226: they stay separate
+// warp.hip (over the mesh's culling structure: warp_accel.hpp, built by warp_accel_build.hip) at the ray's posed point first.  That search is wave-cooperative and compiled for <= 128 VGPRs, the sdf_tile code needs about 226: they stay separate
 // kernels and the root finder's loop is unrolled on the HOST -- a sequence on one stream, the per-ray state kept in the scratch between the launches:
 //   posed_start_kernel: near / far, the ray state, the first posed point;
 //   max_iters times: the search (unchanged, through its internal launcher; the per-ray `stopped` byte is its ray_dead with one sample per ray), then

@@ -9,7 +9,7 @@ namespace {
 
 #define AC_DOT3(u, v) ((u)[0] * (v)[0] + (u)[1] * (v)[1] + (u)[2] * (v)[2])
 
-// barycentrics of q on the face (f0v, f1v, f2v): finish_sample's formula
+// barycentrics of q on the face (f0v, f1v, f2v); the inverse warp (warp.hip's finish_sample) and the forward one share this formula
 __device__ __forceinline__ void face_bary(const double (&q)[3], const float *__restrict__ verts, int32_t f0v, int32_t f1v, int32_t f2v, double (&bc)[3])
 {
     double a[3], b[3], c[3], v0[3], v1[3], v2[3];

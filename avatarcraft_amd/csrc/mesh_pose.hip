@@ -2,10 +2,11 @@
 //
 // The posed renderer draws the surface { p : sdf(W^-1(p)) = 0 }, W^-1 = the SMPL-guided inverse warp of ac_warp_samples (warp.hip).  The posed position of a
 // canonical vertex c is therefore the p with W^-1(p) = c: a fixed point of p <- fwd(M(p), c), M(p) = the blended transform at the closest face of the
-// posed guide.  The closest-face searches are warp.hip's, launched through their public entries exactly as they are; this file adds the per-vertex
+// posed guide.  The closest-face searches are warp.hip's (over the structure that warp_accel_build.hip builds), launched through their public entries
+// exactly as they are; this file adds the per-vertex
 // arithmetic around them.  All of it in fp64 unless stated, every operation rounded once (-ffp-contract=off), so that it can be restated in numpy:
 //
-// Blended transform.  A face (i0, i1, i2) and a point q on it.  Barycentrics (bu, bv, bw) by the formula of warp.hip's finish_sample: with a, b, c the
+// Blended transform.  A face (i0, i1, i2) and a point q on it.  Barycentrics (bu, bv, bw) by mesh_blend.hpp's face_bary, the one formula warp.hip's finish_sample uses too: with a, b, c the
 //   face's corners widened to fp64, v0 = b - a, v1 = c - a, v2 = q - a, d00 = v0.v0, d01 = v0.v1, d11 = v1.v1, d20 = v2.v0, d21 = v2.v1 (each dot product
 //   x x + y y + z z, left to right), den = d00 d11 - d01 d01, bv = (d11 d20 - d01 d21) / den, bw = (d00 d21 - d01 d20) / den, bu = 1 - bv - bw.
 //   M = T[i0] bu + T[i1] bv + T[i2] bw, element by element, in that order.  Write M = [[A, t], [., kappa]], so kappa = M[3][3].
