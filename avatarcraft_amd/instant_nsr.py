@@ -414,21 +414,22 @@ class NeRFRenderer(nn.Module):
                 t.grad = torch.zeros_like(t)
         g_sdf_p, g_col_p, g_invs, *g_vd = nsr_ops.render_core_backward(field, out.opts, out, ro, rd, bg, g_image, g_weights_sum, None, None, g_eik,
                                                                        enc.embeddings.grad, split=split, eik_groups=eik_groups)
-        c0_src, c0_stride = (g_col_p, 0), 32
-        if g_vd:                                                 # use_viewdirs: the gradient of the [64,37] effective matrix, columns in the reference's order
-            c0_src, c0_stride = (nsr_ops.join_viewdir_grad(g_col_p[:2048].view(64, 32)[:, :21], g_vd[0]).contiguous(), 0), 37
+        S, K = nsr_ops.SDF_PARAM_GRADS, nsr_ops.COLOR_PARAM_GRADS          # where each matrix lies in the two packed vectors
         s0, s1, c0, c1, c2 = self.sdf_net[0], self.sdf_net[1], self.color_net[0], self.color_net[1], self.color_net[2]
         WN, ADD, VAR = nsr_ops.PG_WEIGHT_NORM, nsr_ops.PG_ADD, nsr_ops.PG_VARIANCE
         var = self.deviation_net.variance
         with torch.no_grad():
             inv_s = self.forward_variance()
-        wn = lambda src, off, stride, l: (WN, (src, off), stride, l.weight_v.shape[0], l.weight_v.shape[1], l.weight_v.detach(), l.weight_g.detach(),
-                                          l.weight_v.grad, l.weight_g.grad)
-        wn_c0 = (WN, c0_src, c0_stride, c0.weight_v.shape[0], c0.weight_v.shape[1], c0.weight_v.detach(), c0.weight_g.detach(), c0.weight_v.grad, c0.weight_g.grad)
+        wn = lambda src, at, l: (WN, (src, at.offset), at.stride, l.weight_v.shape[0], l.weight_v.shape[1], l.weight_v.detach(), l.weight_g.detach(),
+                                 l.weight_v.grad, l.weight_g.grad)
+        add = lambda src, at, l: (ADD, (src, at.offset), at.stride, at.shape[0], 1, None, None, l.bias.grad, None)
+        wn_c0 = wn(g_col_p, K["Wc1"], c0)
+        if g_vd:                                                 # use_viewdirs: the gradient of the [64,37] effective matrix, columns in the reference's order
+            g37 = nsr_ops.join_viewdir_grad(nsr_ops.split_color_param_grads(g_col_p)[0], g_vd[0]).contiguous()
+            wn_c0 = wn(g37, nsr_ops.PackedSlot(0, 37, (64, 37)), c0)
         nsr_ops.param_grads([
-            wn(g_sdf_p, 0, 36, s0), (ADD, (g_sdf_p, 35), 36, 64, 1, None, None, s0.bias.grad, None),
-            wn(g_sdf_p, 64 * 36, 64, s1), (ADD, (g_sdf_p, 64 * 36 + 1024), 1, 16, 1, None, None, s1.bias.grad, None),
-            wn_c0, wn(g_col_p, 2048, 64, c1), wn(g_col_p, 6144, 64, c2),
+            wn(g_sdf_p, S["W1"], s0), add(g_sdf_p, S["b1"], s0), wn(g_sdf_p, S["W2"], s1), add(g_sdf_p, S["b2"], s1),
+            wn_c0, wn(g_col_p, K["Wc2"], c1), wn(g_col_p, K["Wc3"], c2),
             (VAR, g_invs, 1, g_invs.shape[0], 1, None, inv_s.reshape(-1), var.grad.reshape(-1), None)], ro.device)
         # the kernels wrote the gradients through raw pointers: bump their version counters, so that anything keyed on them -- stylize.Adam.grads_cleared --
         # sees that the buffers are no longer what they were (views of one flat buffer share a counter: one bump per distinct base is enough)
@@ -513,13 +514,10 @@ class NeRFRenderer(nn.Module):
         cached = getattr(self, "_field_sdf_cache", None)
         if cached is not None and cached[0] == key:
             return cached[1]
-        dev = enc.embeddings.device
-        z = lambda *sh: torch.zeros(sh, dtype=torch.float32, device=dev)
         with torch.no_grad():
             W = nsr_ops.weight_norm_all(list(self.sdf_net))
-            f = nsr_ops.Field(enc.embeddings.detach(), self._offsets_host(), enc.per_level_scale, enc.base_resolution, W[0],
-                              self.sdf_net[0].bias.detach().contiguous(), W[1], self.sdf_net[1].bias.detach().contiguous(),
-                              z(64, 21), z(64, 64), z(3, 64))
+            f = nsr_ops.Field.sdf_only(enc.embeddings.detach(), self._offsets_host(), enc.per_level_scale, enc.base_resolution, W[0],
+                                       self.sdf_net[0].bias.detach().contiguous(), W[1], self.sdf_net[1].bias.detach().contiguous())
         self._field_sdf_cache = (key, f)
         return f
 

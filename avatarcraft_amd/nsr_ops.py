@@ -5,8 +5,8 @@ CUDA tensors and enqueues the HIP kernels on torch's current stream.  The numeri
 NeRFRenderer.run (reference models/instant_nsr.py:133-299) is entirely inside
 libavatarcraft_hip.so; there is no eager fallback.
 """
+import collections
 import ctypes as C
-import math
 import os
 
 import numpy as np
@@ -27,6 +27,15 @@ def _chk(t, name, shape=None):
     if shape is not None and tuple(t.shape) != tuple(shape):
         raise RuntimeError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
     return t
+
+
+def _f32(dev, *shape, zero=False):
+    """an uninitialised (zero: a zeroed) float32 tensor of that shape on `dev`"""
+    return (torch.zeros if zero else torch.empty)(shape, dtype=_F32, device=dev)
+
+
+def _dc(t):
+    return t.detach().contiguous()
 
 
 class Field:
@@ -62,6 +71,20 @@ class Field:
         self.prepared = None
         self._half = None
 
+    @classmethod
+    def sdf_only(cls, table, offsets, per_level_scale, base_resolution, W1, b1, W2, b2):
+        """the SDF side only (zero colour matrices): what the sampling stage and the SDF-query operator read"""
+        dev = table.device
+        return cls(table, offsets, per_level_scale, base_resolution, W1, b1, W2, b2, _f32(dev, 64, 21, zero=True), _f32(dev, 64, 64, zero=True),
+                   _f32(dev, 3, 64, zero=True))
+
+    @classmethod
+    def color_only(cls, Wc1, Wc2, Wc3):
+        """the colour side only: zero SDF matrices and a dummy 16-level layout of one entry per level (the colour kernels never touch the table)"""
+        dev = Wc1.device
+        return cls(_f32(dev, 16, 2, zero=True), list(range(0, 17)), 2.0, 16, _f32(dev, 64, 35, zero=True), _f32(dev, 64, zero=True),
+                   _f32(dev, 16, 64, zero=True), _f32(dev, 16, zero=True), Wc1, Wc2, Wc3)
+
     def half_table(self):
         """the hash table in half precision (ac_table_to_half): an int32 [n_entries] device tensor, one dword per entry (channel 0 in the low half), 4
         bytes per entry instead of 8.  Made once per Field -- a Field is a snapshot of the parameters, a changed table gets a new Field -- and what
@@ -88,6 +111,34 @@ class Field:
         L.check(L.lib().ac_field_prepare(C.byref(self.c), self.prepared.data_ptr(), L.current_stream(self.device)), "field_prepare")
         self.c.prepared = self.prepared.data_ptr()
         return self
+
+
+# The packed parameter gradients of the training kernels (include/avatarcraft_hip.h), w.r.t. the EFFECTIVE matrices:
+#   g_sdf_params   = dW1 [64][36] (column 35 = db1) | dW2 [16][64] | db2 [16]                        (render core backward, SDF-stencil backward)
+#   g_color_params = dWc1 [64][32] (columns 0..20) | dWc2 [64][64] | dWc3 [16][64] (rows 0..2)       (render core backward, colour backward)
+# THE definition on this side: per tensor its element offset in the vector, the stride between its rows and its shape.
+PackedSlot = collections.namedtuple("PackedSlot", "offset stride shape")
+SDF_PARAM_GRADS = dict(W1=PackedSlot(0, 36, (64, 35)), b1=PackedSlot(35, 36, (64,)), W2=PackedSlot(64 * 36, 64, (16, 64)),
+                       b2=PackedSlot(64 * 36 + 16 * 64, 1, (16,)))
+SDF_PARAM_GRADS_LEN = 64 * 36 + 16 * 64 + 16
+COLOR_PARAM_GRADS = dict(Wc1=PackedSlot(0, 32, (64, 21)), Wc2=PackedSlot(64 * 32, 64, (64, 64)), Wc3=PackedSlot(64 * 32 + 64 * 64, 64, (3, 64)))
+COLOR_PARAM_GRADS_LEN = 64 * 32 + 64 * 64 + 16 * 64
+
+
+def _split_packed(g, slots, length):
+    if g.dim() != 1 or g.shape[0] != length or not g.is_contiguous():
+        raise RuntimeError(f"a packed parameter gradient of {length} contiguous elements, got {tuple(g.shape)}")
+    return tuple(g.as_strided(s.shape, (s.stride, 1)[:len(s.shape)], g.storage_offset() + s.offset) for s in slots.values())
+
+
+def split_sdf_param_grads(g):
+    """g_sdf_params [SDF_PARAM_GRADS_LEN] -> (dW1 [64,35], db1 [64], dW2 [16,64], db2 [16]), views of g"""
+    return _split_packed(g, SDF_PARAM_GRADS, SDF_PARAM_GRADS_LEN)
+
+
+def split_color_param_grads(g):
+    """g_color_params [COLOR_PARAM_GRADS_LEN] -> (dWc1 [64,21], dWc2 [64,64], dWc3 [3,64]), views of g"""
+    return _split_packed(g, COLOR_PARAM_GRADS, COLOR_PARAM_GRADS_LEN)
 
 
 _LIN_CACHE = {}
@@ -160,9 +211,10 @@ def render_rays(field, rays_o, rays_d, num_steps=64, upsample_steps=64, bound=1.
     entry instead of 8 -- through ac_render_rays_h16 / ac_render_rays_warped_h16; every output is bit-identical to this call on a field whose table is
     table.half().float().  "half" with train_extras or opacity_only raises RuntimeError."""
     check_table_dtype("render_rays", table_dtype, train_extras=train_extras, opacity_only=opacity_only)
-    return _render(field, rays_o, rays_d, num_steps, upsample_steps, bound, inv_s, bg, noise, cos_anneal_ratio, normal_epsilon_ratio, extras,
-                   debug_indices, out, events, warp, train_extras, near_far, precision, skip_masked, opacity_only, long=False,
-                   half=table_dtype == "half")
+    return _render(field, rays_o, rays_d, num_steps=num_steps, upsample_steps=upsample_steps, bound=bound, inv_s=inv_s, bg=bg, noise=noise,
+                   cos_anneal_ratio=cos_anneal_ratio, normal_epsilon_ratio=normal_epsilon_ratio, extras=extras, debug_indices=debug_indices, out=out,
+                   events=events, warp=warp, train_extras=train_extras, near_far=near_far, precision=precision, skip_masked=skip_masked,
+                   opacity_only=opacity_only, long=False, half=table_dtype == "half")
 
 
 LONG_MAX_SAMPLES = 512
@@ -213,9 +265,10 @@ def render_rays_long(field, rays_o, rays_d, num_steps=64, upsample_steps=64, bou
         check_save_stencil("render_rays_long", num_steps, upsample_steps)
         if warp is not None or not train_extras:
             raise RuntimeError("render_rays_long: save_stencil keeps the stencil features of a canonical training render (train_extras=True, no warp)")
-    return _render(field, rays_o, rays_d, num_steps, upsample_steps, bound, inv_s, bg, noise, cos_anneal_ratio, normal_epsilon_ratio, extras,
-                   debug_indices, out, events, warp, train_extras, near_far, precision, skip_masked, opacity_only, long=True,
-                   save_stencil=bool(save_stencil))
+    return _render(field, rays_o, rays_d, num_steps=num_steps, upsample_steps=upsample_steps, bound=bound, inv_s=inv_s, bg=bg, noise=noise,
+                   cos_anneal_ratio=cos_anneal_ratio, normal_epsilon_ratio=normal_epsilon_ratio, extras=extras, debug_indices=debug_indices, out=out,
+                   events=events, warp=warp, train_extras=train_extras, near_far=near_far, precision=precision, skip_masked=skip_masked,
+                   opacity_only=opacity_only, long=True, save_stencil=bool(save_stencil))
 
 
 FD_STEP = 0.005                        # finite-difference step of the normals at normal_epsilon_ratio = 0 (instant_nsr.py:687-704)
@@ -251,7 +304,26 @@ def _render_opts(N, num_steps, upsample_steps, bound, has_noise, inv_s=1.0, cos_
     return op, inv_s_t, nm, fm
 
 
-def _render(field, rays_o, rays_d, num_steps, upsample_steps, bound, inv_s, bg, noise, cos_anneal_ratio, normal_epsilon_ratio, extras,
+# the output buffers of ac_render_out by name, with the shape that follows [rays] (per ray) or [rays, samples] (per sample)
+_PER_RAY_OUT = dict(image=(3,), weights_sum=(), depth=(), normal_map=(3,), eik=(2,))
+_PER_SAMPLE_OUT = dict(z_vals=(), weights=(), alpha=(), color=(3,), sdf=(), gradient=(3,), sdf_out16=(16,), pts=(3,))
+_OUT_TAIL = {**_PER_RAY_OUT, **_PER_SAMPLE_OUT}
+_EXTRAS_OUT = ("z_vals", "weights", "alpha", "color", "sdf", "gradient")
+_TRAIN_EXTRAS_OUT = ("sdf_out16", "pts")
+
+
+def _feat7_shape(N, T):
+    """ac_render_out.feat7: the hash features of every sample's 7-point stencil, one block per tile of 16 samples (0.9 KB per sample)"""
+    return (N * T // 16, 14, 64, 4)
+
+
+def _fill_out(o, buf, names, lead, prefix=""):
+    """o.<name> = buf(prefix + name, lead + the name's trailing shape) for the given per-ray or per-sample names"""
+    for k in names:
+        setattr(o, k, buf(prefix + k, lead + _OUT_TAIL[k]).data_ptr())
+
+
+def _render(field, rays_o, rays_d, *, num_steps, upsample_steps, bound, inv_s, bg, noise, cos_anneal_ratio, normal_epsilon_ratio, extras,
             debug_indices, out, events, warp, train_extras, near_far, precision, skip_masked, opacity_only, long, half=False, save_stencil=False):
     rays_o, rays_d = _ray_args(rays_o, rays_d)
     N = rays_o.shape[0]
@@ -261,27 +333,17 @@ def _render(field, rays_o, rays_d, num_steps, upsample_steps, bound, inv_s, bg, 
     lin_z, lin_u = linspace_tables(num_steps, dev)
     res, buf = _result_bufs(out, dev)
     o = L.ac_render_out()
-    o.image = buf("image", (N, 3)).data_ptr()
-    o.weights_sum = buf("weights_sum", (N,)).data_ptr()
-    o.depth = buf("depth", (N,)).data_ptr()
-    o.normal_map = buf("normal_map", (N, 3)).data_ptr()
-    o.eik = buf("eik", (N, 2)).data_ptr()
+    _fill_out(o, buf, _PER_RAY_OUT, (N,))
     er = buf("eik_res", (2,))              # (gradient_error, its denominator): reduced by the render launch itself (ac_render_out.eik_reduced)
     o.eik_reduced = er.data_ptr()
     if N == 0:
         er.zero_()
     if extras:
-        o.z_vals = buf("z_vals", (N, T)).data_ptr()
-        o.weights = buf("weights", (N, T)).data_ptr()
-        o.alpha = buf("alpha", (N, T)).data_ptr()
-        o.color = buf("color", (N, T, 3)).data_ptr()
-        o.sdf = buf("sdf", (N, T)).data_ptr()
-        o.gradient = buf("gradient", (N, T, 3)).data_ptr()
+        _fill_out(o, buf, _EXTRAS_OUT, (N, T))
     if train_extras:
-        o.sdf_out16 = buf("sdf_out16", (N, T, 16)).data_ptr()
-        o.pts = buf("pts", (N, T, 3)).data_ptr()
-        if not long or save_stencil:      # the hash features of every sample's 7-point stencil (0.9 KB per sample): the backward streams them back instead of gathering them again
-            o.feat7 = buf("feat7", (N * T // 16, 14, 64, 4)).data_ptr()
+        _fill_out(o, buf, _TRAIN_EXTRAS_OUT, (N, T))
+        if not long or save_stencil:      # the backward streams the stencil features back instead of gathering them again
+            o.feat7 = buf("feat7", _feat7_shape(N, T)).data_ptr()
         else:               # (the long renderer's default: render_core_backward gathers again; a reused result dict must not hand on another launch's)
             res.pop("feat7", None)
     if debug_indices:
@@ -341,33 +403,30 @@ def render_rays_pair(field, rays_o, rays_d, noise2, num_steps=64, upsample_steps
     render_rays(..., noise=noise2[0]) and render_rays(..., noise=noise2[1], extras=True, train_extras=True).
     table_dtype: "float" only ("half" raises: the pair launch is a training launch)."""
     check_table_dtype("render_rays_pair", table_dtype, pair=True)
-    return _render_pair(field, rays_o, rays_d, noise2, num_steps, upsample_steps, bound, inv_s, bg2, cos_anneal_ratio, normal_epsilon_ratio, precision,
-                        out, events, keep_weights, long=False, save_stencil=True)
+    return _render_pair(field, rays_o, rays_d, noise2=noise2, num_steps=num_steps, upsample_steps=upsample_steps, bound=bound, inv_s=inv_s, bg2=bg2,
+                        cos_anneal_ratio=cos_anneal_ratio, normal_epsilon_ratio=normal_epsilon_ratio, precision=precision, out=out, events=events,
+                        keep_weights=keep_weights, long=False, save_stencil=True)
 
 
-def _render_pair(field, rays_o, rays_d, noise2, num_steps, upsample_steps, bound, inv_s, bg2, cos_anneal_ratio, normal_epsilon_ratio, precision,
+def _render_pair(field, rays_o, rays_d, *, noise2, num_steps, upsample_steps, bound, inv_s, bg2, cos_anneal_ratio, normal_epsilon_ratio, precision,
                  out, events, keep_weights, long, save_stencil):
     rays_o, rays_d = _ray_args(rays_o, rays_d)
     N, dev, T = rays_o.shape[0], rays_o.device, num_steps + upsample_steps
     lin_z, lin_u = linspace_tables(num_steps, dev)
     res, buf = _result_bufs(out, dev)
     o = L.ac_render_out()
-    per_ray = {"image": (2 * N, 3), "weights_sum": (2 * N,), "depth": (2 * N,), "normal_map": (2 * N, 3), "eik": (2 * N, 2)}
-    for k, shp in per_ray.items():
-        setattr(o, k, buf("pair_" + k, shp).data_ptr())
+    _fill_out(o, buf, _PER_RAY_OUT, (2 * N,), prefix="pair_")
     er2 = buf("pair_eik_res", (2, 2))      # per copy: (gradient_error, its denominator), reduced by the launch itself
     o.eik_reduced = er2.data_ptr()
     if N == 0:
         er2.zero_()
-    per_sample = {"z_vals": (N, T), "color": (N, T, 3), "sdf": (N, T), "gradient": (N, T, 3), "sdf_out16": (N, T, 16), "pts": (N, T, 3)}      # what the backward reads
-    if keep_weights:
-        per_sample.update({"weights": (N, T), "alpha": (N, T)})
+    per_sample = ("z_vals", "color", "sdf", "gradient") + _TRAIN_EXTRAS_OUT + (("weights", "alpha") if keep_weights else ())      # what the backward reads
+    _fill_out(o, buf, per_sample, (N, T))
     if save_stencil:
-        per_sample["feat7"] = (N * T // 16, 14, 64, 4)
+        o.feat7 = buf("feat7", _feat7_shape(N, T)).data_ptr()
+        per_sample += ("feat7",)
     else:                   # (a reused result dict must not hand on another launch's)
         res.pop("feat7", None)
-    for k, shp in per_sample.items():
-        setattr(o, k, buf(k, shp).data_ptr())
     noise2 = _chk(noise2.reshape(2 * N, num_steps), "noise2")
     if bg2 is not None:
         bg2 = _chk(bg2.reshape(-1, 3), "bg2", (2 * N, 3))
@@ -382,7 +441,7 @@ def _render_pair(field, rays_o, rays_d, noise2, num_steps, upsample_steps, bound
     if events is not None:
         events[1].record()
     ra, rb = RenderResult(), RenderResult()
-    for k in per_ray:
+    for k in _PER_RAY_OUT:
         t = res["pair_" + k]
         ra[k], rb[k] = t[:N], t[N:]
     for k in per_sample:
@@ -404,29 +463,30 @@ def render_rays_long_pair(field, rays_o, rays_d, noise2, num_steps=64, upsample_
     check_long_counts(num_steps, upsample_steps)
     if save_stencil:
         check_save_stencil("render_rays_long_pair", num_steps, upsample_steps)
-    return _render_pair(field, rays_o, rays_d, noise2, num_steps, upsample_steps, bound, inv_s, bg2, cos_anneal_ratio, normal_epsilon_ratio, precision,
-                        out, events, keep_weights, long=True, save_stencil=bool(save_stencil))
+    return _render_pair(field, rays_o, rays_d, noise2=noise2, num_steps=num_steps, upsample_steps=upsample_steps, bound=bound, inv_s=inv_s, bg2=bg2,
+                        cos_anneal_ratio=cos_anneal_ratio, normal_epsilon_ratio=normal_epsilon_ratio, precision=precision, out=out, events=events,
+                        keep_weights=keep_weights, long=True, save_stencil=bool(save_stencil))
 
 
 def sample_rays(field, rays_o, rays_d, num_steps=64, upsample_steps=64, bound=1.6, noise=None, near_far=None):
     """the no-grad sampling stage of run() only -> z_vals [N, num_steps + upsample_steps] (identical to render_rays' z_vals)"""
-    return _sample(field, rays_o, rays_d, num_steps, upsample_steps, bound, noise, near_far, long=False)
+    return _sample(field, rays_o, rays_d, num_steps=num_steps, upsample_steps=upsample_steps, bound=bound, noise=noise, near_far=near_far, long=False)
 
 
 def sample_rays_long(field, rays_o, rays_d, num_steps=64, upsample_steps=64, bound=1.6, noise=None, near_far=None):
     """sample_rays for any count render_rays_long accepts (ac_sample_rays_long) -> z_vals [N, num_steps + upsample_steps], identical to
     render_rays_long's z_vals (and to sample_rays' where both accept the counts)"""
     check_long_counts(num_steps, upsample_steps)
-    return _sample(field, rays_o, rays_d, num_steps, upsample_steps, bound, noise, near_far, long=True)
+    return _sample(field, rays_o, rays_d, num_steps=num_steps, upsample_steps=upsample_steps, bound=bound, noise=noise, near_far=near_far, long=True)
 
 
-def _sample(field, rays_o, rays_d, num_steps, upsample_steps, bound, noise, near_far, long):
+def _sample(field, rays_o, rays_d, *, num_steps, upsample_steps, bound, noise, near_far, long):
     rays_o, rays_d = _ray_args(rays_o, rays_d)
     N, dev = rays_o.shape[0], rays_o.device
     lin_z, lin_u = linspace_tables(num_steps, dev)
     if noise is not None:
         noise = _chk(noise.reshape(N, num_steps), "noise")
-    z = torch.empty((N, num_steps + upsample_steps), dtype=_F32, device=dev)
+    z = _f32(dev, N, num_steps + upsample_steps)
     op, _, nm, fm = _render_opts(N, num_steps, upsample_steps, bound, noise is not None, near_far=near_far)
     name = "sample_rays_long" if long else "sample_rays"
     L.check(getattr(L.lib(), "ac_" + name)(C.byref(field.c), C.byref(op), rays_o.data_ptr(), rays_d.data_ptr(), L.ptr(noise), lin_z.data_ptr(),
@@ -580,9 +640,8 @@ class _RenderCore(torch.autograd.Function):
     def forward(ctx, table, W1, b1, W2, b2, Wc1, Wc2, Wc3, inv_s, rays_o, rays_d, bg, noise, cfg):
         offsets, pls, H, T0, up, bound, car, ner, precision, warp = cfg
         ctx.set_materialize_grads(False)              # an output the loss does not use arrives as None -> a NULL upstream pointer
-        d = lambda t: t.detach().contiguous()
-        Wc1_21, Wc1_sh = split_viewdir_weight(d(Wc1))           # use_viewdirs: [64,37] -> the 21 per-sample columns + the 16 view-direction columns
-        field = Field(d(table), offsets, pls, H, d(W1), d(b1), d(W2), d(b2), Wc1_21, d(Wc2), d(Wc3), Wc1_sh=Wc1_sh).prepare()
+        Wc1_21, Wc1_sh = split_viewdir_weight(_dc(Wc1))           # use_viewdirs: [64,37] -> the 21 per-sample columns + the 16 view-direction columns
+        field = Field(_dc(table), offsets, pls, H, _dc(W1), _dc(b1), _dc(W2), _dc(b2), Wc1_21, _dc(Wc2), _dc(Wc3), Wc1_sh=Wc1_sh).prepare()
         # warp = WarpMesh: posed space (run(render_can=False), instant_nsr.py:166-172,198-207,246-249) -- the launch sequence of an inference render
         # (sampling, SMPL inverse warp, final pass; every sample evaluated: skip_masked off) with the per-sample outputs kept.  The warped points,
         # the mask and the mesh-guided range are constants of the differentiation, as in the reference (the warp is numpy there).
@@ -622,12 +681,10 @@ class _RenderCore(torch.autograd.Function):
         g_table = table.grad if in_place else torch.zeros_like(table)       # accumulated into, like hash_encode_backward (hashgrid.py:61-68)
         saved = (z_vals, pts, sdf, sdf16, gradient, color, eik_res[1:], feat7 if ctx.has_feat else None, ctx.posed[0] if ctx.posed else None)
         g_sdf_p, g_col_p, g_invs, g_sh = _core_backward(field, ctx.opts[0], saved, rays_o, rays_d, bg, (g_image, g_wsum, g_depth, g_nmap, g_eik), g_table)
-        gW1b = g_sdf_p[:64 * 36].view(64, 36)
-        g_Wc1 = g_col_p[:2048].view(64, 32)[:, :21]
+        g_Wc1, g_Wc2, g_Wc3 = split_color_param_grads(g_col_p)
         if g_sh is not None:
             g_Wc1 = join_viewdir_grad(g_Wc1, g_sh)
-        return (None if in_place else g_table, gW1b[:, :35], gW1b[:, 35], g_sdf_p[64 * 36:64 * 36 + 1024].view(16, 64), g_sdf_p[64 * 36 + 1024:],
-                g_Wc1, g_col_p[2048:6144].view(64, 64), g_col_p[6144:].view(16, 64)[:3],
+        return (None if in_place else g_table, *split_sdf_param_grads(g_sdf_p), g_Wc1, g_Wc2, g_Wc3,
                 g_invs.sum().reshape(ctx.inv_s_shape), None, None, None, None, None)
 
 
@@ -713,8 +770,7 @@ def sds_upstream(weights_sum, weights_sum_gt, scale, want_grad=True):
     """opacity term of the stylisation loss: -> (d loss / d weights_sum [N] or None, loss [1]); loss = sum smooth_l1(clamp, clamp) * scale"""
     ws, wg = weights_sum.reshape(-1).contiguous(), weights_sum_gt.reshape(-1).contiguous()
     N, dev = ws.shape[0], ws.device
-    g = torch.empty(N, dtype=_F32, device=dev) if want_grad else None
-    loss = torch.empty(1, dtype=_F32, device=dev)
+    g, loss = _f32(dev, N) if want_grad else None, _f32(dev, 1)
     L.check(L.lib().ac_sds_upstream(ws.data_ptr(), wg.data_ptr(), N, float(scale), L.ptr(g), loss.data_ptr(), L.current_stream(dev)), "sds_upstream")
     return g, loss
 
@@ -741,8 +797,7 @@ def sh_bias(field, rays_d, want_sh=True):
     """ac_sh_bias: the per-ray layer-1 bias of the colour network for the view directions rays_d [N,3] -> (bias [N,64], sh [N,16] or None)"""
     rays_d = _chk(rays_d.reshape(-1, 3), "rays_d")
     N, dev = rays_d.shape[0], rays_d.device
-    bias = torch.empty((N, 64), dtype=_F32, device=dev)
-    sh = torch.empty((N, VIEWDIR_COLS), dtype=_F32, device=dev) if want_sh else None
+    bias, sh = _f32(dev, N, 64), _f32(dev, N, VIEWDIR_COLS) if want_sh else None
     L.check(L.lib().ac_sh_bias(C.byref(field.c), rays_d.data_ptr(), N, bias.data_ptr(), L.ptr(sh), L.current_stream(dev)), "sh_bias")
     return bias, sh
 
@@ -752,7 +807,7 @@ def _viewdir_args(field, rays_d, N, T, sv, gr):
     if not getattr(field, "has_viewdirs", False):
         return None
     bias, sh = sh_bias(field, rays_d)
-    tiles = torch.empty((N * T // 16, 64), dtype=_F32, device=rays_d.device)
+    tiles = _f32(rays_d.device, N * T // 16, 64)
     sv.sh_bias, gr.g_sh_tiles = bias.data_ptr(), tiles.data_ptr()
     return bias, sh, tiles
 
@@ -770,7 +825,7 @@ def eikonal_groups(eik, group_rays):
     (ac_render_out.eik): [groups, 2] = (error, denominator), each by ac_eikonal_reduce2 -- the bits a launch of that group alone reports as eik_res"""
     N = eik.shape[0]
     G = (N + group_rays - 1) // group_rays
-    res = torch.empty((G, 2), dtype=_F32, device=eik.device)
+    res = _f32(eik.device, G, 2)
     st = L.current_stream(eik.device)
     for k in range(G):
         sl = eik[k * group_rays:(k + 1) * group_rays]
@@ -780,7 +835,7 @@ def eikonal_groups(eik, group_rays):
 
 def render_core_backward(field, opts, out, rays_o, rays_d, bg, g_image, g_wsum, g_depth, g_nmap, g_eik, g_table, split=None, eik_groups=None):
     """ac_render_core_backward on the outputs of a render_rays(..., train_extras=True) launch (`out`, its .opts): the table gradient is accumulated
-    into g_table; returns (g_sdf_params [3344], g_color_params [7168], g_inv_s_per_ray [N][, g_Wc1_sh [64,16] for a field with view directions]) w.r.t. the
+    into g_table; returns (g_sdf_params [SDF_PARAM_GRADS_LEN], g_color_params [COLOR_PARAM_GRADS_LEN], g_inv_s_per_ray [N][, g_Wc1_sh [64,16] for a field with view directions]) w.r.t. the
     EFFECTIVE matrices.
     split = (level, torch.cuda.Stream): the scatter completes the table gradient of levels >= level first and orders that stream behind exactly that
     (ac_core_grads.side_stream / split_level): work enqueued there afterwards (the all-reduce of that slice) overlaps the rest of the backward."""
@@ -800,9 +855,7 @@ def _core_backward(field, op, saved, rays_o, rays_d, bg, upstream, g_table, spli
     each.  The table gradient is accumulated into g_table.  -> (g_sdf_params, g_color_params, g_inv_s_per_ray, g_Wc1_sh | None), as render_core_backward."""
     N, T = saved[0].shape
     dev = rays_o.device
-    g_sdf_p = torch.empty(64 * 36 + 16 * 64 + 16, dtype=_F32, device=dev)
-    g_col_p = torch.empty(64 * 32 + 64 * 64 + 16 * 64, dtype=_F32, device=dev)
-    g_invs = torch.empty(N, dtype=_F32, device=dev)
+    g_sdf_p, g_col_p, g_invs = _f32(dev, SDF_PARAM_GRADS_LEN), _f32(dev, COLOR_PARAM_GRADS_LEN), _f32(dev, N)
     sv = L.ac_core_saved(*[L.ptr(t) for t in saved])
     upstream = [None if g is None else g.contiguous().to(_F32) for g in upstream]        # (held until the launch is enqueued)
     upg = L.ac_core_upstream(*[L.ptr(g) for g in upstream], 0, 0)
@@ -830,9 +883,7 @@ class _PackedShading(torch.autograd.Function):
         stride = 1 if deltas.dim() == 1 else int(deltas.shape[1])
         inv_t = inv_s.detach().reshape(1).to(_F32).contiguous()
         nv = n_valid.detach().reshape(1).to(torch.int32).contiguous()
-        alpha = torch.empty(M, dtype=_F32, device=dev)
-        normal = torch.empty((M, 3), dtype=_F32, device=dev)
-        eik = torch.empty((M, 2), dtype=_F32, device=dev)
+        alpha, normal, eik = _f32(dev, M), _f32(dev, M, 3), _f32(dev, M, 2)
         L.check(L.lib().ac_packed_shading_forward(sdf16.data_ptr(), gradient.data_ptr(), xyzs.data_ptr(), dirs.data_ptr(), deltas.data_ptr(), stride, M, nv.data_ptr(),
                                                   0.0, inv_t.data_ptr(), float(car), alpha.data_ptr(), normal.data_ptr(), eik.data_ptr(), L.current_stream(dev)),
                 "packed_shading_forward")
@@ -847,9 +898,7 @@ class _PackedShading(torch.autograd.Function):
         M, dev = sdf16.shape[0], sdf16.device
         c = lambda g: None if g is None else g.contiguous().to(_F32)
         g_alpha, g_normal, g_eik = c(g_alpha), c(g_normal), c(g_eik)
-        g_sdf16 = torch.zeros((M, 16), dtype=_F32, device=dev)
-        g_grad = torch.empty((M, 3), dtype=_F32, device=dev)
-        g_rows = torch.empty(M, dtype=_F32, device=dev)
+        g_sdf16, g_grad, g_rows = _f32(dev, M, 16, zero=True), _f32(dev, M, 3), _f32(dev, M)
         L.check(L.lib().ac_packed_shading_backward(sdf16.data_ptr(), gradient.data_ptr(), xyzs.data_ptr(), dirs.data_ptr(), deltas.data_ptr(), stride, M, nv.data_ptr(),
                                                    0.0, inv_t.data_ptr(), car, L.ptr(g_alpha), L.ptr(g_normal), L.ptr(g_eik), g_sdf16.data_ptr(), g_grad.data_ptr(),
                                                    g_rows.data_ptr(), L.current_stream(dev)), "packed_shading_backward")
@@ -873,41 +922,36 @@ class _SdfStencil(torch.autograd.Function):
         offsets, pls, H, bound, eps = cfg
         x = x.contiguous()
         dev = x.device
-        dummy = lambda *shape: torch.zeros(shape, dtype=_F32, device=dev)
-        field = Field(table.detach().contiguous(), offsets, pls, H, W1.detach().contiguous(), b1.detach().contiguous(), W2.detach().contiguous(),
-                      b2.detach().contiguous(), dummy(64, 21), dummy(64, 64), dummy(3, 64))
+        field = Field.sdf_only(_dc(table), offsets, pls, H, _dc(W1), _dc(b1), _dc(W2), _dc(b2))
         B = x.shape[0]
-        out16 = torch.empty((B, 16), dtype=_F32, device=dev)
-        grad = torch.empty((B, 3), dtype=_F32, device=dev)
+        out16, grad = _f32(dev, B, 16), _f32(dev, B, 3)
         L.check(L.lib().ac_sdf_stencil_forward(C.byref(field.c), x.data_ptr(), B, float(bound), float(eps), out16.data_ptr(), grad.data_ptr(),
                                                L.current_stream(dev)), "sdf_stencil_forward")
         ctx.save_for_backward(x, table, W1, b1, W2, b2)
-        ctx.cfg = cfg
+        ctx.field, ctx.cfg = field, cfg
         return out16, grad
 
     @staticmethod
     def backward(ctx, g_out, g_grad):
-        x, table, W1, b1, W2, b2 = ctx.saved_tensors
+        x, table = ctx.saved_tensors[:2]                # (unpacking them all: autograd's check for a parameter modified in place since the forward)
+        field = ctx.field
         offsets, pls, H, bound, eps = ctx.cfg
         dev = x.device
-        dummy = lambda *shape: torch.zeros(shape, dtype=_F32, device=dev)
-        field = Field(table.detach().contiguous(), offsets, pls, H, W1.detach().contiguous(), b1.detach().contiguous(), W2.detach().contiguous(),
-                      b2.detach().contiguous(), dummy(64, 21), dummy(64, 64), dummy(3, 64))
         B = x.shape[0]
         g_out = g_out.contiguous().float(); g_grad = g_grad.contiguous().float()
-        gfeat = torch.empty((7, 16, B, 2), dtype=_F32, device=dev)
-        gparams = torch.empty(64 * 36 + 16 * 64 + 16, dtype=_F32, device=dev)
+        gfeat = _f32(dev, 7, 16, B, 2)
+        gparams = _f32(dev, SDF_PARAM_GRADS_LEN)
         nbytes = int(L.lib().ac_sdf_stencil_backward_scratch(B))
         scratch = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=dev)
         st = L.current_stream(dev)
         oh = np.asarray(offsets, dtype=np.int32)
         g_x = None
         if ctx.needs_input_grad[0]:
-            g_x = torch.empty((B, 3), dtype=_F32, device=dev)
+            g_x = _f32(dev, B, 3)
             L.check(L.lib().ac_sdf_stencil_backward_inputs(C.byref(field.c), x.data_ptr(), g_out.data_ptr(), g_grad.data_ptr(), B, float(bound), float(eps),
                                                            gfeat.data_ptr(), gparams.data_ptr(), g_x.data_ptr(), scratch.data_ptr(), nbytes, st),
                     "sdf_stencil_backward_inputs")
-            part = torch.empty(((16 + 3) // 4, B, 3), dtype=_F32, device=dev)
+            part = _f32(dev, (16 + 3) // 4, B, 3)
             L.check(L.lib().ac_hash_stencil_input_backward(gfeat.data_ptr(), x.data_ptr(), field.t["table"].data_ptr(), oh.ctypes.data, part.data_ptr(), B, 2, 16,
                                                            field.S, H, float(eps), float(bound), st), "hash_stencil_input_backward")
             g_x = g_x + part.sum(0)
@@ -919,9 +963,8 @@ class _SdfStencil(torch.autograd.Function):
         hs, hbytes = stencil_scratch(oh, 16, field.S, H, dev, B)
         L.check(L.lib().ac_hash_stencil_backward(gfeat.data_ptr(), x.data_ptr(), oh.ctypes.data, g_table.data_ptr(), B, 2, 16, field.S, H, float(eps),
                                                  float(bound), L.ptr(hs), hbytes, st), "hash_stencil_backward")
-        gW1b = gparams[:64 * 36].view(64, 36)
-        return (g_x, g_table, gW1b[:, :35].contiguous(), gW1b[:, 35].contiguous(), gparams[64 * 36:64 * 36 + 1024].view(16, 64),
-                gparams[64 * 36 + 1024:], None)
+        g_W1, g_b1, g_W2, g_b2 = split_sdf_param_grads(gparams)
+        return g_x, g_table, g_W1.contiguous(), g_b1.contiguous(), g_W2, g_b2, None
 
 
 class _ColorMlp(torch.autograd.Function):
@@ -929,37 +972,30 @@ class _ColorMlp(torch.autograd.Function):
     Inputs: x [B,3] (no grad), normal [B,3], sdf_out [B,16] (column 0 unused), the EFFECTIVE colour matrices."""
 
     @staticmethod
-    def _field(dev, Wc1, Wc2, Wc3):
-        z = lambda *shape: torch.zeros(shape, dtype=_F32, device=dev)
-        offs = list(range(0, 17))                  # a dummy 16-level layout of one entry per level: the colour kernels never touch the table
-        return Field(z(16, 2), offs, 2.0, 16, z(64, 35), z(64), z(16, 64), z(16), Wc1.detach().contiguous(), Wc2.detach().contiguous(),
-                     Wc3.detach().contiguous())
-
-    @staticmethod
     def forward(ctx, x, normal, sdf_out, Wc1, Wc2, Wc3):
         x, normal, sdf_out = x.contiguous(), normal.contiguous(), sdf_out.contiguous()
         B, dev = x.shape[0], x.device
-        field = _ColorMlp._field(dev, Wc1, Wc2, Wc3)
-        rgb = torch.empty((B, 3), dtype=_F32, device=dev)
+        field = Field.color_only(_dc(Wc1), _dc(Wc2), _dc(Wc3))
+        rgb = _f32(dev, B, 3)
         L.check(L.lib().ac_color_forward(C.byref(field.c), x.data_ptr(), normal.data_ptr(), sdf_out.data_ptr(), B, rgb.data_ptr(), L.current_stream(dev)),
                 "color_forward")
         ctx.save_for_backward(x, normal, sdf_out, Wc1, Wc2, Wc3)
+        ctx.field = field
         return rgb
 
     @staticmethod
     def backward(ctx, g_rgb):
-        x, normal, sdf_out, Wc1, Wc2, Wc3 = ctx.saved_tensors
+        x, normal, sdf_out = ctx.saved_tensors[:3]      # (unpacking them all: autograd's check for a parameter modified in place since the forward)
+        field = ctx.field
         B, dev = x.shape[0], x.device
-        field = _ColorMlp._field(dev, Wc1, Wc2, Wc3)
         g_rgb = g_rgb.contiguous().float()
-        g_n = torch.empty((B, 3), dtype=_F32, device=dev)
-        g_s = torch.empty((B, 16), dtype=_F32, device=dev)
-        gp = torch.empty(64 * 32 + 64 * 64 + 16 * 64, dtype=_F32, device=dev)
+        g_n, g_s, gp = _f32(dev, B, 3), _f32(dev, B, 16), _f32(dev, COLOR_PARAM_GRADS_LEN)
         nbytes = int(L.lib().ac_color_backward_scratch(B))
         scratch = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=dev)
         L.check(L.lib().ac_color_backward(C.byref(field.c), x.data_ptr(), normal.data_ptr(), sdf_out.data_ptr(), g_rgb.data_ptr(), B, g_n.data_ptr(),
                                           g_s.data_ptr(), gp.data_ptr(), scratch.data_ptr(), nbytes, L.current_stream(dev)), "color_backward")
-        return (None, g_n, g_s, gp[:2048].view(64, 32)[:, :21].contiguous(), gp[2048:6144].view(64, 64), gp[6144:].view(16, 64)[:3].contiguous())
+        g_Wc1, g_Wc2, g_Wc3 = split_color_param_grads(gp)
+        return None, g_n, g_s, g_Wc1.contiguous(), g_Wc2, g_Wc3.contiguous()
 
 
 def color_mlp(x, normal, sdf_out, Wc1, Wc2, Wc3):
@@ -975,8 +1011,7 @@ class _Composite(torch.autograd.Function):
         N, T = z_vals.shape
         dev = z_vals.device
         z_vals, sdf, normal, color = z_vals.contiguous(), sdf.contiguous(), normal.contiguous(), color.contiguous()
-        f = lambda *s: torch.empty(s, dtype=_F32, device=dev)
-        image, wsum, depth, nmap, weights, alpha = f(N, 3), f(N), f(N), f(N, 3), f(N, T), f(N, T)
+        image, wsum, depth, nmap, weights, alpha = (_f32(dev, *sh) for sh in ((N, 3), (N,), (N,), (N, 3), (N, T), (N, T)))
         s = float(inv_s.detach().reshape(-1)[0])
         L.check(L.lib().ac_composite_forward(rays_o.data_ptr(), rays_d.data_ptr(), z_vals.data_ptr(), sdf.data_ptr(), normal.data_ptr(), color.data_ptr(),
                                              L.ptr(bg), N, int(num_steps), T, float(bound), s, float(car), image.data_ptr(), wsum.data_ptr(),
@@ -993,10 +1028,9 @@ class _Composite(torch.autograd.Function):
         num_steps, bound, car, s, has_bg = ctx.cfg
         N, T = z_vals.shape
         dev = z_vals.device
-        c = lambda g, *shape: (g.contiguous().float() if g is not None else torch.zeros(shape, dtype=_F32, device=dev))
+        c = lambda g, *shape: (g.contiguous().float() if g is not None else _f32(dev, *shape, zero=True))
         g_image, g_wsum, g_depth, g_nmap = c(g_image, N, 3), c(g_wsum, N), c(g_depth, N), c(g_nmap, N, 3)
-        f = lambda *sh: torch.empty(sh, dtype=_F32, device=dev)
-        g_sdf, g_nrm, g_col, g_s = f(N, T), f(N, T, 3), f(N, T, 3), f(N)
+        g_sdf, g_nrm, g_col, g_s = (_f32(dev, *sh) for sh in ((N, T), (N, T, 3), (N, T, 3), (N,)))
         L.check(L.lib().ac_composite_backward(rays_o.data_ptr(), rays_d.data_ptr(), z_vals.data_ptr(), sdf.data_ptr(), normal.data_ptr(), color.data_ptr(),
                                               bg.data_ptr() if has_bg else None, N, num_steps, T, bound, s, car, g_image.data_ptr(), g_wsum.data_ptr(),
                                               g_depth.data_ptr(), g_nmap.data_ptr(), g_sdf.data_ptr(), g_nrm.data_ptr(), g_col.data_ptr(), g_s.data_ptr(),
@@ -1035,12 +1069,11 @@ def field_samples(field, xyzs, dirs, deltas, bound, eps, inv_s, cos_anneal_ratio
     if dirs.shape[0] != M or deltas.shape[0] != M or deltas.dim() not in (1, 2):
         raise RuntimeError("field_samples: xyzs [M,3], dirs [M,3], deltas [M] or [M,k]")
     stride = 1 if deltas.dim() == 1 else int(deltas.shape[1])
-    f = lambda *sh: torch.empty(sh, dtype=_F32, device=dev)
-    out = dict(alpha=f(M), rgb=f(M, 3), normal=f(M, 3))
+    out = dict(alpha=_f32(dev, M), rgb=_f32(dev, M, 3), normal=_f32(dev, M, 3))
     if want_sdf:
-        out["sdf"] = f(M)
+        out["sdf"] = _f32(dev, M)
     if want_gradient:
-        out["gradient"] = f(M, 3)
+        out["gradient"] = _f32(dev, M, 3)
     inv_f, inv_t = _inv_s_arg(inv_s)
     L.check(L.lib().ac_field_samples(C.byref(field.c), xyzs.data_ptr(), dirs.data_ptr(), deltas.data_ptr(), stride, M, float(bound), float(eps), inv_f, L.ptr(inv_t),
                                      float(cos_anneal_ratio), out["alpha"].data_ptr(), out["rgb"].data_ptr(), out["normal"].data_ptr(),
@@ -1081,21 +1114,30 @@ def _retire_scratch(cache, key):
         _OCC_FAILURES["dropped"] += _sticky_word(sc)
 
 
+def _occupancy_args(who, rays_o, rays_d, density_grid):
+    """-> (rays_o [N,3], rays_d [N,3], density_grid [H,H,H]), checked: what the two occupancy renderers ask of their rays and grid"""
+    rays_o, rays_d = _ray_args(rays_o, rays_d)
+    grid = _chk(density_grid, "density_grid")
+    if grid.dim() != 3 or grid.shape[0] != grid.shape[1] or grid.shape[0] != grid.shape[2]:
+        raise RuntimeError(f"{who}: density_grid must be [H, H, H]")
+    return rays_o, rays_d, grid
+
+
 def render_rays_occupancy(field, rays_o, rays_d, density_grid, mean_density, bound, eps, inv_s, cos_anneal_ratio=1.0, count_samples=False, max_steps=0,
                           phased=None):
     """ac_render_rays_occupancy / ac_render_rays_occupancy_phased: the inference form of run_cuda in one launch (no host round trips).
     -> dict(weights_sum [N], depth [N] (raw sum of w t), image [N,3] (no background), normal_map [N,3] (+ n_samples, a [1] int32 device tensor))
     max_steps: a ray stops after that many samples (0 = no cap); see include/avatarcraft_hip.h for how that relates to the loop of rounds.
     phased: None = by ray count (OCCUPANCY_PHASED_MIN_RAYS); the two kernels give the same bits."""
-    rays_o = _chk(rays_o.reshape(-1, 3), "rays_o"); rays_d = _chk(rays_d.reshape(-1, 3), "rays_d"); grid = _chk(density_grid, "density_grid")
+    rays_o, rays_d, grid = _occupancy_args("render_rays_occupancy", rays_o, rays_d, density_grid)
     N, dev = rays_o.shape[0], rays_o.device
-    if grid.dim() != 3 or grid.shape[0] != grid.shape[1] or grid.shape[0] != grid.shape[2]:
-        raise RuntimeError("render_rays_occupancy: density_grid must be [H, H, H]")
-    f = lambda *sh: torch.empty(sh, dtype=_F32, device=dev)
-    out = dict(weights_sum=f(N), depth=f(N), image=f(N, 3), normal_map=f(N, 3))
+    out = dict(weights_sum=_f32(dev, N), depth=_f32(dev, N), image=_f32(dev, N, 3), normal_map=_f32(dev, N, 3))
     if count_samples:
         out["n_samples"] = torch.zeros(1, dtype=torch.int32, device=dev)
     inv_f, inv_t = _inv_s_arg(inv_s)
+    args = (C.byref(field.c), rays_o.data_ptr(), rays_d.data_ptr(), N, grid.data_ptr(), int(grid.shape[0]), float(mean_density), float(bound), float(eps),
+            inv_f, L.ptr(inv_t), float(cos_anneal_ratio), out["weights_sum"].data_ptr(), out["depth"].data_ptr(), out["image"].data_ptr(),
+            out["normal_map"].data_ptr(), L.ptr(out.get("n_samples")), max(0, int(max_steps)))       # what the two entry points share
     if phased is None:
         phased = N >= OCCUPANCY_PHASED_MIN_RAYS
     if phased and N > 0:
@@ -1106,18 +1148,11 @@ def render_rays_occupancy(field, rays_o, rays_d, density_grid, mean_density, bou
             _retire_scratch(_OP_SCRATCH, key)
             sc = _OP_SCRATCH[key] = torch.zeros(need, dtype=torch.uint8, device=dev)          # zeroed once: every launch re-arms its sync words
             sc._ac_seen_failures = 0
-        L.check(L.lib().ac_render_rays_occupancy_phased(C.byref(field.c), rays_o.data_ptr(), rays_d.data_ptr(), N, grid.data_ptr(), int(grid.shape[0]),
-                                                        float(mean_density), float(bound), float(eps), inv_f, L.ptr(inv_t), float(cos_anneal_ratio),
-                                                        out["weights_sum"].data_ptr(), out["depth"].data_ptr(), out["image"].data_ptr(),
-                                                        out["normal_map"].data_ptr(), L.ptr(out.get("n_samples")), max(0, int(max_steps)), sc.data_ptr(),
-                                                        sc.numel(), L.current_stream(dev)), "render_rays_occupancy_phased")
+        L.check(L.lib().ac_render_rays_occupancy_phased(*args, sc.data_ptr(), sc.numel(), L.current_stream(dev)), "render_rays_occupancy_phased")
         # (a launch whose grid barrier timed out is answered ON THE DEVICE: the library queues the barrier-free kernel behind the phased one, conditional on that
         #  launch's verdict word -- no read-back here, never a partial result; occupancy_launch_failures() counts such launches)
         return out
-    L.check(L.lib().ac_render_rays_occupancy(C.byref(field.c), rays_o.data_ptr(), rays_d.data_ptr(), N, grid.data_ptr(), int(grid.shape[0]), float(mean_density),
-                                             float(bound), float(eps), inv_f, L.ptr(inv_t), float(cos_anneal_ratio), out["weights_sum"].data_ptr(),
-                                             out["depth"].data_ptr(), out["image"].data_ptr(), out["normal_map"].data_ptr(), L.ptr(out.get("n_samples")),
-                                             max(0, int(max_steps)), L.current_stream(dev)), "render_rays_occupancy")
+    L.check(L.lib().ac_render_rays_occupancy(*args, L.current_stream(dev)), "render_rays_occupancy")
     return out
 
 
@@ -1131,10 +1166,8 @@ def render_rays_occupancy_train(field, rays_o, rays_d, density_grid, mean_densit
     composite_rays_train, both > 0 (a budgeted call: the packed layout lives in the launch's scratch); counter: the [2] int32 step counter (+= samples,
     += N); bg: None (raw sums), a number, a [3] / [1,3] or an [N,3] tensor -- image + (1 - weights_sum) * bg.
     -> dict(weights_sum [N], image [N,3], normal_map [N,3], gradient_error [1])"""
-    rays_o = _chk(rays_o.reshape(-1, 3), "rays_o"); rays_d = _chk(rays_d.reshape(-1, 3), "rays_d"); grid = _chk(density_grid, "density_grid")
+    rays_o, rays_d, grid = _occupancy_args("render_rays_occupancy_train", rays_o, rays_d, density_grid)
     N, dev = rays_o.shape[0], rays_o.device
-    if grid.dim() != 3 or grid.shape[0] != grid.shape[1] or grid.shape[0] != grid.shape[2]:
-        raise RuntimeError("render_rays_occupancy_train: density_grid must be [H, H, H]")
     if counter is not None and (counter.dtype != torch.int32 or counter.numel() < 2 or not counter.is_cuda or not counter.is_contiguous()):
         raise RuntimeError("render_rays_occupancy_train: counter must be a contiguous [2] int32 device tensor")
     cap, ccap = int(capacity), int(composite_capacity) or int(capacity)
@@ -1155,8 +1188,7 @@ def render_rays_occupancy_train(field, rays_o, rays_d, density_grid, mean_densit
                 raise RuntimeError(f"render_rays_occupancy_train: background of {tuple(bg.shape)} for {N} rays")
         else:
             bg_mode, bg_value = 1, float(bg)
-    f = lambda *sh: torch.empty(sh, dtype=_F32, device=dev)
-    out = dict(weights_sum=f(N), image=f(N, 3), normal_map=f(N, 3), gradient_error=f(1))
+    out = dict(weights_sum=_f32(dev, N), image=_f32(dev, N, 3), normal_map=_f32(dev, N, 3), gradient_error=_f32(dev, 1))
     need = int(L.lib().ac_render_rays_occupancy_train_scratch(N, cap))
     key = (str(dev), int(L.current_stream(dev) or 0), N, cap)      # (the layout depends on N and the capacity: a buffer is re-armed for calls of ITS shape)
     sc = _OT_SCRATCH.get(key)
@@ -1206,7 +1238,7 @@ def debug_hold_cus(blocks, lds_bytes, millis, stream=None):
 def field_sdf(field, x, bound):
     """forward_sdf (instant_nsr.py:627-642): x [B,3] -> [B,16] (sdf, 15 features)"""
     x = _chk(x.reshape(-1, 3), "x")
-    out = torch.empty((x.shape[0], 16), dtype=_F32, device=x.device)
+    out = _f32(x.device, x.shape[0], 16)
     L.check(L.lib().ac_field_sdf(C.byref(field.c), x.data_ptr(), x.shape[0], float(bound), out.data_ptr(),
                                  L.current_stream(x.device)), "field_sdf")
     return out
@@ -1217,7 +1249,7 @@ def field_color(field, x, n, sdfout, dirs=None):
     x = _chk(x.reshape(-1, 3), "x"); n = _chk(n.reshape(-1, 3), "n"); sdfout = _chk(sdfout.reshape(-1, 16), "sdfout")
     if dirs is not None:
         dirs = _chk(dirs.reshape(-1, 3), "dirs", (x.shape[0], 3))
-    out = torch.empty((x.shape[0], 3), dtype=_F32, device=x.device)
+    out = _f32(x.device, x.shape[0], 3)
     L.check(L.lib().ac_field_color_dirs(C.byref(field.c), x.data_ptr(), L.ptr(dirs), n.data_ptr(), sdfout.data_ptr(), x.shape[0], out.data_ptr(),
                                         L.current_stream(x.device)), "field_color")
     return out
@@ -1230,7 +1262,7 @@ def field_sdf_grid(field, axis_x, axis_y, axis_z, bound, negate=False, out=None)
     ax, ay, az = _chk(axis_x.reshape(-1), "axis_x"), _chk(axis_y.reshape(-1), "axis_y"), _chk(axis_z.reshape(-1), "axis_z")
     nx, ny, nz = ax.shape[0], ay.shape[0], az.shape[0]
     if out is None:
-        out = torch.empty((nx, ny, nz), dtype=_F32, device=ax.device)
+        out = _f32(ax.device, nx, ny, nz)
     elif tuple(out.shape) != (nx, ny, nz) or out.dtype != _F32 or not out.is_contiguous():
         raise RuntimeError("field_sdf_grid: out must be a contiguous float32 [nx, ny, nz] tensor")
     L.check(L.lib().ac_field_sdf_grid(C.byref(field.c), ax.data_ptr(), ay.data_ptr(), az.data_ptr(), nx, ny, nz, float(bound), int(bool(negate)),
@@ -1281,8 +1313,8 @@ def mesh_vertex_attrs(field, vertices, bound, eps=FD_STEP, refine_steps=3, tol=1
     if max_move is None:
         max_move = 2.0 * float(bound) / 511.0
     opts = L.ac_mesh_attr_opts(float(bound), float(eps), float(target_sdf), int(refine_steps), float(tol), float(max_move))
-    f = lambda *sh: torch.empty(sh, dtype=_F32, device=dev)
-    out = dict(positions=f(V, 3), normals=f(V, 3), rgb=f(V, 3) if want_rgb else None, sdf=f(V), status=torch.empty(V, dtype=torch.uint8, device=dev))
+    out = dict(positions=_f32(dev, V, 3), normals=_f32(dev, V, 3), rgb=_f32(dev, V, 3) if want_rgb else None, sdf=_f32(dev, V),
+               status=torch.empty(V, dtype=torch.uint8, device=dev))
     L.check(L.lib().ac_mesh_vertex_attrs(C.byref(field.c), vertices.data_ptr(), V, L.ptr(dirs), C.byref(opts), out["positions"].data_ptr(),
                                          out["normals"].data_ptr(), L.ptr(out["rgb"]), out["sdf"].data_ptr(), out["status"].data_ptr(),
                                          L.current_stream(dev)), "mesh_vertex_attrs")
@@ -1317,9 +1349,8 @@ def mesh_bake_texture(field, positions, triangles, size, cell, bound, eps=FD_STE
         raise RuntimeError(f"mesh_bake_texture: size {S} outside 1 .. 32768")
     atlas = L.ac_atlas_opts(S, max(int(cell), 0))
     opts = L.ac_mesh_attr_opts(float(bound), float(eps), float(target_sdf), int(refine_steps), float(tol), float(max_move))
-    f = lambda *sh: torch.empty(sh, dtype=_F32, device=dev)
-    out = dict(rgb=f(S, S, 3), owner=torch.empty((S, S), dtype=torch.int32, device=dev), normals=f(S, S, 3) if want_normals else None, sdf=f(S, S),
-               status=torch.empty((S, S), dtype=torch.uint8, device=dev))
+    out = dict(rgb=_f32(dev, S, S, 3), owner=torch.empty((S, S), dtype=torch.int32, device=dev), normals=_f32(dev, S, S, 3) if want_normals else None,
+               sdf=_f32(dev, S, S), status=torch.empty((S, S), dtype=torch.uint8, device=dev))
     L.check(L.lib().ac_mesh_bake_texture(C.byref(field.c), positions.data_ptr(), V, triangles.data_ptr(), T, C.byref(atlas), C.byref(opts), out["rgb"].data_ptr(),
                                          out["owner"].data_ptr(), L.ptr(out["normals"]), out["sdf"].data_ptr(), out["status"].data_ptr(),
                                          L.current_stream(dev)), "mesh_bake_texture")
@@ -1356,25 +1387,38 @@ def render_rays_surface(field, rays_o, rays_d, bound, fd_eps, *, level=0.0, tol=
     (0 hit, 1 out of iterations inside a bracket, 2 miss, 3 starts inside, 4 out of iterations without a bracket, 5 value not finite; shaded =
     0, 1 or 3), iters [N] uint8 = SDF evaluations of the root finder)"""
     opts = surface_opts(bound, fd_eps, level, tol, max_iters, step_scale, min_step, guard)
-    rays_o = _chk(rays_o, "rays_o")
-    if rays_o.dim() != 2 or rays_o.shape[1] != 3:
-        raise RuntimeError(f"render_rays_surface: rays_o must be [N,3], got {tuple(rays_o.shape)}")
-    N, dev = rays_o.shape[0], rays_o.device
-    rays_d = _chk(rays_d, "rays_d", (N, 3))
-    if bg is not None:
-        bg = _chk(bg, "bg", (N, 3))
-    if rays_d.device != dev or (bg is not None and bg.device != dev) or field.device != dev:
-        raise RuntimeError("render_rays_surface: field, rays_o, rays_d and bg must live on one device")
-    f = lambda *sh: torch.empty(sh, dtype=_F32, device=dev)
-    u8 = lambda: torch.empty(N, dtype=torch.uint8, device=dev)
-    out = dict(image=f(N, 3) if want_rgb else None, weights_sum=f(N), depth=f(N), position=f(N, 3), normal_map=f(N, 3), sdf=f(N), status=u8(), iters=u8())
-    so = L.ac_surface_out(*[L.ptr(out[k]) for k in ("image", "weights_sum", "depth", "position", "normal_map", "sdf", "status", "iters")])
+    N, dev, out, so = _surface_args("render_rays_surface", field, rays_o, rays_d, bg, want_rgb)
     L.check(L.lib().ac_render_rays_surface(C.byref(field.c), C.byref(opts), rays_o.data_ptr(), rays_d.data_ptr(), N, L.ptr(bg), C.byref(so),
                                            L.current_stream(dev)), "render_rays_surface")
     return out
 
 
-SURFACE_WARPED_OUTPUTS = ("image", "weights_sum", "depth", "position", "normal_map", "sdf", "status", "iters", "canonical", "normal_can", "face_id")
+def _surface_args(who, field, rays_o, rays_d, bg, want_rgb, posed=False, warp=None):
+    """the tensor checks of the two surface renderers (rays_o, rays_d, bg are used as given: no copies), their result dict and its ac_surface_out ->
+    (N, device, out, ac_surface_out).  posed: + the checks of the mesh `warp` and the three posed outputs."""
+    _chk(rays_o, "rays_o")
+    if rays_o.dim() != 2 or rays_o.shape[1] != 3:
+        raise RuntimeError(f"{who}: rays_o must be [N,3], got {tuple(rays_o.shape)}")
+    if posed and not isinstance(warp, WarpMesh):
+        raise RuntimeError(f"{who}: warp must be an nsr_ops.WarpMesh")
+    N, dev = rays_o.shape[0], rays_o.device
+    _chk(rays_d, "rays_d", (N, 3))
+    if bg is not None:
+        _chk(bg, "bg", (N, 3))
+    if rays_d.device != dev or (bg is not None and bg.device != dev) or field.device != dev or (posed and warp.verts.device != dev):
+        raise RuntimeError(f"{who}: field, rays_o, rays_d" + (", bg and the mesh" if posed else " and bg") + " must live on one device")
+    if posed and warp.faces.shape[0] == 0:
+        raise RuntimeError(f"{who}: a mesh without faces")
+    u8 = lambda: torch.empty(N, dtype=torch.uint8, device=dev)
+    out = dict(image=_f32(dev, N, 3) if want_rgb else None, weights_sum=_f32(dev, N), depth=_f32(dev, N), position=_f32(dev, N, 3),
+               normal_map=_f32(dev, N, 3), sdf=_f32(dev, N), status=u8(), iters=u8())
+    if posed:
+        out.update(canonical=_f32(dev, N, 3), normal_can=_f32(dev, N, 3), face_id=torch.empty(N, dtype=torch.int32, device=dev))
+    so = L.ac_surface_out(*[L.ptr(out[k]) for k in ("image", "weights_sum", "depth", "position", "normal_map", "sdf", "status", "iters")])
+    return N, dev, out, so
+
+
+SURFACE_WARPED_OUTPUTS =("image", "weights_sum", "depth", "position", "normal_map", "sdf", "status", "iters", "canonical", "normal_can", "face_id")
 
 
 def surface_warped_opts(bound, fd_eps, level=0.0, tol=1e-4, max_iters=64, step_scale=1.0, min_step=1e-3, guard=0.125, w_tol=1e-4):
@@ -1402,24 +1446,7 @@ def render_rays_surface_warped(field, rays_o, rays_d, bound, warp, fd_eps=FD_STE
     of the root finder), canonical [N,3] (the shaded point in canonical space), normal_can [N,3], face_id [N] int32 (closest guide face; -1 where not shaded))"""
     who = "render_rays_surface_warped"
     opts, w_tol = surface_warped_opts(bound, fd_eps, level, tol, max_iters, step_scale, min_step, guard, w_tol)
-    rays_o = _chk(rays_o, "rays_o")
-    if rays_o.dim() != 2 or rays_o.shape[1] != 3:
-        raise RuntimeError(f"{who}: rays_o must be [N,3], got {tuple(rays_o.shape)}")
-    if not isinstance(warp, WarpMesh):
-        raise RuntimeError(f"{who}: warp must be an nsr_ops.WarpMesh")
-    N, dev = rays_o.shape[0], rays_o.device
-    rays_d = _chk(rays_d, "rays_d", (N, 3))
-    if bg is not None:
-        bg = _chk(bg, "bg", (N, 3))
-    if rays_d.device != dev or (bg is not None and bg.device != dev) or field.device != dev or warp.verts.device != dev:
-        raise RuntimeError(f"{who}: field, rays_o, rays_d, bg and the mesh must live on one device")
-    if warp.faces.shape[0] == 0:
-        raise RuntimeError(f"{who}: a mesh without faces")
-    f = lambda *sh: torch.empty(sh, dtype=_F32, device=dev)
-    u8 = lambda: torch.empty(N, dtype=torch.uint8, device=dev)
-    out = dict(image=f(N, 3) if want_rgb else None, weights_sum=f(N), depth=f(N), position=f(N, 3), normal_map=f(N, 3), sdf=f(N), status=u8(), iters=u8(),
-               canonical=f(N, 3), normal_can=f(N, 3), face_id=torch.empty(N, dtype=torch.int32, device=dev))
-    so = L.ac_surface_out(*[L.ptr(out[k]) for k in ("image", "weights_sum", "depth", "position", "normal_map", "sdf", "status", "iters")])
+    N, dev, out, so = _surface_args(who, field, rays_o, rays_d, bg, want_rgb, posed=True, warp=warp)
     sw = L.ac_surface_warped_out(*[L.ptr(out[k]) for k in ("canonical", "normal_can", "face_id")])
     need = int(L.lib().ac_render_rays_surface_warped_scratch(N))
     scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
@@ -1490,8 +1517,7 @@ def mesh_pose(points, normals, bind, mesh, iters=3, tol=1e-5, want=("residual", 
     if unknown:
         raise ValueError(f"mesh_pose: unknown outputs {sorted(unknown)}")
     opts = L.ac_mesh_pose_opts(int(iters), float(tol))
-    out = dict(positions=torch.empty((V, 3), dtype=_F32, device=dev), normals=torch.empty((V, 3), dtype=_F32, device=dev) if normals is not None else None,
-               residual=torch.empty(V, dtype=_F32, device=dev) if "residual" in want else None,
+    out = dict(positions=_f32(dev, V, 3), normals=_f32(dev, V, 3) if normals is not None else None, residual=_f32(dev, V) if "residual" in want else None,
                status=torch.empty(V, dtype=torch.uint8, device=dev) if "status" in want else None,
                mask=torch.empty(V, dtype=torch.uint8, device=dev) if "mask" in want else None)
     need = int(L.lib().ac_mesh_pose_scratch(V))

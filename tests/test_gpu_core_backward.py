@@ -46,9 +46,9 @@ def dev(t):
 
 def unpack(g_table, g_sdf_p, g_col_p, g_invs):
     """the operator's flat results -> {tensor: device tensor} and the whole-table gradient"""
-    gW1b = g_sdf_p[:64 * 36].view(64, 36)
-    return dict(g_W1=gW1b[:, :35], g_b1=gW1b[:, 35], g_W2=g_sdf_p[64 * 36:64 * 36 + 1024].view(16, 64), g_b2=g_sdf_p[64 * 36 + 1024:],
-                g_Wc1=g_col_p[:2048].view(64, 32)[:, :21], g_Wc2=g_col_p[2048:6144].view(64, 64), g_Wc3=g_col_p[6144:].view(16, 64)[:3], g_inv_s=g_invs,
+    from avatarcraft_amd import nsr_ops
+    names = ("g_W1", "g_b1", "g_W2", "g_b2", "g_Wc1", "g_Wc2", "g_Wc3")
+    return dict(zip(names, nsr_ops.split_sdf_param_grads(g_sdf_p) + nsr_ops.split_color_param_grads(g_col_p)), g_inv_s=g_invs,
                 g_table=g_table, flat=(g_sdf_p, g_col_p, g_invs))
 
 

@@ -35,7 +35,8 @@ def _setup():
     T = T0 + UP
     e = dict(L=L, f=f, out=out, ro=ro, rd=rd, T=T, Wsh=t(rs.normal(0, 0.1, (64, 16))), sh_bias=t(rs.normal(0, 0.1, (N, 64))), near=t(np.full(N, 0.5)),
              far=t(np.full(N, 3.0)), up=[t(rs.normal(0, 1, s)) for s in ((N, 3), (N,), (N,), (N, 3))] + [t([0.01])],
-             g_table=torch.empty_like(f.t["table"]), g_sdf=torch.empty(3344, device=DEV), g_col=torch.empty(7168, device=DEV), g_invs=torch.empty(N, device=DEV),
+             g_table=torch.empty_like(f.t["table"]), g_sdf=torch.empty(nsr_ops.SDF_PARAM_GRADS_LEN, device=DEV),
+             g_col=torch.empty(nsr_ops.COLOR_PARAM_GRADS_LEN, device=DEV), g_invs=torch.empty(N, device=DEV),
              g_tiles=torch.empty((N * T // 16, 64), device=DEV))
     e["scratch"] = torch.empty(int(L.lib().ac_render_core_backward_scratch(C.byref(f.c), N, T)), dtype=torch.uint8, device=DEV)
     e["written"] = [e[k] for k in ("g_table", "g_sdf", "g_col", "g_invs", "scratch")]

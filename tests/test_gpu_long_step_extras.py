@@ -114,9 +114,7 @@ def test_saved_features_backward_matches_oracle_fp64(T0, up):
     worst = {}
     for form, x in res.items():
         g_sdf_p, g_col_p = x["g_sdf_params"], x["g_color_params"]
-        gW1b = g_sdf_p[:64 * 36].view(64, 36)
-        g = dict(W1=gW1b[:, :35], b1=gW1b[:, 35], W2=g_sdf_p[64 * 36:64 * 36 + 1024].view(16, 64), b2=g_sdf_p[64 * 36 + 1024:],
-                 Wc1=g_col_p[:2048].view(64, 32)[:, :21], Wc2=g_col_p[2048:6144].view(64, 64), Wc3=g_col_p[6144:].view(16, 64)[:3])
+        g = dict(zip(("W1", "b1", "W2", "b2", "Wc1", "Wc2", "Wc3"), nsr_ops.split_sdf_param_grads(g_sdf_p) + nsr_ops.split_color_param_grads(g_col_p)))
         w = {k: float(np.abs(v.cpu().numpy().astype(np.float64) - r["g_" + k]).max() / np.abs(r["g_" + k]).max()) for k, v in g.items()}
         w["inv_s"] = abs(float(x["g_inv_s_per_ray"].sum()) - r["g_inv_s"]) / abs(r["g_inv_s"])
         w["table"] = float(np.abs(x["g_table"].cpu().numpy().astype(np.float64) - r["g_table"]).max() / np.abs(r["g_table"]).max())

@@ -110,9 +110,7 @@ def test_long_backward_matches_oracle_fp64(T0, up):
     g_sdf_p, g_col_p, g_invs = nsr_ops.render_core_backward(f, out.opts, out, tro, trd, tbg, t(g_img), t(g_ws), t(g_dp), t(g_nm),
                                                             torch.tensor(g_eik, device=DEV), g_table)
     torch.cuda.synchronize()
-    gW1b = g_sdf_p[:64 * 36].view(64, 36)
-    g = dict(W1=gW1b[:, :35], b1=gW1b[:, 35], W2=g_sdf_p[64 * 36:64 * 36 + 1024].view(16, 64), b2=g_sdf_p[64 * 36 + 1024:],
-             Wc1=g_col_p[:2048].view(64, 32)[:, :21], Wc2=g_col_p[2048:6144].view(64, 64), Wc3=g_col_p[6144:].view(16, 64)[:3])
+    g = dict(zip(("W1", "b1", "W2", "b2", "Wc1", "Wc2", "Wc3"), nsr_ops.split_sdf_param_grads(g_sdf_p) + nsr_ops.split_color_param_grads(g_col_p)))
     z = out["z_vals"].cpu().numpy()
     r = O.render_core_backward(of, ro, rd, z, T0, up, 1.6, inv_s, bg=bg, g_image=g_img, g_weights_sum=g_ws, g_depth=g_dp, g_normal_map=g_nm, g_eik=g_eik)
     assert np.abs(r["image"] - out["image"].cpu().numpy()).max() <= 2e-5

@@ -43,6 +43,36 @@ def test_struct_layout_matches_header():
     assert _lib.ac_field.offsets.offset == 8 and _lib.ac_field.S.offset == 8 + 17 * 4 and _lib.ac_field.W1.offset == 88 and _lib.ac_field.prepared.offset == 88 + 7 * 8 and _lib.ac_field.Wc1_sh.offset == 88 + 8 * 8 and ctypes.sizeof(_lib.ac_field) == 88 + 9 * 8
 
 
+def test_packed_param_grad_layout_matches_header():
+    """nsr_ops.split_sdf_param_grads / split_color_param_grads against the layouts as include/avatarcraft_hip.h words them, in literals:
+    g_sdf_params [3344] = dW1 [64][36] (column 35 = db1) | dW2 [16][64] | db2 [16];
+    g_color_params [7168] = dWc1 [64][32] (columns 0..20) | dWc2 [64][64] | dWc3 [16][64] (rows 0..2).  Needs neither the library nor a GPU."""
+    from avatarcraft_amd import nsr_ops
+    assert (nsr_ops.SDF_PARAM_GRADS_LEN, nsr_ops.COLOR_PARAM_GRADS_LEN) == (3344, 7168)
+    r, c = torch.arange(64.)[:, None], torch.arange(64.)[None, :]
+    g = torch.arange(3344.)
+    W1, b1, W2, b2 = nsr_ops.split_sdf_param_grads(g)
+    assert [tuple(t.shape) for t in (W1, b1, W2, b2)] == [(64, 35), (64,), (16, 64), (16,)]
+    assert torch.equal(W1, 36 * r + c[:, :35]) and torch.equal(b1, 36 * r[:, 0] + 35)
+    assert torch.equal(W2, 2304 + 64 * r[:16] + c) and torch.equal(b2, 3328 + r[:16, 0])
+    assert [t.data_ptr() - g.data_ptr() for t in (W1, b1, W2, b2)] == [0, 4 * 35, 4 * 2304, 4 * 3328]
+    k = torch.arange(7168.)
+    Wc1, Wc2, Wc3 = nsr_ops.split_color_param_grads(k)
+    assert [tuple(t.shape) for t in (Wc1, Wc2, Wc3)] == [(64, 21), (64, 64), (3, 64)]
+    assert torch.equal(Wc1, 32 * r + c[:, :21]) and torch.equal(Wc2, 2048 + 64 * r + c) and torch.equal(Wc3, 6144 + 64 * r[:3] + c)
+    assert [t.data_ptr() - k.data_ptr() for t in (Wc1, Wc2, Wc3)] == [0, 4 * 2048, 4 * 6144]
+    for t, base in ((W1, g), (b1, g), (W2, g), (b2, g), (Wc1, k), (Wc2, k), (Wc3, k)):         # views: same storage, and a write shows in the vector
+        assert t.untyped_storage().data_ptr() == base.untyped_storage().data_ptr()
+    W2[3, 5] = -1.0
+    assert g[2304 + 64 * 3 + 5] == -1.0
+    # the table the no-autograd step hands to ac_param_grads as (offset, row stride) says the same
+    S, K = nsr_ops.SDF_PARAM_GRADS, nsr_ops.COLOR_PARAM_GRADS
+    assert [(S[n].offset, S[n].stride) for n in ("W1", "b1", "W2", "b2")] == [(0, 36), (35, 36), (2304, 64), (3328, 1)]
+    assert [(K[n].offset, K[n].stride) for n in ("Wc1", "Wc2", "Wc3")] == [(0, 32), (2048, 64), (6144, 64)]
+    with pytest.raises(RuntimeError, match="3344"):
+        nsr_ops.split_sdf_param_grads(torch.zeros(7168))
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     from avatarcraft_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)
