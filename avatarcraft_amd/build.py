@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libavatarcraft_hip.so")
 SOURCES = ["ac_capi.hip", "hashgrid.hip", "hash_stencil.hip", "shencoder.hip", "raymarching.hip", "render_fused.hip", "render_long.hip", "render_occupancy.hip", "sdf_stencil_train.hip", "color_train.hip",
-           "composite.hip", "render_core_backward.hip", "warp.hip", "warp_accel_build.hip", "step_glue.hip", "geometry.hip", "mesh_pose.hip"]
+           "composite.hip", "render_core_backward.hip", "warp.hip", "warp_accel_build.hip", "step_glue.hip", "field_grid.hip", "marching_cubes.hip", "mesh_shade.hip", "surface_rays.hip", "mesh_pose.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fvisibility=hidden",
          "-Wno-unused-result",
          # no compiler-formed packed-fp32 (v_pk_*_f32) code: the one run-to-run non-determinism ever observed in the renderer (round 2: the "face-value"
@@ -81,6 +81,14 @@ def _supported(hipcc, flags):
     return _PROBED[key]
 
 
+def _max_jobs():
+    """compilers at once: MAX_JOBS where it is set (a shared machine grants a share of its CPUs, not all that os.cpu_count() shows), else every CPU"""
+    try:
+        return max(1, int(os.environ["MAX_JOBS"]))
+    except (KeyError, ValueError):
+        return os.cpu_count() or 1
+
+
 def _stale(target, deps):
     if not os.path.exists(target):
         return True
@@ -112,7 +120,7 @@ def build(force=False, verbose=False):
             raise RuntimeError(f"hipcc failed for {s}:\n{r.stdout}")
         return r.stdout
 
-    with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 1) or 1) as ex:
+    with ThreadPoolExecutor(max_workers=min(len(jobs), _max_jobs()) or 1) as ex:
         list(ex.map(cc, jobs))
     objs = [os.path.join(bdir, s.replace(".hip", ".o")) for s in SOURCES]
     if force or jobs or _stale(OUT, objs):

@@ -1,0 +1,220 @@
+// avatarcraft_amd/csrc/field_grid.hip -- the learned SDF on a regular grid, for its two consumers:
+//
+//   mesh export   NeRFNetwork.extract_geometry (models/instant_nsr.py:706-764; the reference's one call: stylize.py:267, resolution 512):
+//                 forward_sdf on a resolution^3 grid over [-bound, bound]^3 (extract_fields :728-745, 256^3-point blocks through query_func, assembled
+//                 on the HOST) -> u = -sdf -> marching cubes (marching_cubes.hip).
+//                 Here: ac_field_sdf_grid (grid coordinates formed in the kernel from the three axis tables, the volume stays on the device).
+//   density grid  NeRFRenderer.update_extra_state (:303-356): forward_sdf on the 129^3 grid -> logistic density -> zero pad + 2^3 max pool ->
+//                 maximum(grid * decay, new) -> mean.  Here two launches (ac_density_grid_update): the density of every grid point on the x-tiles of
+//                 ac_field_sdf_grid into a scratch volume, then one streaming pass that pools, merges into the running grid in place and forms the mean.
+//
+// The SDF itself is the renderer's own tile code (nsr_device.hpp: sdf_tile = hash gather + MFMA SDF network), so every value is bit-identical to
+// ac_field_sdf / density() and therefore to the CPU oracle's orc_field_sdf.
+#include "field_tile.hpp"
+
+namespace {
+
+// ---------------------------------------------------------------------------------------------------------------- SDF on a regular grid
+// update_extra_state's density (:331-337): inv_s e^(-inv_s sdf) / (1 + e^(-inv_s sdf)) for sdf > 0, the mirrored form for sdf <= 0 -- the two
+// overflow-free branches, every operation in the reference's order (mul, exp, mul | add, div) in fp32
+__device__ __forceinline__ float dg_density(float sdf, float inv_s)
+{
+    const float e = expf(sdf > 0.0f ? -inv_s * sdf : inv_s * sdf);
+    return (inv_s * e) / (1.0f + e);
+}
+
+constexpr uint32_t GB_X = 16, GB_Y = 4, GB_Z = 16;           // a brick of grid points: 64 tiles of 16 points along X
+
+// The volume is cut into bricks of 16 x 4 x 16 points; a workgroup evaluates one brick at a time, its 8 waves take 8 tiles each, and a
+//   tile is 16 consecutive points ALONG X.  Why x: the spatial hash of the fine levels is x ^ y P1 ^ z P2 (hashencoder.cu:54-70) -- linear in x, so the eight cells
+//   x in [8k, 8k + 8) of one (y, z) row are the eight entries of ONE 64-byte sector of the table (and consecutive entries on the dense levels).  A gather
+//   instruction serves one corner of the 16 points of a tile: along x those 16 entries sit in 2 .. 9 sectors, along y or z in 16 (the primes scatter them
+//   over the level's 4 MB).  The per-CU gather path and the fabric behind L2 -- what this kernel is short of -- see a fraction of the requests.
+//   The results are staged in LDS and written with z fastest (64-byte runs) -- the volume keeps the reference's [x][y][z] layout.
+//   Every XCD (workgroup index mod 8) walks through its own contiguous eighth of the bricks: coarse and middle levels are re-used from its L2.
+__global__ __launch_bounds__(BLOCK) void field_sdf_grid_kernel(const RenderArgs a, const float *__restrict__ ax, const float *__restrict__ ay,
+                                                               const float *__restrict__ az, uint32_t nx, uint32_t ny, uint32_t nz, int mode, float inv_s,
+                                                               float *__restrict__ vol)
+{
+    // mode: what is stored per grid point -- 0 the sdf, 1 its negative (the mesh export's u), 2 update_extra_state's logistic density of it (dg_density)
+    auto value = [&](float sdf) { return mode == 2 ? dg_density(sdf, inv_s) : (mode == 1 ? -sdf : sdf); };
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    fill_lds_sdf(lds, a);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
+    const FieldCtx fc = make_ctx(a);
+    float *stage = lds + OFF_WAVE;                                                               // [GB_X][GB_Y][GB_Z]
+    const uint32_t nbz = (nz + GB_Z - 1) / GB_Z, nby = (ny + GB_Y - 1) / GB_Y, nbx = (nx + GB_X - 1) / GB_X;
+    const uint32_t nbricks = nbx * nby * nbz, per_xcd = (nbricks + 7u) / 8u;
+    const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3, slots = gridDim.x >> 3;        // (the grid is a multiple of 8 workgroups)
+    for (uint32_t bi = slot; bi < per_xcd; bi += slots) {
+        const uint32_t brick = xcd * per_xcd + bi;
+        if (brick >= nbricks) break;                                                             // (workgroup-uniform)
+        const uint32_t bz = brick % nbz, bt = brick / nbz, by = bt % nby, bx = bt / nby;
+#pragma unroll 1
+        for (uint32_t t = (uint32_t)wave; t < GB_Y * GB_Z; t += WAVES_PER_BLOCK) {
+            const uint32_t ly = t >> 4, lz = t & 15u;
+            const uint32_t ix = bx * GB_X + (uint32_t)n, iy = by * GB_Y + ly, iz = bz * GB_Z + lz;
+            if (iy >= ny || iz >= nz) continue;                                                  // (wave-uniform)
+            const uint32_t cx = ix < nx ? ix : nx - 1u;
+            const f32x4 o = sdf_tile(lds, fc, lane, ax[cx], ay[iy], az[iz]);
+            if (g == 0) stage[((uint32_t)n * GB_Y + ly) * GB_Z + lz] = value(o[0]);
+        }
+        __syncthreads();
+        for (uint32_t o = threadIdx.x; o < GB_X * GB_Y * GB_Z; o += BLOCK) {
+            const uint32_t lz = o & 15u, ly = (o >> 4) & 3u, lx = o >> 6;
+            const uint32_t ix = bx * GB_X + lx, iy = by * GB_Y + ly, iz = bz * GB_Z + lz;
+            if (ix < nx && iy < ny && iz < nz) vol[((size_t)ix * ny + iy) * nz + iz] = stage[o];
+        }
+        __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- density grid of the ray marcher
+// Round 6: two launches instead of one.  Round 5 gave every workgroup a brick of 16 x 8 x 8 outputs PLUS the one-point halo the 2^3 max pool reads
+// (17 x 9 x 9 = 1377 evaluations for 1024 outputs, 3.58 M for the 2.15 M points of the 129^3 grid) and cut them into tiles of 16 consecutive evaluations of
+// a 17-wide row -- tiles that straddle two rows, i.e. none of what makes field_sdf_grid_kernel fast (16 points along x = 2 .. 9 sectors per gather).
+//   1. field_sdf_grid_kernel<.., true> in mode 2: the density of every grid point ONCE, on x-tiles, into a scratch volume (8.6 MB at 129^3: L2-resident);
+//   2. density_pool_kernel: zero pad + 2^3 max pool of that volume, maximum(grid * decay, new) in place, the mean -- one short streaming pass.
+// 0.94 -> 0.3x ms per update (bench.py: density_grid_update); the same values (sdf bits, expf / divide, max).
+struct DgArgs {
+    const float *dens;        // [H,H,H] the densities of pass 1
+    uint32_t H;
+    float decay;
+    float *grid;              // [H,H,H] in / out
+    double *partials;         // [number of workgroups]
+    uint32_t *ticket;         // [1], zero between launches (the last workgroup re-arms it)
+    double *mean_out;         // [1]
+};
+constexpr int DP_BLOCK = 256;
+
+__global__ __launch_bounds__(DP_BLOCK) void density_pool_kernel(const DgArgs g_)
+{
+    __shared__ double red[DP_BLOCK / 64];
+    __shared__ uint32_t last;
+    const uint32_t H = g_.H, N = H * H * H;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double part = 0.0;
+#pragma unroll 4
+    for (uint32_t p = blockIdx.x * DP_BLOCK + threadIdx.x; p < N; p += gridDim.x * DP_BLOCK) {       // z fastest: the grid's own order
+        const uint32_t gz = p % H, t = p / H, gy = t % H, gx = t / H;
+        float m = 0.0f;                                                      // (F.max_pool3d over the zero-padded tmp_grid (:341); densities are >= 0)
+#pragma unroll
+        for (uint32_t dx = 0; dx < 2; ++dx)
+#pragma unroll
+            for (uint32_t dy = 0; dy < 2; ++dy)
+#pragma unroll
+                for (uint32_t dz = 0; dz < 2; ++dz)
+                    if (gx + dx < H && gy + dy < H && gz + dz < H) m = fmaxf(m, g_.dens[((size_t)(gx + dx) * H + (gy + dy)) * H + (gz + dz)]);
+        const float v = fmaxf(g_.grid[p] * g_.decay, m);                     // torch.maximum(density_grid * decay, tmp_grid)  (:345)
+        g_.grid[p] = v;
+        part += (double)v;
+    }
+    // mean: per-wave shuffle tree -> per-workgroup sum (fixed order) -> the last workgroup adds the workgroups' partials (fixed order); in double, where the
+    // reference's torch.mean reduces in fp32 -- the two agree to ~1e-7 relative (tests: <= 1e-6), not bit for bit: mean_density is a threshold of the marcher
+    // (density > min(mean, 0.01 ...)), compared against values that differ from it by orders of magnitude
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) part += __shfl_xor(part, d);
+    if (lane == 0) red[wave] = part;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int w = 0; w < DP_BLOCK / 64; ++w) s += red[w];
+        g_.partials[blockIdx.x] = s;
+        __threadfence();
+        last = atomicAdd(g_.ticket, 1u) == gridDim.x - 1u ? 1u : 0u;
+    }
+    __syncthreads();
+    if (!last) return;
+    __threadfence();
+    double s = 0.0;
+    for (uint32_t b = threadIdx.x; b < gridDim.x; b += DP_BLOCK)             // (agent-scope loads: served by L2, never by a stale vector-L1 line)
+        s += __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<unsigned long long *>(g_.partials) + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d);
+    __syncthreads();
+    if (lane == 0) red[wave] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double tot = 0.0;
+        for (int w = 0; w < DP_BLOCK / 64; ++w) tot += red[w];
+        g_.mean_out[0] = tot / ((double)H * (double)H * (double)H);
+        *g_.ticket = 0u;
+    }
+}
+
+int geo_args(RenderArgs &a, const ac_field *field, float bound)
+{
+    if (int rc = fill_args(a, field, bound)) return rc;
+    a.T0 = 0; a.lin_z = nullptr; a.lin_u = nullptr;
+    return AC_OK;
+}
+
+// the regular-grid launch shared by ac_field_sdf_grid and ac_density_grid_update (mode: see field_sdf_grid_kernel)
+int launch_grid(const RenderArgs &a, const float *axis_x, const float *axis_y, const float *axis_z, uint32_t nx, uint32_t ny, uint32_t nz, int mode, float inv_s,
+                float *volume, hipStream_t stream, const char *what)
+{
+    const size_t lds_bytes = (OFF_WAVE + GB_X * GB_Y * GB_Z) * sizeof(float);
+    uint32_t blocks = ((nx + GB_X - 1) / GB_X) * ((ny + GB_Y - 1) / GB_Y) * ((nz + GB_Z - 1) / GB_Z);
+    // persistent workgroups, exactly as many as the device keeps resident at once (43 KB of LDS each; the registers decide): a workgroup that had to
+    // wait for a slot would start its share of the tiles when the others are done
+    static int per_cu = 0;
+    if (!per_cu) {
+        int n = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, field_sdf_grid_kernel, BLOCK, lds_bytes) != hipSuccess || n < 1) n = 1;
+        per_cu = n;
+    }
+    const uint32_t cap = (uint32_t)per_cu * ac::cu_count();
+    if (blocks > cap) blocks = cap;
+    blocks = (blocks + 7u) & ~7u;                                     // every XCD the same number of workgroups
+    hipLaunchKernelGGL(field_sdf_grid_kernel, dim3(blocks), dim3(BLOCK), lds_bytes, stream, a, axis_x, axis_y, axis_z, nx, ny, nz, mode, inv_s, volume);
+    return ac::check_launch(what);
+}
+
+uint32_t dp_blocks(uint32_t H)
+{
+    // few workgroups, several points per thread: every workgroup ends with a device-scope fence + a ticket (the mean's fixed-order reduction), and with one
+    // point per thread (8403 workgroups at 129^3) those epilogues were the pass: 223 us against 65 us with 2048 workgroups
+    const uint64_t n = ((uint64_t)H * H * H + DP_BLOCK - 1) / DP_BLOCK;
+    const uint32_t cap = 4u * ac::cu_count();
+    return (uint32_t)(n < cap ? n : cap);
+}
+size_t dg_dens_offset(uint32_t H) { return (256 + (size_t)dp_blocks(H) * sizeof(double) + 255) & ~(size_t)255; }
+
+}  // namespace
+
+AC_API int ac_field_sdf_grid(const ac_field *field, const float *axis_x, const float *axis_y, const float *axis_z, uint32_t nx, uint32_t ny, uint32_t nz,
+                             float bound, int negate, float *volume, ac_stream_t stream)
+{
+    if (nx == 0 || ny == 0 || nz == 0) return AC_OK;
+    if (!axis_x || !axis_y || !axis_z || !volume) { ac::set_error("field_sdf_grid: NULL buffer"); return AC_ERR_BAD_ARG; }
+    if ((uint64_t)nx * ny * nz >= (1ull << 32) - 16) { ac::set_error("field_sdf_grid: more than 2^32 grid points"); return AC_ERR_BAD_ARG; }
+    RenderArgs a{};
+    if (int rc = geo_args(a, field, bound)) return rc;
+    return launch_grid(a, axis_x, axis_y, axis_z, nx, ny, nz, negate ? 1 : 0, 0.0f, volume, (hipStream_t)stream, "field_sdf_grid");
+}
+
+AC_API size_t ac_density_grid_update_scratch(uint32_t H)
+{
+    if (H < 2 || H > 1024) return 0;
+    return dg_dens_offset(H) + (size_t)H * H * H * sizeof(float);           // ticket | per-workgroup partial sums | the densities of pass 1
+}
+
+AC_API int ac_density_grid_update(const ac_field *field, const float *axis, uint32_t H, float bound, float inv_s, float decay, float *grid,
+                                  double *mean_out, void *scratch, size_t scratch_bytes, ac_stream_t stream)
+{
+    if (!axis || !grid || !mean_out || !scratch) { ac::set_error("density_grid_update: NULL buffer"); return AC_ERR_BAD_ARG; }
+    const size_t need = ac_density_grid_update_scratch(H);
+    if (!need || scratch_bytes < need) { ac::set_error("density_grid_update: H = %u unsupported or scratch of %zu bytes needed, %zu given", H, need, scratch_bytes); return AC_ERR_BAD_ARG; }
+    RenderArgs a{};
+    if (int rc = geo_args(a, field, bound)) return rc;
+    float *dens = reinterpret_cast<float *>(static_cast<char *>(scratch) + dg_dens_offset(H));
+    if (int rc = launch_grid(a, axis, axis, axis, H, H, H, 2, inv_s, dens, (hipStream_t)stream, "density_grid_update")) return rc;
+    DgArgs g{};
+    g.dens = dens; g.H = H; g.decay = decay; g.grid = grid;
+    g.ticket = static_cast<uint32_t *>(scratch);
+    g.partials = reinterpret_cast<double *>(static_cast<char *>(scratch) + 256);
+    g.mean_out = mean_out;
+    hipLaunchKernelGGL(density_pool_kernel, dim3(dp_blocks(H)), dim3(DP_BLOCK), 0, (hipStream_t)stream, g);
+    return ac::check_launch("density_grid_update");
+}

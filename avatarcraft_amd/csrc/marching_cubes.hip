@@ -1,0 +1,293 @@
+// avatarcraft_amd/csrc/marching_cubes.hip -- marching cubes on the device: ac_marching_cubes_count / _emit turn a volume u (the mesh export's -sdf of
+// ac_field_sdf_grid, or any other [nx][ny][nz] floats) into the mesh PyMCubes' marching_cubes(u, threshold) would give extract_geometry
+// (models/instant_nsr.py:747-764): classify -> scan -> emit, shared-edge vertex indexing, no atomics: a deterministic mesh.  No field code is involved.
+//
+// Marching cubes: the 256-case table is GENERATED from the algorithm's definition (tools/gen_mc_table.py -> ac_mc_table.hpp): corner flagged <=> u <= iso
+// (PyMCubes' convention), one vertex per sign-changing grid edge at the linear zero crossing (formed in double like PyMCubes: it evaluates its float32
+// input in double), ambiguous faces always cut off the flagged corners (a rule of the face's own 4 flags: watertight by construction), triangles oriented
+// with the normal towards u <= iso = out of the body for u = -sdf.  PyMCubes is not in this image: "unpinned vs PyMCubes, pinned vs the definition".
+// Order of the output (what makes the mesh reproducible bit for bit, and equal to the CPU oracle's serial loop): vertices by owning grid point (linear
+// index, z fastest) then by axis x, y, z; triangles by cell (linear index) then by table position.
+#include "ac_common.hpp"
+
+#define AC_MC_CONST static __constant__ const
+#include "ac_mc_table.hpp"
+
+namespace {
+
+// ---------------------------------------------------------------------------------------------------------------- marching cubes
+constexpr int MC_PTS = 1024;                     // grid points per workgroup (256 threads x 4 consecutive points: their four count bytes are one dword)
+struct McDims { uint32_t nx, ny, nz, npts; };
+
+__device__ __forceinline__ bool mc_flag(float u, float iso) { return u <= iso; }
+
+// The corner flags of the whole volume as a bit array (1 bit per grid point: 16.8 MB at 512^3, L2-resident), written by ONE coalesced pass over the
+// volume: a wave takes 64 consecutive points per step, the ballot of `u <= iso` is their 64 flags.  The classification then reads bits: its eight
+// look-ups per point (four rows of the volume) were 2.1 GB of L2 traffic on floats (0.95 ms at 512^3), on bits they are nothing.
+__global__ __launch_bounds__(256) void mc_flags_kernel(const float *__restrict__ vol, uint32_t npts, float iso, unsigned long long *__restrict__ bits64)
+{
+    const uint32_t lane = threadIdx.x & 63u, nchunks = (npts + 1023u) >> 10;            // a wave's unit of work: 1024 points = 16 steps
+    for (uint32_t chunk = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; chunk < nchunks; chunk += (gridDim.x * blockDim.x) >> 6) {
+        const uint32_t base = chunk << 10;
+        unsigned long long mine = 0ull;
+#pragma unroll
+        for (uint32_t it = 0; it < 16; ++it) {
+            const uint32_t p = base + it * 64u + lane;
+            const unsigned long long m = __ballot(p < npts && mc_flag(vol[p < npts ? p : npts - 1u], iso));
+            if (lane == it) mine = m;
+        }
+        if (lane < 16u && base + lane * 64u < npts) bits64[(base >> 6) + lane] = mine;     // 16 consecutive 8-byte words
+    }
+}
+__device__ __forceinline__ bool mc_bit(const uint32_t *__restrict__ bits, uint32_t q) { return (bits[q >> 5] >> (q & 31u)) & 1u; }
+
+// count byte of a grid point: bits 0-2 = which of its three OWNED edges (towards +x, +y, +z) change sign; bits 3-5 = triangles of the cell it is the origin of
+__device__ __forceinline__ uint32_t mc_classify(const uint32_t *__restrict__ bits, const McDims d, uint32_t p, uint32_t *case_out = nullptr)
+{
+    const uint32_t k = p % d.nz, t = p / d.nz, j = t % d.ny, i = t / d.ny;
+    const bool hx = i + 1u < d.nx, hy = j + 1u < d.ny, hz = k + 1u < d.nz;
+    const uint32_t sx = d.ny * d.nz, sy = d.nz;
+    const bool f0 = mc_bit(bits, p);
+    uint32_t vmask = 0, cs = f0 ? 1u : 0u;
+    bool f1 = false, f2 = false, f4 = false;
+    if (hx) { f1 = mc_bit(bits, p + sx); vmask |= (f1 != f0) ? 1u : 0u; }
+    if (hy) { f2 = mc_bit(bits, p + sy); vmask |= (f2 != f0) ? 2u : 0u; }
+    if (hz) { f4 = mc_bit(bits, p + 1u); vmask |= (f4 != f0) ? 4u : 0u; }
+    uint32_t nt = 0;
+    if (hx && hy && hz) {
+        cs |= (f1 ? 2u : 0u) | (f2 ? 4u : 0u) | (f4 ? 16u : 0u);
+        cs |= mc_bit(bits, p + sx + sy) ? 8u : 0u;
+        cs |= mc_bit(bits, p + sx + 1u) ? 32u : 0u;
+        cs |= mc_bit(bits, p + sy + 1u) ? 64u : 0u;
+        cs |= mc_bit(bits, p + sx + sy + 1u) ? 128u : 0u;
+        nt = AC_MC_NTRI[cs];
+    } else cs = 0u;
+    if (case_out) *case_out = cs;
+    return vmask | (nt << 3);
+}
+
+// workgroup-wide exclusive scan of one value per thread (256 threads), in thread order; total -> every thread
+__device__ __forceinline__ uint32_t block_exscan_256(uint32_t v, uint32_t *sh /* [8] */, uint32_t &total)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = (uint32_t)__shfl_up((int)inc, d); if (lane >= d) inc += o; }
+    __syncthreads();                              // (sh may still be read by a previous call)
+    if (lane == 63) sh[wave] = inc;
+    __syncthreads();
+    uint32_t base = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) if (w < wave) base += sh[w];
+    total = sh[0] + sh[1] + sh[2] + sh[3];
+    return base + inc - v;
+}
+
+__global__ __launch_bounds__(256) void mc_classify_kernel(const uint32_t *__restrict__ bits, const McDims d, uint32_t *__restrict__ cnt4,
+                                                          uint32_t *__restrict__ bsum)
+{
+    __shared__ uint32_t sh[8];
+    const uint32_t p0 = blockIdx.x * MC_PTS + threadIdx.x * 4u;
+    uint32_t packed = 0, nv = 0, nt = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < 4; ++r) {
+        const uint32_t p = p0 + r;
+        uint32_t c = 0;
+        if (p < d.npts) c = mc_classify(bits, d, p);
+        packed |= c << (8 * r);
+        nv += (uint32_t)__builtin_popcount(c & 7u); nt += c >> 3;
+    }
+    if (p0 < d.npts) cnt4[p0 >> 2] = packed;      // (the count array is padded to a multiple of 4 points)
+    uint32_t tot;
+    (void)block_exscan_256(nv | (nt << 16), sh, tot);      // 1024 points: at most 3072 vertices / 5120 triangles per workgroup -- 16 bits each
+    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
+}
+
+// exclusive scan of the per-workgroup totals (vertices in the low, triangles in the high 16 bits) -> boff[2 * b], boff[2 * b + 1]; totals -> counts[0..1].
+// One workgroup of 16 waves; a wave owns a contiguous range of the totals and walks it 64 at a time (coalesced loads, shuffle scan, running carry);
+// the waves' totals are combined through LDS and added in a second coalesced pass (131 072 totals at 512^3: 128 steps per wave and pass).
+__device__ __forceinline__ uint32_t wave_incscan(uint32_t v, int lane)
+{
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = (uint32_t)__shfl_up((int)v, d); if (lane >= d) v += o; }
+    return v;
+}
+__global__ __launch_bounds__(1024) void mc_scan_kernel(const uint32_t *__restrict__ bsum, uint32_t nblk, uint32_t *__restrict__ boff, uint32_t *__restrict__ counts)
+{
+    __shared__ uint32_t wv[16], wt[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t per = (((nblk + 15u) / 16u) + 63u) & ~63u, lo = (uint32_t)wave * per, hi = lo + per < nblk ? lo + per : nblk;
+    uint32_t cv = 0, ct = 0;
+    for (uint32_t b0 = lo; b0 < hi; b0 += 64u) {
+        const uint32_t b = b0 + (uint32_t)lane;
+        const uint32_t sv = b < hi ? bsum[b] : 0u;
+        const uint32_t v = sv & 0xffffu, t = sv >> 16;
+        const uint32_t iv = wave_incscan(v, lane), it = wave_incscan(t, lane);
+        if (b < hi) { boff[2 * b] = cv + iv - v; boff[2 * b + 1] = ct + it - t; }
+        cv += (uint32_t)__shfl((int)iv, 63); ct += (uint32_t)__shfl((int)it, 63);
+    }
+    if (lane == 0) { wv[wave] = cv; wt[wave] = ct; }
+    __syncthreads();
+    uint32_t bv = 0, bt = 0;
+    for (int w = 0; w < wave; ++w) { bv += wv[w]; bt += wt[w]; }
+    if (bv | bt)
+        for (uint32_t b = lo + (uint32_t)lane; b < hi; b += 64u) { boff[2 * b] += bv; boff[2 * b + 1] += bt; }
+    if (threadIdx.x == 1023) { counts[0] = bv + cv; counts[1] = bt + ct; }
+}
+
+struct McXform { double den, span[3], lo[3]; };   // world = index / den * span + lo, the reference's three operations in its order (instant_nsr.py:760-762)
+
+__global__ __launch_bounds__(256) void mc_vertices_kernel(const float *__restrict__ vol, const McDims d, float iso, const uint32_t *__restrict__ cnt4,
+                                                          const uint32_t *__restrict__ bsum, const uint32_t *__restrict__ boff, uint32_t *__restrict__ voff,
+                                                          const McXform xf, double *__restrict__ verts, uint32_t n_verts)
+{
+    __shared__ uint32_t sh[8];
+    if ((bsum[blockIdx.x] & 0xffffu) == 0u) return;
+    const uint32_t p0 = blockIdx.x * MC_PTS + threadIdx.x * 4u;
+    const uint32_t packed = p0 < d.npts ? cnt4[p0 >> 2] : 0u;
+    uint32_t nv = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < 4; ++r) nv += (uint32_t)__builtin_popcount((packed >> (8 * r)) & 7u);
+    uint32_t tot;
+    uint32_t vid = boff[2 * blockIdx.x] + block_exscan_256(nv, sh, tot);
+    const uint32_t stride[3] = { d.ny * d.nz, d.nz, 1u };
+#pragma unroll
+    for (uint32_t r = 0; r < 4; ++r) {
+        const uint32_t m = (packed >> (8 * r)) & 7u;
+        if (!m) continue;
+        const uint32_t p = p0 + r;
+        voff[p] = vid;
+        const uint32_t k = p % d.nz, t = p / d.nz, j = t % d.ny, i = t / d.ny;
+        const double va = (double)vol[p];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            if (!((m >> a) & 1u)) continue;
+            const double vb = (double)vol[p + stride[a]];
+            const double tt = ((double)iso - va) / (vb - va);            // the linear zero crossing between the two grid points, 0 <= tt <= 1
+            double c[3] = { (double)i, (double)j, (double)k };
+            c[a] += tt;
+            if (vid < n_verts) {
+                verts[3 * (size_t)vid] = c[0] / xf.den * xf.span[0] + xf.lo[0];
+                verts[3 * (size_t)vid + 1] = c[1] / xf.den * xf.span[1] + xf.lo[1];
+                verts[3 * (size_t)vid + 2] = c[2] / xf.den * xf.span[2] + xf.lo[2];
+            }
+            ++vid;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void mc_triangles_kernel(const uint32_t *__restrict__ bits, const McDims d, const uint32_t *__restrict__ cnt4,
+                                                           const uint32_t *__restrict__ bsum, const uint32_t *__restrict__ boff, const uint32_t *__restrict__ voff,
+                                                           int32_t *__restrict__ tris, uint32_t n_tris)
+{
+    __shared__ uint32_t sh[8];
+    if ((bsum[blockIdx.x] >> 16) == 0u) return;
+    const uint32_t p0 = blockIdx.x * MC_PTS + threadIdx.x * 4u;
+    const uint32_t packed = p0 < d.npts ? cnt4[p0 >> 2] : 0u;
+    uint32_t nt = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < 4; ++r) nt += (packed >> (8 * r + 3)) & 7u;
+    uint32_t tot;
+    uint32_t tid = boff[2 * blockIdx.x + 1] + block_exscan_256(nt, sh, tot);
+    const uint8_t *cnt8 = reinterpret_cast<const uint8_t *>(cnt4);
+    const uint32_t sx = d.ny * d.nz, sy = d.nz;
+#pragma unroll
+    for (uint32_t r = 0; r < 4; ++r) {
+        const uint32_t n = (packed >> (8 * r + 3)) & 7u;
+        if (!n) continue;
+        const uint32_t p = p0 + r;
+        uint32_t cs;
+        (void)mc_classify(bits, d, p, &cs);
+        for (uint32_t t = 0; t < n; ++t) {
+            int32_t id[3];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                const int e = AC_MC_TRI[cs][3 * t + q];
+                const uint32_t c0 = AC_MC_EDGE[e][0], a = (uint32_t)e >> 2;
+                const uint32_t pq = p + (c0 & 1u) * sx + ((c0 >> 1) & 1u) * sy + ((c0 >> 2) & 1u);     // the grid point that owns edge e of this cell
+                const uint32_t m = cnt8[pq] & 7u;
+                id[q] = (int32_t)(voff[pq] + (uint32_t)__builtin_popcount(m & ((1u << a) - 1u)));
+            }
+            if (tid < n_tris) { tris[3 * (size_t)tid] = id[0]; tris[3 * (size_t)tid + 1] = id[1]; tris[3 * (size_t)tid + 2] = id[2]; }
+            ++tid;
+        }
+    }
+}
+
+struct McLayout { size_t cnt, voff, bsum, boff, bits, total; uint32_t nblk; };
+McLayout mc_layout(uint32_t nx, uint32_t ny, uint32_t nz)
+{
+    McLayout l{};
+    const uint64_t npts = (uint64_t)nx * ny * nz;
+    l.nblk = (uint32_t)((npts + MC_PTS - 1) / MC_PTS);
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    size_t o = 0;
+    l.cnt = o; o += al((size_t)l.nblk * MC_PTS);
+    l.voff = o; o += al((size_t)npts * 4);
+    l.bsum = o; o += al((size_t)l.nblk * 4);
+    l.boff = o; o += al((size_t)l.nblk * 8);
+    l.bits = o; o += al(((size_t)l.nblk * MC_PTS / 64 + 2) * 8);
+    l.total = o;
+    return l;
+}
+
+int mc_check(const char *who, const float *vol, uint32_t nx, uint32_t ny, uint32_t nz, const void *scratch, size_t scratch_bytes, McLayout &l)
+{
+    if (!vol || !scratch) { ac::set_error("%s: NULL buffer", who); return AC_ERR_BAD_ARG; }
+    if (nx < 2 || ny < 2 || nz < 2 || (uint64_t)nx * ny * nz >= (1ull << 31)) { ac::set_error("%s: grid %u x %u x %u unsupported (2 <= n, fewer than 2^31 points)", who, nx, ny, nz); return AC_ERR_BAD_ARG; }
+    l = mc_layout(nx, ny, nz);
+    if (scratch_bytes < l.total) { ac::set_error("%s: scratch of %zu bytes needed, %zu given", who, l.total, scratch_bytes); return AC_ERR_BAD_ARG; }
+    return AC_OK;
+}
+
+}  // namespace
+
+AC_API size_t ac_marching_cubes_scratch(uint32_t nx, uint32_t ny, uint32_t nz)
+{
+    if (nx < 2 || ny < 2 || nz < 2 || (uint64_t)nx * ny * nz >= (1ull << 31)) return 0;
+    return mc_layout(nx, ny, nz).total;
+}
+
+AC_API int ac_marching_cubes_count(const float *volume, uint32_t nx, uint32_t ny, uint32_t nz, float iso, void *scratch, size_t scratch_bytes,
+                                   uint32_t *counts, ac_stream_t stream)
+{
+    McLayout l;
+    if (int rc = mc_check("marching_cubes_count", volume, nx, ny, nz, scratch, scratch_bytes, l)) return rc;
+    if (!counts) { ac::set_error("marching_cubes_count: NULL counts"); return AC_ERR_BAD_ARG; }
+    char *sc = static_cast<char *>(scratch);
+    const McDims d{ nx, ny, nz, nx * ny * nz };
+    {
+        const uint32_t nchunks = (d.npts + 1023u) >> 10;
+        uint32_t blocks = (nchunks + 3u) / 4u;
+        const uint32_t cap = 32u * ac::cu_count();
+        if (blocks > cap) blocks = cap;
+        hipLaunchKernelGGL(mc_flags_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, volume, d.npts, iso, reinterpret_cast<unsigned long long *>(sc + l.bits));
+    }
+    hipLaunchKernelGGL(mc_classify_kernel, dim3(l.nblk), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t *>(sc + l.bits), d,
+                       reinterpret_cast<uint32_t *>(sc + l.cnt), reinterpret_cast<uint32_t *>(sc + l.bsum));
+    hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t *>(sc + l.bsum), l.nblk,
+                       reinterpret_cast<uint32_t *>(sc + l.boff), counts);
+    return ac::check_launch("marching_cubes_count");
+}
+
+AC_API int ac_marching_cubes_emit(const float *volume, uint32_t nx, uint32_t ny, uint32_t nz, float iso, void *scratch, size_t scratch_bytes,
+                                  double den, const double span[3], const double lo[3], double *vertices, uint32_t n_vertices, int32_t *triangles,
+                                  uint32_t n_triangles, ac_stream_t stream)
+{
+    McLayout l;
+    if (int rc = mc_check("marching_cubes_emit", volume, nx, ny, nz, scratch, scratch_bytes, l)) return rc;
+    if ((n_vertices && !vertices) || (n_triangles && !triangles) || !span || !lo || !(den != 0.0)) { ac::set_error("marching_cubes_emit: NULL buffer or den == 0"); return AC_ERR_BAD_ARG; }
+    char *sc = static_cast<char *>(scratch);
+    const McDims d{ nx, ny, nz, nx * ny * nz };
+    McXform xf{ den, { span[0], span[1], span[2] }, { lo[0], lo[1], lo[2] } };
+    const uint32_t *cnt4 = reinterpret_cast<const uint32_t *>(sc + l.cnt), *bsum = reinterpret_cast<const uint32_t *>(sc + l.bsum);
+    const uint32_t *boff = reinterpret_cast<const uint32_t *>(sc + l.boff);
+    uint32_t *voff = reinterpret_cast<uint32_t *>(sc + l.voff);
+    if (n_vertices)
+        hipLaunchKernelGGL(mc_vertices_kernel, dim3(l.nblk), dim3(256), 0, (hipStream_t)stream, volume, d, iso, cnt4, bsum, boff, voff, xf, vertices, n_vertices);
+    if (n_triangles)
+        hipLaunchKernelGGL(mc_triangles_kernel, dim3(l.nblk), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t *>(sc + l.bits), d, cnt4, bsum, boff, voff,
+                           triangles, n_triangles);
+    return ac::check_launch("marching_cubes_emit");
+}
+

@@ -1,5 +1,5 @@
 // avatarcraft_amd/csrc/mesh_blend.hpp -- the blended SMPL transform at a point of a guide face and what is formed from it, shared by the mesh posing
-// (mesh_pose.hip) and the posed first-hit render (geometry.hip).  All fp64, every operation rounded once (-ffp-contract=off), in the order
+// (mesh_pose.hip) and the posed first-hit render (surface_rays.hip).  All fp64, every operation rounded once (-ffp-contract=off), in the order
 // include/avatarcraft_hip.h states (ac_mesh_pose: Blended transform, Forward application, Normal).  Anonymous namespace: each translation unit gets its own copy.
 #pragma once
 #include <stdint.h>

@@ -1234,7 +1234,7 @@ class NeRFNetwork(NeRFRenderer):
         """density grid for raymarching.march_rays_train / march_rays (only with cuda_ray=True, like the reference): the SDF on the 129^3
         grid -> a logistic density with inv_s = 512 (inv_s * sigmoid'(-|...|) written in two overflow-free branches), dilated by a 2^3 max
         pool, merged into the running grid with max(grid * decay, new); mean density and the step-counter bookkeeping.
-        On the GPU the grid update is ONE launch (ac_density_grid_update, csrc/geometry.hip; the grid is updated in place); the torch chain below
+        On the GPU the grid update is ONE launch (ac_density_grid_update, csrc/field_grid.hip; the grid is updated in place); the torch chain below
         is the formulation of the reference, kept for the CPU and as the cross-check of the tests (fused_density_grid = False)."""
         if not self.cuda_ray:
             return

@@ -1255,7 +1255,7 @@ def field_color(field, x, n, sdfout, dirs=None):
     return out
 
 
-# ---------------------------------------------------------------------------------------------------- geometry (csrc/geometry.hip)
+# ---------------------------------------------------------------------------------------------------- geometry (csrc/field_grid.hip, marching_cubes.hip, mesh_shade.hip, surface_rays.hip)
 def field_sdf_grid(field, axis_x, axis_y, axis_z, bound, negate=False, out=None):
     """ac_field_sdf_grid: forward_sdf(.)[0] on the grid axis_x x axis_y x axis_z (three 1-D float32 device tensors: the coordinates
     torch.linspace gives the reference's extract_fields, models/instant_nsr.py:728-745) -> [nx, ny, nz] float32 on the device; negate: -sdf"""

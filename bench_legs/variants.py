@@ -54,7 +54,7 @@ def time_viewdirs(dev, p, table, ro_t, rd_t, steps=8):
 def time_geometry(dev, p, table, reps=3):
     """SURVEY 8(f) rank 3 at the reference's own sizes: the mesh export -- extract_geometry(NSR_BOUND, 512) (stylize.py:267: 512^3 = 134 M forward_sdf
     queries + marching cubes) -- and the density-grid update of update_extra_state (129^3 queries -> density -> max pool -> merge -> mean), both on the
-    device (csrc/geometry.hip).  Per-launch times by HIP events on the launch stream; gather-request roofline like the headline's (1024 B per query)."""
+    device (csrc/field_grid.hip, csrc/marching_cubes.hip).  Per-launch times by HIP events on the launch stream; gather-request roofline like the headline's (1024 B per query)."""
     from avatarcraft_amd import nsr_ops
     from avatarcraft_amd.render_utils import NSR_BOUND
     net = make_net(p, table, dev, False, cuda_ray=True)

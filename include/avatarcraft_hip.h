@@ -815,7 +815,7 @@ int ac_mesh_pose(const float *points /*[V,3]*/, const float *normals /*optional 
                  float *positions /*[V,3]*/, float *normals_out /*optional [V,3]*/, float *residual /*optional [V]*/, uint8_t *status /*optional [V]*/,
                  uint8_t *mask /*optional [V]*/, ac_stream_t stream);
 
-/* ---- first-hit render of the POSED level set (csrc/geometry.hip; added entries and one new struct, no struct of an existing call changes: ABI stays 10)
+/* ---- first-hit render of the POSED level set (csrc/surface_rays.hip; added entries and one new struct, no struct of an existing call changes: ABI stays 10)
  * ac_render_rays_surface_warped: ac_render_rays_surface through the SMPL warp -- per ray the first point p of { p : sdf(W^-1(p)) = level, p inside the mask },
  * W^-1 the inverse warp of ac_warp_samples for the frame's mesh: the set ac_render_rays_warped draws (alpha * mask) and ac_mesh_pose moves a mesh onto.  It
  * stands in for nothing in the reference.  Inputs: those of ac_render_rays_surface, plus w_tol (1e-4) and an ac_warp_mesh of which verts, faces, T, V, F,

@@ -1,4 +1,4 @@
-"""-m gpu: csrc/geometry.hip through the C ABI -- the SDF on a grid (ac_field_sdf_grid), marching cubes on the device (ac_marching_cubes_*) and the
+"""-m gpu: csrc/field_grid.hip and csrc/marching_cubes.hip through the C ABI -- the SDF on a grid (ac_field_sdf_grid), marching cubes on the device (ac_marching_cubes_*) and the
 one-launch density-grid update (ac_density_grid_update) against the CPU oracle (bit for bit: same table, same order, same double arithmetic) and against
 the torch formulation of the reference's chain (models/instant_nsr.py:303-356, 706-764)."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""-m gpu: ac_mesh_vertex_attrs (csrc/geometry.hip) and the coloured export around it -- NeRFNetwork.extract_colored_mesh, nsr_ops.mesh_vertex_attrs.
+"""-m gpu: ac_mesh_vertex_attrs (csrc/mesh_shade.hip) and the coloured export around it -- NeRFNetwork.extract_colored_mesh, nsr_ops.mesh_vertex_attrs.
 The kernel projects marching-cubes vertices onto the level set by Newton steps along the finite-difference gradient and evaluates normal and colour there;
 every output is compared BIT FOR BIT with `restate`, the loop of include/avatarcraft_hip.h written in numpy fp32 around the CPU oracle's
 orc_field_samples.  Measured on the oracle, golden field, bound 1.6, eps 0.005: max |sdf| 4.7e-3 at the 48^3 marching-cubes vertices, 4.9e-5 after 3 steps."""

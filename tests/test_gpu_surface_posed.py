@@ -1,4 +1,4 @@
-"""-m gpu: ac_render_rays_surface_warped (csrc/geometry.hip), the first-hit render of the POSED level set, and what stands on it --
+"""-m gpu: ac_render_rays_surface_warped (csrc/surface_rays.hip), the first-hit render of the POSED level set, and what stands on it --
 nsr_ops.render_rays_surface_warped, NeRFNetwork.render_surface_posed, drivers.render_animation(surface=True).  Every output is compared BIT FOR BIT with
 `restate_posed` (tests/surface_posed_cases.py): the procedure of include/avatarcraft_hip.h in numpy around the CPU oracle's orc_warp_samples / orc_field_sdf /
 orc_field_samples.  What the procedure achieves on the shared case is recorded on the CPU tier (tests/test_surface_posed_host.py)."""

@@ -1,4 +1,4 @@
-"""-m gpu: ac_render_rays_surface (csrc/geometry.hip), the first-hit render of the level set, and what stands on it -- nsr_ops.render_rays_surface,
+"""-m gpu: ac_render_rays_surface (csrc/surface_rays.hip), the first-hit render of the level set, and what stands on it -- nsr_ops.render_rays_surface,
 NeRFNetwork.render_surface, drivers.render_canonical_360(surface=True).  Every output is compared BIT FOR BIT with `restate` (tests/surface_cases.py): the
 procedure of include/avatarcraft_hip.h in numpy fp32 around the CPU oracle's orc_field_sdf / orc_field_samples.  Measured on the oracle, golden field, bound 1.6,
 tol 1e-4, the 588 shared rays: status histogram [453, 0, 128, 1, 6, 0] at the defaults, 10 569 evaluations (18 per ray), max |sdf| over the hits 9.93e-5."""

@@ -1,4 +1,4 @@
-"""-m gpu: ac_mesh_bake_texture (csrc/geometry.hip) and the textured export around it -- nsr_ops.mesh_bake_texture, NeRFNetwork.extract_textured_mesh,
+"""-m gpu: ac_mesh_bake_texture (csrc/mesh_shade.hip) and the textured export around it -- nsr_ops.mesh_bake_texture, NeRFNetwork.extract_textured_mesh,
 drivers.export_mesh(".obj").  The kernel runs ac_mesh_vertex_attrs' per-point body over the texels of the closed-form atlas (avatarcraft_amd/geometry.py); every
 output is compared BIT FOR BIT with `bake_reference`: the atlas' weights and point in numpy fp32, then tests/test_gpu_mesh_attrs.py's `restate` around the CPU
 oracle's orc_field_samples.  Measured on the oracle (golden field, bound 1.6, eps 0.005, the 24^3 mesh of 364 triangles projected by 3 steps, S = 128, c = 8,

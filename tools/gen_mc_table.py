@@ -1,4 +1,4 @@
-"""Generate the 256-case marching-cubes table of csrc/geometry.hip (and its twin for the CPU oracle) from the DEFINITION of the algorithm
+"""Generate the 256-case marching-cubes table of csrc/marching_cubes.hip (and its twin for the CPU oracle) from the DEFINITION of the algorithm
 (Lorensen & Cline 1987) instead of typing a published table in: for every sign configuration of a cube's 8 corners
 
   1. every cube edge whose two corners differ carries one surface vertex;
