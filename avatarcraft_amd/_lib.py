@@ -178,6 +178,10 @@ _SIGS = {
     "ac_marching_cubes_scratch": ([u32, u32, u32], C.c_size_t),
     "ac_marching_cubes_count": ([vp, u32, u32, u32, f32, vp, C.c_size_t, vp, vp], C.c_int),
     "ac_marching_cubes_emit": ([vp, u32, u32, u32, f32, vp, C.c_size_t, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, u32, vp, u32, vp], C.c_int),
+    "ac_marching_cubes_slab_scratch": ([u32, u32, u32], C.c_size_t),
+    "ac_marching_cubes_slab_count": ([vp, u32, u32, u32, f32, u32, u32, vp, C.c_size_t, vp, vp], C.c_int),
+    "ac_marching_cubes_slab_emit": ([vp, u32, u32, u32, f32, u32, u32, vp, C.c_size_t, u32, u32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                     vp, u32, vp, u32, vp], C.c_int),
     "ac_mesh_vertex_attrs": ([C.POINTER(ac_field), vp, u32, vp, C.POINTER(ac_mesh_attr_opts), vp, vp, vp, vp, vp, vp], C.c_int),
     "ac_mesh_bake_texture": ([C.POINTER(ac_field), vp, u32, vp, u32, C.POINTER(ac_atlas_opts), C.POINTER(ac_mesh_attr_opts), vp, vp, vp, vp, vp, vp], C.c_int),
     "ac_render_rays_surface": ([C.POINTER(ac_field), C.POINTER(ac_surface_opts), vp, vp, u32, vp, C.POINTER(ac_surface_out), vp], C.c_int),

@@ -137,12 +137,21 @@ __global__ __launch_bounds__(1024) void mc_scan_kernel(const uint32_t *__restric
 
 struct McXform { double den, span[3], lo[3]; };   // world = index / den * span + lo, the reference's three operations in its order (instant_nsr.py:760-762)
 
-__global__ __launch_bounds__(256) void mc_vertices_kernel(const float *__restrict__ vol, const McDims d, float iso, const uint32_t *__restrict__ cnt4,
-                                                          const uint32_t *__restrict__ bsum, const uint32_t *__restrict__ boff, uint32_t *__restrict__ voff,
-                                                          const McXform xf, double *__restrict__ verts, uint32_t n_verts)
+// A window of a larger grid (ac_marching_cubes_slab_*): layers [x0, x0 + d.nx) along x.  The scan of the count pass runs over the whole window, so a vertex
+// has a window-local index; the count pass leaves in info[MC_INFO_SHIFT] the local index of the first vertex the window emits.  Global index = local -
+// shift + vertex_base (the carried layer 0 gets the indices just below vertex_base: the ones the previous window wrote them under); position in this
+// window's piece = local - shift.  Emitted: vertices of layers [vlo, vhi), triangles of cell layers [0, tlayers).
+struct McSlab { uint32_t x0, vertex_base, vlo, vhi, tlayers; const uint32_t *info; };
+enum { MC_INFO_TOTALS = 0 /* [2]: mc_scan_kernel's totals over the window */, MC_INFO_SHIFT = 2, MC_INFO_WORDS = 64 };
+
+template <bool SLAB>
+__device__ __forceinline__ void mc_vertices_body(const float *__restrict__ vol, const McDims d, float iso, const uint32_t *__restrict__ cnt4,
+                                                 const uint32_t *__restrict__ bsum, const uint32_t *__restrict__ boff, uint32_t *__restrict__ voff,
+                                                 const McXform &xf, double *__restrict__ verts, uint32_t n_verts, const McSlab &s)
 {
     __shared__ uint32_t sh[8];
     if ((bsum[blockIdx.x] & 0xffffu) == 0u) return;
+    const uint32_t shift = SLAB ? s.info[MC_INFO_SHIFT] : 0u;
     const uint32_t p0 = blockIdx.x * MC_PTS + threadIdx.x * 4u;
     const uint32_t packed = p0 < d.npts ? cnt4[p0 >> 2] : 0u;
     uint32_t nv = 0;
@@ -156,32 +165,49 @@ __global__ __launch_bounds__(256) void mc_vertices_kernel(const float *__restric
         const uint32_t m = (packed >> (8 * r)) & 7u;
         if (!m) continue;
         const uint32_t p = p0 + r;
-        voff[p] = vid;
+        voff[p] = SLAB ? vid - shift + s.vertex_base : vid;
         const uint32_t k = p % d.nz, t = p / d.nz, j = t % d.ny, i = t / d.ny;
+        if (SLAB && (i < s.vlo || i >= s.vhi)) { vid += (uint32_t)__builtin_popcount(m); continue; }      // a carried or an incomplete layer: indexed, not written
         const double va = (double)vol[p];
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             if (!((m >> a) & 1u)) continue;
             const double vb = (double)vol[p + stride[a]];
             const double tt = ((double)iso - va) / (vb - va);            // the linear zero crossing between the two grid points, 0 <= tt <= 1
-            double c[3] = { (double)i, (double)j, (double)k };
+            double c[3] = { (double)(SLAB ? s.x0 + i : i), (double)j, (double)k };
             c[a] += tt;
-            if (vid < n_verts) {
-                verts[3 * (size_t)vid] = c[0] / xf.den * xf.span[0] + xf.lo[0];
-                verts[3 * (size_t)vid + 1] = c[1] / xf.den * xf.span[1] + xf.lo[1];
-                verts[3 * (size_t)vid + 2] = c[2] / xf.den * xf.span[2] + xf.lo[2];
+            const uint32_t o = vid - shift;
+            if (o < n_verts) {
+                verts[3 * (size_t)o] = c[0] / xf.den * xf.span[0] + xf.lo[0];
+                verts[3 * (size_t)o + 1] = c[1] / xf.den * xf.span[1] + xf.lo[1];
+                verts[3 * (size_t)o + 2] = c[2] / xf.den * xf.span[2] + xf.lo[2];
             }
             ++vid;
         }
     }
 }
+__global__ __launch_bounds__(256) void mc_vertices_kernel(const float *__restrict__ vol, const McDims d, float iso, const uint32_t *__restrict__ cnt4,
+                                                          const uint32_t *__restrict__ bsum, const uint32_t *__restrict__ boff, uint32_t *__restrict__ voff,
+                                                          const McXform xf, double *__restrict__ verts, uint32_t n_verts)
+{
+    mc_vertices_body<false>(vol, d, iso, cnt4, bsum, boff, voff, xf, verts, n_verts, McSlab{});
+}
+__global__ __launch_bounds__(256) void mc_slab_vertices_kernel(const float *__restrict__ vol, const McDims d, float iso, const uint32_t *__restrict__ cnt4,
+                                                               const uint32_t *__restrict__ bsum, const uint32_t *__restrict__ boff, uint32_t *__restrict__ voff,
+                                                               const McXform xf, double *__restrict__ verts, uint32_t n_verts, const McSlab s)
+{
+    mc_vertices_body<true>(vol, d, iso, cnt4, bsum, boff, voff, xf, verts, n_verts, s);
+}
 
-__global__ __launch_bounds__(256) void mc_triangles_kernel(const uint32_t *__restrict__ bits, const McDims d, const uint32_t *__restrict__ cnt4,
-                                                           const uint32_t *__restrict__ bsum, const uint32_t *__restrict__ boff, const uint32_t *__restrict__ voff,
-                                                           int32_t *__restrict__ tris, uint32_t n_tris)
+// (tlayers: triangles of cell layers [0, tlayers) only.  They come first in the scan's order, so their indices are the piece's; voff holds global indices.)
+template <bool SLAB>
+__device__ __forceinline__ void mc_triangles_body(const uint32_t *__restrict__ bits, const McDims d, const uint32_t *__restrict__ cnt4,
+                                                  const uint32_t *__restrict__ bsum, const uint32_t *__restrict__ boff, const uint32_t *__restrict__ voff,
+                                                  int32_t *__restrict__ tris, uint32_t n_tris, uint32_t tlayers)
 {
     __shared__ uint32_t sh[8];
     if ((bsum[blockIdx.x] >> 16) == 0u) return;
+    if (SLAB && (uint64_t)blockIdx.x * MC_PTS >= (uint64_t)tlayers * d.ny * d.nz) return;
     const uint32_t p0 = blockIdx.x * MC_PTS + threadIdx.x * 4u;
     const uint32_t packed = p0 < d.npts ? cnt4[p0 >> 2] : 0u;
     uint32_t nt = 0;
@@ -196,6 +222,7 @@ __global__ __launch_bounds__(256) void mc_triangles_kernel(const uint32_t *__res
         const uint32_t n = (packed >> (8 * r + 3)) & 7u;
         if (!n) continue;
         const uint32_t p = p0 + r;
+        if (SLAB && p / sx >= tlayers) continue;     // (the last ones of the order: nothing after them needs tid)
         uint32_t cs;
         (void)mc_classify(bits, d, p, &cs);
         for (uint32_t t = 0; t < n; ++t) {
@@ -211,6 +238,52 @@ __global__ __launch_bounds__(256) void mc_triangles_kernel(const uint32_t *__res
             if (tid < n_tris) { tris[3 * (size_t)tid] = id[0]; tris[3 * (size_t)tid + 1] = id[1]; tris[3 * (size_t)tid + 2] = id[2]; }
             ++tid;
         }
+    }
+}
+__global__ __launch_bounds__(256) void mc_triangles_kernel(const uint32_t *__restrict__ bits, const McDims d, const uint32_t *__restrict__ cnt4,
+                                                           const uint32_t *__restrict__ bsum, const uint32_t *__restrict__ boff, const uint32_t *__restrict__ voff,
+                                                           int32_t *__restrict__ tris, uint32_t n_tris)
+{
+    mc_triangles_body<false>(bits, d, cnt4, bsum, boff, voff, tris, n_tris, d.nx);
+}
+__global__ __launch_bounds__(256) void mc_slab_triangles_kernel(const uint32_t *__restrict__ bits, const McDims d, const uint32_t *__restrict__ cnt4,
+                                                                const uint32_t *__restrict__ bsum, const uint32_t *__restrict__ boff, const uint32_t *__restrict__ voff,
+                                                                int32_t *__restrict__ tris, uint32_t n_tris, uint32_t tlayers)
+{
+    mc_triangles_body<true>(bits, d, cnt4, bsum, boff, voff, tris, n_tris, tlayers);
+}
+
+// What a window emits, from the count bytes and the scan of the whole window: the scan's exclusive prefix (vertices low, triangles high word of a pair) at the
+// first point of four layers.  One workgroup; a prefix = the offset of the point's workgroup + the count bytes before the point in it.
+__device__ __forceinline__ void mc_prefix_at(const uint32_t *__restrict__ cnt4, const uint32_t *__restrict__ boff, const McDims d, uint32_t layer,
+                                             const uint32_t *__restrict__ totals, uint32_t *sh, uint32_t &pv, uint32_t &pt)
+{
+    if (layer >= d.nx) { pv = totals[0]; pt = totals[1]; return; }                     // (uniform over the workgroup)
+    const uint32_t p = layer * d.ny * d.nz, blk = p / MC_PTS, q0 = blk * MC_PTS + threadIdx.x * 4u;
+    const uint32_t packed = q0 < p ? cnt4[q0 >> 2] : 0u;                                // (q0 < p < npts: a dword mc_classify_kernel wrote)
+    uint32_t nv = 0, nt = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < 4; ++r) {
+        const uint32_t c = q0 + r < p ? (packed >> (8 * r)) & 0xffu : 0u;
+        nv += (uint32_t)__builtin_popcount(c & 7u); nt += c >> 3;
+    }
+    uint32_t tot;
+    (void)block_exscan_256(nv | (nt << 16), sh, tot);
+    pv = boff[2 * blk] + (tot & 0xffffu); pt = boff[2 * blk + 1] + (tot >> 16);
+}
+__global__ __launch_bounds__(256) void mc_slab_counts_kernel(const uint32_t *__restrict__ cnt4, const uint32_t *__restrict__ boff, const McDims d, uint32_t vlo,
+                                                             uint32_t vhi, uint32_t tlayers, uint32_t *__restrict__ info, uint32_t *__restrict__ counts)
+{
+    __shared__ uint32_t sh[8];
+    uint32_t v_lo, v_one, v_top, v_hi, t_hi, unused;
+    mc_prefix_at(cnt4, boff, d, vlo, info + MC_INFO_TOTALS, sh, v_lo, unused);
+    mc_prefix_at(cnt4, boff, d, 1u, info + MC_INFO_TOTALS, sh, v_one, unused);
+    mc_prefix_at(cnt4, boff, d, vhi - 1u, info + MC_INFO_TOTALS, sh, v_top, unused);
+    mc_prefix_at(cnt4, boff, d, vhi, info + MC_INFO_TOTALS, sh, v_hi, unused);
+    mc_prefix_at(cnt4, boff, d, tlayers, info + MC_INFO_TOTALS, sh, unused, t_hi);
+    if (threadIdx.x == 0) {
+        info[MC_INFO_SHIFT] = v_lo;
+        counts[0] = v_hi - v_lo; counts[1] = t_hi; counts[2] = v_one; counts[3] = v_hi - v_top;
     }
 }
 
@@ -240,7 +313,75 @@ int mc_check(const char *who, const float *vol, uint32_t nx, uint32_t ny, uint32
     return AC_OK;
 }
 
+// a window's scratch: the dense layout of an n x ny x nz grid, then the info words
+bool mc_slab_dims_ok(uint32_t n, uint32_t ny, uint32_t nz) { return n >= 2 && ny >= 2 && nz >= 2 && (uint64_t)n * ny * nz < (1ull << 31); }
+struct McSlabPlan { McLayout l; McDims d; uint32_t vlo, vhi, tlayers; uint32_t *info; };
+int mc_slab_check(const char *who, const float *window, uint32_t n, uint32_t ny, uint32_t nz, uint32_t first, uint32_t last, void *scratch, size_t scratch_bytes,
+                  McSlabPlan &s)
+{
+    if (!window || !scratch) { ac::set_error("%s: NULL buffer", who); return AC_ERR_BAD_ARG; }
+    if (!mc_slab_dims_ok(n, ny, nz) || (n == 2 && !(first && last))) {
+        ac::set_error("%s: window %u x %u x %u unsupported (3 <= n, or n = 2 for a window both first and last; 2 <= ny, nz; fewer than 2^31 points)", who, n, ny, nz);
+        return AC_ERR_BAD_ARG;
+    }
+    s.l = mc_layout(n, ny, nz);
+    if (scratch_bytes < s.l.total + MC_INFO_WORDS * 4) { ac::set_error("%s: scratch of %zu bytes needed, %zu given", who, s.l.total + MC_INFO_WORDS * 4, scratch_bytes); return AC_ERR_BAD_ARG; }
+    s.d = McDims{ n, ny, nz, n * ny * nz };
+    s.vlo = first ? 0u : 1u; s.vhi = last ? n : n - 1u; s.tlayers = last ? n : n - 2u;
+    s.info = reinterpret_cast<uint32_t *>(static_cast<char *>(scratch) + s.l.total);
+    return AC_OK;
+}
+
 }  // namespace
+
+AC_API size_t ac_marching_cubes_slab_scratch(uint32_t n, uint32_t ny, uint32_t nz)
+{
+    if (n < 3 || !mc_slab_dims_ok(n, ny, nz)) return 0;     // (n = 2, the whole of a two-layer grid, runs in the scratch of any larger window)
+    return mc_layout(n, ny, nz).total + MC_INFO_WORDS * 4;
+}
+
+AC_API int ac_marching_cubes_slab_count(const float *window, uint32_t n, uint32_t ny, uint32_t nz, float iso, uint32_t first, uint32_t last, void *scratch,
+                                        size_t scratch_bytes, uint32_t *counts, ac_stream_t stream)
+{
+    McSlabPlan s;
+    if (int rc = mc_slab_check("marching_cubes_slab_count", window, n, ny, nz, first, last, scratch, scratch_bytes, s)) return rc;
+    if (!counts) { ac::set_error("marching_cubes_slab_count: NULL counts"); return AC_ERR_BAD_ARG; }
+    char *sc = static_cast<char *>(scratch);
+    uint32_t *cnt4 = reinterpret_cast<uint32_t *>(sc + s.l.cnt), *boff = reinterpret_cast<uint32_t *>(sc + s.l.boff), *bsum = reinterpret_cast<uint32_t *>(sc + s.l.bsum);
+    {
+        const uint32_t nchunks = (s.d.npts + 1023u) >> 10;
+        uint32_t blocks = (nchunks + 3u) / 4u;
+        const uint32_t cap = 32u * ac::cu_count();
+        if (blocks > cap) blocks = cap;
+        hipLaunchKernelGGL(mc_flags_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, window, s.d.npts, iso, reinterpret_cast<unsigned long long *>(sc + s.l.bits));
+    }
+    hipLaunchKernelGGL(mc_classify_kernel, dim3(s.l.nblk), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t *>(sc + s.l.bits), s.d, cnt4, bsum);
+    hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, bsum, s.l.nblk, boff, s.info + MC_INFO_TOTALS);
+    hipLaunchKernelGGL(mc_slab_counts_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, cnt4, boff, s.d, s.vlo, s.vhi, s.tlayers, s.info, counts);
+    return ac::check_launch("marching_cubes_slab_count");
+}
+
+AC_API int ac_marching_cubes_slab_emit(const float *window, uint32_t n, uint32_t ny, uint32_t nz, float iso, uint32_t first, uint32_t last, void *scratch,
+                                       size_t scratch_bytes, uint32_t x0, uint32_t vertex_base, double den, const double span[3], const double lo[3],
+                                       double *vertices, uint32_t n_vertices, int32_t *triangles, uint32_t n_triangles, ac_stream_t stream)
+{
+    McSlabPlan s;
+    if (int rc = mc_slab_check("marching_cubes_slab_emit", window, n, ny, nz, first, last, scratch, scratch_bytes, s)) return rc;
+    if ((n_vertices && !vertices) || (n_triangles && !triangles) || !span || !lo || !(den != 0.0)) { ac::set_error("marching_cubes_slab_emit: NULL buffer or den == 0"); return AC_ERR_BAD_ARG; }
+    if ((uint64_t)x0 + n > 0xffffffffull || (first && x0 != 0u)) { ac::set_error("marching_cubes_slab_emit: x0 %u + n %u overflows 32 bits, or a first window with x0 != 0", x0, n); return AC_ERR_BAD_ARG; }
+    char *sc = static_cast<char *>(scratch);
+    McXform xf{ den, { span[0], span[1], span[2] }, { lo[0], lo[1], lo[2] } };
+    const uint32_t *cnt4 = reinterpret_cast<const uint32_t *>(sc + s.l.cnt), *bsum = reinterpret_cast<const uint32_t *>(sc + s.l.bsum);
+    const uint32_t *boff = reinterpret_cast<const uint32_t *>(sc + s.l.boff);
+    uint32_t *voff = reinterpret_cast<uint32_t *>(sc + s.l.voff);
+    const McSlab sl{ x0, vertex_base, s.vlo, s.vhi, s.tlayers, s.info };
+    if (n_vertices || n_triangles)                // (triangles of cell layer 0 may use carried vertices only: their indices are formed by this pass all the same)
+        hipLaunchKernelGGL(mc_slab_vertices_kernel, dim3(s.l.nblk), dim3(256), 0, (hipStream_t)stream, window, s.d, iso, cnt4, bsum, boff, voff, xf, vertices, n_vertices, sl);
+    if (n_triangles)
+        hipLaunchKernelGGL(mc_slab_triangles_kernel, dim3(s.l.nblk), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t *>(sc + s.l.bits), s.d, cnt4, bsum, boff,
+                           voff, triangles, n_triangles, s.tlayers);
+    return ac::check_launch("marching_cubes_slab_emit");
+}
 
 AC_API size_t ac_marching_cubes_scratch(uint32_t nx, uint32_t ny, uint32_t nz)
 {

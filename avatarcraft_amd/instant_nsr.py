@@ -1009,9 +1009,12 @@ class NeRFNetwork(NeRFRenderer):
             c[key] = torch.linspace(-bound, bound, resolution).to(dev)
         return c[key]
 
-    def extract_fields_device(self, bound: float, resolution: int, negate: bool = False):
+    def extract_fields_device(self, bound: float, resolution: int, negate: bool = False, slab_layers=None):
         """the SDF (negate: -SDF) on the resolution^3 grid over [-bound, bound]^3 as a device tensor [res, res, res]: ONE launch (ac_field_sdf_grid) -- the
-        kernel forms the grid points from the axis table; no meshgrid / cat tensors, no 256^3 blocks, no host round trip"""
+        kernel forms the grid points from the axis table; no meshgrid / cat tensors, no 256^3 blocks, no host round trip.
+        slab_layers is refused: a streamed volume (extract_geometry(slab_layers=...)) is never whole."""
+        if slab_layers is not None:
+            raise RuntimeError("extract_fields_device: slab_layers is refused here -- a streamed volume is never whole; extract_geometry(slab_layers=...) meshes it slab by slab")
         if not (self.encoder.embeddings.is_cuda and self._sdf_supported()):
             raise RuntimeError("extract_fields_device: needs the default SDF side of NeRFNetwork on the GPU")
         ax = self._grid_axis(bound, resolution)
@@ -1037,23 +1040,41 @@ class NeRFNetwork(NeRFRenderer):
                         u[xi * N: xi * N + len(x), yi * N: yi * N + len(y), zi * N: zi * N + len(z)] = self.density(pts, bound).reshape(len(x), len(y), len(z))
         return u.cpu().numpy()
 
-    def extract_geometry(self, bound: float, resolution: int, threshold: int = 0.0, device=None, mesher=None, return_torch=False):
+    def extract_geometry(self, bound: float, resolution: int, threshold: int = 0.0, device=None, mesher=None, return_torch=False, slab_layers=None):
         """iso-surface of the SDF (reference :706-764; its one call is extract_geometry(NSR_BOUND, 512), stylize.py:267): vertices [V,3] float64 in world
         units, triangles [F,3].  The reference runs PyMCubes' marching_cubes on u = -sdf (third party, not in this image).
         mesher: "native" (default on the GPU) = ac_field_sdf_grid + ac_marching_cubes on the device: the volume never leaves it, one shared vertex per
                 sign-changing grid edge at the linear zero crossing, the 256-case table of the definition, triangles oriented out of the body; only the
                 finished mesh is copied to the host (return_torch=True: not even that -- device tensors);
                 "mcubes" = the reference's own call when PyMCubes is installed; "tetra" = the marching-tetrahedra mesher of round 3 (geometry.py:
-                the same vertex set, a different triangulation -- kept as the cross-check of the tests)."""
+                the same vertex set, a different triangulation -- kept as the cross-check of the tests).
+        slab_layers: None = the whole volume at once (9 bytes per grid point, fewer than 2^31 points: resolution <= 1290); an integer >= 2 = the native mesher
+                STREAMED (nsr_ops.marching_cubes_streamed): the grid is evaluated slab_layers x-layers at a time into one window of slab_layers + 2 layers and
+                meshed window by window -- the same mesh bit for bit, in the memory of one window, at any resolution whose window stays below 2^31 points
+                (extract_geometry(1.6, 2048, slab_layers=64): the hash grid's own finest resolution, 0.92 s).  Multiples of 16 keep the x-tiles of the grid kernel
+                full; other values are legal.  Needs mesher "native" (or None on the GPU)."""
         native_ok = self.encoder.embeddings.is_cuda and self._sdf_supported()
+        if slab_layers is not None:
+            slab_layers = nsr_ops.check_slab_layers(slab_layers, "extract_geometry")
+            if mesher not in (None, "native") or not native_ok:
+                raise RuntimeError("extract_geometry(slab_layers=...) streams the native mesher: it needs mesher='native' and the default SDF side of NeRFNetwork on the GPU")
         if mesher is None:
             mesher = "native" if native_ok else "tetra"
         if mesher == "native":
             if not native_ok:
                 raise RuntimeError("extract_geometry(mesher='native') needs the default SDF side of NeRFNetwork on the GPU")
-            u = self.extract_fields_device(bound, resolution, negate=True)
             bmin, bmax = np.float32(-bound), np.float32(bound)                       # (the reference's bounds are float32 tensors, :712)
-            v, t = nsr_ops.marching_cubes(u, float(threshold), den=resolution - 1.0, span=[float(bmax - bmin)] * 3, lo=[float(bmin)] * 3)
+            xf = dict(den=resolution - 1.0, span=[float(bmax - bmin)] * 3, lo=[float(bmin)] * 3)
+            if slab_layers is None:
+                u = self.extract_fields_device(bound, resolution, negate=True)
+                v, t = nsr_ops.marching_cubes(u, float(threshold), **xf)
+            else:
+                ax = self._grid_axis(bound, resolution)
+                with torch.no_grad():
+                    f = self._field() if self._fused_supported() else self._field_sdf_only()
+                    fill = lambda x0, out: nsr_ops.field_sdf_grid(f, ax[x0:x0 + out.shape[0]], ax, ax, bound, negate=True, out=out)
+                    v, t = nsr_ops.marching_cubes_streamed(fill, resolution, resolution, resolution, slab_layers=slab_layers, iso=float(threshold),
+                                                           device=ax.device, **xf)
             return (v, t) if return_torch else (v.cpu().numpy(), t.cpu().numpy())
         u = -1.0 * self.extract_fields(bound, resolution)
         if mesher == "mcubes":
@@ -1069,20 +1090,23 @@ class NeRFNetwork(NeRFRenderer):
         return vertices, triangles
 
     def extract_colored_mesh(self, bound: float, resolution: int, threshold: float = 0.0, refine_steps: int = 3, tol: float = 1e-5, colors: bool = True,
-                             return_torch=False):
+                             return_torch=False, slab_layers=None):
         """the mesh of extract_geometry(mesher="native") with what a viewer wants on it (the reference's save_mesh, stylize.py:263-269, writes bare geometry):
         every vertex projected from the grid edge's linear zero crossing onto the level set sdf = -threshold (at most refine_steps Newton steps along the
         finite-difference gradient, never further than one grid cell), the field's normal and the colour network there -- one launch over the marching-cubes
         buffer (ac_mesh_vertex_attrs).  -> dict(vertices [V,3] float64, triangles [F,3] int32 (extract_geometry's), normals [V,3] float32, colors [V,3]
         float32 in [0, 1] (colors=True), sdf [V] at the final positions, status [V] uint8: 0 converged to tol, 1 all steps taken (sdf tells how close), 2 degenerate gradient,
         3 stopped by the one-cell limit); numpy arrays, or device tensors with return_torch=True.  With view directions the colour is the one seen along -normal.
-        colors=True needs the default colour side (RuntimeError otherwise); colors=False works wherever extract_geometry(mesher="native") does."""
+        colors=True needs the default colour side (RuntimeError otherwise); colors=False works wherever extract_geometry(mesher="native") does.
+        slab_layers: extract_geometry's (None: the whole volume at once; an integer: streamed, the same mesh in the memory of one window)."""
+        if slab_layers is not None:
+            slab_layers = nsr_ops.check_slab_layers(slab_layers, "extract_colored_mesh")
         if not (self.encoder.embeddings.is_cuda and self._sdf_supported()):
             raise RuntimeError("extract_colored_mesh needs the default SDF side of NeRFNetwork on the GPU")
         if colors and not self._fused_supported(ignore_curvature=True):
             raise RuntimeError("extract_colored_mesh(colors=True): the colour side of this model is not the default one (colour net 21-64-64-3, or 37-64-64-3 "
                                "with the degree-4 view-direction encoder); colors=False exports positions and normals")
-        v, t = self.extract_geometry(bound, resolution, threshold=threshold, mesher="native", return_torch=True)
+        v, t = self.extract_geometry(bound, resolution, threshold=threshold, mesher="native", return_torch=True, slab_layers=slab_layers)
         with torch.no_grad():
             f = self._field() if self._fused_supported(ignore_curvature=True) else self._field_sdf_only()
             a = nsr_ops.mesh_vertex_attrs(f, v, bound, nsr_ops.FD_STEP, refine_steps=refine_steps, tol=tol, max_move=2.0 * bound / (resolution - 1.0),
@@ -1165,15 +1189,17 @@ class NeRFNetwork(NeRFRenderer):
                 "face_id": o["face_id"].reshape(B, N)}
 
     def extract_textured_mesh(self, bound: float, resolution: int, texture_size: int = 2048, cell=None, threshold: float = 0.0, refine_steps: int = 3,
-                              tol: float = 1e-5, return_torch=False):
+                              tol: float = 1e-5, return_torch=False, slab_layers=None):
         """extract_colored_mesh's mesh with the colour network baked into a texture instead of sampled at the vertices, so that colour detail no longer depends on
         the vertex density: every triangle gets half a cell of a closed-form texture_size^2 atlas (geometry.atlas_layout; cell=None: the largest that fits), every
         owned texel's point on its triangle is projected onto the level set like a vertex (never further than one grid cell) and shaded there, one launch
         (ac_mesh_bake_texture).  -> the dict of extract_colored_mesh plus uv [T,3,2] float64 (three corners per triangle, OBJ convention), texture [S,S,3] uint8
         (q = floor(clamp(x, 0, 1) 255 + 0.5), row 0 on top), owner [S,S] int32 (-1: nobody, texture 0), texel_sdf [S,S], texel_status [S,S] uint8.
-        The atlas guarantees bilinear lookups only (no mip chain).  Same model requirements as extract_colored_mesh(colors=True)."""
+        The atlas guarantees bilinear lookups only (no mip chain).  Same model requirements as extract_colored_mesh(colors=True).
+        slab_layers: extract_geometry's; an atlas too small for the triangle count of a finer mesh raises as ever."""
         from .geometry import atlas_layout
-        m = self.extract_colored_mesh(bound, resolution, threshold=threshold, refine_steps=refine_steps, tol=tol, colors=True, return_torch=True)
+        m = self.extract_colored_mesh(bound, resolution, threshold=threshold, refine_steps=refine_steps, tol=tol, colors=True, return_torch=True,
+                                      slab_layers=slab_layers)
         T = m["triangles"].shape[0]
         try:
             lay = atlas_layout(T, texture_size, cell)

@@ -1296,6 +1296,98 @@ def marching_cubes(volume, iso=0.0, den=1.0, span=(1.0, 1.0, 1.0), lo=(0.0, 0.0,
     return verts, tris
 
 
+def check_slab_layers(slab_layers, who):
+    """slab_layers of the streamed mesh export as an int >= 2 (RuntimeError naming it otherwise); no device work"""
+    if isinstance(slab_layers, bool) or not isinstance(slab_layers, (int, np.integer)) or slab_layers < 2:
+        raise RuntimeError(f"{who}: slab_layers {slab_layers!r} must be an integer >= 2")
+    return int(slab_layers)
+
+
+def slab_windows(nx, slab_layers):
+    """the windows in which marching_cubes_streamed walks nx grid layers: [(x0, n, first, last, new_lo, new_n)], window = layers [x0, x0 + n) of the grid, of which
+    [new_lo, new_lo + new_n) (window-relative) are new and the ones before them carried from the previous window.  The first window has min(slab_layers, nx)
+    layers, all new; every later one carries 2 and adds up to slab_layers: x0' = x0 + n - 2, no window longer than slab_layers + 2.  A window emits the vertices
+    of its layers 1 .. n-2 (and 0 if first, n-1 if last) and the triangles of its cell layers 0 .. n-3 (and n-2 if last): a partition of the grid.  Pure Python."""
+    slab_layers = check_slab_layers(slab_layers, "slab_windows")
+    if isinstance(nx, bool) or not isinstance(nx, (int, np.integer)) or nx < 2:
+        raise RuntimeError(f"slab_windows: nx {nx!r} must be an integer >= 2")
+    end = min(slab_layers, int(nx))
+    wins = [(0, end, True, end == nx, 0, end)]
+    while end < nx:
+        new = min(slab_layers, nx - end)
+        wins.append((end - 2, new + 2, False, end + new == nx, 2, new))
+        end += new
+    return wins
+
+
+def marching_cubes_streamed(fill, nx, ny, nz, slab_layers=64, iso=0.0, den=1.0, span=(1.0, 1.0, 1.0), lo=(0.0, 0.0, 0.0), device="cuda"):
+    """marching_cubes of an [nx, ny, nz] volume that is never whole (ac_marching_cubes_slab_count / _emit): the volume is produced slab by slab along x into ONE
+    window buffer of slab_layers + 2 layers, each window is meshed with the shared-edge vertex indices carried across its border, and the pieces are joined --
+    bit for bit and in order the mesh marching_cubes gives for the whole volume, in the memory of one window (9 bytes per point of the window instead of the
+    grid), and for grids of 2^31 points and more (only a window has to stay below that).
+    fill(x0, out) writes grid layers [x0, x0 + out.shape[0]) into out, a contiguous float32 [m, ny, nz] view of the window buffer on `device`; every layer is
+    asked for exactly once, slab_layers at a time (the last call: what is left).  Per window: two carried layers copied to the front, fill, count, one 16-byte
+    read-back, emit into the window's own piece.  slab_layers: any integer >= 2 (slab_windows); the default is the fastest of 16 / 32 / 64 / 128 at 512^3
+    (profiles/mesh_streamed.txt: 15.20 ms beside the dense route's 15.65), and multiples of 16 keep the x-tiles of field_sdf_grid full.
+    -> (vertices [V,3] float64 = index / den * span + lo, triangles [F,3] int32), both on the device.  Options are checked before any device work."""
+    slab_layers = check_slab_layers(slab_layers, "marching_cubes_streamed")
+    if not callable(fill):
+        raise RuntimeError("marching_cubes_streamed: fill must be callable: fill(x0, out)")
+    for name, v in (("nx", nx), ("ny", ny), ("nz", nz)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 2 <= v < 2 ** 32:
+            raise RuntimeError(f"marching_cubes_streamed: {name} {v!r} must be an integer, 2 <= {name} < 2^32")
+    nx, ny, nz = int(nx), int(ny), int(nz)
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"marching_cubes_streamed: device {device!r} is not a GPU (there is no CPU path)")
+    try:
+        iso, den, span, lo = float(iso), float(den), [float(v) for v in span], [float(v) for v in lo]
+    except (TypeError, ValueError) as e:
+        raise RuntimeError(f"marching_cubes_streamed: iso, den, span and lo must be numbers ({e})") from e
+    if len(span) != 3 or len(lo) != 3 or not den != 0.0:
+        raise RuntimeError("marching_cubes_streamed: span and lo take 3 numbers each, den != 0")
+    wins = slab_windows(nx, slab_layers)
+    layers = max(3, max(w[1] for w in wins))
+    if layers * ny * nz >= 2 ** 31:
+        raise RuntimeError(f"marching_cubes_streamed: a window of {layers} x {ny} x {nz} points reaches 2^31: lower slab_layers ({slab_layers})")
+    need = int(L.lib().ac_marching_cubes_slab_scratch(layers, ny, nz))
+    buf = torch.empty((layers, ny, nz), dtype=_F32, device=dev)
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    counts = torch.zeros(4, dtype=torch.int32, device=dev)
+    span_c, lo_c = (C.c_double * 3)(*span), (C.c_double * 3)(*lo)
+    st = L.current_stream(dev)
+    vparts, tparts, vbase, prev_n, top = [], [], 0, 0, None
+    for x0, n, first, last, new_lo, new_n in wins:
+        if new_lo:
+            tail = buf[prev_n - 2:prev_n]
+            buf[:2].copy_(tail.clone() if prev_n < 4 else tail)                          # (source and target overlap in a window of 3 layers)
+        fill(x0 + new_lo, buf[new_lo:new_lo + new_n])
+        prev_n = n
+        if n == 2 and not last:
+            continue                  # (slab_layers = 2: no layer of this window has both neighbours yet; the next one starts at x0 = 0 as well and is meshed as the first)
+        first = x0 == 0
+        L.check(L.lib().ac_marching_cubes_slab_count(buf.data_ptr(), n, ny, nz, iso, int(first), int(last), scratch.data_ptr(), need, counts.data_ptr(), st),
+                "marching_cubes_slab_count")
+        nv, nt, carried, new_top = (int(v) for v in counts.tolist())
+        if not first and carried != top:
+            raise RuntimeError(f"marching_cubes_streamed: the window at x0 = {x0} finds {carried} vertices in its carried layer, the window before it emitted {top} "
+                               f"there: fill({x0}, .) and the call before it disagree, or the carry is broken")
+        top = new_top
+        if vbase + nv > 2 ** 31 - 1:
+            raise RuntimeError(f"marching_cubes_streamed: more than {2 ** 31 - 1} vertices: triangle indices are int32")
+        verts = torch.empty((nv, 3), dtype=torch.float64, device=dev)
+        tris = torch.empty((nt, 3), dtype=torch.int32, device=dev)
+        if nv or nt:
+            L.check(L.lib().ac_marching_cubes_slab_emit(buf.data_ptr(), n, ny, nz, iso, int(first), int(last), scratch.data_ptr(), need, x0, vbase, den, span_c, lo_c,
+                                                        L.ptr(verts) if nv else None, nv, L.ptr(tris) if nt else None, nt, st), "marching_cubes_slab_emit")
+            vparts.append(verts); tparts.append(tris)
+        vbase += nv
+    join = lambda parts, dt: parts[0] if len(parts) == 1 else torch.cat(parts) if parts else torch.empty((0, 3), dtype=dt, device=dev)
+    verts = join(vparts, torch.float64)
+    del vparts
+    return verts, join(tparts, torch.int32)
+
+
 def mesh_vertex_attrs(field, vertices, bound, eps=FD_STEP, refine_steps=3, tol=1e-5, max_move=None, target_sdf=0.0, dirs=None, want_rgb=True):
     """ac_mesh_vertex_attrs: what a coloured export needs per vertex, in one launch.  vertices [V,3] float64 on the device (marching_cubes' buffer as it is);
     every vertex takes at most refine_steps Newton steps along the finite-difference gradient onto sdf = target_sdf (never further than max_move per

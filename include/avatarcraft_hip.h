@@ -500,6 +500,30 @@ int ac_marching_cubes_count(const float *volume, uint32_t nx, uint32_t ny, uint3
 int ac_marching_cubes_emit(const float *volume, uint32_t nx, uint32_t ny, uint32_t nz, float iso, void *scratch, size_t scratch_bytes,
                            double den, const double span[3], const double lo[3], double *vertices, uint32_t n_vertices, int32_t *triangles,
                            uint32_t n_triangles, ac_stream_t stream);
+/* The same mesh from a grid that is never whole: marching cubes on a WINDOW of x layers, so that a grid of NX x ny x nz points is meshed slab by slab in the
+ * memory of one window (the volume costs 4 bytes and the scratch 5 per grid point: 77 GB at 2048^3), and NX x ny x nz may pass 2^31 points.
+ *   window [n][ny][nz] floats (DEVICE, z fastest) = grid layers [x0, x0 + n).  first != 0: x0 == 0.  last != 0: x0 + n == NX.  Consecutive windows overlap by
+ *   exactly two layers: x0' = x0 + n - 2 (a grid point's owned x edge needs the next layer, a cell the vertex indices of two owner layers).
+ *   A window emits the vertices owned by the grid points of its layers 1 .. n-2 (and 0 if first, and n-1 if last) and the triangles of its cell layers
+ *   0 .. n-3 (and n-2 if last): the windows tile the grid without gap or repeat, and their outputs CONCATENATED in window order are, bit for bit and in
+ *   order, what ac_marching_cubes_emit gives for the whole grid (same flag rule, table, double arithmetic on the global index x0 + i, same order).
+ *   ac_marching_cubes_slab_count: flag + classify + scan over the window; counts (DEVICE, [4]) = { vertices emitted, triangles emitted, vertices of layer 0
+ *                            (emitted by the previous window; by this one only if first), vertices of the last emitted layer }.  counts[3] of a window ==
+ *                            counts[2] of the next: the caller's check that the carry holds.  scratch: ac_marching_cubes_slab_scratch(n, ny, nz) bytes
+ *                            (0 for an unsupported window and for n = 2, which runs in the scratch of any larger window), unchanged until the emit call.
+ *   ac_marching_cubes_slab_emit : vertices [n_vertices,3] double and triangles [n_triangles,3] int32 of THIS window (n_vertices = counts[0], n_triangles =
+ *                            counts[1]).  vertex_base = the global index of the first vertex this window emits = the sum of counts[0] over the windows
+ *                            before it; triangle entries are global indices (the carried layer 0 has [vertex_base - counts[2], vertex_base)).
+ *                            den, span, lo as for ac_marching_cubes_emit.
+ * AC_ERR_BAD_ARG before any launch: n < 3 (n == 2 is allowed for a window both first and last), ny < 2, nz < 2, n ny nz >= 2^31, a NULL buffer, den == 0, a
+ * scratch that is too short, x0 + n beyond 32 bits, first with x0 != 0.  No atomics and no waits between workgroups: a deterministic mesh. */
+size_t ac_marching_cubes_slab_scratch(uint32_t n, uint32_t ny, uint32_t nz);
+int ac_marching_cubes_slab_count(const float *window, uint32_t n, uint32_t ny, uint32_t nz, float iso, uint32_t first, uint32_t last,
+                                 void *scratch, size_t scratch_bytes, uint32_t *counts /* DEVICE [4] */, ac_stream_t stream);
+int ac_marching_cubes_slab_emit(const float *window, uint32_t n, uint32_t ny, uint32_t nz, float iso, uint32_t first, uint32_t last,
+                                void *scratch, size_t scratch_bytes, uint32_t x0, uint32_t vertex_base,
+                                double den, const double span[3], const double lo[3],
+                                double *vertices, uint32_t n_vertices, int32_t *triangles, uint32_t n_triangles, ac_stream_t stream);
 /* ac_mesh_vertex_attrs stands in for nothing: the reference's export is utils.save_mesh(vert, face, ...) (stylize.py:263-269), geometry only -- the avatar's
  * colours never reach the file.  One launch over the vertices ac_marching_cubes_emit wrote (DEVICE doubles, read as they are): per vertex, all in fp32,
  *   p = clamp((float)vertex, +-bound); p0 = p; at most refine_steps times: the seven-point stencil at p exactly as ac_field_samples evaluates it (fd_eps) ->
