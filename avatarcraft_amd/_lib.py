@@ -192,6 +192,11 @@ _SIGS = {
     "ac_mesh_bind": ([vp, u32, vp, u32, vp, u32, vp, vp, vp, vp, vp, C.c_size_t, vp], C.c_int),
     "ac_mesh_pose_scratch": ([u32], C.c_size_t),
     "ac_mesh_pose": ([vp, vp, u32, vp, vp, C.POINTER(ac_warp_mesh), C.POINTER(ac_mesh_pose_opts), vp, C.c_size_t, vp, vp, vp, vp, vp, vp], C.c_int),
+    "ac_mesh_components_scratch": ([u32, u32], C.c_size_t),
+    "ac_mesh_components": ([vp, u32, u32, vp, vp, vp, u32, vp, vp, C.c_size_t, vp], C.c_int),
+    "ac_mesh_compact_scratch": ([u32, u32], C.c_size_t),
+    "ac_mesh_compact_count": ([vp, u32, u32, vp, vp, u32, vp, C.c_size_t, vp, vp], C.c_int),
+    "ac_mesh_compact_emit": ([vp, u32, u32, vp, vp, u32, vp, C.c_size_t, vp, vp, u32, vp, vp, u32, vp], C.c_int),
     "ac_density_grid_update_scratch": ([u32], C.c_size_t),
     "ac_density_grid_update": ([C.POINTER(ac_field), vp, u32, f32, f32, f32, vp, vp, vp, C.c_size_t, vp], C.c_int),
     "ac_table_to_half": ([vp, u32, vp, vp, vp], C.c_int),

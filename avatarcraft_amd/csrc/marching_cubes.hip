@@ -9,6 +9,7 @@
 // Order of the output (what makes the mesh reproducible bit for bit, and equal to the CPU oracle's serial loop): vertices by owning grid point (linear
 // index, z fastest) then by axis x, y, z; triangles by cell (linear index) then by table position.
 #include "ac_common.hpp"
+#include "ac_scan.hpp"      // block_exscan_256, wave_incscan, pair_scan_kernel: the scan of the per-workgroup totals (vertices in the low, triangles in the high 16 bits)
 
 #define AC_MC_CONST static __constant__ const
 #include "ac_mc_table.hpp"
@@ -66,23 +67,6 @@ __device__ __forceinline__ uint32_t mc_classify(const uint32_t *__restrict__ bit
     return vmask | (nt << 3);
 }
 
-// workgroup-wide exclusive scan of one value per thread (256 threads), in thread order; total -> every thread
-__device__ __forceinline__ uint32_t block_exscan_256(uint32_t v, uint32_t *sh /* [8] */, uint32_t &total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = (uint32_t)__shfl_up((int)inc, d); if (lane >= d) inc += o; }
-    __syncthreads();                              // (sh may still be read by a previous call)
-    if (lane == 63) sh[wave] = inc;
-    __syncthreads();
-    uint32_t base = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) if (w < wave) base += sh[w];
-    total = sh[0] + sh[1] + sh[2] + sh[3];
-    return base + inc - v;
-}
-
 __global__ __launch_bounds__(256) void mc_classify_kernel(const uint32_t *__restrict__ bits, const McDims d, uint32_t *__restrict__ cnt4,
                                                           uint32_t *__restrict__ bsum)
 {
@@ -103,38 +87,6 @@ __global__ __launch_bounds__(256) void mc_classify_kernel(const uint32_t *__rest
     if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
 }
 
-// exclusive scan of the per-workgroup totals (vertices in the low, triangles in the high 16 bits) -> boff[2 * b], boff[2 * b + 1]; totals -> counts[0..1].
-// One workgroup of 16 waves; a wave owns a contiguous range of the totals and walks it 64 at a time (coalesced loads, shuffle scan, running carry);
-// the waves' totals are combined through LDS and added in a second coalesced pass (131 072 totals at 512^3: 128 steps per wave and pass).
-__device__ __forceinline__ uint32_t wave_incscan(uint32_t v, int lane)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = (uint32_t)__shfl_up((int)v, d); if (lane >= d) v += o; }
-    return v;
-}
-__global__ __launch_bounds__(1024) void mc_scan_kernel(const uint32_t *__restrict__ bsum, uint32_t nblk, uint32_t *__restrict__ boff, uint32_t *__restrict__ counts)
-{
-    __shared__ uint32_t wv[16], wt[16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t per = (((nblk + 15u) / 16u) + 63u) & ~63u, lo = (uint32_t)wave * per, hi = lo + per < nblk ? lo + per : nblk;
-    uint32_t cv = 0, ct = 0;
-    for (uint32_t b0 = lo; b0 < hi; b0 += 64u) {
-        const uint32_t b = b0 + (uint32_t)lane;
-        const uint32_t sv = b < hi ? bsum[b] : 0u;
-        const uint32_t v = sv & 0xffffu, t = sv >> 16;
-        const uint32_t iv = wave_incscan(v, lane), it = wave_incscan(t, lane);
-        if (b < hi) { boff[2 * b] = cv + iv - v; boff[2 * b + 1] = ct + it - t; }
-        cv += (uint32_t)__shfl((int)iv, 63); ct += (uint32_t)__shfl((int)it, 63);
-    }
-    if (lane == 0) { wv[wave] = cv; wt[wave] = ct; }
-    __syncthreads();
-    uint32_t bv = 0, bt = 0;
-    for (int w = 0; w < wave; ++w) { bv += wv[w]; bt += wt[w]; }
-    if (bv | bt)
-        for (uint32_t b = lo + (uint32_t)lane; b < hi; b += 64u) { boff[2 * b] += bv; boff[2 * b + 1] += bt; }
-    if (threadIdx.x == 1023) { counts[0] = bv + cv; counts[1] = bt + ct; }
-}
-
 struct McXform { double den, span[3], lo[3]; };   // world = index / den * span + lo, the reference's three operations in its order (instant_nsr.py:760-762)
 
 // A window of a larger grid (ac_marching_cubes_slab_*): layers [x0, x0 + d.nx) along x.  The scan of the count pass runs over the whole window, so a vertex
@@ -142,7 +94,7 @@ struct McXform { double den, span[3], lo[3]; };   // world = index / den * span 
 // shift + vertex_base (the carried layer 0 gets the indices just below vertex_base: the ones the previous window wrote them under); position in this
 // window's piece = local - shift.  Emitted: vertices of layers [vlo, vhi), triangles of cell layers [0, tlayers).
 struct McSlab { uint32_t x0, vertex_base, vlo, vhi, tlayers; const uint32_t *info; };
-enum { MC_INFO_TOTALS = 0 /* [2]: mc_scan_kernel's totals over the window */, MC_INFO_SHIFT = 2, MC_INFO_WORDS = 64 };
+enum { MC_INFO_TOTALS = 0 /* [2]: pair_scan_kernel's totals over the window */, MC_INFO_SHIFT = 2, MC_INFO_WORDS = 64 };
 
 template <bool SLAB>
 __device__ __forceinline__ void mc_vertices_body(const float *__restrict__ vol, const McDims d, float iso, const uint32_t *__restrict__ cnt4,
@@ -356,7 +308,7 @@ AC_API int ac_marching_cubes_slab_count(const float *window, uint32_t n, uint32_
         hipLaunchKernelGGL(mc_flags_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, window, s.d.npts, iso, reinterpret_cast<unsigned long long *>(sc + s.l.bits));
     }
     hipLaunchKernelGGL(mc_classify_kernel, dim3(s.l.nblk), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t *>(sc + s.l.bits), s.d, cnt4, bsum);
-    hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, bsum, s.l.nblk, boff, s.info + MC_INFO_TOTALS);
+    hipLaunchKernelGGL(pair_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, bsum, s.l.nblk, boff, s.info + MC_INFO_TOTALS);
     hipLaunchKernelGGL(mc_slab_counts_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, cnt4, boff, s.d, s.vlo, s.vhi, s.tlayers, s.info, counts);
     return ac::check_launch("marching_cubes_slab_count");
 }
@@ -406,7 +358,7 @@ AC_API int ac_marching_cubes_count(const float *volume, uint32_t nx, uint32_t ny
     }
     hipLaunchKernelGGL(mc_classify_kernel, dim3(l.nblk), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t *>(sc + l.bits), d,
                        reinterpret_cast<uint32_t *>(sc + l.cnt), reinterpret_cast<uint32_t *>(sc + l.bsum));
-    hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t *>(sc + l.bsum), l.nblk,
+    hipLaunchKernelGGL(pair_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t *>(sc + l.bsum), l.nblk,
                        reinterpret_cast<uint32_t *>(sc + l.boff), counts);
     return ac::check_launch("marching_cubes_count");
 }

@@ -135,6 +135,70 @@ def skin_weights(bind, faces, lbs_weights):
     return np.einsum("vk,vkj->vj", bc, w[f[fid]])
 
 
+# ---------------------------------------------------------------------------------------------------- cleaning the mesh: which components stay (nsr_ops.mesh_components / mesh_compact)
+def select_components(sizes, spec):
+    """which components of a mesh stay: sizes [C,2] (vertices, triangles per component: nsr_ops.mesh_components' table; a tensor or an array) -> bool [C], numpy.
+    spec: "largest" = the component with the most triangles, ties to the lower component id | ("largest", k) = the k largest by triangles, same tie rule (k >= C:
+    all) | ("min_faces", n) = every component with at least n triangles | a bool array of length C, used as given | a callable sizes -> such a mask.
+    ValueError for anything else and for a mask of the wrong length.  Selection by area or bounding box is not built: pass a mask."""
+    import numpy as np
+    s = np.asarray(sizes.detach().cpu().numpy() if isinstance(sizes, torch.Tensor) else sizes).astype(np.int64).reshape(-1, 2)
+    n = len(s)
+    if callable(spec):
+        spec = spec(s)
+        if isinstance(spec, (str, tuple)):
+            raise ValueError("select_components: a callable spec must return a bool mask")
+    if isinstance(spec, str):
+        spec = (spec, 1) if spec == "largest" else (spec,)
+    if isinstance(spec, tuple):
+        if len(spec) != 2 or spec[0] not in ("largest", "min_faces") or isinstance(spec[1], bool) or not isinstance(spec[1], (int, np.integer)) or spec[1] < 0:
+            raise ValueError(f"select_components: unknown spec {spec!r} ('largest', ('largest', k), ('min_faces', n), a bool mask or a callable)")
+        if spec[0] == "min_faces":
+            return s[:, 1] >= int(spec[1])
+        mask = np.zeros(n, dtype=bool)
+        mask[np.argsort(-s[:, 1], kind="stable")[:int(spec[1])]] = True                # (stable: equal counts stay in component order -- ties to the lower id)
+        return mask
+    if isinstance(spec, torch.Tensor):
+        spec = spec.detach().cpu().numpy()
+    if not isinstance(spec, (np.ndarray, list)):
+        raise ValueError(f"select_components: unknown spec {spec!r} ('largest', ('largest', k), ('min_faces', n), a bool mask or a callable)")
+    mask = np.asarray(spec)
+    if mask.dtype != bool or mask.shape != (n,):
+        raise ValueError(f"select_components: a mask must be a bool array of length {n}, got {mask.dtype} {mask.shape}")
+    return mask.copy()
+
+
+def clean_mesh(mesh, spec):
+    """the mesh without the components `spec` drops (select_components), on the device: mesh = the dict of NeRFNetwork.extract_colored_mesh(return_torch=True) or
+    dict(vertices, triangles) of extract_geometry -- device tensors.  -> a new dict: vertices and every other per-vertex entry (first dimension V: normals, colors,
+    sdf, status, ...) gathered through the kept vertices in their order, triangles re-indexed, plus component_sizes [C,2] int64 (of the INPUT mesh) and
+    components_kept [C] bool.  A dict with `uv` or `texture` is refused: the atlas addresses its cells by triangle index, so a textured mesh is cleaned before
+    the bake (extract_textured_mesh(components=...)), not after."""
+    from . import nsr_ops
+    if "uv" in mesh or "texture" in mesh:
+        raise RuntimeError("clean_mesh: a textured mesh cannot be cleaned (the atlas addresses cells by triangle index): pass components= to extract_textured_mesh")
+    v, t = mesh["vertices"], mesh["triangles"]
+    if not isinstance(v, torch.Tensor) or not isinstance(t, torch.Tensor) or not v.is_cuda or not t.is_cuda:
+        raise RuntimeError("clean_mesh: vertices and triangles must be CUDA tensors (there is no CPU path)")
+    V = v.shape[0]
+    cc = nsr_ops.mesh_components(t, V)
+    keep = select_components(cc["sizes"], spec)
+    keep_dev = torch.from_numpy(keep).to(t.device)
+    cm = nsr_ops.mesh_compact(t, cc["component"], keep_dev)
+    idx = cm["kept_vertices"].long()
+    out = {}
+    for k, x in mesh.items():
+        if k == "triangles":
+            out[k] = cm["triangles"]
+        elif isinstance(x, torch.Tensor) and x.dim() >= 1 and x.shape[0] == V:
+            out[k] = x.index_select(0, idx)
+        else:
+            out[k] = x
+    out["component_sizes"] = cc["sizes"]
+    out["components_kept"] = keep_dev
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------- texture atlas (closed form; the kernel restates it in integers)
 # The S x S texture is cut into R x R square cells of c x c texels (R = S // c; texels beyond R c belong to nobody).  Triangle t lives in cell k = t >> 1, at
 # column k % R and row k // R, in half h = t & 1: texel (i, j) of a cell -- i along x, centre at (i + 0.5, j + 0.5) -- belongs to half 0 iff i + j <= c - 2.

@@ -1040,7 +1040,7 @@ class NeRFNetwork(NeRFRenderer):
                         u[xi * N: xi * N + len(x), yi * N: yi * N + len(y), zi * N: zi * N + len(z)] = self.density(pts, bound).reshape(len(x), len(y), len(z))
         return u.cpu().numpy()
 
-    def extract_geometry(self, bound: float, resolution: int, threshold: int = 0.0, device=None, mesher=None, return_torch=False, slab_layers=None):
+    def extract_geometry(self, bound: float, resolution: int, threshold: int = 0.0, device=None, mesher=None, return_torch=False, slab_layers=None, components=None):
         """iso-surface of the SDF (reference :706-764; its one call is extract_geometry(NSR_BOUND, 512), stylize.py:267): vertices [V,3] float64 in world
         units, triangles [F,3].  The reference runs PyMCubes' marching_cubes on u = -sdf (third party, not in this image).
         mesher: "native" (default on the GPU) = ac_field_sdf_grid + ac_marching_cubes on the device: the volume never leaves it, one shared vertex per
@@ -1052,8 +1052,13 @@ class NeRFNetwork(NeRFRenderer):
                 STREAMED (nsr_ops.marching_cubes_streamed): the grid is evaluated slab_layers x-layers at a time into one window of slab_layers + 2 layers and
                 meshed window by window -- the same mesh bit for bit, in the memory of one window, at any resolution whose window stays below 2^31 points
                 (extract_geometry(1.6, 2048, slab_layers=64): the hash grid's own finest resolution, 0.92 s).  Multiples of 16 keep the x-tiles of the grid kernel
-                full; other values are legal.  Needs mesher "native" (or None on the GPU)."""
+                full; other values are legal.  Needs mesher "native" (or None on the GPU).
+        components: None = every connected component the field has, floaters included (as ever); a spec of geometry.select_components -- "largest",
+                ("largest", k), ("min_faces", n), a bool mask or a callable on the size table -- = only those components, labelled and compacted on the device
+                (geometry.clean_mesh: order preserved, so the dense and the streamed route give the same cleaned mesh).  Native mesher only."""
         native_ok = self.encoder.embeddings.is_cuda and self._sdf_supported()
+        if components is not None and (mesher not in (None, "native") or not native_ok):
+            raise RuntimeError("extract_geometry(components=...) cleans the native mesher's mesh on the device: it needs mesher='native' and the default SDF side of NeRFNetwork on the GPU")
         if slab_layers is not None:
             slab_layers = nsr_ops.check_slab_layers(slab_layers, "extract_geometry")
             if mesher not in (None, "native") or not native_ok:
@@ -1075,6 +1080,10 @@ class NeRFNetwork(NeRFRenderer):
                     fill = lambda x0, out: nsr_ops.field_sdf_grid(f, ax[x0:x0 + out.shape[0]], ax, ax, bound, negate=True, out=out)
                     v, t = nsr_ops.marching_cubes_streamed(fill, resolution, resolution, resolution, slab_layers=slab_layers, iso=float(threshold),
                                                            device=ax.device, **xf)
+            if components is not None:
+                from .geometry import clean_mesh
+                m = clean_mesh(dict(vertices=v, triangles=t), components)
+                v, t = m["vertices"], m["triangles"]
             return (v, t) if return_torch else (v.cpu().numpy(), t.cpu().numpy())
         u = -1.0 * self.extract_fields(bound, resolution)
         if mesher == "mcubes":
@@ -1090,7 +1099,7 @@ class NeRFNetwork(NeRFRenderer):
         return vertices, triangles
 
     def extract_colored_mesh(self, bound: float, resolution: int, threshold: float = 0.0, refine_steps: int = 3, tol: float = 1e-5, colors: bool = True,
-                             return_torch=False, slab_layers=None):
+                             return_torch=False, slab_layers=None, components=None):
         """the mesh of extract_geometry(mesher="native") with what a viewer wants on it (the reference's save_mesh, stylize.py:263-269, writes bare geometry):
         every vertex projected from the grid edge's linear zero crossing onto the level set sdf = -threshold (at most refine_steps Newton steps along the
         finite-difference gradient, never further than one grid cell), the field's normal and the colour network there -- one launch over the marching-cubes
@@ -1098,7 +1107,10 @@ class NeRFNetwork(NeRFRenderer):
         float32 in [0, 1] (colors=True), sdf [V] at the final positions, status [V] uint8: 0 converged to tol, 1 all steps taken (sdf tells how close), 2 degenerate gradient,
         3 stopped by the one-cell limit); numpy arrays, or device tensors with return_torch=True.  With view directions the colour is the one seen along -normal.
         colors=True needs the default colour side (RuntimeError otherwise); colors=False works wherever extract_geometry(mesher="native") does.
-        slab_layers: extract_geometry's (None: the whole volume at once; an integer: streamed, the same mesh in the memory of one window)."""
+        slab_layers: extract_geometry's (None: the whole volume at once; an integer: streamed, the same mesh in the memory of one window).
+        components: extract_geometry's (None: every component).  The mesh is cleaned right after the geometry and BEFORE the vertices are shaded: a dropped vertex
+        costs nothing, and a kept one gets what it would have got (the attributes are per vertex).  The dict then also carries component_sizes [C,2] (vertices,
+        triangles of every component of the unfiltered mesh) and components_kept [C] bool."""
         if slab_layers is not None:
             slab_layers = nsr_ops.check_slab_layers(slab_layers, "extract_colored_mesh")
         if not (self.encoder.embeddings.is_cuda and self._sdf_supported()):
@@ -1107,6 +1119,11 @@ class NeRFNetwork(NeRFRenderer):
             raise RuntimeError("extract_colored_mesh(colors=True): the colour side of this model is not the default one (colour net 21-64-64-3, or 37-64-64-3 "
                                "with the degree-4 view-direction encoder); colors=False exports positions and normals")
         v, t = self.extract_geometry(bound, resolution, threshold=threshold, mesher="native", return_torch=True, slab_layers=slab_layers)
+        cleaned = None
+        if components is not None:
+            from .geometry import clean_mesh
+            cleaned = clean_mesh(dict(vertices=v, triangles=t), components)
+            v, t = cleaned["vertices"], cleaned["triangles"]
         with torch.no_grad():
             f = self._field() if self._fused_supported(ignore_curvature=True) else self._field_sdf_only()
             a = nsr_ops.mesh_vertex_attrs(f, v, bound, nsr_ops.FD_STEP, refine_steps=refine_steps, tol=tol, max_move=2.0 * bound / (resolution - 1.0),
@@ -1114,6 +1131,8 @@ class NeRFNetwork(NeRFRenderer):
         out = dict(vertices=a["positions"].double(), triangles=t, normals=a["normals"], sdf=a["sdf"], status=a["status"])
         if colors:
             out["colors"] = a["rgb"]
+        if cleaned is not None:
+            out.update(component_sizes=cleaned["component_sizes"], components_kept=cleaned["components_kept"])
         return out if return_torch else {k: x.cpu().numpy() for k, x in out.items()}
 
     def render_surface(self, rays_o, rays_d, bound, bg_color=None, normal_epsilon_ratio=0.0, max_ray_batch=None, **opts):
@@ -1189,17 +1208,19 @@ class NeRFNetwork(NeRFRenderer):
                 "face_id": o["face_id"].reshape(B, N)}
 
     def extract_textured_mesh(self, bound: float, resolution: int, texture_size: int = 2048, cell=None, threshold: float = 0.0, refine_steps: int = 3,
-                              tol: float = 1e-5, return_torch=False, slab_layers=None):
+                              tol: float = 1e-5, return_torch=False, slab_layers=None, components=None):
         """extract_colored_mesh's mesh with the colour network baked into a texture instead of sampled at the vertices, so that colour detail no longer depends on
         the vertex density: every triangle gets half a cell of a closed-form texture_size^2 atlas (geometry.atlas_layout; cell=None: the largest that fits), every
         owned texel's point on its triangle is projected onto the level set like a vertex (never further than one grid cell) and shaded there, one launch
         (ac_mesh_bake_texture).  -> the dict of extract_colored_mesh plus uv [T,3,2] float64 (three corners per triangle, OBJ convention), texture [S,S,3] uint8
         (q = floor(clamp(x, 0, 1) 255 + 0.5), row 0 on top), owner [S,S] int32 (-1: nobody, texture 0), texel_sdf [S,S], texel_status [S,S] uint8.
         The atlas guarantees bilinear lookups only (no mip chain).  Same model requirements as extract_colored_mesh(colors=True).
-        slab_layers: extract_geometry's; an atlas too small for the triangle count of a finer mesh raises as ever."""
+        slab_layers: extract_geometry's; an atlas too small for the triangle count of a finer mesh raises as ever.
+        components: extract_colored_mesh's.  The mesh is cleaned BEFORE the atlas is laid out, so the cells are sized for the kept triangles only: debris no longer
+        lowers the texel density of the body."""
         from .geometry import atlas_layout
         m = self.extract_colored_mesh(bound, resolution, threshold=threshold, refine_steps=refine_steps, tol=tol, colors=True, return_torch=True,
-                                      slab_layers=slab_layers)
+                                      slab_layers=slab_layers, components=components)
         T = m["triangles"].shape[0]
         try:
             lay = atlas_layout(T, texture_size, cell)

@@ -1620,6 +1620,70 @@ def mesh_pose(points, normals, bind, mesh, iters=3, tol=1e-5, want=("residual", 
     return out
 
 
+def _chk_triangles(who, triangles):
+    if not isinstance(triangles, torch.Tensor) or not triangles.is_cuda:
+        raise RuntimeError(f"{who}: triangles must be a CUDA tensor (there is no CPU path)")
+    if triangles.dtype != torch.int32 or triangles.dim() != 2 or triangles.shape[1] != 3 or not triangles.is_contiguous():
+        raise RuntimeError(f"{who}: triangles must be a contiguous int32 [T,3] tensor")
+    return triangles
+
+
+def mesh_components(triangles, n_vertices):
+    """ac_mesh_components: the connected components of a mesh, triangles [T,3] int32 on the device over n_vertices vertices (the definitions:
+    include/avatarcraft_hip.h).  -> dict(root [V] int32: the smallest vertex index of the vertex's component, component [V] int32: the rank of that root among the
+    roots, sizes [C,2] (vertices, triangles per component; int64 on the device), n_components = C).  One 8-byte read-back: the two counts (C, invalid triangles).
+    RuntimeError, giving the count, for triangles with an index outside [0, V): a mesh of this project never has one."""
+    tris = _chk_triangles("mesh_components", triangles)
+    if isinstance(n_vertices, bool) or not isinstance(n_vertices, (int, np.integer)) or not 0 <= n_vertices < 2 ** 31:
+        raise RuntimeError(f"mesh_components: n_vertices {n_vertices!r} must be an integer in [0, 2^31)")
+    V, T, dev = int(n_vertices), tris.shape[0], tris.device
+    if V == 0 and T:
+        raise RuntimeError(f"mesh_components: {T} triangles over no vertex")
+    root = torch.empty(V, dtype=torch.int32, device=dev)
+    comp = torch.empty(V, dtype=torch.int32, device=dev)
+    sizes = torch.empty((V, 2), dtype=torch.int32, device=dev)                       # (uint32 rows; a count stays below 2^31)
+    counts = torch.zeros(2, dtype=torch.int32, device=dev)
+    need = int(L.lib().ac_mesh_components_scratch(V, T))
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    L.check(L.lib().ac_mesh_components(L.ptr(tris) if T else None, T, V, L.ptr(root) if V else None, L.ptr(comp) if V else None, L.ptr(sizes) if V else None, V,
+                                       counts.data_ptr(), L.ptr(scratch) if need else None, need, L.current_stream(dev)), "mesh_components")
+    n_comp, n_bad = (int(v) for v in counts.tolist())
+    if n_bad:
+        raise RuntimeError(f"mesh_components: {n_bad} of {T} triangles have an index outside [0, {V})")
+    return dict(root=root, component=comp, sizes=sizes[:n_comp].to(torch.int64), n_components=n_comp)
+
+
+def mesh_compact(triangles, component, keep):
+    """ac_mesh_compact_count + _emit: the mesh restricted to the components with keep[c] != 0, order preserved.  triangles [T,3] int32, component [V] int32
+    (mesh_components'), keep [C] bool or uint8, all on one device.  -> dict(vertex_map [V] int32: new index or -1, kept_vertices [V'] int32: old indices
+    ascending, triangles [T',3] int32 re-indexed, kept_triangles [T'] int32: old triangle indices ascending).  One 8-byte read-back between count and emit."""
+    tris = _chk_triangles("mesh_compact", triangles)
+    for t, name in ((component, "component"), (keep, "keep")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"mesh_compact: {name} must be a CUDA tensor (there is no CPU path)")
+    if component.dtype != torch.int32 or component.dim() != 1 or not component.is_contiguous() or component.device != tris.device:
+        raise RuntimeError("mesh_compact: component must be a contiguous int32 [V] tensor on the device of triangles")
+    if keep.dtype not in (torch.bool, torch.uint8) or keep.dim() != 1 or keep.device != tris.device:
+        raise RuntimeError("mesh_compact: keep must be a bool or uint8 [C] tensor on the device of triangles")
+    keep8 = keep.to(torch.uint8).contiguous()
+    V, T, Cn, dev = component.shape[0], tris.shape[0], keep8.shape[0], tris.device
+    if Cn > V:
+        raise RuntimeError(f"mesh_compact: keep has {Cn} entries for {V} vertices")
+    need = int(L.lib().ac_mesh_compact_scratch(V, T))
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    counts = torch.zeros(2, dtype=torch.int32, device=dev)
+    st = L.current_stream(dev)
+    head = (L.ptr(tris) if T else None, T, V, L.ptr(component) if V else None, L.ptr(keep8) if Cn else None, Cn, L.ptr(scratch) if need else None, need)
+    L.check(L.lib().ac_mesh_compact_count(*head, counts.data_ptr(), st), "mesh_compact_count")
+    nv, nt = (int(v) for v in counts.tolist())
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    out = dict(vertex_map=i32(V), kept_vertices=i32(nv), triangles=i32(nt, 3), kept_triangles=i32(nt))
+    if V:
+        L.check(L.lib().ac_mesh_compact_emit(*head, out["vertex_map"].data_ptr(), L.ptr(out["kept_vertices"]) if nv else None, nv,
+                                             L.ptr(out["triangles"]) if nt else None, L.ptr(out["kept_triangles"]) if nt else None, nt, st), "mesh_compact_emit")
+    return out
+
+
 _DG_SCRATCH = {}
 
 

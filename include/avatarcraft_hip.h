@@ -902,6 +902,45 @@ int ac_render_rays_surface_warped(const ac_field *field, const ac_surface_opts *
                                   uint32_t N, const float *bg /*optional [N,3]*/, const ac_warp_mesh *mesh, void *scratch, size_t scratch_bytes,
                                   const ac_surface_out *out, const ac_surface_warped_out *out_w /*optional*/, ac_stream_t stream);
 
+/* ---- cleaning the exported mesh: connected components and compaction on the device (csrc/mesh_components.hip; added entries, no struct of an existing call
+ * changes: ABI stays 10).  It stands in for nothing in the reference, whose export writes every detached blob ("floater") the field has.
+ * A mesh is triangles [T,3] int32 over V vertices.  Definitions:
+ *   Valid triangle: its three indices lie in [0, V).  An invalid triangle joins nothing, is counted in n_bad, belongs to no component and is never emitted by
+ *     the compaction.  A degenerate triangle (a, a, b) or a duplicate triangle is valid: it counts as a triangle and joins what it names.
+ *   Connectivity: two vertices are connected iff a chain of edges of valid triangles joins them.  A vertex that no valid triangle names is a component of its
+ *     own, of size (1 vertex, 0 triangles).
+ *   root[v]: the smallest vertex index in v's component -- a canonical labelling: it depends on neither triangle order nor scheduling, so the result is the same
+ *     from run to run and equal to any CPU union-find although the kernel hooks with atomics.
+ *   component[v]: the rank of root[v] among the roots in ascending order; C = the number of components.  The component of a valid triangle is that of its first
+ *     vertex (all three agree).
+ *   sizes[c] = { vertices, triangles }: two uint32 per component.
+ *   Compaction with keep [C] uint8: a vertex is kept iff keep[component[v]] != 0, a valid triangle iff its component is kept; kept vertices and kept triangles
+ *     keep their relative order.  vertex_map [V] int32 = new index or -1; kept_vertices [V'] = old indices, ascending; triangles_out [T',3] = the kept triangles
+ *     re-indexed through vertex_map; kept_triangles [T'] = old triangle indices, ascending.
+ * ac_mesh_components: a union-find over parent[V] in scratch (initialise; ONE hooking launch over the triangles that always links the larger root under the
+ *   smaller, every access of parent[] an agent-scope atomic; flatten), then is_root -> exclusive scan -> component, then the sizes by integer adds aggregated in
+ *   the wave (one add per component a wave holds, for its first four; a wave that agrees does one add).  No wave waits for another one (every retry is a lock-free retry whose observed value strictly decreased), no floating-point atomics.
+ *   counts (DEVICE, [2]) = { C, n_bad }.  sizes rows [C, max_components) are left untouched; max_components = V always suffices, and then the call does not
+ *   synchronise.  With max_components < V the call reads C back (it waits for the stream) and, if C > max_components, returns AC_ERR_BAD_ARG saying so AFTER
+ *   writing counts, root, component and the rows that fit.  V == 0 (then T must be 0): C = 0, no launch.  T == 0 with V > 0: V singleton components.
+ *   scratch: the _scratch function of (V, T) bytes (4 per vertex and a little).
+ * ac_mesh_compact_count: keep flags + scan; counts (DEVICE, [2]) = { V', T' }.  The scratch (its own _scratch function) is kept unchanged until the emit call.
+ * ac_mesh_compact_emit : the four outputs, n_kept_vertices = V', n_kept_triangles = T' of the count call (nothing is written past them).  Flags -> scans ->
+ *   ordered writes, no atomics.  V' = T' = 0 is legal (vertex_map is all -1; kept_vertices, triangles_out and kept_triangles may be NULL).
+ * AC_ERR_BAD_ARG before any launch, with the rule in the message: a NULL required buffer (triangles may be NULL when T == 0, keep when C == 0, sizes when
+ * max_components == 0), V or T above 2^31 - 1, triangles over V == 0, a scratch that is too short, C > V, n_kept_vertices > V or n_kept_triangles > T.
+ * PRECONDITION of the compaction: component is the labelling of THESE triangles (values outside [0, C) are treated as not kept, never read through). */
+size_t ac_mesh_components_scratch(uint32_t V, uint32_t T);
+int ac_mesh_components(const int32_t *triangles /*[T,3]*/, uint32_t T, uint32_t V, int32_t *root /*[V]*/, int32_t *component /*[V]*/,
+                       uint32_t *sizes /*[max_components][2]*/, uint32_t max_components, uint32_t *counts /* DEVICE [2] = { C, n_bad } */,
+                       void *scratch, size_t scratch_bytes, ac_stream_t stream);
+size_t ac_mesh_compact_scratch(uint32_t V, uint32_t T);
+int ac_mesh_compact_count(const int32_t *triangles /*[T,3]*/, uint32_t T, uint32_t V, const int32_t *component /*[V]*/, const uint8_t *keep /*[C]*/, uint32_t C,
+                          void *scratch, size_t scratch_bytes, uint32_t *counts /* DEVICE [2] = { V', T' } */, ac_stream_t stream);
+int ac_mesh_compact_emit(const int32_t *triangles /*[T,3]*/, uint32_t T, uint32_t V, const int32_t *component /*[V]*/, const uint8_t *keep /*[C]*/, uint32_t C,
+                         void *scratch, size_t scratch_bytes, int32_t *vertex_map /*[V]*/, int32_t *kept_vertices /*[V']*/, uint32_t n_kept_vertices,
+                         int32_t *triangles_out /*[T',3]*/, int32_t *kept_triangles /*[T']*/, uint32_t n_kept_triangles, ac_stream_t stream);
+
 /* ---- rendering from a half-precision hash table (opt-in, inference only) ----------------------------------------------------------------------------
  * The half table holds ONE dword per entry of the fp32 table [n_entries][2] (n_entries = field->offsets[16]): channel 0 as an IEEE binary16 in the low
  * half, channel 1 in the high half -- 4 bytes per entry instead of 8, the same level offsets.  ac_table_to_half makes it: every value is rounded to
