@@ -29,7 +29,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 
 # per-source additions: the instruction scheduler LLVM's AMDGPU back end uses for that file (scheduling only -- no arithmetic changes; every kernel stays bit-identical to
 # the oracle, which the GPU tests check).  Measured same-box, profiles/r03_experiments.txt sections 20 - 21:
-#   hash_stencil.hip (table-gradient scatter): max-memory-clause -- the queue fill is a long sequence of LDS record traffic between short arithmetic sections:
+#   hash_stencil.hip (with table_scatter.hpp, the table-gradient scatter, which only it includes): max-memory-clause -- the queue fill is a long sequence of LDS record traffic between short arithmetic sections:
 #       1.246 -> 1.188 ms per 4096-ray patch (the same strategy costs the render kernel 7 %, so it is not a global flag);
 #   render_fused.hip: iterative-maxocc -- 0.763 -> 0.752 ms per 4096-ray launch of the instantiation without per-sample outputs (+0.6 % on the training one);
 #   warp.hip: iterative-maxocc -- posed frame 8.21 -> 8.08 ms (warp_accel_build.hip: the structure's builder kernels, compiled as they were inside warp.hip).
@@ -43,7 +43,8 @@ PER_FILE_FLAGS = {"hash_stencil.hip": ["-mllvm", "-amdgpu-sched-strategy=max-mem
 # Library variants built next to the product (in-tree, so that they travel to the GPU box; git-ignored like every .so): the same objects except the listed
 # sources, which are compiled with extra defines.  Loaded through AC_LIB_PATH by the tests that keep a compile-time alternative exercised.
 #   rec12: the table-gradient scatter with full-fp32 12-byte queue records (-DAC_REC8=0) instead of the 8-byte records whose values are rounded to 16 / 17
-#          mantissa bits (the precision reduction is a compile-time choice; the fp32 form must stay covered by the parity matrix)
+#          mantissa bits (the precision reduction is a compile-time choice; the fp32 form must stay covered by the parity matrix).  The
+#          record codec and everything that sees a record live in csrc/table_scatter.hpp, included by hash_stencil.hip ALONE: one define covers them all
 VARIANTS = {"rec12": {"hash_stencil.hip": ["-DAC_REC8=0"]}}
 
 

@@ -1,5 +1,5 @@
 // avatarcraft_amd/csrc/train_common.hpp -- what the training operators share: the workgroup shape of their backward kernels, and the functions through which
-// the whole-core backward (render_core_backward.hip) chains the operators (sdf_stencil_train.hip, color_train.hip, composite.hip, hash_stencil.hip).
+// the whole-core backward (render_core_backward.hip) chains the operators (sdf_stencil_train.hip, color_train.hip, composite.hip, hash_stencil.hip with its table_scatter.hpp).
 // RenderArgs and every kernel live in anonymous namespaces (one copy per translation unit), so what crosses files takes the C ABI's own types only.
 #pragma once
 #include "field_tile.hpp"
@@ -42,7 +42,7 @@ int composite_backward_core(const ac_render_opts *op, const float *rays_o, const
                             const ac_core_upstream *up, float *g_sdf, float *g_nrm, float *g_col, float *g_inv_s_per_ray, ac_stream_t stream);
 
 // hash_stencil.hip: the argument rules of ac_hash_stencil_backward, and that entry with the accumulation split at a level and a side stream ordered behind
-// the first part
+// the first part (queue_scatter, table_scatter.hpp)
 int hash_stencil_backward_check(uint32_t C, uint32_t L, const int32_t *offsets_host, float eps, float bound);
 int hash_stencil_backward_split(const float *grad, const float *x, const int32_t *offsets_host, float *grad_embeddings, uint32_t B,
                                 uint32_t C, uint32_t L, float S, uint32_t H, float eps, float bound, void *scratch, size_t scratch_bytes,

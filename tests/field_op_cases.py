@@ -237,7 +237,7 @@ class SdfLayer1(torch.autograd.Function):
 
 
 def round_record(v, drop):
-    """rec_round of hash_stencil.hip: to nearest at bit `drop` of the float32 pattern"""
+    """rec_round of table_scatter.hpp: to nearest at bit `drop` of the float32 pattern"""
     b = np.ascontiguousarray(v, F32).view(np.uint32)
     return ((b + np.uint32(1 << (drop - 1))) & np.uint32(~((1 << drop) - 1) & 0xffffffff)).view(F32)
 

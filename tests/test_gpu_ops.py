@@ -514,6 +514,55 @@ def test_hash_stencil_backward_paths_agree():
     assert float((res[1] - res[0]).abs().max()) <= 1e-4 * float(res[0].abs().max())
 
 
+def stencil_fill_case(B):
+    """inputs of test_hash_stencil_backward_fill_sizes: B points drawn like those of test_hash_stencil_forward_backward (uniform in the cube, a few on
+    its faces, a few on cell borders of the coarse levels) and their feature gradients [7,16,B,2], every third sample's exactly zero"""
+    rs = np.random.RandomState(100 + B)
+    x = rs.uniform(-1.6, 1.6, size=(B, 3)).astype(np.float32)
+    x[1:5] = np.sign(x[1:5]) * 1.6                                   # (sample 0 stays inside: B = 1 is one ordinary point)
+    x[5:8, 0] = 1.6; x[8:11, 1] = -1.6
+    x[11:23] = (np.round(x[11:23] * 40) / 40).astype(np.float32)
+    g = rs.normal(size=(7, 16, B, 2)).astype(np.float32)
+    g[:, :, 2::3] = 0.0
+    return x, g
+
+
+def stencil_backward_table(offs, S, x, g, binned):
+    """ac_hash_stencil_backward on a 16-level grid (offs, S; base resolution 16), eps 0.005, bound 1.6: the table gradient through the queues (scratch
+    for B samples) or, without scratch, through the direct float atomics"""
+    from avatarcraft_amd import _lib as Lb
+    B = x.shape[0]
+    xt, gt_ = T(x), T(g)
+    nbytes = int(Lb.lib().ac_hash_stencil_backward_scratch(offs.ctypes.data, 16, S, 16, 16, B)) if binned else 0
+    assert (nbytes > 0) == binned
+    sc = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=DEV)
+    table = torch.zeros(int(offs[-1]), 2, device=DEV)
+    Lb.check(Lb.lib().ac_hash_stencil_backward(gt_.data_ptr(), xt.data_ptr(), offs.ctypes.data, table.data_ptr(), B, 2, 16, S, 16, 0.005, 1.6,
+                                               sc.data_ptr() if binned else None, nbytes, None))
+    torch.cuda.synchronize()
+    return table
+
+
+@pytest.mark.parametrize("B", [1, 63, 65, 197])
+def test_hash_stencil_backward_fill_sizes(oracle, B):
+    """the queue fill at the sizes where it can go wrong, not the workload's: one live lane; a partial last group (the lanes past B read sample B - 1
+    with a zero gradient); a second group; and 197 = four groups in one workgroup, where on the fine levels a group of 64 yields more than 1024
+    records (7 points x 8 corners, two samples in three live), so the wave buffer is flushed inside add8.  The binned path against the direct
+    atomics at the bound of test_hash_stencil_backward_paths_agree -- the library of the commit before the scatter got its own header stays
+    inside it at these shapes (measured ratios in profiles/hash_scatter_split.txt) -- and twice on the same inputs bit for bit: the
+    order-independence the accumulate kernel promises."""
+    offs, pls = oracle.hash_offsets(desired_resolution=2048)                 # the default 16-level grid
+    S = float(np.float32(np.log2(pls)))
+    x, g = stencil_fill_case(B)
+    direct = stencil_backward_table(offs, S, x, g, binned=False)
+    first, second = stencil_backward_table(offs, S, x, g, binned=True), stencil_backward_table(offs, S, x, g, binned=True)
+    scale = float(direct.abs().max())
+    err = float((first - direct).abs().max())
+    print(f"B={B}: max|binned - direct| = {err:.3e} = {err / scale:.3e} of max|direct| = {scale:.3e}")
+    assert scale > 0 and err <= 2e-5 * scale
+    assert torch.equal(first, second)
+
+
 @pytest.mark.parametrize("L,base,log2T,pls,binned", [(4, 4, 12, 2.0, True), (8, 16, 15, 1.5, True), (6, 5, 14, 1.7, True), (3, 2, 10, 2.0, False)])
 def test_hash_backward_binned_other_grids(oracle, L, base, log2T, pls, binned):
     """binned scatter on grids other than the default one (bucket size = a power of two that covers each level with <= 64 buckets;
