@@ -623,20 +623,26 @@ __device__ __forceinline__ void coarse_finish(const AxisGeo<K, SIGN> &a, const u
 // coarse offset points from bilinear face values (fast precision only): removed, the one run-to-run non-determinism ever seen -- DESIGN.md section 2.1
 
 // ---- fine level (eps spans one cell or more): every offset point gathers its own 8 corners ---------------------------
-template <int K, int GM, bool H16>
-__device__ __forceinline__ void fine_issue(rsrc_t table, const LvlC &L, const uint32_t (&tx)[2], const uint32_t (&ty)[2],
-                                           const uint32_t (&tz)[2], bool oob_c, float u, u32x2 (&v)[8], float &qk, bool &oob)
+// the offset point's own cell along K: its two index terms tk[0 / 1], its weight and its out-of-range flag
+template <int K>
+__device__ __forceinline__ void fine_geo(const LvlC &L, bool oob_c, float u, uint32_t (&tk)[2], float &qk, bool &oob)
 {
     oob = oob_c | (u < 0.0f) | (u > 1.0f);
     const float pos = fma_(u, L.scale, 0.5f);
     const uint32_t gk = (uint32_t)__builtin_floorf(pos);
     qk = pos - (float)gk;
     const uint32_t mk = K == 0 ? 1u : (K == 1 ? L.my : L.mz);
-    const uint32_t t0 = gk * mk, t1 = t0 + mk;
+    tk[0] = gk * mk; tk[1] = tk[0] + mk;
+}
+template <int K, int GM, bool H16>
+__device__ __forceinline__ void fine_issue(rsrc_t table, const LvlC &L, const uint32_t (&tx)[2], const uint32_t (&ty)[2],
+                                           const uint32_t (&tz)[2], bool oob_c, float u, u32x2 (&v)[8], float &qk, bool &oob)
+{
+    uint32_t tk[2];
+    fine_geo<K>(L, oob_c, u, tk, qk, oob);
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-        const uint32_t tk = ((c >> K) & 1) ? t1 : t0;
-        const uint32_t ax = K == 0 ? tk : tx[c & 1], ay = K == 1 ? tk : ty[(c >> 1) & 1], az = K == 2 ? tk : tz[(c >> 2) & 1];
+        const uint32_t ax = K == 0 ? tk[c & 1] : tx[c & 1], ay = K == 1 ? tk[(c >> 1) & 1] : ty[(c >> 1) & 1], az = K == 2 ? tk[(c >> 2) & 1] : tz[(c >> 2) & 1];
         v[c] = table_entry<H16>(table, L.offset + gidx<GM>(L, ax, ay, az));
     }
 }
@@ -660,12 +666,12 @@ __device__ __forceinline__ void stencil_levels(const float *__restrict__ lds, fl
     }
     uint32_t tx[2], ty[2], tz[2];
     tx[0] = gc[0]; tx[1] = gc[0] + 1u; ty[0] = gc[1] * L.my; ty[1] = ty[0] + L.my; tz[0] = gc[2] * L.mz; tz[1] = tz[0] + L.mz;
-    u32x2 vc[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c)
-        vc[c] = table_entry<H16>(table, L.offset + gidx<GM>(L, tx[c & 1], ty[(c >> 1) & 1], tz[c >> 2]));
+    u32x2 vc[8];                // the centre's corners: each branch issues them where its order wants them
     if (!fine) {
         u32x2 w0[4], w1[4], w2[4], w3[4], w4[4], w5[4];
+#pragma unroll
+        for (int c = 0; c < 8; ++c)
+            vc[c] = table_entry<H16>(table, L.offset + gidx<GM>(L, tx[c & 1], ty[(c >> 1) & 1], tz[c >> 2]));
         const auto a0 = coarse_issue<0, 0, GM, H16>(table, L, gc, tx, ty, tz, oob, xp, w0);
         const auto a1 = coarse_issue<0, 1, GM, H16>(table, L, gc, tx, ty, tz, oob, xm, w1);
         const auto a2 = coarse_issue<1, 0, GM, H16>(table, L, gc, tx, ty, tz, oob, yp, w2);
@@ -681,11 +687,29 @@ __device__ __forceinline__ void stencil_levels(const float *__restrict__ lds, fl
         coarse_finish<1, 1>(a3, vc, w3, qc, f0, f1); AC_FSTORE(4, f0, f1)
         coarse_finish<2, 0>(a4, vc, w4, qc, f0, f1); AC_FSTORE(5, f0, f1)
         coarse_finish<2, 1>(a5, vc, w5, qc, f0, f1); AC_FSTORE(6, f0, f1)
-    } else {                // all 48 gathers of the six offset points in flight at once: one memory round trip instead of three (221 VGPRs, -2 % time)
+    } else {                // all 56 gathers of the seven points in flight at once: one memory round trip instead of three (221 VGPRs, -2 % time)
         u32x2 va[8], vb[8], vc2[8], vd[8], ve[8], vf[8];
         float qa, qb, qc2, qd, qe, qf, f0, f1; bool oa, ob, oc2, od, oe, of;
-        fine_issue<0, GM, H16>(table, L, tx, ty, tz, oob, xp, va, qa, oa);
-        fine_issue<0, GM, H16>(table, L, tx, ty, tz, oob, xm, vb, qb, ob);
+        // Issue order.  The centre and the +x / -x points share the (y, z) terms of their corners and lie within a few cells in x, and entries that differ
+        // in x inside an aligned block of 8 share a 64-byte sector (dense levels: linear in x; hashed levels: xor with the (y, z) term permutes a block
+        // within itself).  Eight waves of gathers go through the CU's L1 at once, so a line is found there only if it is asked for again within a few
+        // instructions: for each of the four (y, z) combinations the x-pairs of the three points leave back to back (6 gathers on 1 - 2 sectors), then
+        // the +-y / +-z points with their x-pairs adjacent as before.  The barriers pin that order; same values into the same registers.
+        // L1 -> L2 requests of a 4096-ray launch 107.2 M -> 100.4 M, launch 0.742 -> 0.715 ms: profiles/stencil_gather_order.txt
+        uint32_t xa[2], xb[2];
+        fine_geo<0>(L, oob, xp, xa, qa, oa);
+        fine_geo<0>(L, oob, xm, xb, qb, ob);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint32_t y = ty[i & 1], z = tz[i >> 1];
+            vc[2 * i] = table_entry<H16>(table, L.offset + gidx<GM>(L, tx[0], y, z));
+            vc[2 * i + 1] = table_entry<H16>(table, L.offset + gidx<GM>(L, tx[1], y, z));
+            va[2 * i] = table_entry<H16>(table, L.offset + gidx<GM>(L, xa[0], y, z));
+            va[2 * i + 1] = table_entry<H16>(table, L.offset + gidx<GM>(L, xa[1], y, z));
+            vb[2 * i] = table_entry<H16>(table, L.offset + gidx<GM>(L, xb[0], y, z));
+            vb[2 * i + 1] = table_entry<H16>(table, L.offset + gidx<GM>(L, xb[1], y, z));
+            __builtin_amdgcn_sched_barrier(0);
+        }
         fine_issue<1, GM, H16>(table, L, tx, ty, tz, oob, yp, vc2, qc2, oc2);
         fine_issue<1, GM, H16>(table, L, tx, ty, tz, oob, ym, vd, qd, od);
         fine_issue<2, GM, H16>(table, L, tx, ty, tz, oob, zp, ve, qe, oe);
