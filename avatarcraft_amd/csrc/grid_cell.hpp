@@ -1,6 +1,7 @@
-// avatarcraft_amd/csrc/grid_cell.hpp -- hash-grid addressing of the training-path encoder (hash_stencil.hip and the table-gradient scatter it includes,
-// table_scatter.hpp): a level's constants, the table index of a grid vertex (from coordinates, or from pre-multiplied axis terms), and the cell + fraction of a
-// coordinate on one axis.  Arithmetic per point is the one of hash_fwd_kernel (fma(x, scale, 0.5), floor, trilinear weights as products in d order).
+// avatarcraft_amd/csrc/grid_cell.hpp -- hash-grid addressing of the encoder operators (hashgrid.hip; hash_stencil.hip and the table-gradient scatter it includes,
+// table_scatter.hpp): a level's constants, the table index of a grid vertex (from coordinates, or from pre-multiplied axis terms), a cell's corners with their
+// interpolation weights, and the cell + fraction of a coordinate on one axis.  Arithmetic per point is the reference's (hashencoder.cu:122-166: fma(x, scale, 0.5),
+// floor, trilinear weights as products in d order).
 // Anonymous namespace, like field_tile.hpp: the including translation unit gets its own copy.
 #pragma once
 #include "ac_common.hpp"
@@ -19,14 +20,48 @@ __device__ __forceinline__ LevelC level_of(const ac::LevelTable &lt, uint32_t le
     return L;
 }
 
-__device__ __forceinline__ uint32_t gindex(const LevelC &L, uint32_t x, uint32_t y, uint32_t z)
+// the table index of grid vertex pg (hashencoder.cu:46-70): the hash of its coordinates on a hashed level, its row-major position on a dense one
+template <uint32_t D>
+__device__ __forceinline__ uint32_t gindex(const LevelC &L, const uint32_t (&pg)[D])
 {
+    constexpr uint32_t primes[3] = { 1u, 2654435761u, 805459861u };
     uint32_t index;
-    if (L.hashed) index = x ^ (y * 2654435761u) ^ (z * 805459861u);
-    else index = x + (y + z * L.stride1) * L.stride1;
+    if (L.hashed) {
+        index = pg[0];
+#pragma unroll
+        for (uint32_t d = 1; d < D; ++d) index ^= pg[d] * primes[d];
+    } else {
+        index = pg[D - 1];
+#pragma unroll
+        for (uint32_t d = D - 1; d-- > 0;) index = pg[d] + index * L.stride1;
+    }
     if (L.mask) index &= L.mask;
     else if (index >= L.size) index %= L.size;
     return index;
+}
+
+__device__ __forceinline__ uint32_t gindex(const LevelC &L, uint32_t x, uint32_t y, uint32_t z)
+{
+    const uint32_t pg[3] = { x, y, z };
+    return gindex<3>(L, pg);
+}
+
+// corner idx of the cell pg with fractions pos: its grid vertex pl and its interpolation weight, w0 times the factors of the axes in d order.  Bit n of idx
+// set: + 1 along the n-th axis.  skip < D leaves that axis out of both (the derivative along it, hashencoder.cu:177-220: the caller sets pl[skip], and
+// seeds the weight with the level's scale); skip = D: all axes
+template <uint32_t D>
+__device__ __forceinline__ float cell_vertex(uint32_t idx, uint32_t skip, float w0, const float (&pos)[D], const uint32_t (&pg)[D], uint32_t (&pl)[D])
+{
+    float w = w0;
+    uint32_t n = 0;
+#pragma unroll
+    for (uint32_t d = 0; d < D; ++d) {
+        if (d == skip) continue;
+        if ((idx & (1u << n)) == 0) { w *= 1.0f - pos[d]; pl[d] = pg[d]; }
+        else { w *= pos[d]; pl[d] = pg[d] + 1u; }
+        ++n;
+    }
+    return w;
 }
 
 // the same index from PRE-MULTIPLIED axis terms: ty = y * my, tz = z * mz with (my, mz) = the two hash primes on a hashed level, (stride, stride^2) on a dense one

@@ -64,14 +64,9 @@ class _Backend:
         # the reference dispatches on inputs.scalar_type() over Float / Half / Double (hashencoder.cu:352): one dtype for every tensor of the call
         code = L.dtype_code(inputs, "inputs", ((embeddings, "embeddings"), (outputs, "outputs"), (dy_dx, "dy_dx")))
         oh = _Backend._offsets_host(offsets)
-        if code != 0:
-            L.check(L.lib().ac_hash_encode_forward_typed(code, inputs.data_ptr(), embeddings.data_ptr(), offsets.data_ptr(), oh.ctypes.data,
-                                                         outputs.data_ptr(), B, D, C, L_, float(np.float32(S)), H, int(bool(calc_grad_inputs)),
-                                                         dy_dx.data_ptr(), L.current_stream(inputs.device)), "hash_encode_forward")
-            return
-        L.check(L.lib().ac_hash_encode_forward(inputs.data_ptr(), embeddings.data_ptr(), offsets.data_ptr(), oh.ctypes.data,
-                                               outputs.data_ptr(), B, D, C, L_, float(np.float32(S)), H, int(bool(calc_grad_inputs)),
-                                               dy_dx.data_ptr(), L.current_stream(inputs.device)), "hash_encode_forward")
+        L.check(L.lib().ac_hash_encode_forward_typed(code, inputs.data_ptr(), embeddings.data_ptr(), offsets.data_ptr(), oh.ctypes.data,
+                                                     outputs.data_ptr(), B, D, C, L_, float(np.float32(S)), H, int(bool(calc_grad_inputs)),
+                                                     dy_dx.data_ptr(), L.current_stream(inputs.device)), "hash_encode_forward")
 
     @staticmethod
     def hash_encode_backward(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C, L_, S, H, calc_grad_inputs, dy_dx,

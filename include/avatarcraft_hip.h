@@ -100,7 +100,7 @@ int ac_sh_encode_backward(const float *grad, const float *inputs, uint32_t B, ui
 /* ---- half / double tensors of the two encoders ------------------------------------------------
  * The reference dispatches both extensions over the dtype of their tensors (AT_DISPATCH_FLOATING_TYPES_AND_HALF: hashencoder.cu:352,391,
  * shencoder.cu:337,380; `CHECK_IS_FLOATING` accepts Float, Half, Double).  Same arguments as the fp32 entry points above with `dtype` in front and
- * untyped pointers: AC_DTYPE_F32 forwards to them; AC_DTYPE_F16 / AC_DTYPE_F64 are every tensor of the call (inputs, embeddings, outputs, dy_dx, grad,
+ * untyped pointers: AC_DTYPE_F32 is the fp32 entry points' call (they pass it); AC_DTYPE_F16 / AC_DTYPE_F64 are every tensor of the call (inputs, embeddings, outputs, dy_dx, grad,
  * grad_embeddings, grad_inputs) in that type.  Arithmetic: cell positions and interpolation weights in fp32 whatever the dtype (`float pos[D]`,
  * hashencoder.cu:125-133); half tensors are widened on load, accumulated in fp32 and rounded once on store (the table gradient: packed half2 atomics,
  * hashencoder.cu:293-299); double tensors accumulate in double.  Any other code: AC_ERR_BAD_ARG ("... must be a floating tensor"). */

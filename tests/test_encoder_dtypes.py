@@ -73,7 +73,8 @@ def _t(a, dtype):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("D,C,L,base,log2T,B", [(3, 2, 8, 4, 12, 600), (3, 4, 5, 4, 10, 333), (2, 2, 6, 8, 10, 300), (3, 1, 4, 16, 14, 129), (3, 8, 3, 4, 8, 64)])
+@pytest.mark.parametrize("D,C,L,base,log2T,B", [(3, 2, 8, 4, 12, 600), (3, 4, 5, 4, 10, 333), (2, 2, 6, 8, 10, 300), (3, 1, 4, 16, 14, 129), (3, 8, 3, 4, 8, 64),
+                                                (2, 4, 4, 4, 6, 257), (2, 8, 4, 4, 6, 257), (2, 1, 2, 2, 6, 257)])
 @pytest.mark.parametrize("dtype", ["float16", "float64"])
 def test_hash_encoder_half_and_double_vs_oracle(oracle, dtype, D, C, L, base, log2T, B):
     from avatarcraft_amd.encoder.hashencoder.backend import _backend

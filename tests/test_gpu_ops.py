@@ -20,7 +20,8 @@ def T(a, dtype=None):
 
 # ------------------------------------------------------------------ hash encoder
 @pytest.mark.parametrize("D,C,L,base,log2T,B", [(3, 2, 16, 16, 19, 5000), (3, 4, 8, 4, 12, 777), (2, 2, 6, 8, 10, 300),
-                                                (3, 1, 4, 16, 14, 129), (3, 8, 3, 4, 8, 64), (2, 1, 2, 2, 6, 1)])
+                                                (3, 1, 4, 16, 14, 129), (3, 8, 3, 4, 8, 64), (2, 1, 2, 2, 6, 1),
+                                                (2, 4, 4, 4, 6, 257), (2, 8, 4, 4, 6, 257)])
 def test_hash_forward_backward(oracle, D, C, L, base, log2T, B):
     from avatarcraft_amd.encoder.hashencoder.backend import _backend
     O = oracle
