@@ -83,6 +83,7 @@ __device__ __forceinline__ float dv_log1p(float x)
 //   (ac_sp_table.hpp; tools/gen_softplus_table.py; row 128 = 0) -- no exponential, no division: 10 VALU + one ds_read_b128
 //   (v_mul | v_min |.| | v_cvt_u32 | v_fract | v_lshlrev | 3 v_fma | 2 v_fma adding max(x, 0) as 0.5 x + 0.5 |x|); 14 before round 3.
 // spg: the table, [129][4] floats (LDS or global).  Bit-identical to oracle/ac_math.h: orc_softplus100.
+constexpr int SPQ_FLOATS = 129 * 4;              // softplus G table [129][4] (row 128 = 0)
 __device__ __forceinline__ float dv_softplus100(const float *__restrict__ spg, float x)
 {
     const float a4 = __builtin_fminf(__builtin_fabsf(x * 400.0f), 128.0f);
@@ -92,6 +93,22 @@ __device__ __forceinline__ float dv_softplus100(const float *__restrict__ spg, f
     float q = c.w;
     q = fma_(q, v, c.z); q = fma_(q, v, c.y); q = fma_(q, v, c.x);
     return fma_(0.5f, __builtin_fabsf(x), fma_(0.5f, x, q));
+}
+
+// softplus_100 and its derivative from the same table row: d/dx [max(x,0) + q(fract(|400 x|))] = [x > 0] + sign(x) 400 q'(v)
+__device__ __forceinline__ void softplus100_vg(const float *__restrict__ spg, float x, float &val, float &der)
+{
+    const float a4 = __builtin_fminf(__builtin_fabsf(x * 400.0f), 128.0f);
+    const uint32_t idx = (uint32_t)a4;
+    const float v = __builtin_amdgcn_fractf(a4);
+    const float4 c = *reinterpret_cast<const float4 *>(spg + idx * 4);
+    float q = c.w;
+    q = fma_(q, v, c.z); q = fma_(q, v, c.y); q = fma_(q, v, c.x);
+    float dq = 3.0f * c.w;
+    dq = fma_(dq, v, 2.0f * c.z); dq = fma_(dq, v, c.y);
+    const bool pos = x > 0.0f;
+    val = fma_(0.5f, __builtin_fabsf(x), fma_(0.5f, x, q));
+    der = (pos ? 1.0f : 0.0f) + (pos ? 400.0f : -400.0f) * dq;
 }
 
 // N values at once: all table rows are requested before any of them is used -- one LDS round trip per batch instead of one per value
@@ -137,5 +154,21 @@ __device__ __forceinline__ float unit_div(float a, float d, float inv) { const f
 
 // torch.sigmoid
 __device__ __forceinline__ float dv_sigmoid(float x) { return 1.0f / (1.0f + dv_exp(-x)); }
+
+// near_far_from_bound (cube)  instant_nsr.py:58-77
+__device__ __forceinline__ void cube_near_far(float ox, float oy, float oz, float dx, float dy, float dz, float bound, float &near, float &far)
+{
+    const float ex = dx + 1e-15f, ey = dy + 1e-15f, ez = dz + 1e-15f;
+    const float ax = (-bound - ox) / ex, bx = (bound - ox) / ex;
+    const float ay = (-bound - oy) / ey, by = (bound - oy) / ey;
+    const float az = (-bound - oz) / ez, bz = (bound - oz) / ez;
+    const float lx = ax < bx ? ax : bx, hx = ax > bx ? ax : bx;
+    const float ly = ay < by ? ay : by, hy = ay > by ? ay : by;
+    const float lz = az < bz ? az : bz, hz = az > bz ? az : bz;
+    near = lx; if (ly > near) near = ly; if (lz > near) near = lz;
+    far = hx; if (hy < far) far = hy; if (hz < far) far = hz;
+    if (near < 0.05f) near = 0.05f;
+}
+__device__ __forceinline__ bool is_inf(float v) { return __builtin_fabsf(v) == __builtin_inff(); }
 
 }  // namespace acdev

@@ -12,6 +12,8 @@
 // accurate flips enough of them to show (dWc1 3e-3 of max against the fp64 oracle, measured); the weight gradients (K = the tile's samples, through
 // LDS) stay fp32 as well
 #include "train_common.hpp"
+#include "field_color.hpp"
+#include "field_host.hpp"
 
 namespace {
 

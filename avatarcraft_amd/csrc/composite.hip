@@ -11,6 +11,11 @@
 //     to the transmittance scan and exact zeros (weight 0) to every sum, and writes nothing.  The weights and transmittances it recomputes are
 //     therefore the long forward's bit for bit.
 #include "train_common.hpp"
+#include "wave_ops.hpp"
+#include "ac_devmath.hpp"
+#include "ac_sp_table.hpp"
+
+using namespace acdev;
 
 namespace {
 

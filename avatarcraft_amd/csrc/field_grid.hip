@@ -8,9 +8,10 @@
 //                 maximum(grid * decay, new) -> mean.  Here two launches (ac_density_grid_update): the density of every grid point on the x-tiles of
 //                 ac_field_sdf_grid into a scratch volume, then one streaming pass that pools, merges into the running grid in place and forms the mean.
 //
-// The SDF itself is the renderer's own tile code (nsr_device.hpp: sdf_tile = hash gather + MFMA SDF network), so every value is bit-identical to
+// The SDF itself is the renderer's own tile code (sdf_mlp.hpp: sdf_tile = hash gather + MFMA SDF network), so every value is bit-identical to
 // ac_field_sdf / density() and therefore to the CPU oracle's orc_field_sdf.
-#include "field_tile.hpp"
+#include "sdf_mlp.hpp"
+#include "field_host.hpp"
 
 namespace {
 

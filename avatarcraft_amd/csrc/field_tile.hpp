@@ -1,8 +1,11 @@
-// avatarcraft_amd/csrc/field_tile.hpp -- the field on a tile of 16 packed samples, shared by the training operators (train_common.hpp) and the occupancy-grid
-// renderers (render_occupancy.hip): the workgroup shape and LDS image of the forward SDF query, the seven-evaluation stencil (fd_forward) and the whole
-// per-sample body (field_tile: stencil, normal, colour, NeuS alpha).  Anonymous namespace, like nsr_device.hpp: each translation unit gets its own copy.
+// avatarcraft_amd/csrc/field_tile.hpp -- the field on a tile of 16 packed samples: the workgroup shape and LDS image of the forward SDF query, the
+// seven-evaluation stencil (fd_forward) and the whole per-sample body (field_tile: stencil, normal, colour, NeuS alpha).
+// Included by sdf_stencil_train.hip, render_occupancy.hip and shade_tile.hpp (mesh_shade.hip, surface_rays.hip).
+// Anonymous namespace, like the field headers it includes: each translation unit gets its own copy.
 #pragma once
-#include "nsr_device.hpp"
+#include "sdf_mlp.hpp"
+#include "field_stencil.hpp"
+#include "field_color.hpp"
 
 namespace {
 
@@ -10,22 +13,6 @@ constexpr int FW = 8;                              // waves per workgroup of the
 constexpr int FBLOCK = FW * 64;
 constexpr int FWD_LDS_FLOATS = OFF_WAVE + FW * FE_SLAB;
 static_assert(FWD_LDS_FLOATS * 4 <= 160 * 1024, "LDS budget");
-
-// softplus_100 and its derivative from the same table row: d/dx [max(x,0) + q(fract(|400 x|))] = [x > 0] + sign(x) 400 q'(v)
-__device__ __forceinline__ void softplus100_vg(const float *__restrict__ spg, float x, float &val, float &der)
-{
-    const float a4 = __builtin_fminf(__builtin_fabsf(x * 400.0f), 128.0f);
-    const uint32_t idx = (uint32_t)a4;
-    const float v = __builtin_amdgcn_fractf(a4);
-    const float4 c = *reinterpret_cast<const float4 *>(spg + idx * 4);
-    float q = c.w;
-    q = fma_(q, v, c.z); q = fma_(q, v, c.y); q = fma_(q, v, c.x);
-    float dq = 3.0f * c.w;
-    dq = fma_(dq, v, 2.0f * c.z); dq = fma_(dq, v, c.y);
-    const bool pos = x > 0.0f;
-    val = fma_(0.5f, __builtin_fabsf(x), fma_(0.5f, x, q));
-    der = (pos ? 1.0f : 0.0f) + (pos ? 400.0f : -400.0f) * dq;
-}
 
 // the 7 evaluations of one tile: centre outputs (o = 4g + r) and the finite-difference gradient (the same in all four lanes of a sample)
 // (the renderers' exact stencil; they keep their own copy inline, because one helper shared with them changes the generated code)
@@ -92,13 +79,6 @@ __device__ __forceinline__ void field_tile(const float *__restrict__ lds, float 
     } else color_tile(lds, lane, px, py, pz, fn.nx, fn.ny, fn.nz, o16, rgb);
     sdf0 = o16[0];
     alpha = neus_alpha(lds, a, (dx * fn.nx + dy * fn.ny) + dz * fn.nz, sdf0, delta, inv_s);
-}
-
-int prep_args(RenderArgs &a, const ac_field *field, float bound, float eps)
-{
-    if (int rc = fill_args(a, field, bound)) return rc;
-    set_fd_eps(a, eps);
-    return AC_OK;
 }
 
 }  // namespace

@@ -216,7 +216,7 @@ __device__ __forceinline__ void stencil_scatter(Sink &sink, const LevelC &L, boo
                             *reinterpret_cast<float4 *>(row + 4 * w) = make_float4(v[16 * g + 4 * w], v[16 * g + 4 * w + 1], v[16 * g + 4 * w + 2], v[16 * g + 4 * w + 3]);
                         if (g == 0) { row[16] = __uint_as_float(c[0].pg); row[17] = __uint_as_float(cty); row[18] = __uint_as_float(ctz); }
                     }
-                    wave_sync_lds();
+                    wave_sync();
                     const float2 val = *reinterpret_cast<const float2 *>(st + t * PACK_STRIDE + 2 * k);
                     if (g == 0) { q0 = __float_as_uint(st[t * PACK_STRIDE + 16]); qy = __float_as_uint(st[t * PACK_STRIDE + 17]); qz = __float_as_uint(st[t * PACK_STRIDE + 18]); }
                     uint32_t tx, ty, tz;
@@ -229,7 +229,7 @@ __device__ __forceinline__ void stencil_scatter(Sink &sink, const LevelC &L, boo
                         else { tx = q0 + (lo ? 1u : 0u); ty = qy + (hi ? cmy : 0u); tz = side ? qz + 2u * cmz : qz - cmz; }
                     }
                     sink.add1(valid && (val.x != 0.0f || val.y != 0.0f), gindex_t(L, tx, ty, tz), val.x, val.y);
-                    wave_sync_lds();                                // (the next group's values overwrite the rows)
+                    wave_sync();                                // (the next group's values overwrite the rows)
                 }
             }
             sink.tick(1);

@@ -2,6 +2,7 @@
 // (mesh_pose.hip) and the posed first-hit render (surface_rays.hip).  All fp64, every operation rounded once (-ffp-contract=off), in the order
 // include/avatarcraft_hip.h states (ac_mesh_pose: Blended transform, Forward application, Normal).  Anonymous namespace: each translation unit gets its own copy.
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
 

@@ -2,6 +2,7 @@
 // (ac_mesh_vertex_attrs) and the texels of its atlas (ac_mesh_bake_texture).  Nothing in the reference: utils.save_mesh(vert, face, ...)
 // (stylize.py:263-269) writes geometry only.  Both kernels are the refine-and-shade tile body of shade_tile.hpp over tiles of 16 points.
 #include "shade_tile.hpp"
+#include "field_host.hpp"
 
 namespace {
 

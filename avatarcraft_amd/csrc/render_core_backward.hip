@@ -3,6 +3,7 @@
 // eikonal glue -> SDF query (sdf_stencil_train.hip) -> table-gradient scatter (hash_stencil.hip) -- and its two glue kernels.  The driver refuses a call
 // before it queues anything: check_core_backward holds every rule.
 #include "train_common.hpp"
+#include "field_host.hpp"
 
 namespace {
 

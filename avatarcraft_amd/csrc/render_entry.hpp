@@ -1,8 +1,8 @@
 // avatarcraft_amd/csrc/render_entry.hpp -- the host side that the C entries of the two ray renderers share (render_fused.hip, render_long.hip; included
-// behind nsr_device.hpp like it): what an entry is (RenderEntry), the one check of its options and buffers, the RenderArgs fill, the view of the posed
+// behind render_slab.hpp): what an entry is (RenderEntry), the one check of its options and buffers, the RenderArgs fill, the view of the posed
 // scratch and the posed sequence.  An entry is: its descriptor, check_render_entry, fill_entry_args, its launch.
 #pragma once
-#include "nsr_device.hpp"
+#include "render_slab.hpp"
 
 namespace {
 

@@ -31,7 +31,10 @@
 #include <map>
 #include <mutex>
 #include <vector>
-#include "nsr_device.hpp"
+#include "sdf_mlp.hpp"
+#include "field_stencil.hpp"
+#include "field_color.hpp"
+#include "render_slab.hpp"
 #include "render_entry.hpp"
 #include "render_worklist.hpp"      // (AC_XCD_CHUNK, AC_WORKLIST_POLICY and the XCD chunking live there, with the builder of the work lists)
 

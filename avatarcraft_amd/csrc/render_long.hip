@@ -1,7 +1,7 @@
 // avatarcraft_amd/csrc/render_long.hip -- the fused Instant-NSR renderer for any sample count the reference accepts (ac_render_rays_long,
 // ac_render_rays_long_pair, ac_sample_rays_long): num_steps >= 2 (not necessarily a multiple of 16), upsample_steps a multiple of 16, at most 512 samples per ray.
 //
-// The per-ray algorithm is render_rays_kernel's (render_fused.hip, MODE_FULL / MODE_UPSAMPLE): the same device blocks of nsr_device.hpp
+// The per-ray algorithm is render_rays_kernel's (render_fused.hip, MODE_FULL / MODE_UPSAMPLE): the same device blocks of the field headers (sdf_mlp.hpp, field_stencil.hpp, field_color.hpp)
 // (fd_normal among them), the same scans in the same order; the blocks still written out in both kernels are marked where they stand.
 // Where both renderers accept a sample count they agree bit for bit (tests/test_gpu_long_rays.py).
 // What differs:
@@ -18,7 +18,10 @@
 #ifndef AC_WPB
 #define AC_WPB 7
 #endif
-#include "nsr_device.hpp"
+#include "sdf_mlp.hpp"
+#include "field_stencil.hpp"
+#include "field_color.hpp"
+#include "render_slab.hpp"
 #include "render_entry.hpp"
 
 namespace {

@@ -8,6 +8,7 @@
 // Every form gives a sample, and a ray, the bits of the chain of stand-alone operators (tests/test_gpu_run_cuda.py, tests/test_gpu_marcher_edges.py).
 #include <atomic>
 #include "field_tile.hpp"
+#include "field_host.hpp"
 #include "rm_device.hpp"
 
 namespace {

@@ -2,7 +2,7 @@
 // table format, with
 //   AC_RENDER_KERNEL  the kernel's name
 //   AC_RENDER_H16     false: the fp32 hash table (two floats per entry);  true: the half table of ac_table_to_half (one dword per entry: a.table /
-//                     a.table_bytes describe n_entries dwords) -- every gather is one dword, widened exactly (nsr_device.hpp: table_entry); nothing else
+//                     a.table_bytes describe n_entries dwords) -- every gather is one dword, widened exactly (hash_gather.hpp: table_entry); nothing else
 //                     differs, so a render equals the fp32 kernel's render of the widened table bit for bit.
 // A second inclusion instead of a template parameter or a shared body function: the fp32 kernels keep their names and their instruction stream
 // (DESIGN.md section 5.9); no include guard on purpose.
@@ -355,7 +355,7 @@ __global__ __launch_bounds__(BLOCK) void AC_RENDER_KERNEL(const RenderArgs a)
             // coherence point, whichever XCD either wave runs on); the publisher drains its state stores (s_waitcnt vmcnt(0)) before it issues the flag
             // store; the taker issues its state loads only after lane 0 has observed the flag (control dependence + the wave barrier below), and the
             // memory pipeline returns a wave's loads in issue order.  No ordinary (cached) access ever touches these words.
-            // COMPILER ordering is pinned, not assumed: wave_sync() is `fence acq_rel, wavefront` + wave barrier (nsr_device.hpp) -- a wavefront-scope fence
+            // COMPILER ordering is pinned, not assumed: wave_sync() is `fence acq_rel, wavefront` + wave barrier (wave_ops.hpp) -- a wavefront-scope fence
             // costs no instruction (no cache maintenance) but forbids LLVM to move the relaxed state loads below above the flag load of the loop above
             // (ADVICE round 4); the publisher's side has the same fence between its state stores and its flag store.
             wave_sync();

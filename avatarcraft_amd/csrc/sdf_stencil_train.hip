@@ -19,6 +19,8 @@
 //   dW1 += d1 inp^T        48 MFMA   } accumulators live in registers for the whole kernel (a column of ones gives db1)
 // Weight-gradient partials are written per wave (no atomics) and summed by partials_reduce_kernel (deterministic).
 #include "train_common.hpp"
+#include "field_tile.hpp"
+#include "field_host.hpp"
 
 namespace {
 

@@ -4,6 +4,7 @@
 //                                  on the host over three kernels.
 // Both trace with the same scalar rule (root_step), shade through refine_shade_tile (shade_tile.hpp) and write the rows of ac_surface_out through one epilogue.
 #include "shade_tile.hpp"
+#include "field_host.hpp"
 #include "mesh_blend.hpp"
 
 namespace {

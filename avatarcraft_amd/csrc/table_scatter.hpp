@@ -8,6 +8,7 @@
 #pragma once
 #include <mutex>
 #include "grid_cell.hpp"
+#include "wave_ops.hpp"
 
 // ---- tuning constants (each may be overridden with -D: tools/build_variants.py) -----------------------------------------------------------------------------------
 #ifndef AC_ACC_W
@@ -29,12 +30,6 @@
 #endif
 
 namespace {
-
-__device__ __forceinline__ void wave_sync_lds()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 __device__ __forceinline__ bool nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
 
@@ -318,13 +313,13 @@ struct BinSink {
     __device__ __forceinline__ void flush()
     {
         tick(1);
-        wave_sync_lds();
+        wave_sync();
         {
             const uint32_t c = hist[lane];
             base[lane] = c ? atomicAdd(&qcount[lane], c) : 0u;
             hist[lane] = 0u;
         }
-        wave_sync_lds();
+        wave_sync();
         tick(2);
         // write-out, WU records per lane and trip: the LDS reads of a trip are issued together (one LDS latency per trip, not per record)
         constexpr uint32_t WU = 4;
@@ -354,7 +349,7 @@ struct BinSink {
                 }
             }
         }
-        wave_sync_lds();
+        wave_sync();
         cnt = 0;
         tick(3);
 #ifdef AC_PROFILE_FILL

@@ -2,7 +2,7 @@
 // the whole-core backward (render_core_backward.hip) chains the operators (sdf_stencil_train.hip, color_train.hip, composite.hip, hash_stencil.hip with its table_scatter.hpp).
 // RenderArgs and every kernel live in anonymous namespaces (one copy per translation unit), so what crosses files takes the C ABI's own types only.
 #pragma once
-#include "field_tile.hpp"
+#include "ac_common.hpp"
 
 namespace {
 

@@ -14,6 +14,7 @@
 #include "ac_common.hpp"
 #include "mesh_blend.hpp"
 #include "warp_accel.hpp"
+#include "wave_ops.hpp"
 
 namespace {
 
@@ -258,11 +259,6 @@ constexpr int PK_WAVES = 8;                     // waves per workgroup (they sha
 constexpr int WARP_WAVES = 4;                   // waves per SIMD the search kernel is compiled for (<= 128 VGPRs)
 constexpr uint32_t PK_WAVE_BYTES = 64 * 8 + 64 * 4 + 3 * 64 * 4 + FQ * 4 + GQ * 4 + TQ * 2;
 
-__device__ __forceinline__ void wave_sync_lds()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 // the closest point to p on face f of the mesh as the caller gave it (corners from verts / faces)
 __device__ __forceinline__ void face_closest(const float *__restrict__ verts, const int32_t *__restrict__ faces, size_t f, const double (&p)[3], double (&cq)[3])
 {
@@ -384,7 +380,7 @@ __global__ __launch_bounds__(PK_WAVES * 64, WARP_WAVES) void warp_samples_accel_
     sbid[lane] = 0x7fffffffu;
 #pragma unroll
     for (int k = 0; k < 3; ++k) sq[k * 64 + lane] = pf[k];
-    wave_sync_lds();
+    wave_sync();
     WP_TICK(7)
     uint32_t th = 0, tt = 0, gh = 0, gt = 0, fh = 0, ft = 0;             // wave-uniform ring positions: tile pairs, group triples, face pairs
     // work counters of this wave (wave-uniform; one atomic each at the end -> AccelView::work: what bench.py prices the search with)
@@ -392,7 +388,7 @@ __global__ __launch_bounds__(PK_WAVES * 64, WARP_WAVES) void warp_samples_accel_
 
     // exact distances of n queued (sample, face) pairs, folded into the samples' running minima
     auto exact_batch = [&](uint32_t n) {
-        wave_sync_lds();
+        wave_sync();
         bool act = (uint32_t)lane < n;
         const uint32_t e = fq[(fh + (act ? (uint32_t)lane : 0u)) & (FQ - 1)];
         const uint32_t s = e >> 14, slot = e & 16383u;
@@ -408,20 +404,20 @@ __global__ __launch_bounds__(PK_WAVES * 64, WARP_WAVES) void warp_samples_accel_
         }
         n_exact += n;
         const unsigned long long prev = sbest[s];
-        wave_sync_lds();
+        wave_sync();
         if (act) atomicMin(&sbest[s], d2b);
-        wave_sync_lds();
+        wave_sync();
         const unsigned long long cur = sbest[s];
         if (act && d2b == cur && cur < prev) sbid[s] = 0x7fffffffu;      // a strictly better distance: ids recorded for the old one are void
-        wave_sync_lds();
+        wave_sync();
         if (act && d2b == cur) atomicMin(&sbid[s], (uint32_t)id);
         fh += n;
-        wave_sync_lds();
+        wave_sync();
     };
     // up to GSTEPS x 16 queued (sample, tile) pairs: the four sub-boxes of the tile (groups of 8 consecutive faces, boxes in the tile's frame) against
     // the sample's current bound, lane = (pair, group); the survivors are queued as (sample, tile, group)
     auto group_trip = [&]() {
-        wave_sync_lds();
+        wave_sync();
         const uint32_t np = (tt - th) < (uint32_t)(16 * GSTEPS) ? (tt - th) : (uint32_t)(16 * GSTEPS);
 #pragma unroll
         for (int u = 0; u < GSTEPS; ++u) {
@@ -450,7 +446,7 @@ __global__ __launch_bounds__(PK_WAVES * 64, WARP_WAVES) void warp_samples_accel_
     // up to DSTEPS x 8 queued (sample, tile, group) triples: the group's 8 faces against their bounding discs (a lower bound of a face's distance)
     // under the sample's current bound, lane = (triple, face); survivors are queued for the exact routine
     auto disc_trip = [&]() {
-        wave_sync_lds();
+        wave_sync();
         const uint32_t ne = (gt - gh) < (uint32_t)(8 * DSTEPS) ? (gt - gh) : (uint32_t)(8 * DSTEPS);
         uint32_t slot[DSTEPS], smp[DSTEPS]; bool have[DSTEPS];
         float4 sp[DSTEPS], sn[DSTEPS];

@@ -1,4 +1,4 @@
-"""-m gpu: the issue order of the finite-difference stencil's gathers (nsr_device.hpp: stencil_levels).
+"""-m gpu: the issue order of the finite-difference stencil's gathers (field_stencil.hpp: stencil_levels).
 
 The stencil issues the centre's and the +x / -x points' corners grouped by their (y, z) combination, so that gathers of one cache line leave back to
 back.  That is instruction order only: every corner must still land in the register its interpolation reads.  Small renders (<= 64 rays, 16 + 16

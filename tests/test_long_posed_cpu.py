@@ -16,7 +16,7 @@ F32 = np.float32
 
 
 def cube_near_far(ro, rd, bound):
-    """near_far_from_bound (cube) in fp32, the renderers' arithmetic (nsr_device.hpp: cube_near_far)"""
+    """near_far_from_bound (cube) in fp32, the renderers' arithmetic (ac_devmath.hpp: cube_near_far)"""
     ro, rd, b = np.asarray(ro, F32), np.asarray(rd, F32), F32(bound)
     with np.errstate(divide="ignore", invalid="ignore"):
         e = rd + F32(1e-15)
