@@ -5,6 +5,7 @@ import numpy as np
 import torch
 
 from ... import _lib as L
+from ..._scratch import ScratchCache
 
 
 def _floating(t, name):
@@ -13,7 +14,7 @@ def _floating(t, name):
 
 
 PRIVATE_COPIES = 16         # private copies of the small dense levels in the stencil backward (same-address atomic bursts)
-_SCRATCH = {}               # (kind, device, stream, layout) -> uint8 tensor, grown to the largest batch seen (free_scratch() drops them)
+_SCRATCH = ScratchCache()   # (kind, device, layout, stream) -> uint8 tensor, grown to the largest batch seen (free_scratch() drops them)
 
 
 BINNED_SCATTER = True       # hashed levels through the binned two-pass scatter (needs ~8 KB of device scratch per sample)
@@ -22,12 +23,7 @@ BINNED_SCATTER = True       # hashed levels through the binned two-pass scatter 
 def _scratch_buffer(key, nbytes, device):
     """One buffer per (kind, device, STREAM, table layout): two streams never share queues (concurrent backward passes would race on the
     slot counters), a smaller batch (the last partial batch of an epoch) re-uses the buffer of the largest one instead of re-allocating."""
-    key = key + (int(L.current_stream(device) or 0),)
-    cur = _SCRATCH.get(key)
-    if nbytes and (cur is None or cur.numel() < nbytes):
-        _SCRATCH[key] = None                       # release the old one first
-        cur = _SCRATCH[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    return cur
+    return _SCRATCH.get(key + (int(L.current_stream(device) or 0),), nbytes, device)
 
 
 def free_scratch():
