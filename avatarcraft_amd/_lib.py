@@ -92,6 +92,10 @@ class ac_mesh_pose_opts(C.Structure):
     _fields_ = [("iters", i32), ("tol", f32)]
 
 
+class ac_cluster_grid(C.Structure):
+    _fields_ = [("lo", C.c_double * 3), ("h", C.c_double), ("n", u32 * 3)]
+
+
 _SIGS = {
     "ac_version": ([], C.c_int),
     "ac_last_error": ([], C.c_char_p),
@@ -197,6 +201,9 @@ _SIGS = {
     "ac_mesh_compact_scratch": ([u32, u32], C.c_size_t),
     "ac_mesh_compact_count": ([vp, u32, u32, vp, vp, u32, vp, C.c_size_t, vp, vp], C.c_int),
     "ac_mesh_compact_emit": ([vp, u32, u32, vp, vp, u32, vp, C.c_size_t, vp, vp, u32, vp, vp, u32, vp], C.c_int),
+    "ac_mesh_cluster_scratch": ([u32, u32], C.c_size_t),
+    "ac_mesh_cluster_count": ([vp, u32, vp, u32, C.POINTER(ac_cluster_grid), vp, C.c_size_t, vp, vp, vp], C.c_int),
+    "ac_mesh_cluster_emit": ([vp, u32, vp, u32, C.POINTER(ac_cluster_grid), vp, C.c_size_t, vp, vp, vp, u32, vp, vp, u32, vp], C.c_int),
     "ac_density_grid_update_scratch": ([u32], C.c_size_t),
     "ac_density_grid_update": ([C.POINTER(ac_field), vp, u32, f32, f32, f32, vp, vp, vp, C.c_size_t, vp], C.c_int),
     "ac_table_to_half": ([vp, u32, vp, vp, vp], C.c_int),

@@ -1,0 +1,328 @@
+// avatarcraft_amd/csrc/mesh_cluster.hip -- decimating the exported mesh on the device by vertex clustering on a grid (ac_mesh_cluster_count / _emit).  The contract
+// is worded in include/avatarcraft_hip.h.  It stands in for nothing in the reference (its export writes every marching-cubes triangle).
+//
+// The vertices of one grid cell merge.  A cell is found through an open-addressing table in scratch: slots keyed by the 64-bit cell key, claimed with a 64-bit
+// compare-exchange under linear probing; a slot holds the smallest member index (integer atomic min), the member count and three int64 sums of the members'
+// fixed-point offsets inside the cell (integer atomic adds); every vertex remembers its slot.  A cell's leader is its smallest member, clusters are numbered by
+// ascending leader (flags -> the ordered scans of ac_scan.hpp), and the position is a function of the exact integer sums: nothing depends on scheduling or on
+// the hash, although the table is filled with atomics.  No wave ever waits for another one: see mc_slot.  No floating-point atomics.
+#include "ac_common.hpp"
+#include "ac_scan.hpp"
+
+namespace {
+
+constexpr uint32_t MCL_ITEMS = 1024;              // vertices (and triangles) per workgroup of the scanned passes: 256 threads x 4 consecutive items
+constexpr uint32_t MCL_MAX = 0x7fffffffu;         // indices are int32
+constexpr uint32_t MCL_MAX_N = 1u << 21;          // cells per axis: three of them fit a 63-bit key
+constexpr uint64_t MCL_EMPTY = ~0ull;             // no key: a key stays below 2^63
+enum { MCL_INFO_BAD_V = 0, MCL_INFO_BAD_T = 1, MCL_INFO_WORDS = 64 };
+
+// gfx950 has eight XCDs with private L2s: inside the filling launch the table is touched by agent-scope atomics on GLOBAL pointers only
+typedef __attribute__((address_space(1))) uint64_t mcl_gu64;
+typedef __attribute__((address_space(1))) int32_t mcl_gi32;
+typedef __attribute__((address_space(1))) uint32_t mcl_gu32;
+
+struct MclGrid { double lo[3], h; uint32_t n[3]; };
+
+// a vertex in the grid, per axis (the header's definitions, in their order): t = (v - lo) / h; valid iff 0 <= t < n + 1 (a NaN or an infinity fails the
+// comparisons); c = min(floor(t), n - 1); q = floor((t - c) 2^30), 0 <= q < 2^31
+__device__ __forceinline__ bool mcl_cell(const double *__restrict__ p, const MclGrid &g, uint64_t &key, uint32_t q[3])
+{
+    uint64_t c3[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double t = (p[a] - g.lo[a]) / g.h;
+        if (!(t >= 0.0 && t < (double)(g.n[a] + 1u))) return false;
+        const double fl = floor(t), top = (double)(g.n[a] - 1u);
+        const double c = fl < top ? fl : top;
+        const double f = t - c;
+        c3[a] = (uint64_t)c;
+        q[a] = (uint32_t)(int64_t)floor(f * 1073741824.0);
+    }
+    key = (c3[0] * g.n[1] + c3[1]) * g.n[2] + c3[2];
+    return true;
+}
+
+__device__ __forceinline__ uint64_t mcl_mix(uint64_t x)           // (the finaliser of splitmix64: where a cell's probe starts; no output depends on it)
+{
+    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
+    x ^= x >> 27; x *= 0x94d049bb133111ebull;
+    return x ^ (x >> 31);
+}
+
+// The slot of `key`, claiming one if the key has none.  A lock-free probe, no wait: a slot's key changes once, from MCL_EMPTY to a cell key, and never again.
+// A trip ends the walk if it reads the key or wins the compare-exchange; if the exchange FAILED it returns what the slot holds now -- a key, for good -- and the
+// walk ends there or moves on.  Every slot is looked at once: the table has capacity >= 2 V slots and at most V keys, so an empty slot or the key's own comes up
+// within `capacity` trips whatever other waves do and whether or not they run at all.
+__device__ __forceinline__ uint64_t mcl_slot(uint64_t *keys, uint64_t mask, uint64_t key)
+{
+    uint64_t s = mcl_mix(key) & mask;
+    for (;;) {
+        uint64_t seen = __hip_atomic_load((mcl_gu64 *)(keys + s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (seen == key) return s;
+        if (seen == MCL_EMPTY) {
+            if (__hip_atomic_compare_exchange_strong((mcl_gu64 *)(keys + s), &seen, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return s;
+            if (seen == key) return s;
+        }
+        s = (s + 1u) & mask;
+    }
+}
+
+struct MclTable { uint64_t *keys; int32_t *lead; uint32_t *cnt; uint64_t *sums; int32_t *rank; };
+
+__global__ __launch_bounds__(256) void mcl_init_kernel(MclTable tb, uint64_t capacity, uint32_t *__restrict__ info)
+{
+    const uint64_t s = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (s < capacity) {
+        tb.keys[s] = MCL_EMPTY; tb.lead[s] = 0x7fffffff; tb.cnt[s] = 0u;
+        tb.sums[3 * s] = 0ull; tb.sums[3 * s + 1] = 0ull; tb.sums[3 * s + 2] = 0ull;
+    }
+    if (s < MCL_INFO_WORDS) info[s] = 0u;
+}
+
+// one vertex per lane: its cell's slot, then four integer adds and one integer min on it (sums of non-negative q below 2^31: 2^31 members stay below 2^62)
+__global__ __launch_bounds__(256) void mcl_fill_kernel(const double *__restrict__ verts, uint32_t V, MclGrid g, MclTable tb, uint64_t mask, int64_t *__restrict__ slot,
+                                                       uint32_t *info)
+{
+    const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+    if (v >= V) return;
+    uint64_t key; uint32_t q[3];
+    if (!mcl_cell(verts + 3 * (size_t)v, g, key, q)) { slot[v] = -1; atomicAdd(info + MCL_INFO_BAD_V, 1u); return; }
+    const uint64_t s = mcl_slot(tb.keys, mask, key);
+    slot[v] = (int64_t)s;
+    (void)__hip_atomic_fetch_min((mcl_gi32 *)(tb.lead + s), (int32_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    (void)__hip_atomic_fetch_add((mcl_gu32 *)(tb.cnt + s), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) (void)__hip_atomic_fetch_add((mcl_gu64 *)(tb.sums + 3 * s + a), (uint64_t)q[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// (the table is the filling launch's: read-only from here on)
+__device__ __forceinline__ bool mcl_is_leader(const int64_t *__restrict__ slot, const int32_t *__restrict__ lead, uint32_t v)
+{
+    const int64_t s = slot[v];
+    return s >= 0 && lead[s] == (int32_t)v;
+}
+
+// a triangle's three slots, -1 if it is invalid (an index outside [0, V) or an invalid vertex).  Two vertices share a cluster iff they share a slot.
+__device__ __forceinline__ bool mcl_tri_slots(const int32_t *__restrict__ tris, uint32_t t, uint32_t V, const int64_t *__restrict__ slot, int64_t s[3])
+{
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int32_t i = tris[3 * (size_t)t + k];
+        if ((uint32_t)i >= V) return false;
+        s[k] = slot[i];
+        if (s[k] < 0) return false;
+    }
+    return true;
+}
+__device__ __forceinline__ bool mcl_survives(const int64_t s[3]) { return s[0] != s[1] && s[1] != s[2] && s[0] != s[2]; }
+
+// leaders among a thread's four vertices (bits 0-3), surviving triangles among its four triangles (bits 4-7), invalid triangles (bits 8-11)
+template <bool WANT_V, bool WANT_T>
+__device__ __forceinline__ uint32_t mcl_flags(const int32_t *__restrict__ tris, uint32_t T, uint32_t V, const int64_t *__restrict__ slot,
+                                              const int32_t *__restrict__ lead, uint32_t i0)
+{
+    uint32_t m = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < 4; ++r) {
+        const uint32_t i = i0 + r;
+        if (WANT_V && i < V && mcl_is_leader(slot, lead, i)) m |= 1u << r;
+        if (WANT_T && i < T) {
+            int64_t s[3];
+            if (!mcl_tri_slots(tris, i, V, slot, s)) m |= 256u << r;
+            else if (mcl_survives(s)) m |= 16u << r;
+        }
+    }
+    return m;
+}
+
+__global__ __launch_bounds__(256) void mcl_count_kernel(const int32_t *__restrict__ tris, uint32_t T, uint32_t V, const int64_t *__restrict__ slot,
+                                                        const int32_t *__restrict__ lead, uint32_t *__restrict__ bsum, uint32_t *info)
+{
+    __shared__ uint32_t sh[8];
+    const uint32_t m = mcl_flags<true, true>(tris, T, V, slot, lead, blockIdx.x * MCL_ITEMS + threadIdx.x * 4u);
+    uint32_t tot;
+    (void)block_exscan_256((uint32_t)__builtin_popcount(m & 15u) | ((uint32_t)__builtin_popcount((m >> 4) & 15u) << 16), sh, tot);      // <= 1024 of either: 16 bits each
+    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
+    const uint32_t bad = (uint32_t)__builtin_popcount(m >> 8);
+    if (bad) atomicAdd(info + MCL_INFO_BAD_T, bad);
+}
+
+// rank of every leader among the leaders in ascending order -> rank[its slot]; the two counts the scan does not write
+__global__ __launch_bounds__(256) void mcl_rank_kernel(uint32_t V, const int64_t *__restrict__ slot, const int32_t *__restrict__ lead, const uint32_t *__restrict__ boff,
+                                                       int32_t *__restrict__ rank, const uint32_t *__restrict__ info, uint32_t *__restrict__ counts)
+{
+    __shared__ uint32_t sh[8];
+    const uint32_t i0 = blockIdx.x * MCL_ITEMS + threadIdx.x * 4u;
+    const uint32_t m = mcl_flags<true, false>(nullptr, 0u, V, slot, lead, i0);
+    uint32_t tot;
+    uint32_t c = boff[2 * blockIdx.x] + block_exscan_256((uint32_t)__builtin_popcount(m), sh, tot);
+#pragma unroll
+    for (uint32_t r = 0; r < 4; ++r)
+        if ((m >> r) & 1u) rank[slot[i0 + r]] = (int32_t)c++;
+    if (blockIdx.x == 0 && threadIdx.x == 0) { counts[2] = info[MCL_INFO_BAD_V]; counts[3] = info[MCL_INFO_BAD_T]; }
+}
+
+__global__ __launch_bounds__(256) void mcl_cluster_kernel(uint32_t V, const int64_t *__restrict__ slot, const int32_t *__restrict__ rank, int32_t *__restrict__ cluster)
+{
+    const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+    if (v >= V) return;
+    const int64_t s = slot[v];
+    cluster[v] = s >= 0 ? rank[s] : -1;
+}
+
+// one lane per vertex; a leader writes its cluster's row.  positions = lo + (c + S / (members 2^30)) h per axis, in that order, in fp64 (no contraction: the
+// build's -ffp-contract=off); the cell index c comes back out of the key
+__global__ __launch_bounds__(256) void mcl_emit_clusters_kernel(uint32_t V, MclGrid g, MclTable tb, const int64_t *__restrict__ slot, int32_t *__restrict__ leader,
+                                                                uint32_t *__restrict__ members, double *__restrict__ positions, uint32_t n_clusters)
+{
+    const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+    if (v >= V || !mcl_is_leader(slot, tb.lead, v)) return;
+    const int64_t s = slot[v];
+    const uint32_t c = (uint32_t)tb.rank[s];
+    if (c >= n_clusters) return;
+    const uint32_t n = tb.cnt[s];
+    const uint64_t key = tb.keys[s];
+    const uint64_t cz = key % g.n[2], cxy = key / g.n[2];
+    const uint64_t cell[3] = { cxy / g.n[1], cxy % g.n[1], cz };
+    leader[c] = (int32_t)v;
+    members[c] = n;
+    const double den = (double)n * 1073741824.0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double mean = (double)(int64_t)tb.sums[3 * s + a] / den;
+        const double u = (double)cell[a] + mean;
+        const double w = u * g.h;
+        positions[3 * (size_t)c + a] = g.lo[a] + w;
+    }
+}
+
+__global__ __launch_bounds__(256) void mcl_emit_triangles_kernel(const int32_t *__restrict__ tris, uint32_t T, uint32_t V, const int64_t *__restrict__ slot,
+                                                                 const int32_t *__restrict__ rank, const uint32_t *__restrict__ boff, int32_t *__restrict__ tris_out,
+                                                                 int32_t *__restrict__ kept_triangles, uint32_t n_kept)
+{
+    __shared__ uint32_t sh[8];
+    const uint32_t i0 = blockIdx.x * MCL_ITEMS + threadIdx.x * 4u;
+    const uint32_t m = (mcl_flags<false, true>(tris, T, V, slot, nullptr, i0) >> 4) & 15u;
+    uint32_t tot;
+    uint32_t o = boff[2 * blockIdx.x + 1] + block_exscan_256((uint32_t)__builtin_popcount(m), sh, tot);
+#pragma unroll
+    for (uint32_t r = 0; r < 4; ++r) {
+        if (!((m >> r) & 1u)) continue;
+        const uint32_t t = i0 + r;
+        if (o < n_kept) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) tris_out[3 * (size_t)o + k] = rank[slot[tris[3 * (size_t)t + k]]];
+            kept_triangles[o] = (int32_t)t;
+        }
+        ++o;
+    }
+}
+
+size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
+uint32_t mcl_blocks(uint32_t n) { return (uint32_t)(((uint64_t)n + MCL_ITEMS - 1) / MCL_ITEMS); }
+
+struct MclLayout { size_t info, keys, lead, cnt, sums, rank, slot, bsum, boff, total; uint64_t capacity; uint32_t nblk; };
+MclLayout mcl_layout(uint32_t V, uint32_t T)
+{
+    MclLayout l{};
+    l.capacity = 2;
+    while (l.capacity < 2 * (uint64_t)V) l.capacity <<= 1;        // a power of two >= 2 V: the table is never more than half full
+    l.nblk = mcl_blocks(V > T ? V : T);
+    size_t o = 0;
+    l.info = o; o += al256(MCL_INFO_WORDS * 4);
+    l.keys = o; o += al256((size_t)l.capacity * 8);
+    l.sums = o; o += al256((size_t)l.capacity * 24);
+    l.lead = o; o += al256((size_t)l.capacity * 4);
+    l.cnt = o; o += al256((size_t)l.capacity * 4);
+    l.rank = o; o += al256((size_t)l.capacity * 4);
+    l.slot = o; o += al256((size_t)V * 8);
+    l.bsum = o; o += al256((size_t)l.nblk * 4);
+    l.boff = o; o += al256((size_t)l.nblk * 8);
+    l.total = o;
+    return l;
+}
+
+struct MclView { MclTable tb; uint32_t *info, *bsum, *boff; int64_t *slot; };
+MclView mcl_view(void *scratch, const MclLayout &l)
+{
+    char *sc = static_cast<char *>(scratch);
+    MclView w;
+    w.tb.keys = reinterpret_cast<uint64_t *>(sc + l.keys); w.tb.sums = reinterpret_cast<uint64_t *>(sc + l.sums);
+    w.tb.lead = reinterpret_cast<int32_t *>(sc + l.lead); w.tb.cnt = reinterpret_cast<uint32_t *>(sc + l.cnt); w.tb.rank = reinterpret_cast<int32_t *>(sc + l.rank);
+    w.info = reinterpret_cast<uint32_t *>(sc + l.info); w.bsum = reinterpret_cast<uint32_t *>(sc + l.bsum); w.boff = reinterpret_cast<uint32_t *>(sc + l.boff);
+    w.slot = reinterpret_cast<int64_t *>(sc + l.slot);
+    return w;
+}
+
+// what both entries refuse, before any launch
+int mcl_check(const char *who, const double *verts, uint32_t V, const int32_t *tris, uint32_t T, const ac_cluster_grid *grid, const void *scratch, size_t scratch_bytes,
+              MclLayout &l, MclGrid &g)
+{
+    if (V > MCL_MAX || T > MCL_MAX) { ac::set_error("%s: V %u or T %u above 2^31 - 1 (indices are int32)", who, V, T); return AC_ERR_BAD_ARG; }
+    if (!grid) { ac::set_error("%s: NULL grid", who); return AC_ERR_BAD_ARG; }
+    if (!(grid->h > 0.0) || !isfinite(grid->h)) { ac::set_error("%s: cell edge h %g must be finite and > 0", who, grid->h); return AC_ERR_BAD_ARG; }
+    for (int a = 0; a < 3; ++a) {
+        if (grid->n[a] < 1u || grid->n[a] > MCL_MAX_N) { ac::set_error("%s: n[%d] %u outside [1, 2^21] cells", who, a, grid->n[a]); return AC_ERR_BAD_ARG; }
+        g.lo[a] = grid->lo[a]; g.n[a] = grid->n[a];
+    }
+    g.h = grid->h;
+    if ((V && !verts) || (T && !tris) || ((V || T) && !scratch)) { ac::set_error("%s: NULL buffer", who); return AC_ERR_BAD_ARG; }
+    l = mcl_layout(V, T);
+    if ((V || T) && scratch_bytes < l.total) { ac::set_error("%s: scratch of %zu bytes needed, %zu given", who, l.total, scratch_bytes); return AC_ERR_BAD_ARG; }
+    return AC_OK;
+}
+
+}  // namespace
+
+AC_API size_t ac_mesh_cluster_scratch(uint32_t V, uint32_t T)
+{
+    if (V > MCL_MAX || T > MCL_MAX) return 0;
+    return mcl_layout(V, T).total;
+}
+
+AC_API int ac_mesh_cluster_count(const double *vertices, uint32_t V, const int32_t *triangles, uint32_t T, const ac_cluster_grid *grid, void *scratch,
+                                 size_t scratch_bytes, int32_t *cluster, uint32_t *counts, ac_stream_t stream)
+{
+    MclLayout l; MclGrid g;
+    if (int rc = mcl_check("mesh_cluster_count", vertices, V, triangles, T, grid, scratch, scratch_bytes, l, g)) return rc;
+    if (!counts) { ac::set_error("mesh_cluster_count: NULL counts"); return AC_ERR_BAD_ARG; }
+    if (V && !cluster) { ac::set_error("mesh_cluster_count: NULL cluster"); return AC_ERR_BAD_ARG; }
+    hipStream_t st = (hipStream_t)stream;
+    if (V == 0 && T == 0) {                       // nothing to cluster: no launch
+        if (hipMemsetAsync(counts, 0, 16, st) != hipSuccess) return ac::check_launch("mesh_cluster_count");
+        return AC_OK;
+    }
+    const MclView w = mcl_view(scratch, l);
+    hipLaunchKernelGGL(mcl_init_kernel, dim3((uint32_t)((l.capacity + 255u) / 256u)), dim3(256), 0, st, w.tb, l.capacity, w.info);
+    if (V) hipLaunchKernelGGL(mcl_fill_kernel, dim3((V + 255u) / 256u), dim3(256), 0, st, vertices, V, g, w.tb, l.capacity - 1u, w.slot, w.info);
+    hipLaunchKernelGGL(mcl_count_kernel, dim3(l.nblk), dim3(256), 0, st, triangles, T, V, w.slot, w.tb.lead, w.bsum, w.info);
+    hipLaunchKernelGGL(pair_scan_kernel, dim3(1), dim3(1024), 0, st, w.bsum, l.nblk, w.boff, counts);
+    hipLaunchKernelGGL(mcl_rank_kernel, dim3(l.nblk), dim3(256), 0, st, V, w.slot, w.tb.lead, w.boff, w.tb.rank, w.info, counts);
+    if (V) hipLaunchKernelGGL(mcl_cluster_kernel, dim3((V + 255u) / 256u), dim3(256), 0, st, V, w.slot, w.tb.rank, cluster);
+    return ac::check_launch("mesh_cluster_count");
+}
+
+AC_API int ac_mesh_cluster_emit(const double *vertices, uint32_t V, const int32_t *triangles, uint32_t T, const ac_cluster_grid *grid, void *scratch,
+                                size_t scratch_bytes, int32_t *leader, uint32_t *members, double *positions, uint32_t n_clusters, int32_t *triangles_out,
+                                int32_t *kept_triangles, uint32_t n_kept_triangles, ac_stream_t stream)
+{
+    MclLayout l; MclGrid g;
+    if (int rc = mcl_check("mesh_cluster_emit", vertices, V, triangles, T, grid, scratch, scratch_bytes, l, g)) return rc;
+    if (n_clusters > V || n_kept_triangles > T) {
+        ac::set_error("mesh_cluster_emit: n_clusters %u > V %u or n_kept_triangles %u > T %u", n_clusters, V, n_kept_triangles, T);
+        return AC_ERR_BAD_ARG;
+    }
+    if ((n_clusters && (!leader || !members || !positions)) || (n_kept_triangles && (!triangles_out || !kept_triangles))) {
+        ac::set_error("mesh_cluster_emit: NULL output buffer");
+        return AC_ERR_BAD_ARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const MclView w = mcl_view(scratch, l);
+    if (n_clusters)
+        hipLaunchKernelGGL(mcl_emit_clusters_kernel, dim3((V + 255u) / 256u), dim3(256), 0, st, V, g, w.tb, w.slot, leader, members, positions, n_clusters);
+    if (n_kept_triangles)
+        hipLaunchKernelGGL(mcl_emit_triangles_kernel, dim3(mcl_blocks(T)), dim3(256), 0, st, triangles, T, V, w.slot, w.tb.rank, w.boff, triangles_out,
+                           kept_triangles, n_kept_triangles);
+    return ac::check_launch("mesh_cluster_emit");
+}

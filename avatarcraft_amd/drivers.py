@@ -159,7 +159,9 @@ def export_mesh(net, path, bound=NSR_BOUND, resolution=512, **kw):
     the reference's counterpart (extract_geometry(NSR_BOUND, 512) + save_mesh, stylize.py:263-269) writes vertices and faces only.  Returns the mesh dict.
     A path ending in .obj writes a TEXTURED mesh instead: net.extract_textured_mesh(bound, resolution, **kw) -> name.obj, name.mtl (geometry.save_obj) and
     name.png (geometry.save_png).  components="largest" (or any spec of geometry.select_components, forwarded like every keyword) drops the field's floaters on
-    the device before anything is shaded or baked: export_mesh(net, "avatar.obj", components="largest") writes the body alone."""
+    the device before anything is shaded or baked: export_mesh(net, "avatar.obj", components="largest") writes the body alone.  decimate=k (forwarded as well)
+    merges the vertices of every cluster cell of k marching-cubes cells on the device, after the cleaning and before the shading and the atlas layout:
+    export_mesh(net, "avatar.obj", components="largest", decimate=4) writes a body of about a sixteenth of the triangles, its texture baked from the field."""
     import os
     from .geometry import save_obj, save_ply, save_png
     if str(path).lower().endswith(".obj"):
@@ -204,7 +206,8 @@ def export_animation(net, body_model, poses=None, shape_from=None, shape_to=None
     poses [F,72] (render_type "animate") or shape_from / shape_to [1,10] ("interp_shape"; render_type None picks by which is given).
     out_pattern ending in .obj: frame files (geometry.save_obj) that all reference ONE material and ONE texture image, written before the first frame
     (animation_paths names them); ending in .ply: binary PLYs with vertex normals and colours.  **kw goes to extract_textured_mesh / extract_colored_mesh
-    (texture_size, threshold, refine_steps, components ...: components="largest" keeps the floaters out of every frame); iters / tol to pose_mesh.
+    (texture_size, threshold, refine_steps, components, decimate ...: components="largest" keeps the floaters out of every frame, decimate=k poses the
+    decimated mesh); iters / tol to pose_mesh.
     yields (frame index, posed mesh dict of pose_mesh); rank / world: this process writes the frames shard_indices(n_frames, rank, world) like
     render_animation (the shared files are written by every rank with the same content)."""
     import os

@@ -1040,7 +1040,8 @@ class NeRFNetwork(NeRFRenderer):
                         u[xi * N: xi * N + len(x), yi * N: yi * N + len(y), zi * N: zi * N + len(z)] = self.density(pts, bound).reshape(len(x), len(y), len(z))
         return u.cpu().numpy()
 
-    def extract_geometry(self, bound: float, resolution: int, threshold: int = 0.0, device=None, mesher=None, return_torch=False, slab_layers=None, components=None):
+    def extract_geometry(self, bound: float, resolution: int, threshold: int = 0.0, device=None, mesher=None, return_torch=False, slab_layers=None, components=None,
+                         decimate=None):
         """iso-surface of the SDF (reference :706-764; its one call is extract_geometry(NSR_BOUND, 512), stylize.py:267): vertices [V,3] float64 in world
         units, triangles [F,3].  The reference runs PyMCubes' marching_cubes on u = -sdf (third party, not in this image).
         mesher: "native" (default on the GPU) = ac_field_sdf_grid + ac_marching_cubes on the device: the volume never leaves it, one shared vertex per
@@ -1055,8 +1056,19 @@ class NeRFNetwork(NeRFRenderer):
                 full; other values are legal.  Needs mesher "native" (or None on the GPU).
         components: None = every connected component the field has, floaters included (as ever); a spec of geometry.select_components -- "largest",
                 ("largest", k), ("min_faces", n), a bool mask or a callable on the size table -- = only those components, labelled and compacted on the device
-                (geometry.clean_mesh: order preserved, so the dense and the streamed route give the same cleaned mesh).  Native mesher only."""
+                (geometry.clean_mesh: order preserved, so the dense and the streamed route give the same cleaned mesh).  Native mesher only.
+        decimate: None = every marching-cubes triangle (as ever); a real k >= 1 = the vertices of every cluster cell of k marching-cubes cells merged on the device
+                (mesh_decimate.cluster_grid / decimate_mesh: vertex clustering, order preserved, the same from run to run and on the dense and the streamed
+                route), AFTER the components are cleaned, so that a floater never merges into the body.  This call has no field pass: with decimate the vertices
+                are the clusters' MEAN vertices, near the level set and not on it (at most about one cluster cell off) -- extract_colored_mesh /
+                extract_textured_mesh(decimate=k) project them back.  Triangles that lose a corner to a merge are dropped; duplicates are not removed and the
+                result need not be manifold.  Native mesher only."""
         native_ok = self.encoder.embeddings.is_cuda and self._sdf_supported()
+        if decimate is not None:
+            from .mesh_decimate import cluster_grid, decimate_mesh
+            if mesher not in (None, "native") or not native_ok:
+                raise RuntimeError("extract_geometry(decimate=...) decimates the native mesher's mesh on the device: it needs mesher='native' and the default SDF side of NeRFNetwork on the GPU")
+            decimate = cluster_grid(bound, resolution, decimate)                      # (a bad k raises before any device work)
         if components is not None and (mesher not in (None, "native") or not native_ok):
             raise RuntimeError("extract_geometry(components=...) cleans the native mesher's mesh on the device: it needs mesher='native' and the default SDF side of NeRFNetwork on the GPU")
         if slab_layers is not None:
@@ -1084,6 +1096,9 @@ class NeRFNetwork(NeRFRenderer):
                 from .geometry import clean_mesh
                 m = clean_mesh(dict(vertices=v, triangles=t), components)
                 v, t = m["vertices"], m["triangles"]
+            if decimate is not None:
+                m = decimate_mesh(dict(vertices=v, triangles=t), decimate)
+                v, t = m["vertices"], m["triangles"]
             return (v, t) if return_torch else (v.cpu().numpy(), t.cpu().numpy())
         u = -1.0 * self.extract_fields(bound, resolution)
         if mesher == "mcubes":
@@ -1099,7 +1114,7 @@ class NeRFNetwork(NeRFRenderer):
         return vertices, triangles
 
     def extract_colored_mesh(self, bound: float, resolution: int, threshold: float = 0.0, refine_steps: int = 3, tol: float = 1e-5, colors: bool = True,
-                             return_torch=False, slab_layers=None, components=None):
+                             return_torch=False, slab_layers=None, components=None, decimate=None):
         """the mesh of extract_geometry(mesher="native") with what a viewer wants on it (the reference's save_mesh, stylize.py:263-269, writes bare geometry):
         every vertex projected from the grid edge's linear zero crossing onto the level set sdf = -threshold (at most refine_steps Newton steps along the
         finite-difference gradient, never further than one grid cell), the field's normal and the colour network there -- one launch over the marching-cubes
@@ -1110,9 +1125,16 @@ class NeRFNetwork(NeRFRenderer):
         slab_layers: extract_geometry's (None: the whole volume at once; an integer: streamed, the same mesh in the memory of one window).
         components: extract_geometry's (None: every component).  The mesh is cleaned right after the geometry and BEFORE the vertices are shaded: a dropped vertex
         costs nothing, and a kept one gets what it would have got (the attributes are per vertex).  The dict then also carries component_sizes [C,2] (vertices,
-        triangles of every component of the unfiltered mesh) and components_kept [C] bool."""
+        triangles of every component of the unfiltered mesh) and components_kept [C] bool.
+        decimate: extract_geometry's (None: every triangle; k: clusters of k marching-cubes cells).  The mesh is decimated after the cleaning and BEFORE the
+        vertices are shaded: no removed vertex is ever shaded, and every kept one is projected from its cluster's mean onto the level set, never further than one
+        CLUSTER cell (k grid cells) instead of one grid cell.  The dict then also carries cluster_members [V] (how many marching-cubes vertices each vertex
+        stands for)."""
         if slab_layers is not None:
             slab_layers = nsr_ops.check_slab_layers(slab_layers, "extract_colored_mesh")
+        if decimate is not None:
+            from .mesh_decimate import cluster_grid, decimate_mesh
+            decimate = cluster_grid(bound, resolution, decimate)
         if not (self.encoder.embeddings.is_cuda and self._sdf_supported()):
             raise RuntimeError("extract_colored_mesh needs the default SDF side of NeRFNetwork on the GPU")
         if colors and not self._fused_supported(ignore_curvature=True):
@@ -1124,15 +1146,21 @@ class NeRFNetwork(NeRFRenderer):
             from .geometry import clean_mesh
             cleaned = clean_mesh(dict(vertices=v, triangles=t), components)
             v, t = cleaned["vertices"], cleaned["triangles"]
+        max_move, members = 2.0 * bound / (resolution - 1.0), None
+        if decimate is not None:
+            dm = decimate_mesh(dict(vertices=v, triangles=t), decimate)
+            v, t, members, max_move = dm["vertices"], dm["triangles"], dm["cluster_members"], decimate["h"]
         with torch.no_grad():
             f = self._field() if self._fused_supported(ignore_curvature=True) else self._field_sdf_only()
-            a = nsr_ops.mesh_vertex_attrs(f, v, bound, nsr_ops.FD_STEP, refine_steps=refine_steps, tol=tol, max_move=2.0 * bound / (resolution - 1.0),
+            a = nsr_ops.mesh_vertex_attrs(f, v, bound, nsr_ops.FD_STEP, refine_steps=refine_steps, tol=tol, max_move=max_move,
                                           target_sdf=-float(threshold), want_rgb=colors)
         out = dict(vertices=a["positions"].double(), triangles=t, normals=a["normals"], sdf=a["sdf"], status=a["status"])
         if colors:
             out["colors"] = a["rgb"]
         if cleaned is not None:
             out.update(component_sizes=cleaned["component_sizes"], components_kept=cleaned["components_kept"])
+        if members is not None:
+            out["cluster_members"] = members
         return out if return_torch else {k: x.cpu().numpy() for k, x in out.items()}
 
     def render_surface(self, rays_o, rays_d, bound, bg_color=None, normal_epsilon_ratio=0.0, max_ray_batch=None, **opts):
@@ -1208,7 +1236,7 @@ class NeRFNetwork(NeRFRenderer):
                 "face_id": o["face_id"].reshape(B, N)}
 
     def extract_textured_mesh(self, bound: float, resolution: int, texture_size: int = 2048, cell=None, threshold: float = 0.0, refine_steps: int = 3,
-                              tol: float = 1e-5, return_torch=False, slab_layers=None, components=None):
+                              tol: float = 1e-5, return_torch=False, slab_layers=None, components=None, decimate=None):
         """extract_colored_mesh's mesh with the colour network baked into a texture instead of sampled at the vertices, so that colour detail no longer depends on
         the vertex density: every triangle gets half a cell of a closed-form texture_size^2 atlas (geometry.atlas_layout; cell=None: the largest that fits), every
         owned texel's point on its triangle is projected onto the level set like a vertex (never further than one grid cell) and shaded there, one launch
@@ -1217,10 +1245,16 @@ class NeRFNetwork(NeRFRenderer):
         The atlas guarantees bilinear lookups only (no mip chain).  Same model requirements as extract_colored_mesh(colors=True).
         slab_layers: extract_geometry's; an atlas too small for the triangle count of a finer mesh raises as ever.
         components: extract_colored_mesh's.  The mesh is cleaned BEFORE the atlas is laid out, so the cells are sized for the kept triangles only: debris no longer
-        lowers the texel density of the body."""
+        lowers the texel density of the body.
+        decimate: extract_colored_mesh's.  The mesh is decimated BEFORE the atlas is laid out, so the cells are sized for the decimated triangle count, and the
+        texels carry the colour detail the removed vertices carried; a texel's point is projected never further than one CLUSTER cell."""
         from .geometry import atlas_layout
         m = self.extract_colored_mesh(bound, resolution, threshold=threshold, refine_steps=refine_steps, tol=tol, colors=True, return_torch=True,
-                                      slab_layers=slab_layers, components=components)
+                                      slab_layers=slab_layers, components=components, decimate=decimate)
+        max_move = 2.0 * bound / (resolution - 1.0)
+        if decimate is not None:
+            from .mesh_decimate import cluster_grid
+            max_move = cluster_grid(bound, resolution, decimate)["h"]
         T = m["triangles"].shape[0]
         try:
             lay = atlas_layout(T, texture_size, cell)
@@ -1228,7 +1262,7 @@ class NeRFNetwork(NeRFRenderer):
             raise RuntimeError(f"extract_textured_mesh: {e}") from e
         with torch.no_grad():
             b = nsr_ops.mesh_bake_texture(self._field(), m["vertices"].float(), m["triangles"], texture_size, lay["cell"], bound, nsr_ops.FD_STEP,
-                                          refine_steps=refine_steps, tol=tol, max_move=2.0 * bound / (resolution - 1.0), target_sdf=-float(threshold))
+                                          refine_steps=refine_steps, tol=tol, max_move=max_move, target_sdf=-float(threshold))
             tex = torch.floor(b["rgb"].clamp(0.0, 1.0) * 255.0 + 0.5).to(torch.uint8)
         m.update(texture=tex, owner=b["owner"], texel_sdf=b["sdf"], texel_status=b["status"])
         if not return_torch:

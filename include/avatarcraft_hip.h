@@ -941,6 +941,50 @@ int ac_mesh_compact_emit(const int32_t *triangles /*[T,3]*/, uint32_t T, uint32_
                          void *scratch, size_t scratch_bytes, int32_t *vertex_map /*[V]*/, int32_t *kept_vertices /*[V']*/, uint32_t n_kept_vertices,
                          int32_t *triangles_out /*[T',3]*/, int32_t *kept_triangles /*[T']*/, uint32_t n_kept_triangles, ac_stream_t stream);
 
+/* ---- decimating the exported mesh: vertex clustering on a grid, on the device (csrc/mesh_cluster.hip; added entries and one added struct, no struct of an
+ * existing call changes: ABI stays 10).  It stands in for nothing in the reference, whose export writes every marching-cubes triangle.  The step only decides
+ * WHICH vertices merge and gives a starting point near the surface; position, normal and colour are restored from the field by ac_mesh_vertex_attrs and
+ * ac_mesh_bake_texture, which pull every point onto the level set.  Everything computed here is an integer or a function of exact integer sums: the result
+ * depends on neither scheduling nor any hash and equals a numpy restatement exactly (tests/mesh_decimate_cases.py).
+ * A mesh is vertices [V,3] float64 (as ac_marching_cubes_emit writes them) and triangles [T,3] int32.  Definitions:
+ *   Cluster grid: lo[3], a cell edge h > 0 and n[3] cells per axis, each in [1, 2^21].  For a vertex v, per axis:
+ *     t = (v - lo) / h, an fp64 subtraction then an fp64 division.  The vertex is VALID iff, on every axis, t is finite and 0 <= t < n + 1 (the slack of one
+ *       cell keeps a vertex at the upper bound, whose t may round just above n, inside the grid).
+ *     c = min(floor(t), n - 1);  f = t - (double)c;  q = (int64) floor(f 2^30), so 0 <= q < 2^31.
+ *     Key of the cell = (cx n_y + cy) n_z + cz, in 64 bits.
+ *     An invalid vertex belongs to no cluster (cluster[v] = -1) and is counted.
+ *   Leader of a cell: the smallest index among its valid vertices.  Clusters are numbered by ascending leader.
+ *   cluster[v]: the rank of its cell's leader; leader[c]: the leader's old index (ascending in c); members[c]: the member count;
+ *   positions[c], per axis: lo + ((double)c_axis + (double)S / ((double)members 2^30)) h, S the int64 sum of the members' q -- evaluated in exactly that order in
+ *     fp64, no contraction, correctly rounded division: the mean of the members up to the 2^-30 of a cell their offsets are rounded to.
+ *   Triangles: INVALID if an index lies outside [0, V) or names an invalid vertex: counted, never emitted.  A valid triangle maps to (cluster[a], cluster[b],
+ *     cluster[c]); it is COLLAPSED, and dropped, iff two of the three are equal.  Surviving triangles keep their relative order and their vertex order
+ *     (orientation); kept_triangles [T'] = their old indices, ascending.  Duplicate triangles are NOT removed, back-to-back pairs of a collapsed thin sheet
+ *     included: vertex clustering does not preserve manifoldness and this step does not repair it.
+ * ac_mesh_cluster_count: an open-addressing table in scratch with a power-of-two capacity >= 2 V, slots keyed by the cell key and claimed with a 64-bit
+ *   compare-exchange under linear probing; a slot holds the leader (integer atomic min), the member count and the three sums (integer atomic adds); then
+ *   is_leader -> the ordered scans -> cluster, and the triangle flags through the same scan.  No wave waits for another one (every retry is a lock-free retry:
+ *   a slot's key changes once, from empty to a key), no floating-point atomics.  counts (DEVICE, [4]) = { V', T', invalid vertices, invalid triangles }.
+ *   The scratch (the _scratch function of (V, T) bytes: 44 per table slot, 8 per vertex and a little) is kept unchanged until the emit call.
+ * ac_mesh_cluster_emit : the same head, then the outputs with n_clusters = V' and n_kept_triangles = T' of the count call (nothing is written past them; an
+ *   output of length 0 may be NULL).  Ordered writes, no atomics.  It reads the scratch, the triangles and the grid, not the vertices.
+ * AC_ERR_BAD_ARG before any launch, with the rule in the message: a NULL required buffer (triangles may be NULL when T == 0, vertices and cluster when V == 0),
+ * V or T above 2^31 - 1, h not finite or <= 0, an n outside [1, 2^21], a scratch that is too short, n_clusters > V or n_kept_triangles > T.
+ * V == 0 with T == 0 is legal and launches nothing (counts = 0). */
+typedef struct ac_cluster_grid {
+    double lo[3];                       /* the grid's lower corner */
+    double h;                           /* cell edge */
+    uint32_t n[3];                      /* cells per axis */
+} ac_cluster_grid;
+size_t ac_mesh_cluster_scratch(uint32_t V, uint32_t T);
+int ac_mesh_cluster_count(const double *vertices /*[V,3]*/, uint32_t V, const int32_t *triangles /*[T,3]*/, uint32_t T, const ac_cluster_grid *grid,
+                          void *scratch, size_t scratch_bytes, int32_t *cluster /*[V]*/,
+                          uint32_t *counts /* DEVICE [4] = { V', T', invalid vertices, invalid triangles } */, ac_stream_t stream);
+int ac_mesh_cluster_emit(const double *vertices /*[V,3]*/, uint32_t V, const int32_t *triangles /*[T,3]*/, uint32_t T, const ac_cluster_grid *grid,
+                         void *scratch, size_t scratch_bytes, int32_t *leader /*[V']*/, uint32_t *members /*[V']*/, double *positions /*[V',3]*/,
+                         uint32_t n_clusters, int32_t *triangles_out /*[T',3]*/, int32_t *kept_triangles /*[T']*/, uint32_t n_kept_triangles,
+                         ac_stream_t stream);
+
 /* ---- rendering from a half-precision hash table (opt-in, inference only) ----------------------------------------------------------------------------
  * The half table holds ONE dword per entry of the fp32 table [n_entries][2] (n_entries = field->offsets[16]): channel 0 as an IEEE binary16 in the low
  * half, channel 1 in the high half -- 4 bytes per entry instead of 8, the same level offsets.  ac_table_to_half makes it: every value is rounded to
