@@ -8,6 +8,8 @@ two records must agree byte for byte.
 
 Only public names are used, each spelled nsr_ops.<name>, so the file runs unchanged in an older tree: copy it there.  A section that raises is recorded
 with the exception's text (and compared like any other entry); dump then ends with status 2.  256 rays (a 16 x 16 view), 2 000 samples for the operators.
+The second half (model_sections) drives NeRFNetwork's own methods: render() in eval and with gradients, the step renders, a cuda_ray net, the mesh export
+on a 24^3 grid (texture_size 256: the atlas of its ~1 000 triangles), pose_mesh and the first-hit renders.
 """
 import os
 import sys
@@ -41,6 +43,8 @@ class Record:
             t = v.detach()
             self.items[name + "#meta"] = np.array([str(t.dtype), str(tuple(t.shape)), str(tuple(t.stride()))], dtype="U")
             self.items[name + "#bytes"] = t.cpu().contiguous().reshape(-1).view(torch.uint8).numpy().copy()
+        elif isinstance(v, np.ndarray):
+            self.add(name, torch.from_numpy(np.ascontiguousarray(v)))
         elif v is None or isinstance(v, (bool, int, float, str)):
             self.items[name + "#value"] = np.array(repr(v), dtype="U")
         else:                                               # an object (a WarpMesh): its device tensors
@@ -71,6 +75,148 @@ def golden_net(train):
     sd["encoder.offsets"] = torch.from_numpy(p["offsets"])
     net.load_state_dict(sd, strict=True)
     return net.to(DEV).train(train)
+
+
+def model(train, **ctor):
+    """golden_net's parameters on a NeRFNetwork(**ctor): every entry whose shape the variant keeps (a view-direction colour layer 1 keeps its seeded start)"""
+    from avatarcraft_amd.instant_nsr import NeRFNetwork
+    gold = golden_net(train).state_dict()
+    torch.manual_seed(3)
+    net = NeRFNetwork(**ctor)
+    mine = net.state_dict()
+    net.load_state_dict({k: v for k, v in gold.items() if k in mine and mine[k].shape == v.shape}, strict=False)
+    return net.to(DEV).train(train)
+
+
+def model_sections(rec, ro, rd, bg, up, body):
+    """NeRFNetwork's own methods, public names only: render() in eval and with gradients, the step renders and backward_last, a cuda_ray net, the mesh export,
+    pose_mesh, the first-hit renders.  256 rays, the synthetic body, a 24^3 grid, a 256^2 atlas."""
+    from avatarcraft_amd import nsr_ops
+    verts, faces, Ts = body
+    N = ro.shape[0]
+    ro3, rd3 = ro[None], rd[None]
+    grads = lambda net: {k: v.grad for k, v in net.named_parameters()}
+    common = dict(bg_color=bg, cos_anneal_ratio=0.5, normal_epsilon_ratio=0.0)
+
+    # ---- render() in eval under no_grad
+    net = golden_net(False)
+    with torch.no_grad():
+        rec.section("m_eval_64_64", lambda: net.render(ro3, rd3, 64, BOUND, 64, **common))
+        rec.section("m_eval_lean", lambda: net.render(ro3, rd3, 64, BOUND, 64, per_sample=False, **common))
+        rec.section("m_eval_opacity_only", lambda: net.render(ro3, rd3, 64, BOUND, 64, opacity_only=True, **common))
+        rec.section("m_eval_long_40_16", lambda: net.render(ro3, rd3, 40, BOUND, 16, **common))
+        net.render_table_dtype = "half"
+        rec.section("m_eval_half", lambda: net.render(ro3, rd3, 64, BOUND, 64, **common))
+        net.render_table_dtype = "float"
+        rec.section("m_eval_staged", lambda: net.render(ro3, rd3, 64, BOUND, 64, staged=True, max_ray_batch=100, **dict(common, bg_color=bg[0])))      # (one colour: every batch gets bg_color whole)
+        rec.section("m_eval_guided", lambda: net.render(ro3, rd3, 64, BOUND, 64, render_can=True, verts=torch.from_numpy(verts).to(DEV), **common))
+        posed = dict(render_can=False, verts=verts, faces=faces, Ts=Ts, **common)
+        rec.section("m_posed_32_32", lambda: net.render(ro3, rd3, 32, BOUND, 32, **posed))
+        net.skip_masked_samples = True
+        rec.section("m_posed_32_32_skip", lambda: net.render(ro3, rd3, 32, BOUND, 32, **posed))
+        net.skip_masked_samples = False
+        net.posed_long_rays = True
+        rec.section("m_posed_long_40_16", lambda: net.render(ro3, rd3, 40, BOUND, 16, **posed))
+        net.posed_long_rays = False
+
+    # ---- render() in train mode with gradients: a fixed upstream, every .grad
+    def trained(net, num_steps=64, upsample_steps=64, **kw):
+        def f():
+            net.zero_grad(set_to_none=True)
+            torch.manual_seed(21)
+            out = net.render(ro3, rd3, num_steps, BOUND, upsample_steps, perturb=True, **dict(common, **kw))
+            loss = (out["rgb"].reshape(-1, 3) * up["image"]).sum() + (out["weight_sum"].reshape(-1) * up["wsum"]).sum() + 0.1 * out["gradient_error"]
+            if isinstance(out["curvature_error"], torch.Tensor):
+                loss = loss + 0.05 * out["curvature_error"]
+            loss.backward()
+            net.check_finite()
+            return out, grads(net)
+        return f
+    net = golden_net(True)
+    for how in ("core", "ops", False):
+        net.fused_training = how
+        rec.section(f"m_train_{how}", trained(net))
+    net.fused_training = "core"
+    rec.section("m_train_long_40_16", trained(net, 40, 16))
+    rec.section("m_train_posed_32_32", trained(net, 32, 32, render_can=False, verts=verts, faces=faces, Ts=Ts))
+    rec.section("m_train_viewdirs", trained(model(True, use_viewdirs=True)))
+    rec.section("m_train_curvature", trained(model(True, curvature_loss=True)))
+    nsr_ops.free_scratch()
+
+    # ---- the step renders and backward_last
+    def step_pair():
+        net = golden_net(True)
+        torch.manual_seed(31)
+        out = net.render_step_pair(ro, rd, 64, 64, BOUND, lambda: torch.rand(N, 3, device=DEV))
+        net.backward_last(g_image=up["image"], g_weights_sum=up["wsum"], g_eik=torch.tensor(0.1, device=DEV))
+        net.check_finite()
+        return out, grads(net)
+    rec.section("m_step_pair", step_pair)
+
+    def view_train():
+        net = golden_net(True)
+        torch.manual_seed(32)
+        out = net.render_view_train(ro, rd, 64, 64, BOUND, lambda k, n: torch.rand(n, 3, device=DEV), 100)
+        net.backward_last(g_image=up["image"], g_weights_sum=up["wsum"], g_eik=torch.linspace(0.05, 0.2, out[1].shape[0], device=DEV))
+        net.check_finite()
+        return out, grads(net)
+    rec.section("m_view_train", view_train)
+    net = golden_net(False)
+    for oo in (False, True):
+        def view_nograd():
+            torch.manual_seed(33)
+            with torch.no_grad():
+                return net.render_view_nograd(ro, rd, 64, 64, BOUND, lambda n: torch.rand(n, 3, device=DEV), 100, opacity_only=oo)
+        rec.section(f"m_view_nograd_opacity{int(oo)}", view_nograd)
+    nsr_ops.free_scratch()
+
+    # ---- a cuda_ray net: the density grid, run_cuda in eval (one launch / rounds), in train without and with a graph
+    occ = model(False, cuda_ray=True)
+    state = lambda: (occ.density_grid, occ.mean_density, occ.mean_count, occ.iter_density, occ.local_step)
+    rec.section("m_occ_grid_1", lambda: (occ.update_extra_state(BOUND), state()))
+    rec.section("m_occ_grid_2", lambda: (occ.update_extra_state(BOUND), state()))
+    with torch.no_grad():
+        rec.section("m_occ_eval", lambda: (occ.render(ro3, rd3, 64, BOUND, 64, **common), occ._last_cuda_rounds))
+        occ.occupancy_rounds = True
+        rec.section("m_occ_eval_rounds", lambda: (occ.render(ro3, rd3, 64, BOUND, 64, **common), occ._last_cuda_rounds > 0))
+        occ.occupancy_rounds = False
+        occ.train()
+        torch.manual_seed(41)
+        rec.section("m_occ_train_unbudgeted", lambda: occ.render(ro3, rd3, 64, BOUND, 64, perturb=True, **common))
+        rec.section("m_occ_grid_3", lambda: (occ.update_extra_state(BOUND), state()))
+        rec.section("m_occ_train_budgeted", lambda: (occ.render(ro3, rd3, 64, BOUND, 64, perturb=True, **common), occ.step_counter))
+    for fused in (True, False):
+        occ.occupancy_fused_shading = fused
+        rec.section(f"m_occ_train_grad_fused{int(fused)}", trained(occ))
+    occ.occupancy_fused_shading = True
+
+    # ---- density, the SDF grid, the mesh export in each of its forms
+    net = golden_net(False)
+    G = 24
+    with torch.no_grad():
+        x = (torch.rand(500, 3, generator=torch.Generator().manual_seed(5)) * 2 - 1).to(DEV)
+        rec.section("m_density", lambda: net.density(x, BOUND))
+    rec.section("m_extract_fields", lambda: net.extract_fields(BOUND, G))
+    for name, kw in (("dense", {}), ("slab8", dict(slab_layers=8)), ("largest", dict(components="largest")), ("decimate2", dict(decimate=2)),
+                     ("all", dict(slab_layers=8, components="largest", decimate=2)), ("tetra", dict(mesher="tetra"))):
+        rec.section(f"m_geometry_{name}", lambda: net.extract_geometry(BOUND, G, **kw))
+    rec.section("m_geometry_torch", lambda: net.extract_geometry(BOUND, G, return_torch=True))
+    colored = rec.section("m_colored", lambda: net.extract_colored_mesh(BOUND, G))
+    rec.section("m_colored_no_colors", lambda: net.extract_colored_mesh(BOUND, G, colors=False, return_torch=True))
+    rec.section("m_colored_clean_decimate", lambda: net.extract_colored_mesh(BOUND, G, components="largest", decimate=2, slab_layers=8))
+    rec.section("m_textured", lambda: net.extract_textured_mesh(BOUND, G, texture_size=256))
+    rec.section("m_textured_clean_decimate", lambda: net.extract_textured_mesh(BOUND, G, texture_size=256, components="largest", decimate=2, return_torch=True))
+    if colored is not None:
+        rec.section("m_pose_numpy", lambda: net.pose_mesh(colored, dict(faces=faces), verts, Ts))
+        on_dev = {k: torch.from_numpy(np.ascontiguousarray(v)).to(DEV) for k, v in colored.items()}
+        rec.section("m_pose_torch", lambda: net.pose_mesh(on_dev, dict(faces=torch.from_numpy(faces).to(DEV)), torch.from_numpy(verts).to(DEV),
+                                                          torch.from_numpy(Ts).to(DEV)))
+
+    # ---- the first-hit renders: whole, in three parts, without colours
+    with torch.no_grad():
+        for name, kw in (("whole", {}), ("parts", dict(max_ray_batch=100)), ("no_rgb", dict(want_rgb=False)), ("parts_no_rgb", dict(max_ray_batch=100, want_rgb=False))):
+            rec.section(f"m_surface_{name}", lambda: net.render_surface(ro3, rd3, BOUND, bg_color=bg, **kw))
+            rec.section(f"m_surface_posed_{name}", lambda: net.render_surface_posed(ro3, rd3, BOUND, verts, faces, Ts, bg_color=bg, **kw))
 
 
 def dump(path):
@@ -205,6 +351,8 @@ def dump(path):
         return (z, {k: v for k, v in net.named_parameters()}, {k: v.grad for k, v in net.named_parameters()}, flat,
                 [{k: v for k, v in s.items() if isinstance(v, (int, float, torch.Tensor))} for s in stats])
     rec.section("sds_steps", steps)
+    nsr_ops.free_scratch()
+    model_sections(rec, ro, rd, bg, up, (verts, faces, Ts))
 
     np.savez_compressed(path, **rec.items)
     print(f"DUMP entries {len(rec.items)} tensors {sum(k.endswith('#bytes') for k in rec.items)} errors {rec.errors}", flush=True)
