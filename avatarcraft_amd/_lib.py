@@ -76,6 +76,14 @@ class ac_atlas_opts(C.Structure):
     _fields_ = [("size", u32), ("cell", u32)]
 
 
+class ac_occlusion_opts(C.Structure):
+    _fields_ = [("n_dirs", i32), ("n_steps", i32), ("dirs", vp), ("weights", vp), ("dists", vp), ("gain", f32), ("level", f32)]
+
+
+class ac_bake_out(C.Structure):
+    _fields_ = [("rgb", vp), ("owner", vp), ("normals", vp), ("positions", vp), ("sdf", vp), ("status", vp), ("occlusion", vp)]
+
+
 class ac_surface_opts(C.Structure):
     _fields_ = [("bound", f32), ("fd_eps", f32), ("level", f32), ("tol", f32), ("max_iters", i32), ("step_scale", f32), ("min_step", f32), ("guard", f32)]
 
@@ -188,6 +196,9 @@ _SIGS = {
                                      vp, u32, vp, u32, vp], C.c_int),
     "ac_mesh_vertex_attrs": ([C.POINTER(ac_field), vp, u32, vp, C.POINTER(ac_mesh_attr_opts), vp, vp, vp, vp, vp, vp], C.c_int),
     "ac_mesh_bake_texture": ([C.POINTER(ac_field), vp, u32, vp, u32, C.POINTER(ac_atlas_opts), C.POINTER(ac_mesh_attr_opts), vp, vp, vp, vp, vp, vp], C.c_int),
+    "ac_field_occlusion": ([C.POINTER(ac_field), vp, vp, vp, u32, f32, C.POINTER(ac_occlusion_opts), vp, vp], C.c_int),
+    "ac_mesh_bake_maps": ([C.POINTER(ac_field), vp, u32, vp, u32, C.POINTER(ac_atlas_opts), C.POINTER(ac_mesh_attr_opts), C.POINTER(ac_occlusion_opts),
+                           C.POINTER(ac_bake_out), vp], C.c_int),
     "ac_render_rays_surface": ([C.POINTER(ac_field), C.POINTER(ac_surface_opts), vp, vp, u32, vp, C.POINTER(ac_surface_out), vp], C.c_int),
     "ac_render_rays_surface_warped_scratch": ([u32], C.c_size_t),
     "ac_render_rays_surface_warped": ([C.POINTER(ac_field), C.POINTER(ac_surface_opts), f32, vp, vp, u32, vp, C.POINTER(ac_warp_mesh), vp, C.c_size_t,

@@ -1,7 +1,7 @@
 // avatarcraft_amd/csrc/field_host.hpp -- host only: RenderArgs of a launch from an ac_field -- the level records and gather modes (fill_args), the
 // finite-difference step with its fine-level flags (set_fd_eps), both at once (prep_args).
 // Included by the files whose entries call them: field_grid.hip, render_occupancy.hip, sdf_stencil_train.hip, color_train.hip, render_core_backward.hip,
-// mesh_shade.hip, surface_rays.hip, and render_slab.hpp for the two ray renderers (fill_render_common).
+// bake_atlas.hpp (mesh_shade.hip, mesh_occlusion.hip), surface_rays.hip, and render_slab.hpp for the two ray renderers (fill_render_common).
 // Anonymous namespace: each of them gets its own copy.
 #pragma once
 #include "field_args.hpp"

@@ -1,6 +1,6 @@
 // avatarcraft_amd/csrc/field_tile.hpp -- the field on a tile of 16 packed samples: the workgroup shape and LDS image of the forward SDF query, the
 // seven-evaluation stencil (fd_forward) and the whole per-sample body (field_tile: stencil, normal, colour, NeuS alpha).
-// Included by sdf_stencil_train.hip, render_occupancy.hip and shade_tile.hpp (mesh_shade.hip, surface_rays.hip).
+// Included by sdf_stencil_train.hip, render_occupancy.hip and shade_tile.hpp (mesh_shade.hip, mesh_occlusion.hip, surface_rays.hip).
 // Anonymous namespace, like the field headers it includes: each translation unit gets its own copy.
 #pragma once
 #include "sdf_mlp.hpp"

@@ -1,8 +1,7 @@
 // avatarcraft_amd/csrc/mesh_shade.hip -- position on the level set, normal and colour for the points of an exported mesh: its vertices
 // (ac_mesh_vertex_attrs) and the texels of its atlas (ac_mesh_bake_texture).  Nothing in the reference: utils.save_mesh(vert, face, ...)
 // (stylize.py:263-269) writes geometry only.  Both kernels are the refine-and-shade tile body of shade_tile.hpp over tiles of 16 points.
-#include "shade_tile.hpp"
-#include "field_host.hpp"
+#include "bake_atlas.hpp"
 
 namespace {
 
@@ -56,23 +55,9 @@ __global__ __launch_bounds__(FBLOCK) void mesh_attrs_kernel(const RenderArgs a, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------- texture bake: the same body over texels
-// The atlas is closed form (avatarcraft_amd/geometry.py: atlas_layout): the S x S image is cut into R x R cells of c x c texels, R = S / c; triangle t
-// lives in cell t >> 1 (column k % R, row k / R), half t & 1.  Texel (i, j) of a cell belongs to half 0 iff i + j <= c - 2.  Its barycentric weights, in fp32, every
-// operation rounded once, L = c - 5:  half 0: w1 = (i - 1) / L, w2 = (j - 1) / L;  half 1: w1 = (c - 2 - i) / L, w2 = (c - 2 - j) / L;  w1 = max(w1, 0),
-// w2 = max(w2, 0), s = w1 + w2;  s > 1: w1 /= s, w2 /= s, w0 = 0;  else w0 = 1 - s -- a texel outside the UV triangle takes a point ON the triangle (the gutter).
-// Its point, per coordinate: p = (w0 P0 + w1 P1) + w2 P2, clamped to +-bound; then refine_shade_tile, view direction -normal.
-// A wave takes tiles of 16 consecutive texels of an image row (ceil(S / 16) tiles per row).  A tile without an owned texel issues no field evaluation (the test is
-// wave-uniform); in a tile with some, the lanes of the others ride along at the first owned texel's point without moving, and store owner = -1 and zeros.
-struct BakeArgs {
-    const float *pos;           // [V,3]
-    const int32_t *tris;        // [T,3], every index in [0, V)
-    uint32_t T, S, c, R;
-    RefineOpts ro;
-    float *rgb, *nrm, *sdf;     // [S,S,3], [S,S,3] | NULL, [S,S] | NULL
-    int32_t *owner;             // [S,S]
-    uint8_t *status;            // [S,S] | NULL
-};
-
+// The atlas, a texel's point on its triangle and what a texel stores: bake_atlas.hpp (shared with bake_maps_kernel, mesh_occlusion.hip); then refine_shade_tile,
+// view direction -normal.  A tile without an owned texel issues no field evaluation (the test is wave-uniform); in a tile with some, the lanes of the others ride
+// along at the first owned texel's point without moving, and store owner = -1 and zeros.
 __global__ __launch_bounds__(FBLOCK) void texture_bake_kernel(const RenderArgs a, const BakeArgs m)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -82,48 +67,16 @@ __global__ __launch_bounds__(FBLOCK) void texture_bake_kernel(const RenderArgs a
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
     float *fsl = lds + OFF_WAVE + wave * FE_SLAB;
     const FieldCtx fc = make_ctx(a);
-    const float bound = a.bound;
-    const uint32_t S = m.S, c = m.c, per_row = (S + 15) / 16, ntiles = per_row * S;
-    const float L = (float)(c - 5u);
+    const uint32_t ntiles = ((m.S + 15) / 16) * m.S;
     for (uint32_t tile = blockIdx.x * FW + wave; tile < ntiles; tile += gridDim.x * FW) {
-        const uint32_t y = tile / per_row, x = (tile - y * per_row) * 16 + n;
-        const uint32_t cx = x / c, cy = y / c, i = x - cx * c, j = y - cy * c;
-        const uint32_t h = i + j + 2 <= c ? 0u : 1u, t = 2 * (cy * m.R + cx) + h;
-        const bool owned = x < S && cx < m.R && cy < m.R && t < m.T;
-        float px = 0.0f, py = 0.0f, pz = 0.0f;
+        float px, py, pz;
+        const BakeTexel tx = bake_texel_point(m, tile, n, a.bound, px, py, pz);
         TileShade r{};
-        if (owned) {
-            const int di = h ? (int)(c - 2u - i) : (int)i - 1, dj = h ? (int)(c - 2u - j) : (int)j - 1;
-            float w1 = __builtin_fmaxf((float)di / L, 0.0f), w2 = __builtin_fmaxf((float)dj / L, 0.0f), w0 = 0.0f;
-            const float s = w1 + w2;
-            if (s > 1.0f) { w1 = w1 / s; w2 = w2 / s; } else w0 = 1.0f - s;
-            const int32_t *tv = m.tris + 3 * (size_t)t;
-            const float *P0 = m.pos + 3 * (size_t)tv[0], *P1 = m.pos + 3 * (size_t)tv[1], *P2 = m.pos + 3 * (size_t)tv[2];
-            px = clampf((w0 * P0[0] + w1 * P1[0]) + w2 * P2[0], -bound, bound);
-            py = clampf((w0 * P0[1] + w1 * P1[1]) + w2 * P2[1], -bound, bound);
-            pz = clampf((w0 * P0[2] + w1 * P1[2]) + w2 * P2[2], -bound, bound);
-        }
-        if (ride_along(owned, px, py, pz))                                       // (wave-uniform)
-            r = refine_shade_tile(lds, fsl, fc, a, m.ro, lane, nullptr, 0, owned, px, py, pz);
-        if (x < S && g == 0) {
-            const size_t b = (size_t)y * S + x;
-            m.owner[b] = owned ? (int32_t)t : -1;
-            m.rgb[3 * b] = owned ? r.rgb[0] : 0.0f; m.rgb[3 * b + 1] = owned ? r.rgb[1] : 0.0f; m.rgb[3 * b + 2] = owned ? r.rgb[2] : 0.0f;
-            if (m.nrm) { m.nrm[3 * b] = owned ? r.fn.nx : 0.0f; m.nrm[3 * b + 1] = owned ? r.fn.ny : 0.0f; m.nrm[3 * b + 2] = owned ? r.fn.nz : 0.0f; }
-            if (m.sdf) m.sdf[b] = owned ? r.s : 0.0f;
-            if (m.status) m.status[b] = owned ? (uint8_t)r.st : (uint8_t)0;
-        }
+        if (ride_along(tx.owned, px, py, pz))                                    // (wave-uniform)
+            r = refine_shade_tile(lds, fsl, fc, a, m.ro, lane, nullptr, 0, tx.owned, px, py, pz);
+        if (tx.x < m.S && g == 0) bake_texel_store(m, tx, r);
         wave_sync();
     }
-}
-
-// the refusal of ac_mesh_attr_opts that both entries make first
-int check_attr_opts(const char *who, const ac_mesh_attr_opts *opts)
-{
-    if (opts->refine_steps < 0 || opts->refine_steps > 16 || !(opts->max_move > 0.0f) || !(opts->fd_eps > 0.0f) || !(opts->bound > 0.0f)) {
-        ac::set_error("%s: refine_steps outside 0..16, or max_move, fd_eps or bound not > 0", who); return AC_ERR_BAD_ARG;
-    }
-    return AC_OK;
 }
 
 }  // namespace
@@ -146,17 +99,11 @@ AC_API int ac_mesh_vertex_attrs(const ac_field *field, const double *vertices, u
 AC_API int ac_mesh_bake_texture(const ac_field *field, const float *positions, uint32_t V, const int32_t *triangles, uint32_t T, const ac_atlas_opts *atlas,
                                 const ac_mesh_attr_opts *opts, float *rgb, int32_t *owner, float *normals, float *sdf, uint8_t *status, ac_stream_t stream)
 {
-    if (!atlas || !opts) { ac::set_error("mesh_bake_texture: NULL atlas or opts"); return AC_ERR_BAD_ARG; }
-    if (int rc = check_attr_opts("mesh_bake_texture", opts)) return rc;
-    const uint32_t S = atlas->size, c = atlas->cell;
-    if (c < 8) { ac::set_error("mesh_bake_texture: cell %u < 8", c); return AC_ERR_BAD_ARG; }
-    if (S < c || S > 32768u) { ac::set_error("mesh_bake_texture: size %u outside cell .. 32768", S); return AC_ERR_BAD_ARG; }
-    const uint32_t R = S / c;
-    if ((uint64_t)T > 2ull * R * R) { ac::set_error("mesh_bake_texture: %u triangles, but a %u x %u atlas of %u-texel cells holds 2 (size / cell)^2 = %llu", T, S, S, c, 2ull * R * R); return AC_ERR_BAD_ARG; }
-    if (!rgb || !owner || (T && (!positions || !triangles || !V))) { ac::set_error("mesh_bake_texture: NULL buffer"); return AC_ERR_BAD_ARG; }
     RenderArgs a{};
-    if (int rc = prep_args(a, field, opts->bound, opts->fd_eps)) return rc;
-    BakeArgs m{ positions, triangles, T, S, c, R, { opts->refine_steps, opts->target_sdf, opts->tol, opts->max_move, true }, rgb, normals, sdf, owner, status };
+    BakeArgs m{};
+    if (int rc = prep_bake("mesh_bake_texture", a, m, field, positions, V, triangles, T, atlas, opts, rgb && owner, true)) return rc;
+    m.rgb = rgb; m.nrm = normals; m.sdf = sdf; m.owner = owner; m.status = status;
+    const uint32_t S = m.S;
     launch_tiles<texture_bake_kernel>(((S + 15) / 16) * S, FWD_LDS_FLOATS * sizeof(float), (hipStream_t)stream, a, m);
     return ac::check_launch("mesh_bake_texture");
 }

@@ -1,5 +1,5 @@
 // avatarcraft_amd/csrc/shade_tile.hpp -- what the consumers of "normal and colour of the field at a point" share (mesh_shade.hip: vertices and texels;
-// surface_rays.hip: first hits of rays): the refine-and-shade body of one tile of 16 points, the ride-along rule for the lanes of a tile that have no
+// mesh_occlusion.hip: texels with their occlusion; surface_rays.hip: first hits of rays): the refine-and-shade body of one tile of 16 points, the ride-along rule for the lanes of a tile that have no
 // point of their own, and the launch of the persistent tile kernels.  Anonymous namespace, like field_tile.hpp: each translation unit gets its own copy.
 #pragma once
 #include "field_tile.hpp"

@@ -3,6 +3,8 @@
 interpolation through the posed-space renderer), plus the camera of the latter, SMPLDataset.gen_rays_pose (utils/SMPLDataset.py:86-103); and the one
 drivers that do write files: export_mesh, the coloured form of the trainer's extract_geometry + save_mesh (stylize.py:263-269), and export_animation, the
 same mesh posed frame by frame (render_warp.py's sequence as geometry instead of pixels)."""
+import contextlib
+
 import numpy as np
 import torch
 
@@ -161,18 +163,48 @@ def export_mesh(net, path, bound=NSR_BOUND, resolution=512, **kw):
     name.png (geometry.save_png).  components="largest" (or any spec of geometry.select_components, forwarded like every keyword) drops the field's floaters on
     the device before anything is shaded or baked: export_mesh(net, "avatar.obj", components="largest") writes the body alone.  decimate=k (forwarded as well)
     merges the vertices of every cluster cell of k marching-cubes cells on the device, after the cleaning and before the shading and the atlas layout:
-    export_mesh(net, "avatar.obj", components="largest", decimate=4) writes a body of about a sixteenth of the triangles, its texture baked from the field."""
+    export_mesh(net, "avatar.obj", components="largest", decimate=4) writes a body of about a sixteenth of the triangles, its texture baked from the field.
+    occlusion=True (or occlusion_kit's keywords, or a kit: net.export_occlusion for the length of this call) adds ambient occlusion: the PLY gets a
+    `float quality` property per vertex, the OBJ a grey image name_ao.png that its material references as map_Ka."""
     import os
     from .geometry import save_obj, save_ply, save_png
+    if "occlusion" in kw:
+        with _export_occlusion(net, kw.pop("occlusion")):
+            return export_mesh(net, path, bound, resolution, **kw)
     if str(path).lower().endswith(".obj"):
         mesh = net.extract_textured_mesh(bound, resolution, **kw)
         png = os.path.splitext(str(path))[0] + ".png"
         save_png(png, mesh["texture"])
-        save_obj(str(path), mesh["vertices"], mesh["triangles"], mesh["uv"], normals=mesh["normals"], texture=os.path.basename(png))
+        save_obj(str(path), mesh["vertices"], mesh["triangles"], mesh["uv"], normals=mesh["normals"], texture=os.path.basename(png),
+                 occlusion_texture=_save_ao(png, mesh))
         return mesh
     mesh = net.extract_colored_mesh(bound, resolution, **kw)
-    save_ply(path, mesh["vertices"], mesh["triangles"], normals=mesh["normals"], colors=mesh.get("colors"))
+    save_ply(path, mesh["vertices"], mesh["triangles"], normals=mesh["normals"], colors=mesh.get("colors"), quality=mesh.get("occlusion"))
     return mesh
+
+
+@contextlib.contextmanager
+def _export_occlusion(net, occlusion):
+    """net.export_occlusion = occlusion inside the block, what it was afterwards"""
+    prev = net.export_occlusion
+    net.export_occlusion = occlusion
+    try:
+        yield
+    finally:
+        net.export_occlusion = prev
+
+
+def _save_ao(png, mesh):
+    """the occlusion map of a textured mesh as a grey RGB image next to its texture `png` (stem_ao.png) -> its file name, or None for a mesh without one"""
+    import os
+    from .geometry import save_png
+    if "occlusion_map" not in mesh:
+        return None
+    ao = os.path.splitext(png)[0] + "_ao.png"
+    m = mesh["occlusion_map"]
+    m = m.detach().cpu().numpy() if isinstance(m, torch.Tensor) else np.asarray(m)
+    save_png(ao, np.repeat(m[:, :, None], 3, axis=2))
+    return os.path.basename(ao)
 
 
 def animation_paths(out_pattern):
@@ -207,7 +239,8 @@ def export_animation(net, body_model, poses=None, shape_from=None, shape_to=None
     out_pattern ending in .obj: frame files (geometry.save_obj) that all reference ONE material and ONE texture image, written before the first frame
     (animation_paths names them); ending in .ply: binary PLYs with vertex normals and colours.  **kw goes to extract_textured_mesh / extract_colored_mesh
     (texture_size, threshold, refine_steps, components, decimate ...: components="largest" keeps the floaters out of every frame, decimate=k poses the
-    decimated mesh); iters / tol to pose_mesh.
+    decimated mesh; occlusion=... adds the CANONICAL pose's ambient occlusion, one shared name_ao.png or a quality property in every frame); iters / tol to
+    pose_mesh.
     yields (frame index, posed mesh dict of pose_mesh); rank / world: this process writes the frames shard_indices(n_frames, rank, world) like
     render_animation (the shared files are written by every rank with the same content)."""
     import os
@@ -219,10 +252,11 @@ def export_animation(net, body_model, poses=None, shape_from=None, shape_to=None
                                                  max_frames=max_frames)
     faces = np.asarray(body_model.faces)[:, :3]
     mine = list(shard_indices(n_frames, rank, world))
-    mesh = net.extract_textured_mesh(bound, resolution, **kw) if kind == "obj" else net.extract_colored_mesh(bound, resolution, **kw)
+    with _export_occlusion(net, kw.pop("occlusion")) if "occlusion" in kw else contextlib.nullcontext():
+        mesh = net.extract_textured_mesh(bound, resolution, **kw) if kind == "obj" else net.extract_colored_mesh(bound, resolution, **kw)
     if kind == "obj":
         save_png(png, mesh["texture"])
-        save_mtl(mtl, os.path.basename(png))
+        save_mtl(mtl, os.path.basename(png), _save_ao(png, mesh))             # (the occlusion is the canonical pose's: one image for every frame)
     guide = dict(faces=faces, canonical=canonical_guide(world_verts[0], Ts[0])) if n_frames else None
     # one WarpMesh per frame, the next frame's upload + culling structure prepared beside the current frame's searches (nsr_ops.warp_mesh_sequence)
     if torch.device(device).type == "cuda":
@@ -235,5 +269,6 @@ def export_animation(net, body_model, poses=None, shape_from=None, shape_to=None
         if kind == "obj":
             save_obj(frame_path(i), posed["vertices"], posed["triangles"], posed["uv"], normals=posed.get("normals"), mtllib=os.path.basename(mtl))
         else:
-            save_ply(frame_path(i), posed["vertices"], posed["triangles"], normals=posed.get("normals"), colors=posed.get("colors"))
+            save_ply(frame_path(i), posed["vertices"], posed["triangles"], normals=posed.get("normals"), colors=posed.get("colors"),
+                     quality=posed.get("occlusion"))
         yield i, posed

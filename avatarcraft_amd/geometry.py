@@ -83,9 +83,10 @@ def marching_tetrahedra(u, level=0.0):
     return verts, faces
 
 
-def save_ply(path, vertices, triangles, normals=None, colors=None):
-    """binary little-endian PLY: float32 x y z [nx ny nz], uchar red green blue (round(clip(c, 0, 1) * 255)), faces as `list uchar int vertex_indices`.
-    vertices [V,3], triangles [F,3], normals [V,3], colors [V,3] in [0, 1]: numpy arrays or tensors on any device."""
+def save_ply(path, vertices, triangles, normals=None, colors=None, quality=None):
+    """binary little-endian PLY: float32 x y z [nx ny nz], uchar red green blue (round(clip(c, 0, 1) * 255)), [float32 quality], faces as
+    `list uchar int vertex_indices`.  vertices [V,3], triangles [F,3], normals [V,3], colors [V,3] in [0, 1], quality [V] (the per-vertex scalar viewers
+    know by that name: the export's ambient occlusion): numpy arrays or tensors on any device."""
     import numpy as np
     arr = lambda a, dt: np.ascontiguousarray((a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)), dtype=dt)
     v, t = arr(vertices, "<f4").reshape(-1, 3), arr(triangles, "<i4").reshape(-1, 3)
@@ -94,12 +95,16 @@ def save_ply(path, vertices, triangles, normals=None, colors=None):
         cols.append(("n", "<f4", (3,))); props += ["float nx", "float ny", "float nz"]
     if colors is not None:
         cols.append(("rgb", "u1", (3,))); props += ["uchar red", "uchar green", "uchar blue"]
+    if quality is not None:
+        cols.append(("q", "<f4")); props += ["float quality"]
     vert = np.empty(len(v), dtype=cols)
     vert["xyz"] = v
     if normals is not None:
         vert["n"] = arr(normals, "<f4").reshape(-1, 3)
     if colors is not None:
         vert["rgb"] = np.round(np.clip(arr(colors, "<f8").reshape(-1, 3), 0.0, 1.0) * 255.0).astype(np.uint8)
+    if quality is not None:
+        vert["q"] = arr(quality, "<f4").reshape(len(v))
     face = np.empty(len(t), dtype=[("n", "u1"), ("idx", "<i4", (3,))])
     face["n"] = 3; face["idx"] = t
     head = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}"] + ["property " + p for p in props]
@@ -293,15 +298,19 @@ def save_png(path, rgb8):
                  + chunk(b"IEND", b""))
 
 
-def save_mtl(path, texture):
-    """the material file save_obj references: one material `baked` whose diffuse map is the image `texture` (a file name next to the .mtl)"""
+def save_mtl(path, texture, occlusion_texture=None):
+    """the material file save_obj references: one material `baked` whose diffuse map is the image `texture` (a file name next to the .mtl);
+    occlusion_texture: the file name of the ambient-occlusion image, referenced as the ambient map (map_Ka)"""
     with open(path, "w") as fh:
         fh.write(f"newmtl baked\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {texture}\n")
+        if occlusion_texture is not None:
+            fh.write(f"map_Ka {occlusion_texture}\n")
 
 
-def save_obj(path, vertices, triangles, uv, normals=None, texture=None, mtllib=None):
+def save_obj(path, vertices, triangles, uv, normals=None, texture=None, mtllib=None, occlusion_texture=None):
     """Wavefront OBJ: `v` per vertex, `vt` three per triangle (uv [T,3,2], atlas_layout's), `vn` per vertex, `f a/ta/na b/tb/nb c/tc/nc` (`a/ta` without normals),
     1-based; triangle t uses vt 3t+1 .. 3t+3.  texture: the image's file name -- then a sibling .mtl (same stem) with map_Kd is written and referenced.
+    occlusion_texture: with texture, the ambient-occlusion image's file name: the material gets a map_Ka line.
     mtllib: instead, the file name of a material file that exists already (save_mtl) and is only referenced -- the frames of an animation share one.
     Numbers are written with repr, so they read back to the same doubles."""
     import os
@@ -314,8 +323,10 @@ def save_obj(path, vertices, triangles, uv, normals=None, texture=None, mtllib=N
     stem = os.path.splitext(path)[0]
     if texture is not None and mtllib is not None:
         raise ValueError("save_obj: texture (write a sibling .mtl) or mtllib (reference an existing one), not both")
+    if occlusion_texture is not None and texture is None:
+        raise ValueError("save_obj: occlusion_texture goes into the material that texture= writes")
     if texture is not None:
-        save_mtl(stem + ".mtl", texture)
+        save_mtl(stem + ".mtl", texture, occlusion_texture)
         out += [f"mtllib {os.path.basename(stem)}.mtl", "usemtl baked"]
     if mtllib is not None:
         out += [f"mtllib {mtllib}", "usemtl baked"]

@@ -54,6 +54,14 @@ def _native_mesh(net, bound, resolution, threshold, slab_layers, components, gri
     return _NativeMesh(v, t, sizes, kept, members, max_move)
 
 
+def _occlusion_kit(occlusion, bound, threshold):
+    """occlusion (None, True, occlusion_kit's keywords or a kit) -> None, or the checked kit at the export's level; a bad one raises here, before any device work"""
+    if occlusion is None:
+        return None
+    from ..mesh_occlusion import resolve_kit
+    return resolve_kit(occlusion, bound, level=-float(threshold))
+
+
 def _cluster_grid(bound, resolution, decimate):
     """decimate (None, or the k of mesh_decimate.cluster_grid) -> None, or the cluster grid; a bad k raises here, before any device work"""
     if decimate is None:
@@ -64,6 +72,11 @@ def _cluster_grid(bound, resolution, decimate):
 
 class MeshExport:
     """mixed into NeRFNetwork"""
+
+    # opt-in switch of extract_colored_mesh / extract_textured_mesh (their signatures are frozen: tests/test_instant_nsr_package_host.py): None = what they always
+    # returned; True = ambient occlusion from the default kit (mesh_occlusion.occlusion_kit, radius 0.1 bound); a dict = occlusion_kit's keywords, or a kit, passed
+    # as is.  drivers.export_mesh / export_animation(occlusion=...) set it for the length of their call.
+    export_occlusion = None
 
     def _grid_axis(self, bound, resolution):
         """torch.linspace(-bound, bound, resolution) as the reference forms it (on the host, fp32: extract_fields :730-732, update_extra_state :312-314), on the
@@ -158,7 +171,7 @@ class MeshExport:
         vertices = vertices / (resolution - 1.0) * (2 * bound) - bound
         return vertices, triangles
 
-    def _colored_mesh(self, bound, resolution, threshold, refine_steps, tol, colors, slab_layers, components, decimate):
+    def _colored_mesh(self, bound, resolution, threshold, refine_steps, tol, colors, slab_layers, components, decimate, kit=None):
         """extract_colored_mesh on the device -> (its dict of device tensors, the max_move its vertices were projected with: the bake's as well)"""
         if slab_layers is not None:
             slab_layers = nsr_ops.check_slab_layers(slab_layers, "extract_colored_mesh")
@@ -172,6 +185,10 @@ class MeshExport:
         out = dict(vertices=a["positions"].double(), triangles=m.triangles, normals=a["normals"], sdf=a["sdf"], status=a["status"])
         if colors:
             out["colors"] = a["rgb"]
+        if kit is not None:
+            from ..mesh_occlusion import field_occlusion
+            with torch.no_grad():                     # (a vertex without a gradient, status 2, has no normal to open a cone around)
+                out["occlusion"] = field_occlusion(self._field_for(ignore_curvature=True), a["positions"], a["normals"], bound, kit, active=a["status"] != 2)
         if m.component_sizes is not None:
             out.update(component_sizes=m.component_sizes, components_kept=m.components_kept)
         if m.cluster_members is not None:
@@ -194,8 +211,12 @@ class MeshExport:
         decimate: extract_geometry's (None: every triangle; k: clusters of k marching-cubes cells).  The mesh is decimated after the cleaning and BEFORE the
         vertices are shaded: no removed vertex is ever shaded, and every kept one is projected from its cluster's mean onto the level set, never further than one
         CLUSTER cell (k grid cells) instead of one grid cell.  The dict then also carries cluster_members [V] (how many marching-cubes vertices each vertex
-        stands for)."""
-        out = self._colored_mesh(bound, resolution, threshold, refine_steps, tol, colors, slab_layers, components, decimate)[0]
+        stands for).
+        self.export_occlusion (the switch above; None: nothing more, as ever) adds ambient occlusion.  The kit's level is -threshold.  The dict then also carries
+        occlusion [V] float32 in [0, 1], 1 = open: mesh_occlusion.field_occlusion at the final positions and normals (after cleaning and decimation), 0 at a
+        status-2 vertex.  The colours are unlit albedo; a viewer multiplies."""
+        kit = _occlusion_kit(self.export_occlusion, bound, threshold)
+        out = self._colored_mesh(bound, resolution, threshold, refine_steps, tol, colors, slab_layers, components, decimate, kit)[0]
         return out if return_torch else {k: x.cpu().numpy() for k, x in out.items()}
 
     def extract_textured_mesh(self, bound: float, resolution: int, texture_size: int = 2048, cell=None, threshold: float = 0.0, refine_steps: int = 3,
@@ -210,19 +231,30 @@ class MeshExport:
         components: extract_colored_mesh's.  The mesh is cleaned BEFORE the atlas is laid out, so the cells are sized for the kept triangles only: debris no longer
         lowers the texel density of the body.
         decimate: extract_colored_mesh's.  The mesh is decimated BEFORE the atlas is laid out, so the cells are sized for the decimated triangle count, and the
-        texels carry the colour detail the removed vertices carried; a texel's point is projected never further than one CLUSTER cell."""
+        texels carry the colour detail the removed vertices carried; a texel's point is projected never further than one CLUSTER cell.
+        self.export_occlusion: as in extract_colored_mesh.  The dict then also carries occlusion [V], texel_occlusion [S,S] float32 (0 at unowned texels) and occlusion_map [S,S]
+        uint8 (the texture's quantisation rule), the texels' from ONE launch (ac_mesh_bake_maps) in place of the bake's: colour and occlusion share a texel's refine."""
         from ..geometry import atlas_layout
-        m, max_move = self._colored_mesh(bound, resolution, threshold, refine_steps, tol, True, slab_layers, components, decimate)
+        kit = _occlusion_kit(self.export_occlusion, bound, threshold)
+        m, max_move = self._colored_mesh(bound, resolution, threshold, refine_steps, tol, True, slab_layers, components, decimate, kit)
         T = m["triangles"].shape[0]
         try:
             lay = atlas_layout(T, texture_size, cell)
         except ValueError as e:
             raise RuntimeError(f"extract_textured_mesh: {e}") from e
+        quantise = lambda x: torch.floor(x.clamp(0.0, 1.0) * 255.0 + 0.5).to(torch.uint8)
         with torch.no_grad():
-            b = nsr_ops.mesh_bake_texture(self._field(), m["vertices"].float(), m["triangles"], texture_size, lay["cell"], bound, nsr_ops.FD_STEP,
-                                          refine_steps=refine_steps, tol=tol, max_move=max_move, target_sdf=-float(threshold))
-            tex = torch.floor(b["rgb"].clamp(0.0, 1.0) * 255.0 + 0.5).to(torch.uint8)
+            how = dict(refine_steps=refine_steps, tol=tol, max_move=max_move, target_sdf=-float(threshold))
+            if kit is None:
+                b = nsr_ops.mesh_bake_texture(self._field(), m["vertices"].float(), m["triangles"], texture_size, lay["cell"], bound, nsr_ops.FD_STEP, **how)
+            else:
+                from ..mesh_occlusion import mesh_bake_maps
+                b = mesh_bake_maps(self._field(), m["vertices"].float(), m["triangles"], texture_size, lay["cell"], bound, nsr_ops.FD_STEP, kit=kit,
+                                   want=("rgb", "sdf", "status"), **how)
+            tex = quantise(b["rgb"])
         m.update(texture=tex, owner=b["owner"], texel_sdf=b["sdf"], texel_status=b["status"])
+        if kit is not None:
+            m.update(texel_occlusion=b["occlusion"], occlusion_map=quantise(b["occlusion"]))
         if not return_torch:
             m = {k: x.cpu().numpy() for k, x in m.items()}
         m["uv"] = torch.from_numpy(lay["uv"]).to(tex.device) if return_torch else lay["uv"]
@@ -238,7 +270,8 @@ class MeshExport:
         verts [Vg,3], Ts [>= Vg,4,4]: the frame's posed guide and transforms (calc_local_trans), or verts = an nsr_ops.WarpMesh of the frame (Ts unused).
         -> a shallow copy of `mesh` with vertices (float64, the input's convention), normals, and per vertex residual (float32: max-norm of W^-1(p) - vertex at
         the returned p), status (uint8: 0 within tol, 1 iters used up, 2 not finite) and mask (uint8: 0 = farther from the guide than the renderer's mask
-        threshold, where it would draw nothing; kept and flagged); the export's own `status` (of the level-set projection) is replaced: read it from `mesh`.  triangles, uv, texture, colors and every other entry are the input's own objects.
+        threshold, where it would draw nothing; kept and flagged); the export's own `status` (of the level-set projection) is replaced: read it from `mesh`.  triangles, uv, texture, colors and every other entry are the input's own objects --
+        `occlusion` among them: it is the CANONICAL pose's, carried to every frame (per-frame occlusion is not built).
         numpy in, numpy out; device tensors in, device tensors out."""
         from ..geometry import canonical_guide
         dev = self.encoder.embeddings.device

@@ -169,16 +169,12 @@ def mesh_vertex_attrs(field, vertices, bound, eps=FD_STEP, refine_steps=3, tol=1
     return out
 
 
-def mesh_bake_texture(field, positions, triangles, size, cell, bound, eps=FD_STEP, refine_steps=3, tol=1e-5, max_move=None, target_sdf=0.0, want_normals=False):
-    """ac_mesh_bake_texture: mesh_vertex_attrs' work per TEXEL of the closed-form atlas (geometry.atlas_layout), in one launch.  positions [V,3] float32 on the
-    device (mesh_vertex_attrs' `positions`: vertices on the level set), triangles [T,3] int32, size x size texels in cells of `cell` (None: the largest that fits).
-    Every owned texel's point on its triangle takes at most refine_steps Newton steps (max_move from that point; None: one cell of a 512^3 grid), then normal, sdf and
-    the colour seen along -normal are evaluated there.  -> dict(rgb [S,S,3], owner [S,S] int32 (-1: nobody; everything else is 0 there), normals [S,S,3] | None,
-    sdf [S,S], status [S,S] uint8 as mesh_vertex_attrs').  The triangle indices are checked on the device BEFORE the launch (the kernel reads through them unchecked):
-    RuntimeError for one outside [0, V)."""
-    _chk_cuda("mesh_bake_texture: positions and triangles must be CUDA tensors", positions, triangles)
-    _chk_typed(positions, _F32, (None, 3), "mesh_bake_texture: positions must be a contiguous float32 [V,3] tensor")
-    _chk_typed(triangles, torch.int32, (None, 3), "mesh_bake_texture: triangles must be a contiguous int32 [T,3] tensor on the device of positions",
+def _bake_args(who, positions, triangles, size, cell, bound, eps, target_sdf, refine_steps, tol, max_move):
+    """what the launches over the atlas' texels (mesh_bake_texture, mesh_occlusion.mesh_bake_maps) check before any device work, `who` naming the caller
+    -> (V, T, S, device, ac_atlas_opts, ac_mesh_attr_opts)"""
+    _chk_cuda(f"{who}: positions and triangles must be CUDA tensors", positions, triangles)
+    _chk_typed(positions, _F32, (None, 3), f"{who}: positions must be a contiguous float32 [V,3] tensor")
+    _chk_typed(triangles, torch.int32, (None, 3), f"{who}: triangles must be a contiguous int32 [T,3] tensor on the device of positions",
                device=positions.device)
     V, T, S, dev = positions.shape[0], triangles.shape[0], int(size), positions.device
     if cell is None:
@@ -186,14 +182,23 @@ def mesh_bake_texture(field, positions, triangles, size, cell, bound, eps=FD_STE
         try:
             cell = atlas_layout(T, S)["cell"]
         except ValueError as e:
-            raise RuntimeError(f"mesh_bake_texture: {e}") from e
+            raise RuntimeError(f"{who}: {e}") from e
     if T and (int(triangles.min()) < 0 or int(triangles.max()) >= V):
-        raise RuntimeError(f"mesh_bake_texture: a triangle index outside [0, {V}); nothing was launched")
+        raise RuntimeError(f"{who}: a triangle index outside [0, {V}); nothing was launched")
     max_move = _max_move(bound, max_move)             # (here, so that a bound that is no number is refused before the size, as it always was)
     if not 0 < S <= 32768:
-        raise RuntimeError(f"mesh_bake_texture: size {S} outside 1 .. 32768")
-    atlas = L.ac_atlas_opts(S, max(int(cell), 0))
-    opts = _mesh_attr_opts(bound, eps, target_sdf, refine_steps, tol, max_move)
+        raise RuntimeError(f"{who}: size {S} outside 1 .. 32768")
+    return V, T, S, dev, L.ac_atlas_opts(S, max(int(cell), 0)), _mesh_attr_opts(bound, eps, target_sdf, refine_steps, tol, max_move)
+
+
+def mesh_bake_texture(field, positions, triangles, size, cell, bound, eps=FD_STEP, refine_steps=3, tol=1e-5, max_move=None, target_sdf=0.0, want_normals=False):
+    """ac_mesh_bake_texture: mesh_vertex_attrs' work per TEXEL of the closed-form atlas (geometry.atlas_layout), in one launch.  positions [V,3] float32 on the
+    device (mesh_vertex_attrs' `positions`: vertices on the level set), triangles [T,3] int32, size x size texels in cells of `cell` (None: the largest that fits).
+    Every owned texel's point on its triangle takes at most refine_steps Newton steps (max_move from that point; None: one cell of a 512^3 grid), then normal, sdf and
+    the colour seen along -normal are evaluated there.  -> dict(rgb [S,S,3], owner [S,S] int32 (-1: nobody; everything else is 0 there), normals [S,S,3] | None,
+    sdf [S,S], status [S,S] uint8 as mesh_vertex_attrs').  The triangle indices are checked on the device BEFORE the launch (the kernel reads through them unchecked):
+    RuntimeError for one outside [0, V)."""
+    V, T, S, dev, atlas, opts = _bake_args("mesh_bake_texture", positions, triangles, size, cell, bound, eps, target_sdf, refine_steps, tol, max_move)
     out = dict(rgb=_f32(dev, S, S, 3), owner=torch.empty((S, S), dtype=torch.int32, device=dev), normals=_f32(dev, S, S, 3) if want_normals else None,
                sdf=_f32(dev, S, S), status=torch.empty((S, S), dtype=torch.uint8, device=dev))
     L.check(L.lib().ac_mesh_bake_texture(C.byref(field.c), positions.data_ptr(), V, triangles.data_ptr(), T, C.byref(atlas), C.byref(opts), out["rgb"].data_ptr(),

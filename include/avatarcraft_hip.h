@@ -565,6 +565,60 @@ int ac_mesh_bake_texture(const ac_field *field, const float *positions /*[V,3]*/
                          const ac_atlas_opts *atlas, const ac_mesh_attr_opts *opts,
                          float *rgb /*[S,S,3]*/, int32_t *owner /*[S,S]*/, float *normals /*optional [S,S,3]*/, float *sdf /*optional [S,S]*/,
                          uint8_t *status /*optional [S,S]*/, ac_stream_t stream);
+/* ac_field_occlusion: ambient occlusion at points of the level set -- how open the space above a point is, asked of the SDF itself by taps along a cone of directions
+ * around the normal (added entries, no struct of an existing call changes: ac_version() stays 10).  It stands in for nothing in the reference.  A kit is K local
+ * directions l_k = (lx, ly, lz) in the frame whose z axis is the normal, K weights w_k, J distances t_j, a gain and a level.  All fp32, every operation rounded once,
+ * no contraction; fmax / fmin are fmaxf / fminf (a NaN operand is dropped).  Per point, with p = clamp(point, +-bound) per coordinate and n its unit normal:
+ *   sg = copysignf(1, nz); a = -1 / (sg + nz); b = (nx ny) a                                   (|sg + nz| >= 1)
+ *   T = (1 + sg ((nx nx) a), sg b, -(sg nx));  U = (b, sg + (ny ny) a, -ny)
+ *   acc = 0
+ *   for k = 0 .. K-1:
+ *       w_c = (lx T_c + ly U_c) + lz n_c                                  per coordinate c
+ *       v = 1
+ *       for j = 0 .. J-1:
+ *           q_c = fmin(fmax(p_c + t_j w_c, -bound), bound)                (a NaN coordinate becomes -bound)
+ *           s = forward_sdf(q)[0] - level                                 (the bits of ac_field_sdf)
+ *           h = t_j lz                                                    (the free distance a flat ground would leave at this tap)
+ *           r = fmin(fmax((gain s) / h, 0), 1)                            (a NaN value counts as fully occluded)
+ *           v = fmin(v, r)
+ *       acc = acc + w_k v
+ *   occlusion = fmin(acc, 1)
+ * so a plane under a true distance field scores 1, and anything that closes the cone scores less.  A point is ACTIVE if active[i] != 0 (active == NULL: every
+ * point) and its three coordinates and its three normal components are finite.  An inactive point stores 0 and is never evaluated: it rides along at the first
+ * active point of its tile of 16, and a tile without an active point evaluates nothing.  The taps left of a direction are skipped once v is 0 in every active lane
+ * of the wave, which changes no bit.  Nothing else depends on the data: K J evaluations per tile, no atomics, no waits.  N == 0 launches nothing.
+ * The kit's tables are HOST pointers; the entry checks them on the host, before any launch, and copies them into the kernel's arguments.
+ * AC_ERR_BAD_ARG: NULL opts or a NULL table, n_dirs outside 1..32, n_steps outside 1..16, a number that is not finite, an lz < 0.05, a direction whose length is not
+ * within 1e-3 of 1, a negative weight, weights whose sum (in double, in order) is not within 1e-5 of 1, distances not > 0 or not strictly ascending, gain not > 0,
+ * bound not > 0, a NULL buffer with N > 0.  The field's SDF side alone is used.
+ * Bit-identical to the numpy fp32 restatement around the CPU oracle's Field.sdf (tests/mesh_occlusion_cases.py, tests/test_gpu_mesh_occlusion.py). */
+typedef struct ac_occlusion_opts {
+    int32_t n_dirs, n_steps;    /* K in 1..32, J in 1..16                                         */
+    const float *dirs;          /* HOST [K,3] unit directions in the normal's frame, lz >= 0.05   */
+    const float *weights;       /* HOST [K] >= 0, summing to 1                                    */
+    const float *dists;         /* HOST [J] > 0, strictly ascending                               */
+    float gain;                 /* > 0: r = gain s / h                                            */
+    float level;                /* the level set the points lie on (0; -threshold of the export)  */
+} ac_occlusion_opts;
+int ac_field_occlusion(const ac_field *field, const float *points /*[N,3]*/, const float *normals /*[N,3]*/, const uint8_t *active /*optional [N]*/, uint32_t N,
+                       float bound, const ac_occlusion_opts *opts, float *occlusion /*[N]*/, ac_stream_t stream);
+/* ac_mesh_bake_maps: ac_mesh_bake_texture with more maps out of the same launch.  Per texel, in order: the texel -> triangle -> point prologue of ac_mesh_bake_texture,
+ * unchanged; its refine loop and the normal, sdf and (only when out->rgb is given) colour at the final point, unchanged; then, with occ_opts, ac_field_occlusion's
+ * procedure at that final point and normal, active = the texel is owned (and the six numbers are finite).  Colour and occlusion share the texel's refine.
+ * out: every pointer may be NULL except owner; positions = the final point.  Unowned texels: owner = -1, every other output 0, no field evaluation.
+ * out->occlusion must be NULL exactly when occ_opts is NULL (AC_ERR_BAD_ARG otherwise); the other refusals are ac_mesh_bake_texture's and ac_field_occlusion's.
+ * Every output it shares with ac_mesh_bake_texture has the same bits; occlusion has the bits of ac_field_occlusion on (positions, normals, owner >= 0). */
+typedef struct ac_bake_out {
+    float *rgb;                 /* [S,S,3] */
+    int32_t *owner;             /* [S,S], required */
+    float *normals, *positions; /* [S,S,3] each */
+    float *sdf;                 /* [S,S] */
+    uint8_t *status;            /* [S,S] */
+    float *occlusion;           /* [S,S] */
+} ac_bake_out;
+int ac_mesh_bake_maps(const ac_field *field, const float *positions /*[V,3]*/, uint32_t V, const int32_t *triangles /*[T,3]*/, uint32_t T,
+                      const ac_atlas_opts *atlas, const ac_mesh_attr_opts *attr_opts, const ac_occlusion_opts *occ_opts /*optional*/,
+                      const ac_bake_out *out, ac_stream_t stream);
 /* ac_render_rays_surface: the image of the level set itself -- per ray the FIRST point with sdf = level, the field's normal and colour there, its metric distance
  * and a hit mask; one launch, about 18 SDF evaluations per ray where the volumetric render takes 1008 (an added entry, no struct of an existing call changes:
  * ac_version stays 10).  It stands in for nothing in the reference.  All fp32, every operation rounded once (t*d then the add; correctly rounded division); per ray:
