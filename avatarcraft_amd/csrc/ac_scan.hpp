@@ -1,6 +1,6 @@
-// avatarcraft_amd/csrc/ac_scan.hpp -- the ordered scans of the mesh kernels (marching_cubes.hip: classify -> scan -> emit; mesh_components.hip: ranks of the
-// roots, compaction): a workgroup's exclusive scan, a wave's inclusive scan and the one-workgroup scan of the per-workgroup totals.  No atomics, no waits
-// between workgroups: every position is a function of the input alone.  (pair_scan_kernel was marching_cubes.hip's mc_scan_kernel until a second file needed it.)
+// avatarcraft_amd/csrc/ac_scan.hpp -- the scan primitives under the ordered passes of the mesh index kernels (mesh_index.hpp builds the passes on them): a
+// workgroup's exclusive scan, a wave's inclusive scan and the one-workgroup scan of the per-workgroup totals.  No atomics, no waits between workgroups: every
+// position is a function of the input alone.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -8,8 +8,7 @@
 // with the normal towards u <= iso = out of the body for u = -sdf.  PyMCubes is not in this image: "unpinned vs PyMCubes, pinned vs the definition".
 // Order of the output (what makes the mesh reproducible bit for bit, and equal to the CPU oracle's serial loop): vertices by owning grid point (linear
 // index, z fastest) then by axis x, y, z; triangles by cell (linear index) then by table position.
-#include "ac_common.hpp"
-#include "ac_scan.hpp"      // block_exscan_256, wave_incscan, pair_scan_kernel: the scan of the per-workgroup totals (vertices in the low, triangles in the high 16 bits)
+#include "mesh_index.hpp"   // the ordered passes (a workgroup's pair of totals = its vertices and its triangles), the scratch walk, the shared refusals
 
 #define AC_MC_CONST static __constant__ const
 #include "ac_mc_table.hpp"
@@ -17,7 +16,6 @@
 namespace {
 
 // ---------------------------------------------------------------------------------------------------------------- marching cubes
-constexpr int MC_PTS = 1024;                     // grid points per workgroup (256 threads x 4 consecutive points: their four count bytes are one dword)
 struct McDims { uint32_t nx, ny, nz, npts; };
 
 __device__ __forceinline__ bool mc_flag(float u, float iso) { return u <= iso; }
@@ -71,7 +69,7 @@ __global__ __launch_bounds__(256) void mc_classify_kernel(const uint32_t *__rest
                                                           uint32_t *__restrict__ bsum)
 {
     __shared__ uint32_t sh[8];
-    const uint32_t p0 = blockIdx.x * MC_PTS + threadIdx.x * 4u;
+    const uint32_t p0 = mi::first_item();             // (a thread's four consecutive points: their four count bytes are one dword)
     uint32_t packed = 0, nv = 0, nt = 0;
 #pragma unroll
     for (uint32_t r = 0; r < 4; ++r) {
@@ -82,9 +80,7 @@ __global__ __launch_bounds__(256) void mc_classify_kernel(const uint32_t *__rest
         nv += (uint32_t)__builtin_popcount(c & 7u); nt += c >> 3;
     }
     if (p0 < d.npts) cnt4[p0 >> 2] = packed;      // (the count array is padded to a multiple of 4 points)
-    uint32_t tot;
-    (void)block_exscan_256(nv | (nt << 16), sh, tot);      // 1024 points: at most 3072 vertices / 5120 triangles per workgroup -- 16 bits each
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
+    mi::block_totals(nv, nt, sh, bsum);            // 1024 points: at most 3072 vertices / 5120 triangles per workgroup
 }
 
 struct McXform { double den, span[3], lo[3]; };   // world = index / den * span + lo, the reference's three operations in its order (instant_nsr.py:760-762)
@@ -102,15 +98,14 @@ __device__ __forceinline__ void mc_vertices_body(const float *__restrict__ vol, 
                                                  const McXform &xf, double *__restrict__ verts, uint32_t n_verts, const McSlab &s)
 {
     __shared__ uint32_t sh[8];
-    if ((bsum[blockIdx.x] & 0xffffu) == 0u) return;
+    if (mi::block_total<0>(bsum) == 0u) return;
     const uint32_t shift = SLAB ? s.info[MC_INFO_SHIFT] : 0u;
-    const uint32_t p0 = blockIdx.x * MC_PTS + threadIdx.x * 4u;
+    const uint32_t p0 = mi::first_item();
     const uint32_t packed = p0 < d.npts ? cnt4[p0 >> 2] : 0u;
     uint32_t nv = 0;
 #pragma unroll
     for (uint32_t r = 0; r < 4; ++r) nv += (uint32_t)__builtin_popcount((packed >> (8 * r)) & 7u);
-    uint32_t tot;
-    uint32_t vid = boff[2 * blockIdx.x] + block_exscan_256(nv, sh, tot);
+    uint32_t vid = mi::ordered_base<0>(nv, boff, sh);
     const uint32_t stride[3] = { d.ny * d.nz, d.nz, 1u };
 #pragma unroll
     for (uint32_t r = 0; r < 4; ++r) {
@@ -158,15 +153,14 @@ __device__ __forceinline__ void mc_triangles_body(const uint32_t *__restrict__ b
                                                   int32_t *__restrict__ tris, uint32_t n_tris, uint32_t tlayers)
 {
     __shared__ uint32_t sh[8];
-    if ((bsum[blockIdx.x] >> 16) == 0u) return;
-    if (SLAB && (uint64_t)blockIdx.x * MC_PTS >= (uint64_t)tlayers * d.ny * d.nz) return;
-    const uint32_t p0 = blockIdx.x * MC_PTS + threadIdx.x * 4u;
+    if (mi::block_total<1>(bsum) == 0u) return;
+    if (SLAB && (uint64_t)blockIdx.x * mi::ITEMS >= (uint64_t)tlayers * d.ny * d.nz) return;
+    const uint32_t p0 = mi::first_item();
     const uint32_t packed = p0 < d.npts ? cnt4[p0 >> 2] : 0u;
     uint32_t nt = 0;
 #pragma unroll
     for (uint32_t r = 0; r < 4; ++r) nt += (packed >> (8 * r + 3)) & 7u;
-    uint32_t tot;
-    uint32_t tid = boff[2 * blockIdx.x + 1] + block_exscan_256(nt, sh, tot);
+    uint32_t tid = mi::ordered_base<1>(nt, boff, sh);
     const uint8_t *cnt8 = reinterpret_cast<const uint8_t *>(cnt4);
     const uint32_t sx = d.ny * d.nz, sy = d.nz;
 #pragma unroll
@@ -211,7 +205,7 @@ __device__ __forceinline__ void mc_prefix_at(const uint32_t *__restrict__ cnt4, 
                                              const uint32_t *__restrict__ totals, uint32_t *sh, uint32_t &pv, uint32_t &pt)
 {
     if (layer >= d.nx) { pv = totals[0]; pt = totals[1]; return; }                     // (uniform over the workgroup)
-    const uint32_t p = layer * d.ny * d.nz, blk = p / MC_PTS, q0 = blk * MC_PTS + threadIdx.x * 4u;
+    const uint32_t p = layer * d.ny * d.nz, blk = p / mi::ITEMS, q0 = blk * mi::ITEMS + threadIdx.x * 4u;
     const uint32_t packed = q0 < p ? cnt4[q0 >> 2] : 0u;                                // (q0 < p < npts: a dword mc_classify_kernel wrote)
     uint32_t nv = 0, nt = 0;
 #pragma unroll
@@ -219,9 +213,8 @@ __device__ __forceinline__ void mc_prefix_at(const uint32_t *__restrict__ cnt4, 
         const uint32_t c = q0 + r < p ? (packed >> (8 * r)) & 0xffu : 0u;
         nv += (uint32_t)__builtin_popcount(c & 7u); nt += c >> 3;
     }
-    uint32_t tot;
-    (void)block_exscan_256(nv | (nt << 16), sh, tot);
-    pv = boff[2 * blk] + (tot & 0xffffu); pt = boff[2 * blk + 1] + (tot >> 16);
+    const mi::Pair before = mi::block_totals(nv, nt, sh);
+    pv = mi::block_offset<0>(boff, blk) + before.lo; pt = mi::block_offset<1>(boff, blk) + before.hi;
 }
 __global__ __launch_bounds__(256) void mc_slab_counts_kernel(const uint32_t *__restrict__ cnt4, const uint32_t *__restrict__ boff, const McDims d, uint32_t vlo,
                                                              uint32_t vhi, uint32_t tlayers, uint32_t *__restrict__ info, uint32_t *__restrict__ counts)
@@ -239,48 +232,69 @@ __global__ __launch_bounds__(256) void mc_slab_counts_kernel(const uint32_t *__r
     }
 }
 
-struct McLayout { size_t cnt, voff, bsum, boff, bits, total; uint32_t nblk; };
-McLayout mc_layout(uint32_t nx, uint32_t ny, uint32_t nz)
+// The scratch of an nx x ny x nz grid or window: count bytes (padded to whole workgroups), a vertex offset per point, the scans' words, the flag bits; a
+// window's info words come last, so a window runs in the dense scratch of its size plus those.
+struct McScratch { uint32_t *cnt4, *voff; mi::ScanWords scan; unsigned long long *bits64; uint32_t *info; size_t bytes; };
+McScratch mc_scratch(void *base, uint32_t nx, uint32_t ny, uint32_t nz, bool slab)
 {
-    McLayout l{};
+    mi::Carver c(base);
+    McScratch s{};
     const uint64_t npts = (uint64_t)nx * ny * nz;
-    l.nblk = (uint32_t)((npts + MC_PTS - 1) / MC_PTS);
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    size_t o = 0;
-    l.cnt = o; o += al((size_t)l.nblk * MC_PTS);
-    l.voff = o; o += al((size_t)npts * 4);
-    l.bsum = o; o += al((size_t)l.nblk * 4);
-    l.boff = o; o += al((size_t)l.nblk * 8);
-    l.bits = o; o += al(((size_t)l.nblk * MC_PTS / 64 + 2) * 8);
-    l.total = o;
-    return l;
+    const size_t nblk = mi::blocks(npts);
+    s.cnt4 = c.take<uint32_t>(nblk * (mi::ITEMS / 4));
+    s.voff = c.take<uint32_t>((size_t)npts);
+    s.scan = mi::take_scan_words(c, npts);
+    s.bits64 = c.take<unsigned long long>(nblk * (mi::ITEMS / 64) + 2);
+    if (slab) s.info = c.take<uint32_t>(MC_INFO_WORDS);
+    s.bytes = c.bytes;
+    return s;
 }
+const uint32_t *mc_bits(const McScratch &s) { return reinterpret_cast<const uint32_t *>(s.bits64); }      // (the classification reads the flag words by halves)
 
-int mc_check(const char *who, const float *vol, uint32_t nx, uint32_t ny, uint32_t nz, const void *scratch, size_t scratch_bytes, McLayout &l)
+bool mc_grid_ok(uint32_t nx, uint32_t ny, uint32_t nz) { return nx >= 2 && ny >= 2 && nz >= 2 && (uint64_t)nx * ny * nz < (1ull << 31); }
+
+int mc_check(const char *who, const float *vol, uint32_t nx, uint32_t ny, uint32_t nz, void *scratch, size_t scratch_bytes, McDims &d, McScratch &s)
 {
     if (!vol || !scratch) { ac::set_error("%s: NULL buffer", who); return AC_ERR_BAD_ARG; }
-    if (nx < 2 || ny < 2 || nz < 2 || (uint64_t)nx * ny * nz >= (1ull << 31)) { ac::set_error("%s: grid %u x %u x %u unsupported (2 <= n, fewer than 2^31 points)", who, nx, ny, nz); return AC_ERR_BAD_ARG; }
-    l = mc_layout(nx, ny, nz);
-    if (scratch_bytes < l.total) { ac::set_error("%s: scratch of %zu bytes needed, %zu given", who, l.total, scratch_bytes); return AC_ERR_BAD_ARG; }
-    return AC_OK;
+    if (!mc_grid_ok(nx, ny, nz)) { ac::set_error("%s: grid %u x %u x %u unsupported (2 <= n, fewer than 2^31 points)", who, nx, ny, nz); return AC_ERR_BAD_ARG; }
+    d = McDims{ nx, ny, nz, nx * ny * nz };
+    s = mc_scratch(scratch, nx, ny, nz, false);
+    return mi::check_scratch_bytes(who, s.bytes, scratch_bytes);
 }
 
-// a window's scratch: the dense layout of an n x ny x nz grid, then the info words
-bool mc_slab_dims_ok(uint32_t n, uint32_t ny, uint32_t nz) { return n >= 2 && ny >= 2 && nz >= 2 && (uint64_t)n * ny * nz < (1ull << 31); }
-struct McSlabPlan { McLayout l; McDims d; uint32_t vlo, vhi, tlayers; uint32_t *info; };
+struct McSlabPlan { McScratch s; McDims d; uint32_t vlo, vhi, tlayers; };
 int mc_slab_check(const char *who, const float *window, uint32_t n, uint32_t ny, uint32_t nz, uint32_t first, uint32_t last, void *scratch, size_t scratch_bytes,
-                  McSlabPlan &s)
+                  McSlabPlan &p)
 {
     if (!window || !scratch) { ac::set_error("%s: NULL buffer", who); return AC_ERR_BAD_ARG; }
-    if (!mc_slab_dims_ok(n, ny, nz) || (n == 2 && !(first && last))) {
+    if (!mc_grid_ok(n, ny, nz) || (n == 2 && !(first && last))) {
         ac::set_error("%s: window %u x %u x %u unsupported (3 <= n, or n = 2 for a window both first and last; 2 <= ny, nz; fewer than 2^31 points)", who, n, ny, nz);
         return AC_ERR_BAD_ARG;
     }
-    s.l = mc_layout(n, ny, nz);
-    if (scratch_bytes < s.l.total + MC_INFO_WORDS * 4) { ac::set_error("%s: scratch of %zu bytes needed, %zu given", who, s.l.total + MC_INFO_WORDS * 4, scratch_bytes); return AC_ERR_BAD_ARG; }
-    s.d = McDims{ n, ny, nz, n * ny * nz };
-    s.vlo = first ? 0u : 1u; s.vhi = last ? n : n - 1u; s.tlayers = last ? n : n - 2u;
-    s.info = reinterpret_cast<uint32_t *>(static_cast<char *>(scratch) + s.l.total);
+    p.d = McDims{ n, ny, nz, n * ny * nz };
+    p.s = mc_scratch(scratch, n, ny, nz, true);
+    p.vlo = first ? 0u : 1u; p.vhi = last ? n : n - 1u; p.tlayers = last ? n : n - 2u;
+    return mi::check_scratch_bytes(who, p.s.bytes, scratch_bytes);
+}
+
+// flags -> count bytes and the workgroups' totals -> their scan; totals[0..1] = the vertices and triangles of the whole grid or window
+void mc_count_launches(const float *vol, const McDims &d, float iso, const McScratch &s, uint32_t *totals, hipStream_t st)
+{
+    const uint32_t nchunks = (d.npts + 1023u) >> 10;
+    uint32_t blocks = (nchunks + 3u) / 4u;
+    const uint32_t cap = 32u * ac::cu_count();
+    if (blocks > cap) blocks = cap;
+    hipLaunchKernelGGL(mc_flags_kernel, dim3(blocks), dim3(256), 0, st, vol, d.npts, iso, s.bits64);
+    hipLaunchKernelGGL(mc_classify_kernel, dim3(s.scan.nblk), dim3(256), 0, st, mc_bits(s), d, s.cnt4, s.scan.bsum);
+    hipLaunchKernelGGL(pair_scan_kernel, dim3(1), dim3(1024), 0, st, s.scan.bsum, s.scan.nblk, s.scan.boff, totals);
+}
+
+// what both emit entries refuse about their outputs and the transform, then the transform
+int mc_xform(const char *who, double den, const double span[3], const double lo[3], const double *vertices, uint32_t n_vertices, const int32_t *triangles,
+             uint32_t n_triangles, McXform &xf)
+{
+    if ((n_vertices && !vertices) || (n_triangles && !triangles) || !span || !lo || !(den != 0.0)) { ac::set_error("%s: NULL buffer or den == 0", who); return AC_ERR_BAD_ARG; }
+    xf = McXform{ den, { span[0], span[1], span[2] }, { lo[0], lo[1], lo[2] } };
     return AC_OK;
 }
 
@@ -288,28 +302,18 @@ int mc_slab_check(const char *who, const float *window, uint32_t n, uint32_t ny,
 
 AC_API size_t ac_marching_cubes_slab_scratch(uint32_t n, uint32_t ny, uint32_t nz)
 {
-    if (n < 3 || !mc_slab_dims_ok(n, ny, nz)) return 0;     // (n = 2, the whole of a two-layer grid, runs in the scratch of any larger window)
-    return mc_layout(n, ny, nz).total + MC_INFO_WORDS * 4;
+    if (n < 3 || !mc_grid_ok(n, ny, nz)) return 0;     // (n = 2, the whole of a two-layer grid, runs in the scratch of any larger window)
+    return mc_scratch(nullptr, n, ny, nz, true).bytes;
 }
 
 AC_API int ac_marching_cubes_slab_count(const float *window, uint32_t n, uint32_t ny, uint32_t nz, float iso, uint32_t first, uint32_t last, void *scratch,
                                         size_t scratch_bytes, uint32_t *counts, ac_stream_t stream)
 {
-    McSlabPlan s;
-    if (int rc = mc_slab_check("marching_cubes_slab_count", window, n, ny, nz, first, last, scratch, scratch_bytes, s)) return rc;
-    if (!counts) { ac::set_error("marching_cubes_slab_count: NULL counts"); return AC_ERR_BAD_ARG; }
-    char *sc = static_cast<char *>(scratch);
-    uint32_t *cnt4 = reinterpret_cast<uint32_t *>(sc + s.l.cnt), *boff = reinterpret_cast<uint32_t *>(sc + s.l.boff), *bsum = reinterpret_cast<uint32_t *>(sc + s.l.bsum);
-    {
-        const uint32_t nchunks = (s.d.npts + 1023u) >> 10;
-        uint32_t blocks = (nchunks + 3u) / 4u;
-        const uint32_t cap = 32u * ac::cu_count();
-        if (blocks > cap) blocks = cap;
-        hipLaunchKernelGGL(mc_flags_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, window, s.d.npts, iso, reinterpret_cast<unsigned long long *>(sc + s.l.bits));
-    }
-    hipLaunchKernelGGL(mc_classify_kernel, dim3(s.l.nblk), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t *>(sc + s.l.bits), s.d, cnt4, bsum);
-    hipLaunchKernelGGL(pair_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, bsum, s.l.nblk, boff, s.info + MC_INFO_TOTALS);
-    hipLaunchKernelGGL(mc_slab_counts_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, cnt4, boff, s.d, s.vlo, s.vhi, s.tlayers, s.info, counts);
+    McSlabPlan p;
+    if (int rc = mc_slab_check("marching_cubes_slab_count", window, n, ny, nz, first, last, scratch, scratch_bytes, p)) return rc;
+    if (int rc = mi::check_counts("marching_cubes_slab_count", counts)) return rc;
+    mc_count_launches(window, p.d, iso, p.s, p.s.info + MC_INFO_TOTALS, (hipStream_t)stream);
+    hipLaunchKernelGGL(mc_slab_counts_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, p.s.cnt4, p.s.scan.boff, p.d, p.vlo, p.vhi, p.tlayers, p.s.info, counts);
     return ac::check_launch("marching_cubes_slab_count");
 }
 
@@ -317,49 +321,34 @@ AC_API int ac_marching_cubes_slab_emit(const float *window, uint32_t n, uint32_t
                                        size_t scratch_bytes, uint32_t x0, uint32_t vertex_base, double den, const double span[3], const double lo[3],
                                        double *vertices, uint32_t n_vertices, int32_t *triangles, uint32_t n_triangles, ac_stream_t stream)
 {
-    McSlabPlan s;
-    if (int rc = mc_slab_check("marching_cubes_slab_emit", window, n, ny, nz, first, last, scratch, scratch_bytes, s)) return rc;
-    if ((n_vertices && !vertices) || (n_triangles && !triangles) || !span || !lo || !(den != 0.0)) { ac::set_error("marching_cubes_slab_emit: NULL buffer or den == 0"); return AC_ERR_BAD_ARG; }
+    McSlabPlan p; McXform xf;
+    if (int rc = mc_slab_check("marching_cubes_slab_emit", window, n, ny, nz, first, last, scratch, scratch_bytes, p)) return rc;
+    if (int rc = mc_xform("marching_cubes_slab_emit", den, span, lo, vertices, n_vertices, triangles, n_triangles, xf)) return rc;
     if ((uint64_t)x0 + n > 0xffffffffull || (first && x0 != 0u)) { ac::set_error("marching_cubes_slab_emit: x0 %u + n %u overflows 32 bits, or a first window with x0 != 0", x0, n); return AC_ERR_BAD_ARG; }
-    char *sc = static_cast<char *>(scratch);
-    McXform xf{ den, { span[0], span[1], span[2] }, { lo[0], lo[1], lo[2] } };
-    const uint32_t *cnt4 = reinterpret_cast<const uint32_t *>(sc + s.l.cnt), *bsum = reinterpret_cast<const uint32_t *>(sc + s.l.bsum);
-    const uint32_t *boff = reinterpret_cast<const uint32_t *>(sc + s.l.boff);
-    uint32_t *voff = reinterpret_cast<uint32_t *>(sc + s.l.voff);
-    const McSlab sl{ x0, vertex_base, s.vlo, s.vhi, s.tlayers, s.info };
+    const McScratch &s = p.s;
+    const McSlab sl{ x0, vertex_base, p.vlo, p.vhi, p.tlayers, s.info };
     if (n_vertices || n_triangles)                // (triangles of cell layer 0 may use carried vertices only: their indices are formed by this pass all the same)
-        hipLaunchKernelGGL(mc_slab_vertices_kernel, dim3(s.l.nblk), dim3(256), 0, (hipStream_t)stream, window, s.d, iso, cnt4, bsum, boff, voff, xf, vertices, n_vertices, sl);
+        hipLaunchKernelGGL(mc_slab_vertices_kernel, dim3(s.scan.nblk), dim3(256), 0, (hipStream_t)stream, window, p.d, iso, s.cnt4, s.scan.bsum, s.scan.boff, s.voff, xf,
+                           vertices, n_vertices, sl);
     if (n_triangles)
-        hipLaunchKernelGGL(mc_slab_triangles_kernel, dim3(s.l.nblk), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t *>(sc + s.l.bits), s.d, cnt4, bsum, boff,
-                           voff, triangles, n_triangles, s.tlayers);
+        hipLaunchKernelGGL(mc_slab_triangles_kernel, dim3(s.scan.nblk), dim3(256), 0, (hipStream_t)stream, mc_bits(s), p.d, s.cnt4, s.scan.bsum, s.scan.boff, s.voff,
+                           triangles, n_triangles, p.tlayers);
     return ac::check_launch("marching_cubes_slab_emit");
 }
 
 AC_API size_t ac_marching_cubes_scratch(uint32_t nx, uint32_t ny, uint32_t nz)
 {
-    if (nx < 2 || ny < 2 || nz < 2 || (uint64_t)nx * ny * nz >= (1ull << 31)) return 0;
-    return mc_layout(nx, ny, nz).total;
+    if (!mc_grid_ok(nx, ny, nz)) return 0;
+    return mc_scratch(nullptr, nx, ny, nz, false).bytes;
 }
 
 AC_API int ac_marching_cubes_count(const float *volume, uint32_t nx, uint32_t ny, uint32_t nz, float iso, void *scratch, size_t scratch_bytes,
                                    uint32_t *counts, ac_stream_t stream)
 {
-    McLayout l;
-    if (int rc = mc_check("marching_cubes_count", volume, nx, ny, nz, scratch, scratch_bytes, l)) return rc;
-    if (!counts) { ac::set_error("marching_cubes_count: NULL counts"); return AC_ERR_BAD_ARG; }
-    char *sc = static_cast<char *>(scratch);
-    const McDims d{ nx, ny, nz, nx * ny * nz };
-    {
-        const uint32_t nchunks = (d.npts + 1023u) >> 10;
-        uint32_t blocks = (nchunks + 3u) / 4u;
-        const uint32_t cap = 32u * ac::cu_count();
-        if (blocks > cap) blocks = cap;
-        hipLaunchKernelGGL(mc_flags_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, volume, d.npts, iso, reinterpret_cast<unsigned long long *>(sc + l.bits));
-    }
-    hipLaunchKernelGGL(mc_classify_kernel, dim3(l.nblk), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t *>(sc + l.bits), d,
-                       reinterpret_cast<uint32_t *>(sc + l.cnt), reinterpret_cast<uint32_t *>(sc + l.bsum));
-    hipLaunchKernelGGL(pair_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t *>(sc + l.bsum), l.nblk,
-                       reinterpret_cast<uint32_t *>(sc + l.boff), counts);
+    McDims d; McScratch s;
+    if (int rc = mc_check("marching_cubes_count", volume, nx, ny, nz, scratch, scratch_bytes, d, s)) return rc;
+    if (int rc = mi::check_counts("marching_cubes_count", counts)) return rc;
+    mc_count_launches(volume, d, iso, s, counts, (hipStream_t)stream);
     return ac::check_launch("marching_cubes_count");
 }
 
@@ -367,20 +356,14 @@ AC_API int ac_marching_cubes_emit(const float *volume, uint32_t nx, uint32_t ny,
                                   double den, const double span[3], const double lo[3], double *vertices, uint32_t n_vertices, int32_t *triangles,
                                   uint32_t n_triangles, ac_stream_t stream)
 {
-    McLayout l;
-    if (int rc = mc_check("marching_cubes_emit", volume, nx, ny, nz, scratch, scratch_bytes, l)) return rc;
-    if ((n_vertices && !vertices) || (n_triangles && !triangles) || !span || !lo || !(den != 0.0)) { ac::set_error("marching_cubes_emit: NULL buffer or den == 0"); return AC_ERR_BAD_ARG; }
-    char *sc = static_cast<char *>(scratch);
-    const McDims d{ nx, ny, nz, nx * ny * nz };
-    McXform xf{ den, { span[0], span[1], span[2] }, { lo[0], lo[1], lo[2] } };
-    const uint32_t *cnt4 = reinterpret_cast<const uint32_t *>(sc + l.cnt), *bsum = reinterpret_cast<const uint32_t *>(sc + l.bsum);
-    const uint32_t *boff = reinterpret_cast<const uint32_t *>(sc + l.boff);
-    uint32_t *voff = reinterpret_cast<uint32_t *>(sc + l.voff);
+    McDims d; McScratch s; McXform xf;
+    if (int rc = mc_check("marching_cubes_emit", volume, nx, ny, nz, scratch, scratch_bytes, d, s)) return rc;
+    if (int rc = mc_xform("marching_cubes_emit", den, span, lo, vertices, n_vertices, triangles, n_triangles, xf)) return rc;
     if (n_vertices)
-        hipLaunchKernelGGL(mc_vertices_kernel, dim3(l.nblk), dim3(256), 0, (hipStream_t)stream, volume, d, iso, cnt4, bsum, boff, voff, xf, vertices, n_vertices);
+        hipLaunchKernelGGL(mc_vertices_kernel, dim3(s.scan.nblk), dim3(256), 0, (hipStream_t)stream, volume, d, iso, s.cnt4, s.scan.bsum, s.scan.boff, s.voff, xf,
+                           vertices, n_vertices);
     if (n_triangles)
-        hipLaunchKernelGGL(mc_triangles_kernel, dim3(l.nblk), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t *>(sc + l.bits), d, cnt4, bsum, boff, voff,
+        hipLaunchKernelGGL(mc_triangles_kernel, dim3(s.scan.nblk), dim3(256), 0, (hipStream_t)stream, mc_bits(s), d, s.cnt4, s.scan.bsum, s.scan.boff, s.voff,
                            triangles, n_triangles);
     return ac::check_launch("marching_cubes_emit");
 }
-

@@ -4,15 +4,12 @@
 // The vertices of one grid cell merge.  A cell is found through an open-addressing table in scratch: slots keyed by the 64-bit cell key, claimed with a 64-bit
 // compare-exchange under linear probing; a slot holds the smallest member index (integer atomic min), the member count and three int64 sums of the members'
 // fixed-point offsets inside the cell (integer atomic adds); every vertex remembers its slot.  A cell's leader is its smallest member, clusters are numbered by
-// ascending leader (flags -> the ordered scans of ac_scan.hpp), and the position is a function of the exact integer sums: nothing depends on scheduling or on
+// ascending leader (flags -> the ordered passes of mesh_index.hpp), and the position is a function of the exact integer sums: nothing depends on scheduling or on
 // the hash, although the table is filled with atomics.  No wave ever waits for another one: see mc_slot.  No floating-point atomics.
-#include "ac_common.hpp"
-#include "ac_scan.hpp"
+#include "mesh_index.hpp"
 
 namespace {
 
-constexpr uint32_t MCL_ITEMS = 1024;              // vertices (and triangles) per workgroup of the scanned passes: 256 threads x 4 consecutive items
-constexpr uint32_t MCL_MAX = 0x7fffffffu;         // indices are int32
 constexpr uint32_t MCL_MAX_N = 1u << 21;          // cells per axis: three of them fit a 63-bit key
 constexpr uint64_t MCL_EMPTY = ~0ull;             // no key: a key stays below 2^63
 enum { MCL_INFO_BAD_V = 0, MCL_INFO_BAD_T = 1, MCL_INFO_WORDS = 64 };
@@ -106,14 +103,11 @@ __device__ __forceinline__ bool mcl_is_leader(const int64_t *__restrict__ slot, 
 // a triangle's three slots, -1 if it is invalid (an index outside [0, V) or an invalid vertex).  Two vertices share a cluster iff they share a slot.
 __device__ __forceinline__ bool mcl_tri_slots(const int32_t *__restrict__ tris, uint32_t t, uint32_t V, const int64_t *__restrict__ slot, int64_t s[3])
 {
+    const int32_t i[3] = { tris[3 * (size_t)t], tris[3 * (size_t)t + 1], tris[3 * (size_t)t + 2] };
+    if (!mi::tri_in_range(i[0], i[1], i[2], V)) return false;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int32_t i = tris[3 * (size_t)t + k];
-        if ((uint32_t)i >= V) return false;
-        s[k] = slot[i];
-        if (s[k] < 0) return false;
-    }
-    return true;
+    for (int k = 0; k < 3; ++k) s[k] = slot[i[k]];
+    return s[0] >= 0 && s[1] >= 0 && s[2] >= 0;
 }
 __device__ __forceinline__ bool mcl_survives(const int64_t s[3]) { return s[0] != s[1] && s[1] != s[2] && s[0] != s[2]; }
 
@@ -140,10 +134,8 @@ __global__ __launch_bounds__(256) void mcl_count_kernel(const int32_t *__restric
                                                         const int32_t *__restrict__ lead, uint32_t *__restrict__ bsum, uint32_t *info)
 {
     __shared__ uint32_t sh[8];
-    const uint32_t m = mcl_flags<true, true>(tris, T, V, slot, lead, blockIdx.x * MCL_ITEMS + threadIdx.x * 4u);
-    uint32_t tot;
-    (void)block_exscan_256((uint32_t)__builtin_popcount(m & 15u) | ((uint32_t)__builtin_popcount((m >> 4) & 15u) << 16), sh, tot);      // <= 1024 of either: 16 bits each
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
+    const uint32_t m = mcl_flags<true, true>(tris, T, V, slot, lead, mi::first_item());
+    mi::block_totals((uint32_t)__builtin_popcount(m & 15u), (uint32_t)__builtin_popcount((m >> 4) & 15u), sh, bsum);
     const uint32_t bad = (uint32_t)__builtin_popcount(m >> 8);
     if (bad) atomicAdd(info + MCL_INFO_BAD_T, bad);
 }
@@ -152,14 +144,8 @@ __global__ __launch_bounds__(256) void mcl_count_kernel(const int32_t *__restric
 __global__ __launch_bounds__(256) void mcl_rank_kernel(uint32_t V, const int64_t *__restrict__ slot, const int32_t *__restrict__ lead, const uint32_t *__restrict__ boff,
                                                        int32_t *__restrict__ rank, const uint32_t *__restrict__ info, uint32_t *__restrict__ counts)
 {
-    __shared__ uint32_t sh[8];
-    const uint32_t i0 = blockIdx.x * MCL_ITEMS + threadIdx.x * 4u;
-    const uint32_t m = mcl_flags<true, false>(nullptr, 0u, V, slot, lead, i0);
-    uint32_t tot;
-    uint32_t c = boff[2 * blockIdx.x] + block_exscan_256((uint32_t)__builtin_popcount(m), sh, tot);
-#pragma unroll
-    for (uint32_t r = 0; r < 4; ++r)
-        if ((m >> r) & 1u) rank[slot[i0 + r]] = (int32_t)c++;
+    const uint32_t m = mcl_flags<true, false>(nullptr, 0u, V, slot, lead, mi::first_item());
+    mi::ordered_pass<0>(m, boff, [&](uint32_t v, uint32_t c) { rank[slot[v]] = (int32_t)c; });
     if (blockIdx.x == 0 && threadIdx.x == 0) { counts[2] = info[MCL_INFO_BAD_V]; counts[3] = info[MCL_INFO_BAD_T]; }
 }
 
@@ -201,65 +187,36 @@ __global__ __launch_bounds__(256) void mcl_emit_triangles_kernel(const int32_t *
                                                                  const int32_t *__restrict__ rank, const uint32_t *__restrict__ boff, int32_t *__restrict__ tris_out,
                                                                  int32_t *__restrict__ kept_triangles, uint32_t n_kept)
 {
-    __shared__ uint32_t sh[8];
-    const uint32_t i0 = blockIdx.x * MCL_ITEMS + threadIdx.x * 4u;
-    const uint32_t m = (mcl_flags<false, true>(tris, T, V, slot, nullptr, i0) >> 4) & 15u;
-    uint32_t tot;
-    uint32_t o = boff[2 * blockIdx.x + 1] + block_exscan_256((uint32_t)__builtin_popcount(m), sh, tot);
-#pragma unroll
-    for (uint32_t r = 0; r < 4; ++r) {
-        if (!((m >> r) & 1u)) continue;
-        const uint32_t t = i0 + r;
-        if (o < n_kept) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) tris_out[3 * (size_t)o + k] = rank[slot[tris[3 * (size_t)t + k]]];
-            kept_triangles[o] = (int32_t)t;
-        }
-        ++o;
-    }
+    const uint32_t m = mcl_flags<false, true>(tris, T, V, slot, nullptr, mi::first_item()) >> 4;
+    mi::emit_kept_triangles(m, tris, boff, [&](int32_t v) { return rank[slot[v]]; }, tris_out, kept_triangles, n_kept);
 }
 
-size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-uint32_t mcl_blocks(uint32_t n) { return (uint32_t)(((uint64_t)n + MCL_ITEMS - 1) / MCL_ITEMS); }
-
-struct MclLayout { size_t info, keys, lead, cnt, sums, rank, slot, bsum, boff, total; uint64_t capacity; uint32_t nblk; };
-MclLayout mcl_layout(uint32_t V, uint32_t T)
+// the scratch: the info words, the table (`capacity` slots, a power of two >= 2 V: never more than half full), a slot per vertex, the scan's words over
+// vertices and triangles alike
+struct MclScratch { uint32_t *info; MclTable tb; int64_t *slot; mi::ScanWords scan; uint64_t capacity; size_t bytes; };
+MclScratch mcl_scratch(void *base, uint32_t V, uint32_t T)
 {
-    MclLayout l{};
-    l.capacity = 2;
-    while (l.capacity < 2 * (uint64_t)V) l.capacity <<= 1;        // a power of two >= 2 V: the table is never more than half full
-    l.nblk = mcl_blocks(V > T ? V : T);
-    size_t o = 0;
-    l.info = o; o += al256(MCL_INFO_WORDS * 4);
-    l.keys = o; o += al256((size_t)l.capacity * 8);
-    l.sums = o; o += al256((size_t)l.capacity * 24);
-    l.lead = o; o += al256((size_t)l.capacity * 4);
-    l.cnt = o; o += al256((size_t)l.capacity * 4);
-    l.rank = o; o += al256((size_t)l.capacity * 4);
-    l.slot = o; o += al256((size_t)V * 8);
-    l.bsum = o; o += al256((size_t)l.nblk * 4);
-    l.boff = o; o += al256((size_t)l.nblk * 8);
-    l.total = o;
-    return l;
-}
-
-struct MclView { MclTable tb; uint32_t *info, *bsum, *boff; int64_t *slot; };
-MclView mcl_view(void *scratch, const MclLayout &l)
-{
-    char *sc = static_cast<char *>(scratch);
-    MclView w;
-    w.tb.keys = reinterpret_cast<uint64_t *>(sc + l.keys); w.tb.sums = reinterpret_cast<uint64_t *>(sc + l.sums);
-    w.tb.lead = reinterpret_cast<int32_t *>(sc + l.lead); w.tb.cnt = reinterpret_cast<uint32_t *>(sc + l.cnt); w.tb.rank = reinterpret_cast<int32_t *>(sc + l.rank);
-    w.info = reinterpret_cast<uint32_t *>(sc + l.info); w.bsum = reinterpret_cast<uint32_t *>(sc + l.bsum); w.boff = reinterpret_cast<uint32_t *>(sc + l.boff);
-    w.slot = reinterpret_cast<int64_t *>(sc + l.slot);
-    return w;
+    mi::Carver c(base);
+    MclScratch s{};
+    s.capacity = 2;
+    while (s.capacity < 2 * (uint64_t)V) s.capacity <<= 1;
+    s.info = c.take<uint32_t>(MCL_INFO_WORDS);
+    s.tb.keys = c.take<uint64_t>((size_t)s.capacity);
+    s.tb.sums = c.take<uint64_t>(3 * (size_t)s.capacity);
+    s.tb.lead = c.take<int32_t>((size_t)s.capacity);
+    s.tb.cnt = c.take<uint32_t>((size_t)s.capacity);
+    s.tb.rank = c.take<int32_t>((size_t)s.capacity);
+    s.slot = c.take<int64_t>(V);
+    s.scan = mi::take_scan_words(c, V > T ? V : T);
+    s.bytes = c.bytes;
+    return s;
 }
 
 // what both entries refuse, before any launch
-int mcl_check(const char *who, const double *verts, uint32_t V, const int32_t *tris, uint32_t T, const ac_cluster_grid *grid, const void *scratch, size_t scratch_bytes,
-              MclLayout &l, MclGrid &g)
+int mcl_check(const char *who, const double *verts, uint32_t V, const int32_t *tris, uint32_t T, const ac_cluster_grid *grid, void *scratch, size_t scratch_bytes,
+              MclScratch &s, MclGrid &g)
 {
-    if (V > MCL_MAX || T > MCL_MAX) { ac::set_error("%s: V %u or T %u above 2^31 - 1 (indices are int32)", who, V, T); return AC_ERR_BAD_ARG; }
+    if (int rc = mi::check_index_limit(who, V, T)) return rc;
     if (!grid) { ac::set_error("%s: NULL grid", who); return AC_ERR_BAD_ARG; }
     if (!(grid->h > 0.0) || !isfinite(grid->h)) { ac::set_error("%s: cell edge h %g must be finite and > 0", who, grid->h); return AC_ERR_BAD_ARG; }
     for (int a = 0; a < 3; ++a) {
@@ -268,38 +225,36 @@ int mcl_check(const char *who, const double *verts, uint32_t V, const int32_t *t
     }
     g.h = grid->h;
     if ((V && !verts) || (T && !tris) || ((V || T) && !scratch)) { ac::set_error("%s: NULL buffer", who); return AC_ERR_BAD_ARG; }
-    l = mcl_layout(V, T);
-    if ((V || T) && scratch_bytes < l.total) { ac::set_error("%s: scratch of %zu bytes needed, %zu given", who, l.total, scratch_bytes); return AC_ERR_BAD_ARG; }
-    return AC_OK;
+    s = mcl_scratch(scratch, V, T);
+    return V || T ? mi::check_scratch_bytes(who, s.bytes, scratch_bytes) : AC_OK;
 }
 
 }  // namespace
 
 AC_API size_t ac_mesh_cluster_scratch(uint32_t V, uint32_t T)
 {
-    if (V > MCL_MAX || T > MCL_MAX) return 0;
-    return mcl_layout(V, T).total;
+    if (!mi::index_limit_ok(V, T)) return 0;
+    return mcl_scratch(nullptr, V, T).bytes;
 }
 
 AC_API int ac_mesh_cluster_count(const double *vertices, uint32_t V, const int32_t *triangles, uint32_t T, const ac_cluster_grid *grid, void *scratch,
                                  size_t scratch_bytes, int32_t *cluster, uint32_t *counts, ac_stream_t stream)
 {
-    MclLayout l; MclGrid g;
-    if (int rc = mcl_check("mesh_cluster_count", vertices, V, triangles, T, grid, scratch, scratch_bytes, l, g)) return rc;
-    if (!counts) { ac::set_error("mesh_cluster_count: NULL counts"); return AC_ERR_BAD_ARG; }
+    MclScratch s; MclGrid g;
+    if (int rc = mcl_check("mesh_cluster_count", vertices, V, triangles, T, grid, scratch, scratch_bytes, s, g)) return rc;
+    if (int rc = mi::check_counts("mesh_cluster_count", counts)) return rc;
     if (V && !cluster) { ac::set_error("mesh_cluster_count: NULL cluster"); return AC_ERR_BAD_ARG; }
     hipStream_t st = (hipStream_t)stream;
     if (V == 0 && T == 0) {                       // nothing to cluster: no launch
         if (hipMemsetAsync(counts, 0, 16, st) != hipSuccess) return ac::check_launch("mesh_cluster_count");
         return AC_OK;
     }
-    const MclView w = mcl_view(scratch, l);
-    hipLaunchKernelGGL(mcl_init_kernel, dim3((uint32_t)((l.capacity + 255u) / 256u)), dim3(256), 0, st, w.tb, l.capacity, w.info);
-    if (V) hipLaunchKernelGGL(mcl_fill_kernel, dim3((V + 255u) / 256u), dim3(256), 0, st, vertices, V, g, w.tb, l.capacity - 1u, w.slot, w.info);
-    hipLaunchKernelGGL(mcl_count_kernel, dim3(l.nblk), dim3(256), 0, st, triangles, T, V, w.slot, w.tb.lead, w.bsum, w.info);
-    hipLaunchKernelGGL(pair_scan_kernel, dim3(1), dim3(1024), 0, st, w.bsum, l.nblk, w.boff, counts);
-    hipLaunchKernelGGL(mcl_rank_kernel, dim3(l.nblk), dim3(256), 0, st, V, w.slot, w.tb.lead, w.boff, w.tb.rank, w.info, counts);
-    if (V) hipLaunchKernelGGL(mcl_cluster_kernel, dim3((V + 255u) / 256u), dim3(256), 0, st, V, w.slot, w.tb.rank, cluster);
+    hipLaunchKernelGGL(mcl_init_kernel, dim3((uint32_t)((s.capacity + 255u) / 256u)), dim3(256), 0, st, s.tb, s.capacity, s.info);
+    if (V) hipLaunchKernelGGL(mcl_fill_kernel, dim3((V + 255u) / 256u), dim3(256), 0, st, vertices, V, g, s.tb, s.capacity - 1u, s.slot, s.info);
+    hipLaunchKernelGGL(mcl_count_kernel, dim3(s.scan.nblk), dim3(256), 0, st, triangles, T, V, s.slot, s.tb.lead, s.scan.bsum, s.info);
+    hipLaunchKernelGGL(pair_scan_kernel, dim3(1), dim3(1024), 0, st, s.scan.bsum, s.scan.nblk, s.scan.boff, counts);
+    hipLaunchKernelGGL(mcl_rank_kernel, dim3(s.scan.nblk), dim3(256), 0, st, V, s.slot, s.tb.lead, s.scan.boff, s.tb.rank, s.info, counts);
+    if (V) hipLaunchKernelGGL(mcl_cluster_kernel, dim3((V + 255u) / 256u), dim3(256), 0, st, V, s.slot, s.tb.rank, cluster);
     return ac::check_launch("mesh_cluster_count");
 }
 
@@ -307,8 +262,8 @@ AC_API int ac_mesh_cluster_emit(const double *vertices, uint32_t V, const int32_
                                 size_t scratch_bytes, int32_t *leader, uint32_t *members, double *positions, uint32_t n_clusters, int32_t *triangles_out,
                                 int32_t *kept_triangles, uint32_t n_kept_triangles, ac_stream_t stream)
 {
-    MclLayout l; MclGrid g;
-    if (int rc = mcl_check("mesh_cluster_emit", vertices, V, triangles, T, grid, scratch, scratch_bytes, l, g)) return rc;
+    MclScratch s; MclGrid g;
+    if (int rc = mcl_check("mesh_cluster_emit", vertices, V, triangles, T, grid, scratch, scratch_bytes, s, g)) return rc;
     if (n_clusters > V || n_kept_triangles > T) {
         ac::set_error("mesh_cluster_emit: n_clusters %u > V %u or n_kept_triangles %u > T %u", n_clusters, V, n_kept_triangles, T);
         return AC_ERR_BAD_ARG;
@@ -318,11 +273,10 @@ AC_API int ac_mesh_cluster_emit(const double *vertices, uint32_t V, const int32_
         return AC_ERR_BAD_ARG;
     }
     hipStream_t st = (hipStream_t)stream;
-    const MclView w = mcl_view(scratch, l);
     if (n_clusters)
-        hipLaunchKernelGGL(mcl_emit_clusters_kernel, dim3((V + 255u) / 256u), dim3(256), 0, st, V, g, w.tb, w.slot, leader, members, positions, n_clusters);
+        hipLaunchKernelGGL(mcl_emit_clusters_kernel, dim3((V + 255u) / 256u), dim3(256), 0, st, V, g, s.tb, s.slot, leader, members, positions, n_clusters);
     if (n_kept_triangles)
-        hipLaunchKernelGGL(mcl_emit_triangles_kernel, dim3(mcl_blocks(T)), dim3(256), 0, st, triangles, T, V, w.slot, w.tb.rank, w.boff, triangles_out,
+        hipLaunchKernelGGL(mcl_emit_triangles_kernel, dim3(mi::blocks(T)), dim3(256), 0, st, triangles, T, V, s.slot, s.tb.rank, s.scan.boff, triangles_out,
                            kept_triangles, n_kept_triangles);
     return ac::check_launch("mesh_cluster_emit");
 }

@@ -5,14 +5,12 @@
 // Labelling: a union-find over parent[V] in scratch -- initialise, ONE hooking launch over the triangles, flatten.  A hook always links the LARGER root under
 // the SMALLER, so every value ever stored in parent[v] is <= the one before it and <= v, a root is a vertex with parent[v] == v, a vertex that stopped being
 // a root never becomes one again, and the last root left in a component is its smallest vertex: the labelling is canonical (no dependence on triangle order
-// or scheduling) although the hooks are atomics.  Ranks, sizes and the compaction are scans (ac_scan.hpp) and integer adds: deterministic as well.
+// or scheduling) although the hooks are atomics.  Ranks, sizes and the compaction are ordered passes (mesh_index.hpp) and integer adds: deterministic as well.
 // No wave ever waits for another one: see cc_find / cc_unite.  No floating-point atomics.
-#include "ac_common.hpp"
-#include "ac_scan.hpp"
+#include "mesh_index.hpp"
 
 namespace {
 
-constexpr uint32_t CC_ITEMS = 1024;               // vertices (and triangles) per workgroup of the scanned passes: 256 threads x 4 consecutive items
 enum { CC_INFO_TOTALS = 0 /* [2]: pair_scan_kernel's totals = { C, 0 } */, CC_INFO_BAD = 2 /* invalid triangles */, CC_INFO_WORDS = 64 };
 
 // gfx950 has eight XCDs with private L2s: inside the hooking launch parent[] is touched by agent-scope atomics on a GLOBAL pointer only (a plain load may
@@ -55,8 +53,6 @@ __device__ __forceinline__ void cc_unite(int32_t *parent, int32_t u, int32_t v)
     }
 }
 
-__device__ __forceinline__ bool cc_valid(int32_t a, int32_t b, int32_t c, uint32_t V) { return (uint32_t)a < V && (uint32_t)b < V && (uint32_t)c < V; }
-
 __global__ __launch_bounds__(256) void cc_init_kernel(int32_t *__restrict__ parent, uint32_t V, uint32_t *__restrict__ info)
 {
     const uint32_t v = blockIdx.x * 256u + threadIdx.x;
@@ -71,7 +67,7 @@ __global__ __launch_bounds__(256) void cc_hook_kernel(const int32_t *__restrict_
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     if (t >= T) return;
     const int32_t a = tris[3 * (size_t)t], b = tris[3 * (size_t)t + 1], c = tris[3 * (size_t)t + 2];
-    if (!cc_valid(a, b, c, V)) { atomicAdd(info + CC_INFO_BAD, 1u); return; }      // (joins nothing; the compiler forms one add per wave)
+    if (!mi::tri_in_range(a, b, c, V)) { atomicAdd(info + CC_INFO_BAD, 1u); return; }      // (joins nothing; the compiler forms one add per wave)
     cc_unite(parent, a, b);
     cc_unite(parent, a, c);
     cc_unite(parent, b, c);
@@ -81,20 +77,17 @@ __global__ __launch_bounds__(256) void cc_hook_kernel(const int32_t *__restrict_
 __global__ __launch_bounds__(256) void cc_flatten_kernel(const int32_t *__restrict__ parent, uint32_t V, int32_t *__restrict__ root, uint32_t *__restrict__ bsum)
 {
     __shared__ uint32_t sh[8];
-    const uint32_t v0 = blockIdx.x * CC_ITEMS + threadIdx.x * 4u;
     uint32_t n = 0;
 #pragma unroll
     for (uint32_t r = 0; r < 4; ++r) {
-        const uint32_t v = v0 + r;
+        const uint32_t v = mi::first_item() + r;
         if (v >= V) continue;
         int32_t x = (int32_t)v;
         for (;;) { const int32_t p = parent[x]; if (p == x) break; x = p; }
         root[v] = x;
         n += x == (int32_t)v ? 1u : 0u;
     }
-    uint32_t tot;
-    (void)block_exscan_256(n, sh, tot);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;                  // <= 1024 roots per workgroup: the low half of pair_scan_kernel's pair, the high one stays 0
+    mi::block_totals(n, 0u, sh, bsum);                             // the roots are the low count of the pair, the high one stays 0
 }
 
 // rank of every root among the roots in ascending order -> rank[root] (the parent array, which nothing reads any more: root[] has its content), the rows of
@@ -103,21 +96,15 @@ __global__ __launch_bounds__(256) void cc_rank_kernel(const int32_t *__restrict_
                                                       uint32_t *__restrict__ sizes, uint32_t max_components, const uint32_t *__restrict__ info,
                                                       uint32_t *__restrict__ counts)
 {
-    __shared__ uint32_t sh[8];
-    const uint32_t v0 = blockIdx.x * CC_ITEMS + threadIdx.x * 4u;
-    uint32_t is_root = 0, n = 0;
+    const uint32_t v0 = mi::first_item();
+    uint32_t is_root = 0;
 #pragma unroll
     for (uint32_t r = 0; r < 4; ++r)
-        if (v0 + r < V && root[v0 + r] == (int32_t)(v0 + r)) { is_root |= 1u << r; ++n; }
-    uint32_t tot;
-    uint32_t c = boff[2 * blockIdx.x] + block_exscan_256(n, sh, tot);
-#pragma unroll
-    for (uint32_t r = 0; r < 4; ++r) {
-        if (!((is_root >> r) & 1u)) continue;
-        rank[v0 + r] = (int32_t)c;
+        if (v0 + r < V && root[v0 + r] == (int32_t)(v0 + r)) is_root |= 1u << r;
+    mi::ordered_pass<0>(is_root, boff, [&](uint32_t v, uint32_t c) {
+        rank[v] = (int32_t)c;
         if (c < max_components) { sizes[2 * (size_t)c] = 0u; sizes[2 * (size_t)c + 1] = 0u; }
-        ++c;
-    }
+    });
     if (blockIdx.x == 0 && threadIdx.x == 0) { counts[0] = info[CC_INFO_TOTALS]; counts[1] = info[CC_INFO_BAD]; }
 }
 
@@ -157,7 +144,7 @@ __global__ __launch_bounds__(256) void cc_sizes_kernel(const int32_t *__restrict
     c = -1;
     if (i < T) {
         const int32_t a = tris[3 * (size_t)i], b = tris[3 * (size_t)i + 1], d = tris[3 * (size_t)i + 2];
-        if (cc_valid(a, b, d, V)) c = rank[root[a]];
+        if (mi::tri_in_range(a, b, d, V)) c = rank[root[a]];
     }
     cc_wave_add(sizes, 1u, c, max_components);
 }
@@ -178,7 +165,7 @@ __device__ __forceinline__ uint32_t cp_flags(const int32_t *__restrict__ tris, u
         }
         if (WANT_T && i < T) {
             const int32_t a = tris[3 * (size_t)i], b = tris[3 * (size_t)i + 1], d = tris[3 * (size_t)i + 2];
-            if (cc_valid(a, b, d, V)) {
+            if (mi::tri_in_range(a, b, d, V)) {
                 const uint32_t c = (uint32_t)component[a];
                 if (c < C && keep[c]) m |= 16u << r;
             }
@@ -191,29 +178,23 @@ __global__ __launch_bounds__(256) void cp_count_kernel(const int32_t *__restrict
                                                        const uint8_t *__restrict__ keep, uint32_t C, uint32_t *__restrict__ bsum)
 {
     __shared__ uint32_t sh[8];
-    const uint32_t m = cp_flags<true, true>(tris, T, V, component, keep, C, blockIdx.x * CC_ITEMS + threadIdx.x * 4u);
-    uint32_t tot;
-    (void)block_exscan_256((uint32_t)__builtin_popcount(m & 15u) | ((uint32_t)__builtin_popcount(m >> 4) << 16), sh, tot);      // <= 1024 of either: 16 bits each
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
+    const uint32_t m = cp_flags<true, true>(tris, T, V, component, keep, C, mi::first_item());
+    mi::block_totals((uint32_t)__builtin_popcount(m & 15u), (uint32_t)__builtin_popcount(m >> 4), sh, bsum);
 }
 
 __global__ __launch_bounds__(256) void cp_vertices_kernel(uint32_t V, const int32_t *__restrict__ component, const uint8_t *__restrict__ keep, uint32_t C,
                                                           const uint32_t *__restrict__ boff, int32_t *__restrict__ vertex_map,
                                                           int32_t *__restrict__ kept_vertices, uint32_t n_kept)
 {
-    __shared__ uint32_t sh[8];
-    const uint32_t i0 = blockIdx.x * CC_ITEMS + threadIdx.x * 4u;
+    const uint32_t i0 = mi::first_item();
     const uint32_t m = cp_flags<true, false>(nullptr, 0u, V, component, keep, C, i0);
-    uint32_t tot;
-    uint32_t o = boff[2 * blockIdx.x] + block_exscan_256((uint32_t)__builtin_popcount(m), sh, tot);
 #pragma unroll
-    for (uint32_t r = 0; r < 4; ++r) {
-        const uint32_t v = i0 + r;
-        if (v >= V) continue;
-        const bool k = (m >> r) & 1u;
-        vertex_map[v] = k ? (int32_t)o : -1;
-        if (k) { if (o < n_kept) kept_vertices[o] = (int32_t)v; ++o; }
-    }
+    for (uint32_t r = 0; r < 4; ++r)
+        if (i0 + r < V && !((m >> r) & 1u)) vertex_map[i0 + r] = -1;
+    mi::ordered_pass<0>(m, boff, [&](uint32_t v, uint32_t o) {
+        vertex_map[v] = (int32_t)o;
+        if (o < n_kept) kept_vertices[o] = (int32_t)v;
+    });
 }
 
 // (vertex_map is the previous launch's: read-only here)
@@ -222,96 +203,74 @@ __global__ __launch_bounds__(256) void cp_triangles_kernel(const int32_t *__rest
                                                            const int32_t *__restrict__ vertex_map, int32_t *__restrict__ tris_out,
                                                            int32_t *__restrict__ kept_triangles, uint32_t n_kept)
 {
-    __shared__ uint32_t sh[8];
-    const uint32_t i0 = blockIdx.x * CC_ITEMS + threadIdx.x * 4u;
-    const uint32_t m = cp_flags<false, true>(tris, T, V, component, keep, C, i0) >> 4;
-    uint32_t tot;
-    uint32_t o = boff[2 * blockIdx.x + 1] + block_exscan_256((uint32_t)__builtin_popcount(m), sh, tot);
-#pragma unroll
-    for (uint32_t r = 0; r < 4; ++r) {
-        if (!((m >> r) & 1u)) continue;
-        const uint32_t t = i0 + r;
-        if (o < n_kept) {
-#pragma unroll
-            for (int q = 0; q < 3; ++q) tris_out[3 * (size_t)o + q] = vertex_map[tris[3 * (size_t)t + q]];
-            kept_triangles[o] = (int32_t)t;
-        }
-        ++o;
-    }
+    const uint32_t m = cp_flags<false, true>(tris, T, V, component, keep, C, mi::first_item()) >> 4;
+    mi::emit_kept_triangles(m, tris, boff, [&](int32_t v) { return vertex_map[v]; }, tris_out, kept_triangles, n_kept);
 }
 
-constexpr uint32_t CC_MAX = 0x7fffffffu;          // indices are int32
-size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-uint32_t cc_blocks(uint32_t n) { return (uint32_t)(((uint64_t)n + CC_ITEMS - 1) / CC_ITEMS); }
-
-struct CcLayout { size_t info, parent, bsum, boff, total; uint32_t nblk; };
-CcLayout cc_layout(uint32_t V)
+// the labelling's scratch: the info words, parent[V], the scan's words over the vertices
+struct CcScratch { uint32_t *info; int32_t *parent; mi::ScanWords scan; size_t bytes; };
+CcScratch cc_scratch(void *base, uint32_t V)
 {
-    CcLayout l{};
-    l.nblk = cc_blocks(V);
-    size_t o = 0;
-    l.info = o; o += al256(CC_INFO_WORDS * 4);
-    l.parent = o; o += al256((size_t)V * 4);
-    l.bsum = o; o += al256((size_t)l.nblk * 4);
-    l.boff = o; o += al256((size_t)l.nblk * 8);
-    l.total = o;
-    return l;
+    mi::Carver c(base);
+    CcScratch s{};
+    s.info = c.take<uint32_t>(CC_INFO_WORDS);
+    s.parent = c.take<int32_t>(V);
+    s.scan = mi::take_scan_words(c, V);
+    s.bytes = c.bytes;
+    return s;
 }
-struct CpLayout { size_t bsum, boff, total; uint32_t nblk; };
-CpLayout cp_layout(uint32_t V, uint32_t T)
+// the compaction's: one scan's words over vertices and triangles alike
+struct CpScratch { mi::ScanWords scan; size_t bytes; };
+CpScratch cp_scratch(void *base, uint32_t V, uint32_t T)
 {
-    CpLayout l{};
-    l.nblk = cc_blocks(V > T ? V : T);
-    l.bsum = 0; l.boff = al256((size_t)l.nblk * 4);
-    l.total = l.boff + al256((size_t)l.nblk * 8);
-    return l;
+    mi::Carver c(base);
+    CpScratch s{};
+    s.scan = mi::take_scan_words(c, V > T ? V : T);
+    s.bytes = c.bytes;
+    return s;
 }
 
 // what both compaction entries refuse, before any launch
-int cp_check(const char *who, const int32_t *tris, uint32_t T, uint32_t V, const int32_t *component, const uint8_t *keep, uint32_t C, const void *scratch,
-             size_t scratch_bytes, CpLayout &l)
+int cp_check(const char *who, const int32_t *tris, uint32_t T, uint32_t V, const int32_t *component, const uint8_t *keep, uint32_t C, void *scratch,
+             size_t scratch_bytes, CpScratch &s)
 {
-    if (V > CC_MAX || T > CC_MAX) { ac::set_error("%s: V %u or T %u above 2^31 - 1 (indices are int32)", who, V, T); return AC_ERR_BAD_ARG; }
-    if (V == 0 && T != 0) { ac::set_error("%s: %u triangles over no vertex", who, T); return AC_ERR_BAD_ARG; }
+    if (int rc = mi::check_index_limit(who, V, T)) return rc;
+    if (int rc = mi::check_some_vertex(who, V, T)) return rc;
     if (C > V) { ac::set_error("%s: C %u > V %u (a component has at least one vertex)", who, C, V); return AC_ERR_BAD_ARG; }
     if (V && (!component || !scratch || (T && !tris) || (C && !keep))) { ac::set_error("%s: NULL buffer", who); return AC_ERR_BAD_ARG; }
-    l = cp_layout(V, T);
-    if (V && scratch_bytes < l.total) { ac::set_error("%s: scratch of %zu bytes needed, %zu given", who, l.total, scratch_bytes); return AC_ERR_BAD_ARG; }
-    return AC_OK;
+    s = cp_scratch(scratch, V, T);
+    return V ? mi::check_scratch_bytes(who, s.bytes, scratch_bytes) : AC_OK;
 }
 
 }  // namespace
 
 AC_API size_t ac_mesh_components_scratch(uint32_t V, uint32_t T)
 {
-    if (V > CC_MAX || T > CC_MAX) return 0;
-    return cc_layout(V).total;
+    if (!mi::index_limit_ok(V, T)) return 0;
+    return cc_scratch(nullptr, V).bytes;
 }
 
 AC_API int ac_mesh_components(const int32_t *triangles, uint32_t T, uint32_t V, int32_t *root, int32_t *component, uint32_t *sizes, uint32_t max_components,
                               uint32_t *counts, void *scratch, size_t scratch_bytes, ac_stream_t stream)
 {
-    if (V > CC_MAX || T > CC_MAX) { ac::set_error("mesh_components: V %u or T %u above 2^31 - 1 (indices are int32)", V, T); return AC_ERR_BAD_ARG; }
-    if (V == 0 && T != 0) { ac::set_error("mesh_components: %u triangles over no vertex", T); return AC_ERR_BAD_ARG; }
-    if (!counts) { ac::set_error("mesh_components: NULL counts"); return AC_ERR_BAD_ARG; }
+    if (int rc = mi::check_index_limit("mesh_components", V, T)) return rc;
+    if (int rc = mi::check_some_vertex("mesh_components", V, T)) return rc;
+    if (int rc = mi::check_counts("mesh_components", counts)) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (V == 0) {                                 // C = 0, n_bad = 0: no launch
         if (hipMemsetAsync(counts, 0, 8, st) != hipSuccess) return ac::check_launch("mesh_components");
         return AC_OK;
     }
     if (!root || !component || !scratch || (T && !triangles) || (max_components && !sizes)) { ac::set_error("mesh_components: NULL buffer"); return AC_ERR_BAD_ARG; }
-    const CcLayout l = cc_layout(V);
-    if (scratch_bytes < l.total) { ac::set_error("mesh_components: scratch of %zu bytes needed, %zu given", l.total, scratch_bytes); return AC_ERR_BAD_ARG; }
-    char *sc = static_cast<char *>(scratch);
-    uint32_t *info = reinterpret_cast<uint32_t *>(sc + l.info), *bsum = reinterpret_cast<uint32_t *>(sc + l.bsum), *boff = reinterpret_cast<uint32_t *>(sc + l.boff);
-    int32_t *parent = reinterpret_cast<int32_t *>(sc + l.parent);
+    const CcScratch s = cc_scratch(scratch, V);
+    if (int rc = mi::check_scratch_bytes("mesh_components", s.bytes, scratch_bytes)) return rc;
     const uint32_t items = V > T ? V : T;
-    hipLaunchKernelGGL(cc_init_kernel, dim3((V + 255u) / 256u), dim3(256), 0, st, parent, V, info);
-    if (T) hipLaunchKernelGGL(cc_hook_kernel, dim3((T + 255u) / 256u), dim3(256), 0, st, triangles, T, V, parent, info);
-    hipLaunchKernelGGL(cc_flatten_kernel, dim3(l.nblk), dim3(256), 0, st, parent, V, root, bsum);
-    hipLaunchKernelGGL(pair_scan_kernel, dim3(1), dim3(1024), 0, st, bsum, l.nblk, boff, info + CC_INFO_TOTALS);
-    hipLaunchKernelGGL(cc_rank_kernel, dim3(l.nblk), dim3(256), 0, st, root, V, boff, parent, sizes, max_components, info, counts);
-    hipLaunchKernelGGL(cc_sizes_kernel, dim3((items + 255u) / 256u), dim3(256), 0, st, triangles, T, V, root, parent, component, sizes, max_components);
+    hipLaunchKernelGGL(cc_init_kernel, dim3((V + 255u) / 256u), dim3(256), 0, st, s.parent, V, s.info);
+    if (T) hipLaunchKernelGGL(cc_hook_kernel, dim3((T + 255u) / 256u), dim3(256), 0, st, triangles, T, V, s.parent, s.info);
+    hipLaunchKernelGGL(cc_flatten_kernel, dim3(s.scan.nblk), dim3(256), 0, st, s.parent, V, root, s.scan.bsum);
+    hipLaunchKernelGGL(pair_scan_kernel, dim3(1), dim3(1024), 0, st, s.scan.bsum, s.scan.nblk, s.scan.boff, s.info + CC_INFO_TOTALS);
+    hipLaunchKernelGGL(cc_rank_kernel, dim3(s.scan.nblk), dim3(256), 0, st, root, V, s.scan.boff, s.parent, sizes, max_components, s.info, counts);
+    hipLaunchKernelGGL(cc_sizes_kernel, dim3((items + 255u) / 256u), dim3(256), 0, st, triangles, T, V, root, s.parent, component, sizes, max_components);
     if (int rc = ac::check_launch("mesh_components")) return rc;
     if (max_components < V) {                     // a table that may be too short: the one case in which the call has to look at C itself
         uint32_t h[2] = { 0u, 0u };
@@ -326,25 +285,23 @@ AC_API int ac_mesh_components(const int32_t *triangles, uint32_t T, uint32_t V, 
 
 AC_API size_t ac_mesh_compact_scratch(uint32_t V, uint32_t T)
 {
-    if (V > CC_MAX || T > CC_MAX) return 0;
-    return cp_layout(V, T).total;
+    if (!mi::index_limit_ok(V, T)) return 0;
+    return cp_scratch(nullptr, V, T).bytes;
 }
 
 AC_API int ac_mesh_compact_count(const int32_t *triangles, uint32_t T, uint32_t V, const int32_t *component, const uint8_t *keep, uint32_t C, void *scratch,
                                  size_t scratch_bytes, uint32_t *counts, ac_stream_t stream)
 {
-    CpLayout l;
-    if (int rc = cp_check("mesh_compact_count", triangles, T, V, component, keep, C, scratch, scratch_bytes, l)) return rc;
-    if (!counts) { ac::set_error("mesh_compact_count: NULL counts"); return AC_ERR_BAD_ARG; }
+    CpScratch s;
+    if (int rc = cp_check("mesh_compact_count", triangles, T, V, component, keep, C, scratch, scratch_bytes, s)) return rc;
+    if (int rc = mi::check_counts("mesh_compact_count", counts)) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (V == 0) {
         if (hipMemsetAsync(counts, 0, 8, st) != hipSuccess) return ac::check_launch("mesh_compact_count");
         return AC_OK;
     }
-    char *sc = static_cast<char *>(scratch);
-    uint32_t *bsum = reinterpret_cast<uint32_t *>(sc + l.bsum), *boff = reinterpret_cast<uint32_t *>(sc + l.boff);
-    hipLaunchKernelGGL(cp_count_kernel, dim3(l.nblk), dim3(256), 0, st, triangles, T, V, component, keep, C, bsum);
-    hipLaunchKernelGGL(pair_scan_kernel, dim3(1), dim3(1024), 0, st, bsum, l.nblk, boff, counts);
+    hipLaunchKernelGGL(cp_count_kernel, dim3(s.scan.nblk), dim3(256), 0, st, triangles, T, V, component, keep, C, s.scan.bsum);
+    hipLaunchKernelGGL(pair_scan_kernel, dim3(1), dim3(1024), 0, st, s.scan.bsum, s.scan.nblk, s.scan.boff, counts);
     return ac::check_launch("mesh_compact_count");
 }
 
@@ -352,8 +309,8 @@ AC_API int ac_mesh_compact_emit(const int32_t *triangles, uint32_t T, uint32_t V
                                 size_t scratch_bytes, int32_t *vertex_map, int32_t *kept_vertices, uint32_t n_kept_vertices, int32_t *triangles_out,
                                 int32_t *kept_triangles, uint32_t n_kept_triangles, ac_stream_t stream)
 {
-    CpLayout l;
-    if (int rc = cp_check("mesh_compact_emit", triangles, T, V, component, keep, C, scratch, scratch_bytes, l)) return rc;
+    CpScratch s;
+    if (int rc = cp_check("mesh_compact_emit", triangles, T, V, component, keep, C, scratch, scratch_bytes, s)) return rc;
     if (n_kept_vertices > V || n_kept_triangles > T) {
         ac::set_error("mesh_compact_emit: n_kept_vertices %u > V %u or n_kept_triangles %u > T %u", n_kept_vertices, V, n_kept_triangles, T);
         return AC_ERR_BAD_ARG;
@@ -364,10 +321,9 @@ AC_API int ac_mesh_compact_emit(const int32_t *triangles, uint32_t T, uint32_t V
     }
     if (V == 0) return AC_OK;
     hipStream_t st = (hipStream_t)stream;
-    const uint32_t *boff = reinterpret_cast<const uint32_t *>(static_cast<char *>(scratch) + l.boff);
-    hipLaunchKernelGGL(cp_vertices_kernel, dim3(cc_blocks(V)), dim3(256), 0, st, V, component, keep, C, boff, vertex_map, kept_vertices, n_kept_vertices);
+    hipLaunchKernelGGL(cp_vertices_kernel, dim3(mi::blocks(V)), dim3(256), 0, st, V, component, keep, C, s.scan.boff, vertex_map, kept_vertices, n_kept_vertices);
     if (n_kept_triangles)
-        hipLaunchKernelGGL(cp_triangles_kernel, dim3(cc_blocks(T)), dim3(256), 0, st, triangles, T, V, component, keep, C, boff, vertex_map, triangles_out,
+        hipLaunchKernelGGL(cp_triangles_kernel, dim3(mi::blocks(T)), dim3(256), 0, st, triangles, T, V, component, keep, C, s.scan.boff, vertex_map, triangles_out,
                            kept_triangles, n_kept_triangles);
     return ac::check_launch("mesh_compact_emit");
 }

@@ -103,10 +103,11 @@ def test_nothing_one_triangle_and_cells_of_their_own():
 
 
 # ---------------------------------------------------------------------------------------------------- the scan seams
-@pytest.mark.parametrize("V", [63, 64, 65, 255, 256, 257, 1025])
-def test_sizes_around_a_wave_a_workgroup_and_a_scanned_block(V):
-    """64 cells: clusters of many members from V = 255 on, leaders and dropped triangles on both sides of every seam; T = 2 V + 3 differs from V"""
-    v, t, g = K.random_mesh(V, 2 * V + 3, n=4, seed=V)
+@pytest.mark.parametrize("V,T,seed", [pytest.param(V, 2 * V + 3, V, id=str(V)) for V in (63, 64, 65, 255, 256, 257, 1025)] + [pytest.param(2049, 5, 1, id="2049-5")])
+def test_sizes_around_a_wave_a_workgroup_and_a_scanned_block(V, T, seed):
+    """64 cells: clusters of many members from V = 255 on, leaders and dropped triangles on both sides of every seam; T = 2 V + 3 differs from V.  The last
+    case has more workgroups of vertices (three) than of triangles (one): the scan's words are sized by the larger, each pass is launched over its own"""
+    v, t, g = K.random_mesh(V, T, n=4, seed=seed)
     ref = K.cluster(v, t, g)
     assert 0 < len(ref["leader"]) <= 64 and 0 < len(ref["triangles"]) < len(t)
     _same(_cluster(v, t, g), ref)
