@@ -5,19 +5,13 @@
 // compare-exchange under linear probing; a slot holds the smallest member index (integer atomic min), the member count and three int64 sums of the members'
 // fixed-point offsets inside the cell (integer atomic adds); every vertex remembers its slot.  A cell's leader is its smallest member, clusters are numbered by
 // ascending leader (flags -> the ordered passes of mesh_index.hpp), and the position is a function of the exact integer sums: nothing depends on scheduling or on
-// the hash, although the table is filled with atomics.  No wave ever waits for another one: see mc_slot.  No floating-point atomics.
+// the hash, although the table is filled with atomics.  No wave ever waits for another one: see mi::key_slot (mesh_index.hpp).  No floating-point atomics.
 #include "mesh_index.hpp"
 
 namespace {
 
 constexpr uint32_t MCL_MAX_N = 1u << 21;          // cells per axis: three of them fit a 63-bit key
-constexpr uint64_t MCL_EMPTY = ~0ull;             // no key: a key stays below 2^63
 enum { MCL_INFO_BAD_V = 0, MCL_INFO_BAD_T = 1, MCL_INFO_WORDS = 64 };
-
-// gfx950 has eight XCDs with private L2s: inside the filling launch the table is touched by agent-scope atomics on GLOBAL pointers only
-typedef __attribute__((address_space(1))) uint64_t mcl_gu64;
-typedef __attribute__((address_space(1))) int32_t mcl_gi32;
-typedef __attribute__((address_space(1))) uint32_t mcl_gu32;
 
 struct MclGrid { double lo[3], h; uint32_t n[3]; };
 
@@ -40,38 +34,13 @@ __device__ __forceinline__ bool mcl_cell(const double *__restrict__ p, const Mcl
     return true;
 }
 
-__device__ __forceinline__ uint64_t mcl_mix(uint64_t x)           // (the finaliser of splitmix64: where a cell's probe starts; no output depends on it)
-{
-    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-    x ^= x >> 27; x *= 0x94d049bb133111ebull;
-    return x ^ (x >> 31);
-}
-
-// The slot of `key`, claiming one if the key has none.  A lock-free probe, no wait: a slot's key changes once, from MCL_EMPTY to a cell key, and never again.
-// A trip ends the walk if it reads the key or wins the compare-exchange; if the exchange FAILED it returns what the slot holds now -- a key, for good -- and the
-// walk ends there or moves on.  Every slot is looked at once: the table has capacity >= 2 V slots and at most V keys, so an empty slot or the key's own comes up
-// within `capacity` trips whatever other waves do and whether or not they run at all.
-__device__ __forceinline__ uint64_t mcl_slot(uint64_t *keys, uint64_t mask, uint64_t key)
-{
-    uint64_t s = mcl_mix(key) & mask;
-    for (;;) {
-        uint64_t seen = __hip_atomic_load((mcl_gu64 *)(keys + s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (seen == key) return s;
-        if (seen == MCL_EMPTY) {
-            if (__hip_atomic_compare_exchange_strong((mcl_gu64 *)(keys + s), &seen, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return s;
-            if (seen == key) return s;
-        }
-        s = (s + 1u) & mask;
-    }
-}
-
 struct MclTable { uint64_t *keys; int32_t *lead; uint32_t *cnt; uint64_t *sums; int32_t *rank; };
 
 __global__ __launch_bounds__(256) void mcl_init_kernel(MclTable tb, uint64_t capacity, uint32_t *__restrict__ info)
 {
     const uint64_t s = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (s < capacity) {
-        tb.keys[s] = MCL_EMPTY; tb.lead[s] = 0x7fffffff; tb.cnt[s] = 0u;
+        tb.keys[s] = mi::KEY_EMPTY; tb.lead[s] = 0x7fffffff; tb.cnt[s] = 0u;
         tb.sums[3 * s] = 0ull; tb.sums[3 * s + 1] = 0ull; tb.sums[3 * s + 2] = 0ull;
     }
     if (s < MCL_INFO_WORDS) info[s] = 0u;
@@ -85,12 +54,12 @@ __global__ __launch_bounds__(256) void mcl_fill_kernel(const double *__restrict_
     if (v >= V) return;
     uint64_t key; uint32_t q[3];
     if (!mcl_cell(verts + 3 * (size_t)v, g, key, q)) { slot[v] = -1; atomicAdd(info + MCL_INFO_BAD_V, 1u); return; }
-    const uint64_t s = mcl_slot(tb.keys, mask, key);
+    const uint64_t s = mi::key_slot(tb.keys, mask, key);
     slot[v] = (int64_t)s;
-    (void)__hip_atomic_fetch_min((mcl_gi32 *)(tb.lead + s), (int32_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    (void)__hip_atomic_fetch_add((mcl_gu32 *)(tb.cnt + s), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    (void)__hip_atomic_fetch_min((mi::gi32 *)(tb.lead + s), (int32_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    (void)__hip_atomic_fetch_add((mi::gu32 *)(tb.cnt + s), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
-    for (int a = 0; a < 3; ++a) (void)__hip_atomic_fetch_add((mcl_gu64 *)(tb.sums + 3 * s + a), (uint64_t)q[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (int a = 0; a < 3; ++a) (void)__hip_atomic_fetch_add((mi::gu64 *)(tb.sums + 3 * s + a), (uint64_t)q[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // (the table is the filling launch's: read-only from here on)

@@ -1,8 +1,8 @@
-// avatarcraft_amd/csrc/mesh_index.hpp -- what the mesh index kernels share (marching_cubes.hip, mesh_components.hip, mesh_cluster.hip).  Each of them turns
+// avatarcraft_amd/csrc/mesh_index.hpp -- what the mesh index kernels share (marching_cubes.hip, mesh_components.hip, mesh_cluster.hip, mesh_weld.hip).  Each of them turns
 // per-item flags or counts into output indices the same way: a count pass stores a PAIR of totals per workgroup, pair_scan_kernel (ac_scan.hpp) scans them, and
 // an emit pass gives every item the index its place in the input order earns it -- no atomics, so the output is a function of the input alone.
-// Device half: the pair of totals and the ordered passes; a caller never sees how the pair is packed or laid out.  Host half: the scratch walk and the
-// refusals that more than one of the three files states.
+// Device half: the pair of totals and the ordered passes; a caller never sees how the pair is packed or laid out; and the 64-bit key claim of the
+// open-addressing tables (mesh_cluster.hip's cells, mesh_weld.hip's edges).  Host half: the scratch walk and the refusals that more than one of the files states.
 #pragma once
 #include "ac_common.hpp"
 #include "ac_scan.hpp"
@@ -80,6 +80,38 @@ __device__ __forceinline__ void emit_kept_triangles(uint32_t mask, const int32_t
 }
 
 __device__ __forceinline__ bool tri_in_range(int32_t a, int32_t b, int32_t c, uint32_t V) { return (uint32_t)a < V && (uint32_t)b < V && (uint32_t)c < V; }
+
+// ---- the 64-bit key claim of an open-addressing table (a power-of-two capacity, never more than half full, linear probing)
+constexpr uint64_t KEY_EMPTY = ~0ull;             // no key: a key stays below 2^63
+// gfx950 has eight XCDs with private L2s: inside a filling launch a table is touched by agent-scope atomics on GLOBAL pointers only
+typedef __attribute__((address_space(1))) uint64_t gu64;
+typedef __attribute__((address_space(1))) int32_t gi32;
+typedef __attribute__((address_space(1))) uint32_t gu32;
+
+__device__ __forceinline__ uint64_t key_mix(uint64_t x)           // (the finaliser of splitmix64: where a key's probe starts; no output depends on it)
+{
+    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
+    x ^= x >> 27; x *= 0x94d049bb133111ebull;
+    return x ^ (x >> 31);
+}
+
+// The slot of `key`, claiming one if the key has none.  A lock-free probe, no wait: a slot's key changes once, from KEY_EMPTY to a key, and never again.
+// A trip ends the walk if it reads the key or wins the compare-exchange; if the exchange FAILED it returns what the slot holds now -- a key, for good -- and the
+// walk ends there or moves on.  Every slot is looked at once: the table has at least twice as many slots as there are keys, so an empty slot or the key's own
+// comes up within `capacity` trips whatever other waves do and whether or not they run at all.
+__device__ __forceinline__ uint64_t key_slot(uint64_t *keys, uint64_t mask, uint64_t key)
+{
+    uint64_t s = key_mix(key) & mask;
+    for (;;) {
+        uint64_t seen = __hip_atomic_load((gu64 *)(keys + s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (seen == key) return s;
+        if (seen == KEY_EMPTY) {
+            if (__hip_atomic_compare_exchange_strong((gu64 *)(keys + s), &seen, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return s;
+            if (seen == key) return s;
+        }
+        s = (s + 1u) & mask;
+    }
+}
 
 }  // namespace
 

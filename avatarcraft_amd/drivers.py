@@ -165,12 +165,20 @@ def export_mesh(net, path, bound=NSR_BOUND, resolution=512, **kw):
     merges the vertices of every cluster cell of k marching-cubes cells on the device, after the cleaning and before the shading and the atlas layout:
     export_mesh(net, "avatar.obj", components="largest", decimate=4) writes a body of about a sixteenth of the triangles, its texture baked from the field.
     occlusion=True (or occlusion_kit's keywords, or a kit: net.export_occlusion for the length of this call) adds ambient occlusion: the PLY gets a
-    `float quality` property per vertex, the OBJ a grey image name_ao.png that its material references as map_Ka."""
+    `float quality` property per vertex, the OBJ a grey image name_ao.png that its material references as map_Ka.
+    weld=True (net.export_weld for the length of this call) welds the mesh on the device after the decimation and before anything is shaded or baked
+    (mesh_weld.weld_mesh): repeated triangles, back-to-back pairs of a collapsed thin part and the vertices nobody names any more are not written.  The dict
+    then carries weld (what was removed) and topology (mesh_weld.mesh_topology of the written triangles: its closed_manifold says whether the file is one)."""
     import os
     from .geometry import save_obj, save_ply, save_png
     if "occlusion" in kw:
         with _export_occlusion(net, kw.pop("occlusion")):
             return export_mesh(net, path, bound, resolution, **kw)
+    if "weld" in kw:
+        weld = kw.pop("weld")
+        with _export_weld(net, weld):
+            mesh = export_mesh(net, path, bound, resolution, **kw)
+        return _with_topology(net, mesh) if weld else mesh
     if str(path).lower().endswith(".obj"):
         mesh = net.extract_textured_mesh(bound, resolution, **kw)
         png = os.path.splitext(str(path))[0] + ".png"
@@ -192,6 +200,26 @@ def _export_occlusion(net, occlusion):
         yield
     finally:
         net.export_occlusion = prev
+
+
+@contextlib.contextmanager
+def _export_weld(net, weld):
+    """net.export_weld = weld inside the block, what it was afterwards"""
+    prev = net.export_weld
+    net.export_weld = bool(weld)
+    try:
+        yield
+    finally:
+        net.export_weld = prev
+
+
+def _with_topology(net, mesh):
+    """mesh["topology"] = mesh_weld.mesh_topology of the mesh's final triangles (numpy or device) -> mesh"""
+    from .mesh_weld import mesh_topology
+    t = mesh["triangles"]
+    t = t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(t, dtype=np.int32))
+    mesh["topology"] = mesh_topology(t.to(device=net.encoder.embeddings.device, dtype=torch.int32).contiguous(), int(mesh["vertices"].shape[0]))
+    return mesh
 
 
 def _save_ao(png, mesh):
@@ -239,7 +267,8 @@ def export_animation(net, body_model, poses=None, shape_from=None, shape_to=None
     out_pattern ending in .obj: frame files (geometry.save_obj) that all reference ONE material and ONE texture image, written before the first frame
     (animation_paths names them); ending in .ply: binary PLYs with vertex normals and colours.  **kw goes to extract_textured_mesh / extract_colored_mesh
     (texture_size, threshold, refine_steps, components, decimate ...: components="largest" keeps the floaters out of every frame, decimate=k poses the
-    decimated mesh; occlusion=... adds the CANONICAL pose's ambient occlusion, one shared name_ao.png or a quality property in every frame); iters / tol to
+    decimated mesh; occlusion=... adds the CANONICAL pose's ambient occlusion, one shared name_ao.png or a quality property in every frame; weld=True welds
+    the mesh before it is shaded, so no orphan vertex is posed, and every frame's dict carries weld and topology as export_mesh's does); iters / tol to
     pose_mesh.
     yields (frame index, posed mesh dict of pose_mesh); rank / world: this process writes the frames shard_indices(n_frames, rank, world) like
     render_animation (the shared files are written by every rank with the same content)."""
@@ -252,8 +281,12 @@ def export_animation(net, body_model, poses=None, shape_from=None, shape_to=None
                                                  max_frames=max_frames)
     faces = np.asarray(body_model.faces)[:, :3]
     mine = list(shard_indices(n_frames, rank, world))
-    with _export_occlusion(net, kw.pop("occlusion")) if "occlusion" in kw else contextlib.nullcontext():
+    weld = kw.pop("weld", None)
+    with _export_occlusion(net, kw.pop("occlusion")) if "occlusion" in kw else contextlib.nullcontext(), \
+            _export_weld(net, weld) if weld is not None else contextlib.nullcontext():
         mesh = net.extract_textured_mesh(bound, resolution, **kw) if kind == "obj" else net.extract_colored_mesh(bound, resolution, **kw)
+    if weld:
+        _with_topology(net, mesh)
     if kind == "obj":
         save_png(png, mesh["texture"])
         save_mtl(mtl, os.path.basename(png), _save_ao(png, mesh))             # (the occlusion is the canonical pose's: one image for every frame)

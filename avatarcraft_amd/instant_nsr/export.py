@@ -23,12 +23,12 @@ def _check_model(net, needs, colors=None, ok=True):
 
 
 # what the native pipeline hands on: the mesh, and what its steps learned (None where a step did not run); max_move: how far a vertex may be projected
-_NativeMesh = collections.namedtuple("_NativeMesh", "vertices triangles component_sizes components_kept cluster_members max_move")
+_NativeMesh = collections.namedtuple("_NativeMesh", "vertices triangles component_sizes components_kept cluster_members max_move weld")
 
 
 def _native_mesh(net, bound, resolution, threshold, slab_layers, components, grid):
     """THE native mesh pipeline, device tensors throughout: marching cubes on the whole volume or streamed in slabs -> geometry.clean_mesh (components) ->
-    mesh_decimate.decimate_mesh (grid: cluster_grid's result, made by the public call before any device work)"""
+    mesh_decimate.decimate_mesh (grid: cluster_grid's result, made by the public call before any device work) -> mesh_weld.weld_mesh (net.export_weld)"""
     bmin, bmax = np.float32(-bound), np.float32(bound)                       # (the reference's bounds are float32 tensors, :712)
     xf = dict(den=resolution - 1.0, span=[float(bmax - bmin)] * 3, lo=[float(bmin)] * 3)
     if slab_layers is None:
@@ -41,7 +41,7 @@ def _native_mesh(net, bound, resolution, threshold, slab_layers, components, gri
             fill = lambda x0, out: nsr_ops.field_sdf_grid(f, ax[x0:x0 + out.shape[0]], ax, ax, bound, negate=True, out=out)
             v, t = nsr_ops.marching_cubes_streamed(fill, resolution, resolution, resolution, slab_layers=slab_layers, iso=float(threshold),
                                                    device=ax.device, **xf)
-    sizes = kept = members = None
+    sizes = kept = members = weld = None
     max_move = 2.0 * bound / (resolution - 1.0)
     if components is not None:
         from ..geometry import clean_mesh
@@ -51,7 +51,16 @@ def _native_mesh(net, bound, resolution, threshold, slab_layers, components, gri
         from ..mesh_decimate import decimate_mesh
         m = decimate_mesh(dict(vertices=v, triangles=t), grid)
         v, t, members, max_move = m["vertices"], m["triangles"], m["cluster_members"], grid["h"]
-    return _NativeMesh(v, t, sizes, kept, members, max_move)
+    if net.export_weld:
+        from ..mesh_weld import weld_mesh
+        m = weld_mesh(dict(vertices=v, triangles=t) if members is None else dict(vertices=v, triangles=t, cluster_members=members))
+        v, t, members, weld = m["vertices"], m["triangles"], m.get("cluster_members"), m["weld"]
+    return _NativeMesh(v, t, sizes, kept, members, max_move, weld)
+
+
+def _host(mesh):
+    """the mesh dict with its device tensors as numpy arrays (the weld report, a plain dict, stays what it is)"""
+    return {k: x.cpu().numpy() if isinstance(x, torch.Tensor) else x for k, x in mesh.items()}
 
 
 def _occlusion_kit(occlusion, bound, threshold):
@@ -77,6 +86,12 @@ class MeshExport:
     # returned; True = ambient occlusion from the default kit (mesh_occlusion.occlusion_kit, radius 0.1 bound); a dict = occlusion_kit's keywords, or a kit, passed
     # as is.  drivers.export_mesh / export_animation(occlusion=...) set it for the length of their call.
     export_occlusion = None
+
+    # opt-in switch of extract_geometry / extract_colored_mesh / extract_textured_mesh (same reason): False = what they always returned; True = the mesh is
+    # welded on the device (mesh_weld.weld_mesh) after the decimation -- after the cleaning without one -- and before anything is shaded, laid out or baked:
+    # repeated triangles and back-to-back pairs of a collapsed thin part go, and so do the vertices nobody names any more.  The dicts then carry `weld`, the
+    # report of mesh_weld.mesh_weld.  Native mesher only.  drivers.export_mesh / export_animation(weld=True) set it for the length of their call.
+    export_weld = False
 
     def _grid_axis(self, bound, resolution):
         """torch.linspace(-bound, bound, resolution) as the reference forms it (on the host, fp32: extract_fields :730-732, update_extra_state :312-314), on the
@@ -141,12 +156,14 @@ class MeshExport:
                 route), AFTER the components are cleaned, so that a floater never merges into the body.  This call has no field pass: with decimate the vertices
                 are the clusters' MEAN vertices, near the level set and not on it (at most about one cluster cell off) -- extract_colored_mesh /
                 extract_textured_mesh(decimate=k) project them back.  Triangles that lose a corner to a merge are dropped; duplicates are not removed and the
-                result need not be manifold.  Native mesher only."""
+                result need not be manifold (self.export_weld, the switch above, removes them).  Native mesher only."""
         native = mesher in (None, "native")
         grid = None
         if decimate is not None:
             _check_model(self, "extract_geometry(decimate=...) decimates the native mesher's mesh on the device: it needs mesher='native' and", ok=native)
             grid = _cluster_grid(bound, resolution, decimate)
+        if self.export_weld:
+            _check_model(self, "extract_geometry with export_weld welds the native mesher's mesh on the device: it needs mesher='native' and", ok=native)
         if components is not None:
             _check_model(self, "extract_geometry(components=...) cleans the native mesher's mesh on the device: it needs mesher='native' and", ok=native)
         if slab_layers is not None:
@@ -193,6 +210,8 @@ class MeshExport:
             out.update(component_sizes=m.component_sizes, components_kept=m.components_kept)
         if m.cluster_members is not None:
             out["cluster_members"] = m.cluster_members
+        if m.weld is not None:
+            out["weld"] = m.weld
         return out, m.max_move
 
     def extract_colored_mesh(self, bound: float, resolution: int, threshold: float = 0.0, refine_steps: int = 3, tol: float = 1e-5, colors: bool = True,
@@ -214,10 +233,12 @@ class MeshExport:
         stands for).
         self.export_occlusion (the switch above; None: nothing more, as ever) adds ambient occlusion.  The kit's level is -threshold.  The dict then also carries
         occlusion [V] float32 in [0, 1], 1 = open: mesh_occlusion.field_occlusion at the final positions and normals (after cleaning and decimation), 0 at a
-        status-2 vertex.  The colours are unlit albedo; a viewer multiplies."""
+        status-2 vertex.  The colours are unlit albedo; a viewer multiplies.
+        self.export_weld (the switch above; False: nothing more, as ever) welds the mesh after the decimation and BEFORE the vertices are shaded: a vertex that no
+        surviving triangle names is never projected, coloured or posed.  The dict then also carries weld (the report, a plain dict of counts)."""
         kit = _occlusion_kit(self.export_occlusion, bound, threshold)
         out = self._colored_mesh(bound, resolution, threshold, refine_steps, tol, colors, slab_layers, components, decimate, kit)[0]
-        return out if return_torch else {k: x.cpu().numpy() for k, x in out.items()}
+        return out if return_torch else _host(out)
 
     def extract_textured_mesh(self, bound: float, resolution: int, texture_size: int = 2048, cell=None, threshold: float = 0.0, refine_steps: int = 3,
                               tol: float = 1e-5, return_torch=False, slab_layers=None, components=None, decimate=None):
@@ -233,7 +254,8 @@ class MeshExport:
         decimate: extract_colored_mesh's.  The mesh is decimated BEFORE the atlas is laid out, so the cells are sized for the decimated triangle count, and the
         texels carry the colour detail the removed vertices carried; a texel's point is projected never further than one CLUSTER cell.
         self.export_occlusion: as in extract_colored_mesh.  The dict then also carries occlusion [V], texel_occlusion [S,S] float32 (0 at unowned texels) and occlusion_map [S,S]
-        uint8 (the texture's quantisation rule), the texels' from ONE launch (ac_mesh_bake_maps) in place of the bake's: colour and occlusion share a texel's refine."""
+        uint8 (the texture's quantisation rule), the texels' from ONE launch (ac_mesh_bake_maps) in place of the bake's: colour and occlusion share a texel's refine.
+        self.export_weld: as in extract_colored_mesh.  The mesh is welded BEFORE the atlas is laid out: the cells are sized for the welded triangle count."""
         from ..geometry import atlas_layout
         kit = _occlusion_kit(self.export_occlusion, bound, threshold)
         m, max_move = self._colored_mesh(bound, resolution, threshold, refine_steps, tol, True, slab_layers, components, decimate, kit)
@@ -256,7 +278,7 @@ class MeshExport:
         if kit is not None:
             m.update(texel_occlusion=b["occlusion"], occlusion_map=quantise(b["occlusion"]))
         if not return_torch:
-            m = {k: x.cpu().numpy() for k, x in m.items()}
+            m = _host(m)
         m["uv"] = torch.from_numpy(lay["uv"]).to(tex.device) if return_torch else lay["uv"]
         return m
 

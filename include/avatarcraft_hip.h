@@ -1014,7 +1014,8 @@ int ac_mesh_compact_emit(const int32_t *triangles /*[T,3]*/, uint32_t T, uint32_
  *   Triangles: INVALID if an index lies outside [0, V) or names an invalid vertex: counted, never emitted.  A valid triangle maps to (cluster[a], cluster[b],
  *     cluster[c]); it is COLLAPSED, and dropped, iff two of the three are equal.  Surviving triangles keep their relative order and their vertex order
  *     (orientation); kept_triangles [T'] = their old indices, ascending.  Duplicate triangles are NOT removed, back-to-back pairs of a collapsed thin sheet
- *     included: vertex clustering does not preserve manifoldness and this step does not repair it.
+ *     included: vertex clustering does not preserve manifoldness and this step does not repair it -- ac_mesh_weld_count / _emit (below) remove them
+ *     afterwards, and ac_mesh_topology says what is left.
  * ac_mesh_cluster_count: an open-addressing table in scratch with a power-of-two capacity >= 2 V, slots keyed by the cell key and claimed with a 64-bit
  *   compare-exchange under linear probing; a slot holds the leader (integer atomic min), the member count and the three sums (integer atomic adds); then
  *   is_leader -> the ordered scans -> cluster, and the triangle flags through the same scan.  No wave waits for another one (every retry is a lock-free retry:
@@ -1038,6 +1039,50 @@ int ac_mesh_cluster_emit(const double *vertices /*[V,3]*/, uint32_t V, const int
                          void *scratch, size_t scratch_bytes, int32_t *leader /*[V']*/, uint32_t *members /*[V']*/, double *positions /*[V',3]*/,
                          uint32_t n_clusters, int32_t *triangles_out /*[T',3]*/, int32_t *kept_triangles /*[T']*/, uint32_t n_kept_triangles,
                          ac_stream_t stream);
+
+/* ---- welding the decimated mesh and reporting its topology, on the device (csrc/mesh_weld.hip; added entries only, no struct changes: ABI stays 10).  It
+ * stands in for nothing in the reference.  The weld removes what ac_mesh_cluster_emit leaves behind where a thin part collapses onto itself: repeated
+ * triangles, back-to-back pairs, and the vertices no surviving triangle names.  Everything is integer work on index buffers -- no vertex positions are read --
+ * and every output is a function of the input alone: it depends on neither scheduling nor any hash and equals a numpy restatement exactly
+ * (tests/mesh_weld_cases.py).  A mesh is triangles [T,3] int32 over V vertices.  Definitions of the weld:
+ *   INVALID triangle: an index outside [0, V).  Counted, never emitted.  DEGENERATE triangle: valid, two equal corners.  Counted, never emitted.
+ *   Group: all remaining triangles with the same SET of three vertices.  Sign of a member: rotated so that its smallest corner comes first, (a, b, c), it is
+ *     + iff b < c.  net = n+ - n-.
+ *   Kept triangle of a group: none if net == 0 (the group cancels: a fin of zero thickness); otherwise exactly one, the member with the smallest triangle
+ *     index among those of the majority sign, its corner order unchanged.  Kept triangles keep their relative order; kept_triangles [T'] = their old
+ *     indices, ascending.
+ *   Kept vertex: named by at least one kept triangle.  Kept vertices keep their order.  vertex_map [V] int32 = new index or -1; kept_vertices [V'] = old
+ *     indices, ascending; triangles_out [T',3] = the kept triangles re-indexed through vertex_map.
+ *   counts (DEVICE, [8]) = { V', T', invalid, degenerate, cancelled, repeated, excess, 0 }: cancelled = the members of groups with net == 0; repeated = the
+ *     members dropped from groups with net != 0; excess = the sum of |net| - 1 over the groups.  T = T' + invalid + degenerate + cancelled + repeated.
+ *   For the triangles of a closed, consistently oriented mesh after ac_mesh_cluster_emit: if excess == 0, the welded mesh has every directed edge u -> v as
+ *   often as v -> u (the weld removes whole cancelling pairs, and same-sign copies of a chain whose boundary is zero).
+ * ac_mesh_weld_count: an open-addressing table of int32 in scratch with a power-of-two capacity >= 2 T.  The vertex set needs 93 bits, so a slot holds a
+ *   triangle INDEX, claimed with a 32-bit compare-exchange from "empty" under linear probing; equality at an occupied slot is decided by reading the occupant's
+ *   corners from the (immutable) input and comparing sorted triples.  A slot holds the smallest + member and the smallest - member (integer atomic mins) and
+ *   the two member counts (integer atomic adds); then one flag pass (kept triangles, referenced vertices) and the ordered scans.  No wave waits for another
+ *   one (a slot's occupant changes once, from empty to an index), no floating-point atomics.  The scratch (the _scratch function of (V, T) bytes: 20 per table
+ *   slot, 5 per triangle, 1 per vertex and a little) is kept unchanged until the emit call.
+ * ac_mesh_weld_emit : the same head, then the outputs with n_kept_vertices = V' and n_kept_triangles = T' of the count call (nothing is written past them;
+ *   an output of length 0 may be NULL; vertex_map is written whole).  Ordered writes, no atomics.
+ * ac_mesh_topology: the report.  An EDGE is the unordered pair of two corners of a valid, non-degenerate triangle; fwd = its uses in the direction
+ *   min -> max, bwd = its uses in the other direction.  counts (DEVICE, [8]) = { E distinct edges, boundary (fwd + bwd == 1), nonmanifold (fwd + bwd > 2),
+ *   misoriented (fwd + bwd == 2 and fwd != bwd), referenced vertices (named by a valid non-degenerate triangle), F valid non-degenerate triangles, invalid,
+ *   degenerate }.  A closed oriented 2-manifold (up to non-manifold VERTICES, which are not looked for) has boundary = nonmanifold = misoriented = 0.
+ *   The table of ac_mesh_cluster_count, keyed by (min << 31) | max, with a power-of-two capacity >= 6 T and two uint32 use counters per slot (integer
+ *   atomic adds); a pass over the slots reduces them, aggregated in the wave, by integer adds.  scratch: 16 bytes per slot, 1 per vertex and a little.
+ * AC_ERR_BAD_ARG before any launch, with the rule in the message: a NULL required buffer (triangles may be NULL when T == 0, everything but counts when
+ * V == 0), V or T above 2^31 - 1, triangles over V == 0, a scratch that is too short, n_kept_vertices > V or n_kept_triangles > T.
+ * V == 0 with T == 0 is legal and launches nothing (counts = 0).  Not built: splitting non-manifold vertices, filling holes. */
+size_t ac_mesh_weld_scratch(uint32_t V, uint32_t T);
+int ac_mesh_weld_count(const int32_t *triangles /*[T,3]*/, uint32_t T, uint32_t V, void *scratch, size_t scratch_bytes,
+                       uint32_t *counts /* DEVICE [8] = { V', T', invalid, degenerate, cancelled, repeated, excess, 0 } */, ac_stream_t stream);
+int ac_mesh_weld_emit(const int32_t *triangles /*[T,3]*/, uint32_t T, uint32_t V, void *scratch, size_t scratch_bytes, int32_t *vertex_map /*[V]*/,
+                      int32_t *kept_vertices /*[V']*/, uint32_t n_kept_vertices, int32_t *triangles_out /*[T',3]*/, int32_t *kept_triangles /*[T']*/,
+                      uint32_t n_kept_triangles, ac_stream_t stream);
+size_t ac_mesh_topology_scratch(uint32_t V, uint32_t T);
+int ac_mesh_topology(const int32_t *triangles /*[T,3]*/, uint32_t T, uint32_t V, void *scratch, size_t scratch_bytes,
+                     uint32_t *counts /* DEVICE [8] = { E, boundary, nonmanifold, misoriented, referenced, F, invalid, degenerate } */, ac_stream_t stream);
 
 /* ---- rendering from a half-precision hash table (opt-in, inference only) ----------------------------------------------------------------------------
  * The half table holds ONE dword per entry of the fp32 table [n_entries][2] (n_entries = field->offsets[16]): channel 0 as an IEEE binary16 in the low
