@@ -220,6 +220,9 @@ _SIGS = {
     "ac_mesh_weld_emit": ([vp, u32, u32, vp, C.c_size_t, vp, vp, u32, vp, vp, u32, vp], C.c_int),
     "ac_mesh_topology_scratch": ([u32, u32], C.c_size_t),
     "ac_mesh_topology": ([vp, u32, u32, vp, C.c_size_t, vp, vp], C.c_int),
+    "ac_mesh_repair_scratch": ([u32, u32], C.c_size_t),
+    "ac_mesh_repair_count": ([vp, vp, u32, u32, vp, C.c_size_t, vp, vp], C.c_int),
+    "ac_mesh_repair_emit": ([vp, vp, u32, u32, vp, C.c_size_t, vp, vp, u32, vp], C.c_int),
     "ac_density_grid_update_scratch": ([u32], C.c_size_t),
     "ac_density_grid_update": ([C.POINTER(ac_field), vp, u32, f32, f32, f32, vp, vp, vp, C.c_size_t, vp], C.c_int),
     "ac_table_to_half": ([vp, u32, vp, vp, vp], C.c_int),

@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libavatarcraft_hip.so")
 SOURCES = ["ac_capi.hip", "hashgrid.hip", "hash_stencil.hip", "shencoder.hip", "raymarching.hip", "render_fused.hip", "render_long.hip", "render_occupancy.hip", "sdf_stencil_train.hip", "color_train.hip",
-           "composite.hip", "render_core_backward.hip", "warp.hip", "warp_accel_build.hip", "step_glue.hip", "field_grid.hip", "marching_cubes.hip", "mesh_shade.hip", "surface_rays.hip", "mesh_pose.hip", "mesh_components.hip", "mesh_cluster.hip", "mesh_occlusion.hip", "mesh_weld.hip"]
+           "composite.hip", "render_core_backward.hip", "warp.hip", "warp_accel_build.hip", "step_glue.hip", "field_grid.hip", "marching_cubes.hip", "mesh_shade.hip", "surface_rays.hip", "mesh_pose.hip", "mesh_components.hip", "mesh_cluster.hip", "mesh_occlusion.hip", "mesh_weld.hip", "mesh_repair.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fvisibility=hidden",
          "-Wno-unused-result",
          # no compiler-formed packed-fp32 (v_pk_*_f32) code: the one run-to-run non-determinism ever observed in the renderer (round 2: the "face-value"

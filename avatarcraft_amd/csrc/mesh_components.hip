@@ -6,52 +6,12 @@
 // the SMALLER, so every value ever stored in parent[v] is <= the one before it and <= v, a root is a vertex with parent[v] == v, a vertex that stopped being
 // a root never becomes one again, and the last root left in a component is its smallest vertex: the labelling is canonical (no dependence on triangle order
 // or scheduling) although the hooks are atomics.  Ranks, sizes and the compaction are ordered passes (mesh_index.hpp) and integer adds: deterministic as well.
-// No wave ever waits for another one: see cc_find / cc_unite.  No floating-point atomics.
+// No wave ever waits for another one: see mi::cc_find / mi::cc_unite (mesh_index.hpp, shared with mesh_repair.hip).  No floating-point atomics.
 #include "mesh_index.hpp"
 
 namespace {
 
 enum { CC_INFO_TOTALS = 0 /* [2]: pair_scan_kernel's totals = { C, 0 } */, CC_INFO_BAD = 2 /* invalid triangles */, CC_INFO_WORDS = 64 };
-
-// gfx950 has eight XCDs with private L2s: inside the hooking launch parent[] is touched by agent-scope atomics on a GLOBAL pointer only (a plain load may
-// return another XCD's stale line; the compare-exchange would still arbitrate, but progress must not rest on a stale word).
-typedef __attribute__((address_space(1))) int32_t cc_gi32;
-__device__ __forceinline__ int32_t cc_load(int32_t *parent, int32_t x)
-{
-    return __hip_atomic_load((cc_gi32 *)(parent + x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// The root above x, halving the path on the way.  Termination without anyone else running: parent[y] <= y always and a trip goes on only after it has READ
-// p = parent[x] < x (and g = parent[p] < p), then continues from g < x: the index in hand strictly decreases and is bounded by 0.  The atomic min only ever
-// lowers parent[x] to an ancestor of x (g is one, and x is no root: a non-root never becomes a root again), so it keeps every invariant whoever else writes.
-__device__ __forceinline__ int32_t cc_find(int32_t *parent, int32_t x)
-{
-    for (;;) {
-        const int32_t p = cc_load(parent, x);
-        if (p == x) return x;
-        const int32_t g = cc_load(parent, p);
-        if (g == p) return p;
-        (void)__hip_atomic_fetch_min((cc_gi32 *)(parent + x), g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        x = g;
-    }
-}
-
-// Join the components of u and v.  A lock-free retry, no wait: the loop goes round again only when the compare-exchange on parent[hi] FAILED, and a failed
-// exchange returns the word's current value `seen` != hi; values stored in parent[hi] are <= hi, so seen < hi.  The next trip works on (seen, lo), both
-// below hi: max(u, v) strictly decreases from trip to trip, whatever other waves do and whether or not they run at all, and it is bounded by 0 -- at most
-// max(u, v) + 1 trips.  (seen and lo are in the component of hi and lo respectively, so joining them joins what was asked for.)
-__device__ __forceinline__ void cc_unite(int32_t *parent, int32_t u, int32_t v)
-{
-    for (;;) {
-        u = cc_find(parent, u);
-        v = cc_find(parent, v);
-        if (u == v) return;
-        const int32_t hi = u > v ? u : v, lo = u > v ? v : u;
-        int32_t seen = hi;
-        if (__hip_atomic_compare_exchange_strong((cc_gi32 *)(parent + hi), &seen, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
-        u = seen; v = lo;
-    }
-}
 
 __global__ __launch_bounds__(256) void cc_init_kernel(int32_t *__restrict__ parent, uint32_t V, uint32_t *__restrict__ info)
 {
@@ -68,9 +28,9 @@ __global__ __launch_bounds__(256) void cc_hook_kernel(const int32_t *__restrict_
     if (t >= T) return;
     const int32_t a = tris[3 * (size_t)t], b = tris[3 * (size_t)t + 1], c = tris[3 * (size_t)t + 2];
     if (!mi::tri_in_range(a, b, c, V)) { atomicAdd(info + CC_INFO_BAD, 1u); return; }      // (joins nothing; the compiler forms one add per wave)
-    cc_unite(parent, a, b);
-    cc_unite(parent, a, c);
-    cc_unite(parent, b, c);
+    mi::cc_unite(parent, a, b);
+    mi::cc_unite(parent, a, c);
+    mi::cc_unite(parent, b, c);
 }
 
 // parent[] is read-only in this launch (plain loads of what the hooking launch left), root[] is another array; the walk ends because parent[x] < x off a root

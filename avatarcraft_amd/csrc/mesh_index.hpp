@@ -1,8 +1,8 @@
-// avatarcraft_amd/csrc/mesh_index.hpp -- what the mesh index kernels share (marching_cubes.hip, mesh_components.hip, mesh_cluster.hip, mesh_weld.hip).  Each of them turns
+// avatarcraft_amd/csrc/mesh_index.hpp -- what the mesh index kernels share (marching_cubes.hip, mesh_components.hip, mesh_cluster.hip, mesh_weld.hip, mesh_repair.hip).  Each of them turns
 // per-item flags or counts into output indices the same way: a count pass stores a PAIR of totals per workgroup, pair_scan_kernel (ac_scan.hpp) scans them, and
 // an emit pass gives every item the index its place in the input order earns it -- no atomics, so the output is a function of the input alone.
 // Device half: the pair of totals and the ordered passes; a caller never sees how the pair is packed or laid out; and the 64-bit key claim of the
-// open-addressing tables (mesh_cluster.hip's cells, mesh_weld.hip's edges).  Host half: the scratch walk and the refusals that more than one of the files states.
+// open-addressing tables (mesh_cluster.hip's cells, mesh_weld.hip's and mesh_repair.hip's edges), the wave-aggregated counters and the lock-free union-find.  Host half: the scratch walk and the refusals that more than one of the files states.
 #pragma once
 #include "ac_common.hpp"
 #include "ac_scan.hpp"
@@ -110,6 +110,62 @@ __device__ __forceinline__ uint64_t key_slot(uint64_t *keys, uint64_t mask, uint
             if (seen == key) return s;
         }
         s = (s + 1u) & mask;
+    }
+}
+
+// ---- counters: the sum of v over the wave, on every lane.  Every lane of the wave calls this.
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
+    return v;
+}
+// word += the wave's sum of v: one integer add per wave, none for a wave of zeros.  Every lane of the wave calls this.
+__device__ __forceinline__ void wave_add(uint32_t *word, uint32_t v)
+{
+    const uint32_t s = wave_sum(v);
+    if ((threadIdx.x & 63u) == 0u && s) atomicAdd(word, s);
+}
+
+// ---- the lock-free union-find over parent[] (mesh_components.hip's vertices, mesh_repair.hip's corners).  parent[x] == x at the start.  A hook always links
+// the LARGER root under the SMALLER, so every value ever stored in parent[x] is <= the one before it and <= x, a root is an x with parent[x] == x, an x that
+// stopped being a root never becomes one again, and the last root left in a set is its smallest member: the labelling is canonical although the hooks are
+// atomics.  Inside the hooking launch parent[] is touched by agent-scope atomics on a GLOBAL pointer only (a plain load may return another XCD's stale line;
+// the compare-exchange would still arbitrate, but progress must not rest on a stale word).
+__device__ __forceinline__ int32_t cc_load(int32_t *parent, int32_t x)
+{
+    return __hip_atomic_load((gi32 *)(parent + x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The root above x, halving the path on the way.  Termination without anyone else running: parent[y] <= y always and a trip goes on only after it has READ
+// p = parent[x] < x (and g = parent[p] < p), then continues from g < x: the index in hand strictly decreases and is bounded by 0.  The atomic min only ever
+// lowers parent[x] to an ancestor of x (g is one, and x is no root: a non-root never becomes a root again), so it keeps every invariant whoever else writes.
+__device__ __forceinline__ int32_t cc_find(int32_t *parent, int32_t x)
+{
+    for (;;) {
+        const int32_t p = cc_load(parent, x);
+        if (p == x) return x;
+        const int32_t g = cc_load(parent, p);
+        if (g == p) return p;
+        (void)__hip_atomic_fetch_min((gi32 *)(parent + x), g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        x = g;
+    }
+}
+
+// Join the sets of u and v.  A lock-free retry, no wait: the loop goes round again only when the compare-exchange on parent[hi] FAILED, and a failed
+// exchange returns the word's current value `seen` != hi; values stored in parent[hi] are <= hi, so seen < hi.  The next trip works on (seen, lo), both
+// below hi: max(u, v) strictly decreases from trip to trip, whatever other waves do and whether or not they run at all, and it is bounded by 0 -- at most
+// max(u, v) + 1 trips.  (seen and lo are in the set of hi and lo respectively, so joining them joins what was asked for.)
+__device__ __forceinline__ void cc_unite(int32_t *parent, int32_t u, int32_t v)
+{
+    for (;;) {
+        u = cc_find(parent, u);
+        v = cc_find(parent, v);
+        if (u == v) return;
+        const int32_t hi = u > v ? u : v, lo = u > v ? v : u;
+        int32_t seen = hi;
+        if (__hip_atomic_compare_exchange_strong((gi32 *)(parent + hi), &seen, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+        u = seen; v = lo;
     }
 }
 

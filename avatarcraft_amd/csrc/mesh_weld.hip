@@ -38,20 +38,6 @@ __device__ __forceinline__ int mw_read(const int32_t *__restrict__ tris, uint32_
     return MW_TRI_MEMBER;
 }
 
-// the sum of v over the wave, on every lane.  Every lane of the wave calls this.
-__device__ __forceinline__ uint32_t mw_wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
-    return v;
-}
-// word += the wave's sum of v: one integer add per wave, none for a wave of zeros.  Every lane of the wave calls this.
-__device__ __forceinline__ void mw_wave_add(uint32_t *word, uint32_t v)
-{
-    const uint32_t s = mw_wave_sum(v);
-    if ((threadIdx.x & 63u) == 0u && s) atomicAdd(word, s);
-}
-
 // ---------------------------------------------------------------------------------------------------------------- weld
 struct MwTable { int32_t *occ, *min_plus, *min_minus; uint32_t *n_plus, *n_minus; };
 
@@ -121,7 +107,7 @@ __global__ __launch_bounds__(256) void mw_mark_kernel(const int32_t *__restrict_
         if (kept) { vmark[k.v[0]] = 1; vmark[k.v[1]] = 1; vmark[k.v[2]] = 1; }
     }
 #pragma unroll
-    for (int i = 0; i < 5; ++i) mw_wave_add(info + i, n[i]);
+    for (int i = 0; i < 5; ++i) mi::wave_add(info + i, n[i]);
 }
 
 // kept vertices among a thread's four vertices (bits 0-3), kept triangles among its four triangles (bits 4-7)
@@ -239,9 +225,9 @@ __global__ __launch_bounds__(256) void mt_fill_kernel(const int32_t *__restrict_
             }
         }
     }
-    mw_wave_add(info + MT_FACES, cls == MW_TRI_MEMBER ? 1u : 0u);
-    mw_wave_add(info + MT_INVALID, cls == MW_TRI_INVALID ? 1u : 0u);
-    mw_wave_add(info + MT_DEGENERATE, cls == MW_TRI_DEGENERATE ? 1u : 0u);
+    mi::wave_add(info + MT_FACES, cls == MW_TRI_MEMBER ? 1u : 0u);
+    mi::wave_add(info + MT_INVALID, cls == MW_TRI_INVALID ? 1u : 0u);
+    mi::wave_add(info + MT_DEGENERATE, cls == MW_TRI_DEGENERATE ? 1u : 0u);
 }
 
 // (the table and the marks are the filling launch's: read-only here)  One slot and one vertex per lane -> the five sums, aggregated in the wave
@@ -253,11 +239,11 @@ __global__ __launch_bounds__(256) void mt_reduce_kernel(MtTable tb, uint64_t cap
         const uint32_t f = tb.fwd[s], b = tb.bwd[s], n = f + b;
         edge = 1u; boundary = n == 1u; nonmanifold = n > 2u; misoriented = n == 2u && f != b;
     }
-    mw_wave_add(info + MT_EDGES, edge);
-    mw_wave_add(info + MT_BOUNDARY, boundary);
-    mw_wave_add(info + MT_NONMANIFOLD, nonmanifold);
-    mw_wave_add(info + MT_MISORIENTED, misoriented);
-    mw_wave_add(info + MT_REFERENCED, s < V && vmark[s] ? 1u : 0u);
+    mi::wave_add(info + MT_EDGES, edge);
+    mi::wave_add(info + MT_BOUNDARY, boundary);
+    mi::wave_add(info + MT_NONMANIFOLD, nonmanifold);
+    mi::wave_add(info + MT_MISORIENTED, misoriented);
+    mi::wave_add(info + MT_REFERENCED, s < V && vmark[s] ? 1u : 0u);
 }
 
 __global__ __launch_bounds__(64) void mt_counts_kernel(const uint32_t *__restrict__ info, uint32_t *__restrict__ counts)

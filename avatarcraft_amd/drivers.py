@@ -168,7 +168,12 @@ def export_mesh(net, path, bound=NSR_BOUND, resolution=512, **kw):
     `float quality` property per vertex, the OBJ a grey image name_ao.png that its material references as map_Ka.
     weld=True (net.export_weld for the length of this call) welds the mesh on the device after the decimation and before anything is shaded or baked
     (mesh_weld.weld_mesh): repeated triangles, back-to-back pairs of a collapsed thin part and the vertices nobody names any more are not written.  The dict
-    then carries weld (what was removed) and topology (mesh_weld.mesh_topology of the written triangles: its closed_manifold says whether the file is one)."""
+    then carries weld (what was removed) and topology (mesh_weld.mesh_topology of the written triangles: its closed_manifold says whether the file is one).
+    manifold=True (net.export_manifold for the length of this call) makes the mesh manifold on the device after the weld -- after the decimation or the cleaning
+    when weld is off -- and before anything is shaded or baked (mesh_repair.repair_mesh): where clustering pushed two sheets of the surface onto one edge or one
+    vertex, every sheet gets its own copy of the vertex.  The copies are projected identically, so the file holds COINCIDENT vertices that its faces keep apart;
+    no face is added, dropped or turned.  The dict then carries repair (what was split, paired and cut) and topology of the written triangles: what it still
+    counts as nonmanifold are pinched edges, which no vertex duplication separates, and its boundary is at most repair["cut"]."""
     import os
     from .geometry import save_obj, save_ply, save_png
     if "occlusion" in kw:
@@ -178,7 +183,12 @@ def export_mesh(net, path, bound=NSR_BOUND, resolution=512, **kw):
         weld = kw.pop("weld")
         with _export_weld(net, weld):
             mesh = export_mesh(net, path, bound, resolution, **kw)
-        return _with_topology(net, mesh) if weld else mesh
+        return _with_topology(net, mesh) if weld and "topology" not in mesh else mesh
+    if "manifold" in kw:
+        manifold = kw.pop("manifold")
+        with _export_flag(net, "export_manifold", manifold):
+            mesh = export_mesh(net, path, bound, resolution, **kw)
+        return _with_topology(net, mesh) if manifold else mesh
     if str(path).lower().endswith(".obj"):
         mesh = net.extract_textured_mesh(bound, resolution, **kw)
         png = os.path.splitext(str(path))[0] + ".png"
@@ -203,14 +213,18 @@ def _export_occlusion(net, occlusion):
 
 
 @contextlib.contextmanager
-def _export_weld(net, weld):
-    """net.export_weld = weld inside the block, what it was afterwards"""
-    prev = net.export_weld
-    net.export_weld = bool(weld)
+def _export_flag(net, name, value):
+    """the model's opt-in switch `name` (export_weld, export_manifold) = value inside the block, what it was afterwards"""
+    prev = getattr(net, name)
+    setattr(net, name, bool(value))
     try:
         yield
     finally:
-        net.export_weld = prev
+        setattr(net, name, prev)
+
+
+def _export_weld(net, weld):
+    return _export_flag(net, "export_weld", weld)
 
 
 def _with_topology(net, mesh):
@@ -268,8 +282,9 @@ def export_animation(net, body_model, poses=None, shape_from=None, shape_to=None
     (animation_paths names them); ending in .ply: binary PLYs with vertex normals and colours.  **kw goes to extract_textured_mesh / extract_colored_mesh
     (texture_size, threshold, refine_steps, components, decimate ...: components="largest" keeps the floaters out of every frame, decimate=k poses the
     decimated mesh; occlusion=... adds the CANONICAL pose's ambient occlusion, one shared name_ao.png or a quality property in every frame; weld=True welds
-    the mesh before it is shaded, so no orphan vertex is posed, and every frame's dict carries weld and topology as export_mesh's does); iters / tol to
-    pose_mesh.
+    the mesh before it is shaded, so no orphan vertex is posed, and every frame's dict carries weld and topology as export_mesh's does; manifold=True
+    makes it manifold as export_mesh's does: the copies of a split vertex are bound and posed like any vertex and stay coincident in every frame, and every
+    frame's dict carries repair and topology); iters / tol to pose_mesh.
     yields (frame index, posed mesh dict of pose_mesh); rank / world: this process writes the frames shard_indices(n_frames, rank, world) like
     render_animation (the shared files are written by every rank with the same content)."""
     import os
@@ -281,11 +296,12 @@ def export_animation(net, body_model, poses=None, shape_from=None, shape_to=None
                                                  max_frames=max_frames)
     faces = np.asarray(body_model.faces)[:, :3]
     mine = list(shard_indices(n_frames, rank, world))
-    weld = kw.pop("weld", None)
+    weld, manifold = kw.pop("weld", None), kw.pop("manifold", None)
     with _export_occlusion(net, kw.pop("occlusion")) if "occlusion" in kw else contextlib.nullcontext(), \
-            _export_weld(net, weld) if weld is not None else contextlib.nullcontext():
+            _export_weld(net, weld) if weld is not None else contextlib.nullcontext(), \
+            _export_flag(net, "export_manifold", manifold) if manifold is not None else contextlib.nullcontext():
         mesh = net.extract_textured_mesh(bound, resolution, **kw) if kind == "obj" else net.extract_colored_mesh(bound, resolution, **kw)
-    if weld:
+    if weld or manifold:
         _with_topology(net, mesh)
     if kind == "obj":
         save_png(png, mesh["texture"])

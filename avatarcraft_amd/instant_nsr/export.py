@@ -23,12 +23,13 @@ def _check_model(net, needs, colors=None, ok=True):
 
 
 # what the native pipeline hands on: the mesh, and what its steps learned (None where a step did not run); max_move: how far a vertex may be projected
-_NativeMesh = collections.namedtuple("_NativeMesh", "vertices triangles component_sizes components_kept cluster_members max_move weld")
+_NativeMesh = collections.namedtuple("_NativeMesh", "vertices triangles component_sizes components_kept cluster_members max_move weld repair")
 
 
 def _native_mesh(net, bound, resolution, threshold, slab_layers, components, grid):
     """THE native mesh pipeline, device tensors throughout: marching cubes on the whole volume or streamed in slabs -> geometry.clean_mesh (components) ->
-    mesh_decimate.decimate_mesh (grid: cluster_grid's result, made by the public call before any device work) -> mesh_weld.weld_mesh (net.export_weld)"""
+    mesh_decimate.decimate_mesh (grid: cluster_grid's result, made by the public call before any device work) -> mesh_weld.weld_mesh (net.export_weld) ->
+    mesh_repair.repair_mesh (net.export_manifold)"""
     bmin, bmax = np.float32(-bound), np.float32(bound)                       # (the reference's bounds are float32 tensors, :712)
     xf = dict(den=resolution - 1.0, span=[float(bmax - bmin)] * 3, lo=[float(bmin)] * 3)
     if slab_layers is None:
@@ -41,7 +42,7 @@ def _native_mesh(net, bound, resolution, threshold, slab_layers, components, gri
             fill = lambda x0, out: nsr_ops.field_sdf_grid(f, ax[x0:x0 + out.shape[0]], ax, ax, bound, negate=True, out=out)
             v, t = nsr_ops.marching_cubes_streamed(fill, resolution, resolution, resolution, slab_layers=slab_layers, iso=float(threshold),
                                                    device=ax.device, **xf)
-    sizes = kept = members = weld = None
+    sizes = kept = members = weld = repair = None
     max_move = 2.0 * bound / (resolution - 1.0)
     if components is not None:
         from ..geometry import clean_mesh
@@ -55,7 +56,11 @@ def _native_mesh(net, bound, resolution, threshold, slab_layers, components, gri
         from ..mesh_weld import weld_mesh
         m = weld_mesh(dict(vertices=v, triangles=t) if members is None else dict(vertices=v, triangles=t, cluster_members=members))
         v, t, members, weld = m["vertices"], m["triangles"], m.get("cluster_members"), m["weld"]
-    return _NativeMesh(v, t, sizes, kept, members, max_move, weld)
+    if net.export_manifold:
+        from ..mesh_repair import repair_mesh
+        m = repair_mesh(dict(vertices=v, triangles=t) if members is None else dict(vertices=v, triangles=t, cluster_members=members))
+        v, t, members, repair = m["vertices"], m["triangles"], m.get("cluster_members"), m["repair"]
+    return _NativeMesh(v, t, sizes, kept, members, max_move, weld, repair)
 
 
 def _host(mesh):
@@ -92,6 +97,14 @@ class MeshExport:
     # repeated triangles and back-to-back pairs of a collapsed thin part go, and so do the vertices nobody names any more.  The dicts then carry `weld`, the
     # report of mesh_weld.mesh_weld.  Native mesher only.  drivers.export_mesh / export_animation(weld=True) set it for the length of their call.
     export_weld = False
+
+    # opt-in switch of the same three (same reason): False = what they always returned; True = the mesh is made manifold on the device
+    # (mesh_repair.repair_mesh) after the weld -- after the decimation or the cleaning when the weld is off -- and before anything is shaded, laid out or baked:
+    # where clustering pushed two sheets of the surface onto one edge or one vertex, every sheet gets its own copy of the vertex.  No triangle is added, dropped
+    # or turned; the copies of a split vertex start at one position and the export's own projection moves them identically, so the result holds COINCIDENT
+    # vertices that the index buffer keeps apart.  The dicts then carry `repair`, the report of mesh_repair.mesh_repair.  Native mesher only.
+    # drivers.export_mesh / export_animation(manifold=True) set it for the length of their call.
+    export_manifold = False
 
     def _grid_axis(self, bound, resolution):
         """torch.linspace(-bound, bound, resolution) as the reference forms it (on the host, fp32: extract_fields :730-732, update_extra_state :312-314), on the
@@ -164,6 +177,8 @@ class MeshExport:
             grid = _cluster_grid(bound, resolution, decimate)
         if self.export_weld:
             _check_model(self, "extract_geometry with export_weld welds the native mesher's mesh on the device: it needs mesher='native' and", ok=native)
+        if self.export_manifold:
+            _check_model(self, "extract_geometry with export_manifold repairs the native mesher's mesh on the device: it needs mesher='native' and", ok=native)
         if components is not None:
             _check_model(self, "extract_geometry(components=...) cleans the native mesher's mesh on the device: it needs mesher='native' and", ok=native)
         if slab_layers is not None:
@@ -212,6 +227,8 @@ class MeshExport:
             out["cluster_members"] = m.cluster_members
         if m.weld is not None:
             out["weld"] = m.weld
+        if m.repair is not None:
+            out["repair"] = m.repair
         return out, m.max_move
 
     def extract_colored_mesh(self, bound: float, resolution: int, threshold: float = 0.0, refine_steps: int = 3, tol: float = 1e-5, colors: bool = True,
@@ -235,7 +252,10 @@ class MeshExport:
         occlusion [V] float32 in [0, 1], 1 = open: mesh_occlusion.field_occlusion at the final positions and normals (after cleaning and decimation), 0 at a
         status-2 vertex.  The colours are unlit albedo; a viewer multiplies.
         self.export_weld (the switch above; False: nothing more, as ever) welds the mesh after the decimation and BEFORE the vertices are shaded: a vertex that no
-        surviving triangle names is never projected, coloured or posed.  The dict then also carries weld (the report, a plain dict of counts)."""
+        surviving triangle names is never projected, coloured or posed.  The dict then also carries weld (the report, a plain dict of counts).
+        self.export_manifold (the switch above; False: nothing more, as ever) splits non-manifold edges and vertices after the weld and BEFORE the vertices are
+        shaded: the copies of a split vertex start at one position, are projected identically and so stay COINCIDENT -- the same position, normal and colour under
+        different indices.  The dict then also carries repair (the report of mesh_repair.mesh_repair)."""
         kit = _occlusion_kit(self.export_occlusion, bound, threshold)
         out = self._colored_mesh(bound, resolution, threshold, refine_steps, tol, colors, slab_layers, components, decimate, kit)[0]
         return out if return_torch else _host(out)
@@ -255,7 +275,9 @@ class MeshExport:
         texels carry the colour detail the removed vertices carried; a texel's point is projected never further than one CLUSTER cell.
         self.export_occlusion: as in extract_colored_mesh.  The dict then also carries occlusion [V], texel_occlusion [S,S] float32 (0 at unowned texels) and occlusion_map [S,S]
         uint8 (the texture's quantisation rule), the texels' from ONE launch (ac_mesh_bake_maps) in place of the bake's: colour and occlusion share a texel's refine.
-        self.export_weld: as in extract_colored_mesh.  The mesh is welded BEFORE the atlas is laid out: the cells are sized for the welded triangle count."""
+        self.export_weld: as in extract_colored_mesh.  The mesh is welded BEFORE the atlas is laid out: the cells are sized for the welded triangle count.
+        self.export_manifold: as in extract_colored_mesh (coincident copies of the split vertices); the repair keeps every triangle and its place, so the atlas
+        is the one the unrepaired mesh would get."""
         from ..geometry import atlas_layout
         kit = _occlusion_kit(self.export_occlusion, bound, threshold)
         m, max_move = self._colored_mesh(bound, resolution, threshold, refine_steps, tol, True, slab_layers, components, decimate, kit)

@@ -57,7 +57,7 @@ def mesh_topology(triangles, V):
     """ac_mesh_topology: triangles [T,3] int32 on the device over V vertices -> a dict of Python ints: the counts TOPOLOGY_KEYS -- edges E (distinct),
     boundary (used once), nonmanifold (used more than twice), misoriented (used twice in one direction), referenced vertices, faces F (valid, non-degenerate),
     invalid, degenerate -- plus euler = referenced - E + F and closed_manifold = (boundary == nonmanifold == misoriented == 0).  One 32-byte read-back.
-    Non-manifold VERTICES (two fans that touch in a point) are not looked for."""
+    Non-manifold VERTICES (two fans that touch in a point) are not looked for (mesh_repair.mesh_repair splits them, and the non-manifold edges it can)."""
     T, V, dev = _head(triangles, V, "mesh_topology")
     need = int(L.lib().ac_mesh_topology_scratch(V, T))
     scratch = torch.empty(need, dtype=torch.uint8, device=dev)

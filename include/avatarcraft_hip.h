@@ -1073,7 +1073,8 @@ int ac_mesh_cluster_emit(const double *vertices /*[V,3]*/, uint32_t V, const int
  *   atomic adds); a pass over the slots reduces them, aggregated in the wave, by integer adds.  scratch: 16 bytes per slot, 1 per vertex and a little.
  * AC_ERR_BAD_ARG before any launch, with the rule in the message: a NULL required buffer (triangles may be NULL when T == 0, everything but counts when
  * V == 0), V or T above 2^31 - 1, triangles over V == 0, a scratch that is too short, n_kept_vertices > V or n_kept_triangles > T.
- * V == 0 with T == 0 is legal and launches nothing (counts = 0).  Not built: splitting non-manifold vertices, filling holes. */
+ * V == 0 with T == 0 is legal and launches nothing (counts = 0).  Splitting non-manifold vertices
+ * and edges: ac_mesh_repair_count / _emit (below).  Not built: filling holes. */
 size_t ac_mesh_weld_scratch(uint32_t V, uint32_t T);
 int ac_mesh_weld_count(const int32_t *triangles /*[T,3]*/, uint32_t T, uint32_t V, void *scratch, size_t scratch_bytes,
                        uint32_t *counts /* DEVICE [8] = { V', T', invalid, degenerate, cancelled, repeated, excess, 0 } */, ac_stream_t stream);
@@ -1083,6 +1084,50 @@ int ac_mesh_weld_emit(const int32_t *triangles /*[T,3]*/, uint32_t T, uint32_t V
 size_t ac_mesh_topology_scratch(uint32_t V, uint32_t T);
 int ac_mesh_topology(const int32_t *triangles /*[T,3]*/, uint32_t T, uint32_t V, void *scratch, size_t scratch_bytes,
                      uint32_t *counts /* DEVICE [8] = { E, boundary, nonmanifold, misoriented, referenced, F, invalid, degenerate } */, ac_stream_t stream);
+
+/* ---- making the mesh manifold, on the device (csrc/mesh_repair.hip; added entries only, no struct changes: ABI stays 10).  It stands in for nothing in the
+ * reference.  Vertex clustering pushes two sheets of the surface onto one edge or one vertex; the repair tells the sheets apart again and gives every sheet its
+ * own copy of the vertex.  Every output is a function of the input alone and equals a numpy restatement exactly (tests/mesh_repair_cases.py).
+ * Input: vertices [V,3] fp32, triangles [T,3] int32.  INVALID triangle: an index outside [0, V); counted, copied as it stands, takes no part (the Python
+ * front end raises).  DEGENERATE triangle: valid, two equal corners; counted, copied as it stands, takes no part.  The others are MEMBERS.
+ *   Uses.  Corner k of triangle t has the corner id 3 t + k.  Side k runs from corner k to corner (k + 1) % 3; its use id is 3 t + k and its opposite vertex
+ *     is corner (k + 2) % 3.  The uses of the edge (a, b), a < b, are the member sides over { a, b }; a use is FORWARD if it runs a -> b.
+ *   Joining, per edge, by its number of uses n.  n = 1: nothing.  n = 2: the two uses are joined, whatever their directions.  3 <= n <= 8: the edge is
+ *     NON-MANIFOLD; its uses are ordered around it and paired (below); paired uses are joined, the others are CUT.  n > 8: the edge is CROWDED: it counts as
+ *     non-manifold and all its uses are cut.
+ *   Order around an edge.  All arithmetic is fp64 on the fp32 positions widened, every operation rounded on its own (no fused multiply-add).  The cross
+ *     product is (y z' - z y', z x' - x z', x y' - y x'), the dot product (x x' + y y') + z z'.  e = P[b] - P[a]; d_i = P[c_i] - P[a] with c_i the opposite
+ *     vertex of use i; w = e x d_r with r the use of smallest id; u = w x e; X_i = d_i . u, Y_i = d_i . w, s = |X_i| + |Y_i|.  The key of use i is 0 if
+ *     s == 0; otherwise, with q = Y_i / s: q if X_i >= 0 and Y_i >= 0, 2 - q if X_i < 0, and 4 + q otherwise -- a monotone stand-in for the angle, in [0, 4).
+ *     If any key of the edge is not finite, the edge is treated as crowded.  The uses are sorted by (key, use id) into a cyclic list.
+ *   Pairing.  A backward use has the solid on its increasing-angle side, a forward use on its decreasing side.  From the start of the list, find the first
+ *     position whose use is backward and whose cyclic successor is forward and a different use; join the two, remove both from the list, and start again from
+ *     the beginning; stop when no such position is left.  (Cyclic bracket matching: with as many forward as backward uses it pairs every use, and each pair
+ *     bounds one wedge of solid, so two bodies that touch along an edge come apart as two bodies.)
+ *   Fans.  Joining two uses of the edge (a, b) unites the two triangles' corners at a, and their corners at b.  A FAN is a set of united member corners; its
+ *     root is its smallest corner id.  Every vertex v keeps the index v for the fan whose root is smallest among its fans; every other fan gets a new index
+ *     V + j, j = the rank of its root among all such extra roots in ascending order.  source [V'] = the original vertex of every output vertex (the identity
+ *     on the first V).  triangles_out [T,3]: the same T, order and orientation, member corners rewritten to their fan's index.  Vertices nobody names keep
+ *     their index: the repair never removes anything.  Non-manifold VERTICES are split by the same rule: two cones that meet in a point are two fans.
+ *   counts (DEVICE, [8]) = { V', split (vertices with more than one fan), nonmanifold (edges, crowded ones included), paired (uses), cut (uses), crowded
+ *     (edges), invalid, degenerate }.  Repairing the output again adds nothing.  What stays non-manifold afterwards are pinches -- an edge where the surface
+ *     touches itself while both end points keep a single fan --, which no vertex duplication can separate: ac_mesh_topology counts them.
+ * ac_mesh_repair_count: the table of ac_mesh_topology, keyed by (min << 31) | max, capacity >= 6 T, with a use counter and the smallest and largest use id
+ *   per slot (integer atomic add / min / max); the slots with 3 to 8 uses get their use ids into a side list, and the lane that owns the edge computes the
+ *   keys, sorts (key, use id) and matches the brackets in registers; the joins go through the lock-free union-find of ac_mesh_components over the 3 T corner
+ *   ids; then a flatten pass, an integer atomic min of the roots per vertex, the extra-root flags and the ordered scans.  No wave waits for another one, no
+ *   floating-point atomics.  The scratch (the _scratch function of (V, T) bytes: 24 per table slot, 36 per triangle, 8 per vertex and a little) is kept
+ *   unchanged until the emit call.
+ * ac_mesh_repair_emit : the same head, then the outputs with n_vertices = V' of the count call (source is written below n_vertices only, triangles_out
+ *   whole).  Ordered writes, no atomics.
+ * AC_ERR_BAD_ARG before any launch, with the rule in the message: a NULL required buffer (triangles and triangles_out may be NULL when T == 0, everything
+ * but counts when V == 0), V or T above 2^31 - 1, 3 T above 2^31 - 1 (corner ids are int32), triangles over V == 0, a scratch that is too short,
+ * n_vertices outside [V, V + 3 T].  V == 0 with T == 0 is legal and launches nothing (counts = 0).  Not built: re-pairing pinched edges, filling holes. */
+size_t ac_mesh_repair_scratch(uint32_t V, uint32_t T);
+int ac_mesh_repair_count(const float *vertices /*[V,3]*/, const int32_t *triangles /*[T,3]*/, uint32_t T, uint32_t V, void *scratch, size_t scratch_bytes,
+                         uint32_t *counts /* DEVICE [8] = { V', split, nonmanifold, paired, cut, crowded, invalid, degenerate } */, ac_stream_t stream);
+int ac_mesh_repair_emit(const float *vertices /*[V,3]*/, const int32_t *triangles /*[T,3]*/, uint32_t T, uint32_t V, void *scratch, size_t scratch_bytes,
+                        int32_t *triangles_out /*[T,3]*/, int32_t *source /*[V']*/, uint32_t n_vertices, ac_stream_t stream);
 
 /* ---- rendering from a half-precision hash table (opt-in, inference only) ----------------------------------------------------------------------------
  * The half table holds ONE dword per entry of the fp32 table [n_entries][2] (n_entries = field->offsets[16]): channel 0 as an IEEE binary16 in the low
